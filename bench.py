@@ -3,7 +3,7 @@
 synthetic graph (BASELINE.json metric; configs[1] = C2: 30,926 nodes / 849,456 edges /
 3 relations, 64 -> 128 -> 128, fp32 in / fp32 out).
 
-    python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c4]
+    python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c4] [--dump-outputs DIR] [--full]
 
 A step = one pass of the two-layer encoder over the whole graph, forward + backward
 (conv1 -> relu -> conv2, seeded cotangent; dropout p = 0; bucketing excluded - the graph is
@@ -13,7 +13,13 @@ exchange per layer and direction (primekg_rgcn_linkprediction_amd/dist.py), one 
 per GPU, launched by torch.distributed.run; `--workload c4` is BASELINE configs[3]
 (500k nodes / 20M edge columns / 16 relations) and runs at any N.
 
-Rank 0 prints ONE JSON line.  Beside the contract's fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps (`ms_per_step` = their mean), writes
+the last timed step's outputs if `--dump-outputs DIR` is given and prints the line: the contract's fields, the
+configuration and `bucket_ms`.  `--dump-outputs DIR` writes DIR/<name>.npy (float32): the encoder output
+`encoder_out` and the gradient of every parameter (`grad_node_embeddings`, `grad_conv1_weight`, ...), all rows in node
+order; where that would exceed 64 MB, the same fixed, seeded sample of node rows from every [nodes, d] array, its
+row ids in `rows.npy`.  Inputs are seeded: the same arguments give the same inputs in every run.
+With `--full` the line also carries
   roofline         the gather instantiation with the most time per step: algorithmic bytes / live HIP-event time.
                    While the gathered row table is cache resident (C2: 8-16 MB) the bound is the chip's L2-resident
                    indexed-row rate (`bound: "l2"`, peak 16.8 TB/s, MI355X_MICROARCH.md "Indexed rows"): `frac` is
@@ -37,6 +43,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -70,13 +77,18 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2")
     ap.add_argument("--edges", type=int, default=None, help="override E of the PrimeKG-shaped graph (default 849,456)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: per-kernel events and rooflines, the secondary legs, the batch-replica "
+                         "leg (N > 1) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="time eager launches, never a HIP graph replay")
     ap.add_argument("--graph", action="store_true", help="time the HIP graph replay even if eager calibrates faster")
     ap.add_argument("--no-replica", action="store_true",
                     help="N > 1: skip the batch-replica leg reported beside the node-partitioned number")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="headline run: skip the fp32-MFMA pass and the short C4 leg (profiling passes use this)")
+                    help="--full headline run: skip the fp32-MFMA pass and the short C4 leg (profiling passes use this)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--fp16-gather", action="store_true",
                     help="BASELINE configs[4]: forward gathers read an fp16 copy of the feature table "
@@ -199,7 +211,7 @@ class Run:
             emb = self.emb_cpu.to(dev).requires_grad_(True)
             convs = self.convs = [c.to(dev) for c in self.convs]
             cot = self.cot_cpu.to(dev)
-            params = [emb] + [p for c in convs for p in c.parameters()]
+            params = self.params = [emb] + [p for c in convs for p in c.parameters()]
             self._keep = (eid, etd)
 
             def step():
@@ -208,6 +220,7 @@ class Run:
                 for p in params:
                     p.grad = None
                 out.backward(cot)
+                return out
             self.step = step
 
             def drop_in_step():
@@ -230,6 +243,7 @@ class Run:
             torch.cuda.synchronize()
             self.bucket_ms = (time.perf_counter() - t0) * 1e3
             cot = enc.shard_rows(self.cot_cpu).to(dev)
+            self.params = enc.params
             self.step = lambda: enc.step(cot)                                     # noqa: E731
             exchange = "RCCL over xGMI" if backend == "nccl" else f"{backend} (host-staged rehearsal, NOT RCCL)"
             self.summary = summ = enc.exchange_summary()
@@ -245,6 +259,16 @@ class Run:
         return (f"{self.wl['name']}, {self.n} nodes / {self.num_edges} edge columns / {self.r} relations, encoder "
                 f"{d[0]}->{d[1]}->{d[2]}, 2 layers fwd+bwd, full graph per step, dropout 0"
                 + ("" if headline else "  [NOT the headline configuration]"))
+
+    def outputs(self, out):
+        """-> {name: tensor}: what a caller of the step receives - the encoder output (this rank's rows at N > 1) and
+        the gradient of every parameter, the node embedding table's first (references, not copies)"""
+        names = ["node_embeddings"] + [f"conv{i + 1}_{k}" for i, c in enumerate(self.convs) for k, _ in c.named_parameters()]
+        arrays = {"encoder_out": out.detach()}
+        for name, p in zip(names, self.params):
+            if p.grad is not None:
+                arrays[f"grad_{name}"] = p.grad
+        return arrays
 
     def sync(self):
         if self.dist is not None:
@@ -276,7 +300,9 @@ class Run:
         torch.cuda.current_stream().wait_stream(side)
         hip_graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(hip_graph, capture_error_mode="thread_local"):
-            self.step()
+            out = self.step()
+        # the captured step's own tensors: every replay rewrites them (None for a step that returns nothing)
+        self.graph_outputs = self.outputs(out) if out is not None else None
         for _ in range(3):
             hip_graph.replay()
         torch.cuda.synchronize()
@@ -296,13 +322,15 @@ class Run:
             if force_graph or t_graph < 1.1 * t_eager:         # replay unless eager is clearly faster (10 iterations each: noisy)
                 run, mode = hip_graph.replay, "hipGraph replay"
         self.sync()
+        res = None
         t0 = time.perf_counter()
         for _ in range(steps):
-            run()
+            res = run()
         self.sync()
         elapsed = time.perf_counter() - t0
         if self.dist is not None:
             elapsed = self.agree(elapsed, self.dist.ReduceOp.MAX)
+        self.last_step = (mode, res)                           # what the last timed step returned (a replay: None)
         return elapsed, mode
 
     def events(self, event_steps):
@@ -484,6 +512,36 @@ def secondary_c4(args, dev, dist, world):
     return out
 
 
+DUMP_BYTES = 64 * 2 ** 20
+ROW_OUTPUTS = ("encoder_out", "grad_node_embeddings")     # [nodes, d]: one row per node
+
+
+def dump_outputs(run, path, rank):
+    """--dump-outputs: what the last timed step computed -> `path`/<name>.npy, float32, rank 0 writes.  At N > 1 the
+    [nodes, d] arrays are gathered into node order first (collective: every rank calls this).  Beyond DUMP_BYTES in
+    all, every [nodes, d] array keeps the same fixed, seeded sample of rows, whose ids go to `rows.npy`."""
+    mode, res = run.last_step
+    arrays = dict(run.graph_outputs if mode == "hipGraph replay" else run.outputs(res))
+    if run.world > 1:
+        for name in ROW_OUTPUTS:
+            arrays[name] = run.enc.gather_output(arrays[name])
+    if rank != 0:
+        return
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items()}
+    total = sum(4 * v.numel() for v in arrays.values())
+    budget = DUMP_BYTES - 1024 * (len(arrays) + 1)            # each .npy file's header within its KiB
+    if total > budget:
+        row_bytes = sum(4 * arrays[k][0].numel() for k in ROW_OUTPUTS)
+        keep = (budget - (total - row_bytes * run.n)) // (row_bytes + 8)
+        rows = torch.randperm(run.n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        for k in ROW_OUTPUTS:
+            arrays[k] = arrays[k][rows]
+        arrays["rows"] = rows.double()
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), v.numpy())
+
+
 def main():
     args = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -527,10 +585,13 @@ def main():
     run = Run(args.workload, args, dev, dist, world, edges=args.edges, fp16=args.fp16_gather)
     use_graph = world == 1 and not args.no_graph
     elapsed, launch_mode = run.measure(args.steps, args.warmup, use_graph, force_graph=args.graph)
+    if args.dump_outputs:
+        dump_outputs(run, args.dump_outputs, rank)
 
+    # --full: an eager pass with HIP events around every launch -> per-kernel tables and rooflines
     event_steps = min(args.steps, 20)
-    events = run.events(event_steps)
-    overhead_us = event_overhead_us(world)
+    events = run.events(event_steps) if args.full else ([], [], [])
+    overhead_us = event_overhead_us(world) if args.full else None
 
     headline = args.workload == "c2" and not args.fp16_gather and args.edges in (None, synth.PRIMEKG_EDGES)
     result = {
@@ -580,7 +641,7 @@ def main():
     if kernels or calls:
         result["dominant_kernel"] = dominant_kernel_of(kernels, calls)
 
-    if world > 1 and not args.no_replica and not is_c4:
+    if args.full and world > 1 and not args.no_replica and not is_c4:
         # Reported beside the node-partitioned number (never instead of it): batch-replica mode,
         # every GPU the whole graph and its own mini-batch, one flat all-reduce of all parameter
         # gradients per step.  Per-GPU work is fixed, so this one is weak scaling.
@@ -607,11 +668,11 @@ def main():
         # non-zero if it failed or hung (the eager line is still printed first).
         result["graph_attempt"] = "not attempted (opt in with RGCN_BENCH_GRAPH_N=1)"
 
-    # ---- secondary legs of the headline line (short; the whole command stays well inside the driver's limit) ----
+    # ---- --full: secondary legs of the headline line (short; the whole command stays well inside 10 minutes) ----
     want_graph_n = world > 1 and os.environ.get("RGCN_BENCH_GRAPH_N", "0") == "1" and not args.no_graph
-    if headline and not args.no_secondary and want_graph_n:
+    if args.full and headline and not args.no_secondary and want_graph_n:
         result["secondary"] = {"skipped": "RGCN_BENCH_GRAPH_N=1: the graph attempt may end the process, so it runs alone"}
-    if headline and not args.no_secondary and not want_graph_n:
+    if args.full and headline and not args.no_secondary and not want_graph_n:
         secondary = {}
         if world == 1:
             # the same step with exact fp32 MFMA products (RGCN_GEMM_PRECISION=fp32): every module reads
@@ -688,9 +749,9 @@ def main():
         finally:
             watchdog.cancel()
 
-    if rank == 0 and world == 1 and is_c4 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and is_c4 and not args.no_cpu_baseline:
         result["cpu_baseline"] = None            # one oracle step over 20M edge columns takes minutes: timed for C2 only
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+    elif args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         ei, et, n, r, dims, bases = keep_cpu
         result["cpu_baseline"] = cpu_baseline(ei, et, n, r, dims, bases, args.cpu_seconds)
         result["gpu_over_cpu"] = result["value"] / result["cpu_baseline"]["value"]

@@ -93,8 +93,17 @@ def test_layer_golden(case):
     torch.testing.assert_close(out.double(), dense, rtol=0, atol=2e-5)
     torch.testing.assert_close(dense, z["out_dense_f64"], rtol=0, atol=1e-12)
     (out * z["cot"]).sum().backward()
-    for p, k in zip(params, ("grad_x", "grad_weight", "grad_root", "grad_bias")):
-        torch.testing.assert_close(p.grad, z[k], rtol=1e-5, atol=1e-6)
+    # gradients against the float64 autograd of restatement #2, which every host reproduces: the stored fp32 vectors
+    # are one BLAS's summation order, and another host's kernels sum in another (both within ~1e-6 of the tensor's
+    # scale of float64).  The run and the stored vectors are held to the same gate, 1e-6 taken at the tensor's scale
+    p64 = [z[k].double().requires_grad_(True) for k in ("x", "weight", "root", "bias")]
+    c64 = comp.double() if comp is not None else None
+    dense64 = O.rgcn_conv_dense_f64(p64[0], z["edge_index"], z["edge_type"], p64[1], p64[2], p64[3], c64, r)
+    (dense64 * z["cot"].double()).sum().backward()
+    for p, q, k in zip(params, p64, ("grad_x", "grad_weight", "grad_root", "grad_bias")):
+        atol = 1e-6 * max(1.0, q.grad.abs().max().item())
+        torch.testing.assert_close(p.grad.double(), q.grad, rtol=1e-5, atol=atol)
+        torch.testing.assert_close(z[k].double(), q.grad, rtol=1e-5, atol=atol)
     agg = O.mean_aggregate_ref(z["x"], z["edge_index"], z["edge_type"], r)
     torch.testing.assert_close(agg, z["agg"], rtol=0, atol=1e-6)
 

@@ -9,11 +9,11 @@ part=${2:-1}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 out=gpurun_out
 if [ "$part" = 1 ]; then
-python3 bench.py > $out/${tag}_c2_bench.json 2> $out/${tag}_c2_bench.err
+python3 bench.py --full > $out/${tag}_c2_bench.json 2> $out/${tag}_c2_bench.err
 stats() {  # name, extra bench args ...: the line itself first (no profiler attached), then the same command under rocprofv3
   local name=$1; shift
-  [ "$name" = c2 ] || python3 bench.py --no-cpu-baseline --no-secondary "$@" > $out/${tag}_${name}_bench.json 2> $out/${tag}_${name}_bench.err
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag}_$name -o p -- python3 bench.py --no-cpu-baseline --no-secondary "$@" \
+  [ "$name" = c2 ] || python3 bench.py --full --no-cpu-baseline --no-secondary "$@" > $out/${tag}_${name}_bench.json 2> $out/${tag}_${name}_bench.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag}_$name -o p -- python3 bench.py --full --no-cpu-baseline --no-secondary "$@" \
       > $out/${tag}_${name}_prof_bench.json 2> $out/${tag}_${name}_prof.err
   cp "$(find $out/prof_${tag}_$name -name '*kernel_stats.csv' | head -1)" $out/${tag}_${name}_kernel_stats.csv
 }
@@ -29,7 +29,7 @@ if [ "$part" = 2 ]; then
 for set in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TA_TA_BUSY_sum" \
            "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA"; do
   d=$out/pmc_${tag}/$(echo $set | tr ' ' '_' | cut -c1-40)
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $d -o p -- python3 bench.py --no-cpu-baseline --no-secondary --steps 10 --warmup 3 \
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $d -o p -- python3 bench.py --full --no-cpu-baseline --no-secondary --steps 10 --warmup 3 \
       > /dev/null 2> $out/${tag}_pmc.err
 done
 python3 tools/pmc_summary.py $out/pmc_${tag} $out/${tag}_pmc_counters.json "C2 bench (split precision), rocprofv3 --pmc, one counter set per pass" > $out/${tag}_pmc_summary.txt
@@ -39,10 +39,10 @@ if [ "$part" = 3 ]; then
 export RGCN_BENCH_BACKEND=gloo
 echo "gloo rehearsal, 2 ranks, C2 (+ its secondary C4 leg)"
 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 \
-    bench.py --gpus 2 --steps 10 --warmup 3 > $out/${tag}_gloo2_c2_bench.json 2> $out/${tag}_gloo2_c2.err
+    bench.py --full --gpus 2 --steps 10 --warmup 3 > $out/${tag}_gloo2_c2_bench.json 2> $out/${tag}_gloo2_c2.err
 echo "gloo rehearsal, 2 ranks, C4"
 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29542 \
-    bench.py --gpus 2 --steps 5 --warmup 2 --workload c4 --no-secondary > $out/${tag}_gloo2_c4_bench.json 2> $out/${tag}_gloo2_c4.err
+    bench.py --full --gpus 2 --steps 5 --warmup 2 --workload c4 --no-secondary > $out/${tag}_gloo2_c4_bench.json 2> $out/${tag}_gloo2_c4.err
 unset RGCN_BENCH_BACKEND
 echo "host profile"; python3 tools/host_profile.py 12 > $out/${tag}_host_profile.txt 2>&1
 echo "stamps"; tools/gemm_stamps > $out/${tag}_stamps.txt 2>&1
