@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 24
+#define RGCN_ABI_VERSION 25
 
 enum {
   RGCN_OK = 0,
@@ -401,7 +401,9 @@ int rgcn_layer_fwd_fused(const int32_t* rowptr, const int32_t* col, const uint32
  * destinations, w_t = 1 / cnt[destination, relation]) with the same convention for long segments: ONE entry, id =
  * -(row + 1) of hub_agg, weight 1, the row pre-aggregated by rgcn_aggregate over a weighted structure of the long
  * segments.  g_amax: amax buffer of g; gagg_amax_mul: rgcn_graph_weight_bound(g, 1) (the bound that scales the
- * weighted sums).  Shapes: d_out in {64, 128, 256}, d_in in {64, 128, 256}, num_relations < d_out / 2 and <= 32.
+ * weighted sums when gagg_amax is NULL).  gagg_amax (a ZEROED amax buffer, or NULL): a first launch of the kernel
+ * gathers the weighted sums and leaves their maximum there, and they are scaled by it instead of the bound - then
+ * bit-identical to rgcn_aggregate(transposed, amax_out = gagg_amax) -> rgcn_transform_bwd_input_split(gagg_amax, 1).  Shapes: d_out in {64, 128, 256}, d_in in {64, 128, 256}, num_relations < d_out / 2 and <= 32.
  * Bit-identical to rgcn_aggregate(transposed) -> rgcn_transform_bwd_input_split. */
 int rgcn_layer_bwd_input_fused_supported(int64_t num_relations, int64_t d_in, int64_t d_out);
 int rgcn_layer_bwd_input_fused(const int32_t* rowptr_t, const int32_t* col_t, const float* w_t,
@@ -409,7 +411,7 @@ int rgcn_layer_bwd_input_fused(const int32_t* rowptr_t, const int32_t* col_t, co
                                const float* hub_agg, const float* g, const void* packed, int has_root,
                                const float* relu_mask, int64_t d_in, int64_t d_out, const float* g_amax,
                                float gagg_amax_mul, float* grad_x, float* grad_x_amax, void* stream,
-                               float out_scale /* as rgcn_transform_bwd_input_split */);
+                               float out_scale /* as rgcn_transform_bwd_input_split */, float* gagg_amax);
 
 /* ------------------------------------------------------------------------------------
  * DistMult head (rows C1 + C2; rgcn.py:325-326 row gathers + rgcn.py:207-211):

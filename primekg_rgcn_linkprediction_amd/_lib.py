@@ -13,7 +13,7 @@ from ctypes import c_float, POINTER, c_char_p, c_int, c_int64, c_size_t, c_void_
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 LIB_NAME = "librgcn_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -118,7 +118,7 @@ PROTOTYPES = {
     "rgcn_layer_fwd_fused": (c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P, c_int, _P, c_int, _I64, _I64, _P, _P, _P, _P, _P]),
     "rgcn_layer_bwd_input_fused_supported": (c_int, [_I64, _I64, _I64]),
     "rgcn_layer_bwd_input_fused": (c_int, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P, c_int, _P, _I64, _I64, _P, c_float, _P, _P,
-                                           _P, c_float]),
+                                           _P, c_float, _P]),
     "rgcn_sequence_run": (c_int, [_P, c_int, _P, _I64, _P, c_int, _P]),
     "distmult_fwd": (c_int, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P]),
     "rgcn_index_error_fetch": (c_int, [POINTER(c_int), _P]),

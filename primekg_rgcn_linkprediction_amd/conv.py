@@ -141,16 +141,18 @@ def _input_grad(graph: "ops.BucketedGraph", g: Tensor, weight: Tensor, root: Opt
               if (d_out >= ratio * d_in and root is not None and not graph.bipartite) else None)
     # `tail`: the pending slab reduction of this layer's parameter gradients rides in the gather launch
     if merged is None:
+        # the transposed aggregate is scaled from its OWN maximum, which its gather (or the fused kernel's first pass)
+        # leaves: the bound weight_bound * max |g| is hundreds of times looser on hub graphs and would cost its ordinary
+        # rows that many binades of the lo half (tests/test_split_rows.py).  No hub deferral: the maximum must be final.
+        gagg_amax = scales.slot() if (scales is not None and g_amax is not None) else None
         if _fused_backward(graph, g, r, d_in, d_out, g_amax, packed, precision):
-            return ops.layer_bwd_input_fused(graph, g, packed, None, g_amax, inline_limit=_EVAL_INLINE_LIMIT, tail=tail)
-        if _defer_hubs(False, packed, g_amax, d_out, d_in) and precision in (None, "half") and not graph.bipartite:
-            gagg, hubs = ops.aggregate_deferred(graph, g, transposed=True, tail=tail)
-        else:
-            gagg, hubs = ops.aggregate(graph, g, transposed=True, tail=tail), None       # autograd of A3 + A4 (fp32 grads)
-        # |gagg| <= (largest sum of 1/cnt weights over a node's out-edges of one relation) * max |g|
-        return ops.transform_bwd_input(gagg, g, weight, root, graph=graph, amax=(g_amax, g_amax),
-                                       amax_mul=graph.weight_bound(True), packed=packed,
-                                       precision=precision, hubs=hubs)                    # autograd of A6 wrt x
+            return ops.layer_bwd_input_fused(graph, g, packed, None, g_amax, inline_limit=_EVAL_INLINE_LIMIT, tail=tail,
+                                             gagg_amax=gagg_amax)
+        gagg = ops.aggregate(graph, g, transposed=True, tail=tail, amax_out=gagg_amax)   # autograd of A3 + A4 (fp32 grads)
+        # without a slot (fp32 mode): |gagg| <= (largest sum of 1/cnt weights over a node's out-edges of one relation) * max |g|
+        a1, mul = (gagg_amax, 1.0) if gagg_amax is not None else (g_amax, graph.weight_bound(True))
+        return ops.transform_bwd_input(gagg, g, weight, root, graph=graph, amax=(a1, g_amax), amax_mul=mul, packed=packed,
+                                       precision=precision)                              # autograd of A6 wrt x
     if t_first is not None:
         t = t_first                              # (already formed behind conv2's input gradient: ops.transform_bwd_input_chain)
     elif from_packed:
@@ -228,7 +230,7 @@ def _conv_forward(x, weight, root, bias, *, graph, relu, gather_dtype, half):
 def _conv_backward(x, agg, weight, root, x_amax, pkbuf, g, *, graph, has_root, has_bias, need_x, need_p, prec):
     """one layer's backward as a pass -> (gx | None, gw | None, groot | None, gbias | None)"""
     packed = _packs([pkbuf], [(weight, root)])[0]
-    scales = _Scales(g, slots=1)
+    scales = _Scales(g, slots=2)                # max |g|; max |transposed aggregate of g|
     g_amax = scales.first
     pending = None
     if need_p:
@@ -328,32 +330,31 @@ def _enc2_backward(x, agg1, h, agg2, w1, root1, w2, root2, x_amax, h_amax, pk1bu
     has_root1, has_b1, has_root2, has_b2 = flags
     t_first = None
     pk1, pk2 = _packs([pk1buf, pk2buf], [(w1, root1), (w2, root2)])
-    scales = _Scales(g)
-    g_amax, gz_amax = scales.first, scales.slot()
+    scales = _Scales(g, slots=4)         # max |g|, |gz|, |transposed aggregate of g| and (gather-first conv1) of gz
+    g_amax, gz_amax, gagg2_amax = scales.first, scales.slot(), scales.slot()
     wb = graph.weight_bound(True)        # |transposed aggregate| <= wb * max |gradient table|
     # the slab reductions of the parameter gradients ride in the transposed gathers that follow them
     red2 = ops.transform_bwd_params(agg2, h, g, r, want_root=has_root2, want_bias=has_b2, graph=graph,
                                     defer=True, amax=(h_amax, h_amax, g_amax), precision=prec)
     # dropout backward: the factor 1 / (1 - p) goes into the input-gradient epilogue as a scalar (the mask is h itself,
-    # positive exactly where a unit is active and kept) - the weights keep their split images and the hub deferral
+    # positive exactly where a unit is active and kept) - the weights keep their split images
     scale = 1.0 / (1.0 - p) if p > 0 else 1.0
+    # conv2's transposed aggregate is scaled from its own maximum (see _input_grad); wb only in fp32 mode (no slots)
+    a1, mul = (gagg2_amax, 1.0) if gagg2_amax is not None else (g_amax, wb)
     if _fused_backward(graph, g, r, w2.size(1), w2.size(2), g_amax, pk2, prec):
         gz = ops.layer_bwd_input_fused(graph, g, pk2, h, g_amax, amax_out=gz_amax, inline_limit=_EVAL_INLINE_LIMIT,
-                                       tail=red2, out_scale=scale)
+                                       tail=red2, out_scale=scale, gagg_amax=gagg2_amax)
     else:
-        if _defer_hubs(False, pk2, g_amax, w2.size(2), w2.size(1)) and not graph.bipartite:
-            gagg2, hubs2 = ops.aggregate_deferred(graph, g, transposed=True, tail=red2)
-        else:
-            gagg2, hubs2 = ops.aggregate(graph, g, transposed=True, tail=red2), None
+        gagg2 = ops.aggregate(graph, g, transposed=True, tail=red2, amax_out=gagg2_amax)
         # conv1's input gradient is transform-first (T = gz [W1_r^T | root1^T], then one gather): T is formed by the SAME
         # launch that forms gz, from the workgroup's own tile of it (round 4: one launch less, no re-read of gz)
         if (_CHAIN and need_x and prec is None and pk1 is not None and pk2 is not None and g_amax is not None
                 and _transform_first_applies(graph, w1, root1, pk1, prec) and ops.chain_supported(w2, w1)):
-            gz, t_first = ops.transform_bwd_input_chain(gagg2, g, w2, root2, h, pk2, pk1, graph=graph, amax=(g_amax, g_amax),
-                                                        amax_mul=wb, amax_out=gz_amax, hubs=hubs2, out_scale=scale)
+            gz, t_first = ops.transform_bwd_input_chain(gagg2, g, w2, root2, h, pk2, pk1, graph=graph, amax=(a1, g_amax),
+                                                        amax_mul=mul, amax_out=gz_amax, out_scale=scale)
         else:
-            gz = ops.transform_bwd_input(gagg2, g, w2, root2, relu_mask=h, graph=graph, amax=(g_amax, g_amax),
-                                         amax_mul=wb, amax_out=gz_amax, packed=pk2, precision=prec, hubs=hubs2,
+            gz = ops.transform_bwd_input(gagg2, g, w2, root2, relu_mask=h, graph=graph, amax=(a1, g_amax),
+                                         amax_mul=mul, amax_out=gz_amax, packed=pk2, precision=prec,
                                          out_scale=scale)   # d loss / d (pre-ReLU of conv1)
     red1 = ops.transform_bwd_params(agg1, x, gz, r, want_root=has_root1, want_bias=has_b1, graph=graph,
                                     defer=True, amax=(x_amax, x_amax, gz_amax), precision=prec)
@@ -387,8 +388,8 @@ class _Encoder2Function(torch.autograd.Function):
     exactly where ``rgcn.py:125`` draws it.  Its backward costs nothing extra: the dropped
     activations ``hd = relu(z) * m / (1-p)`` are positive exactly where the unit is both active
     and kept, so ``hd`` is the epilogue mask, and the factor ``1/(1-p)`` is one more scalar of that
-    GEMM's epilogue (``out_scale``): the step's split weight images and the hub deferral serve
-    the dropout case unchanged.
+    GEMM's epilogue (``out_scale``): the step's split weight images serve the dropout case
+    unchanged.
 
     Forward and backward are ``ops.Region`` passes: after three steps on a graph their launches are
     issued by one native call each (``rgcn_sequence_run``) instead of ~14 wrapper calls."""

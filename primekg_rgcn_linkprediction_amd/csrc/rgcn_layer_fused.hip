@@ -65,7 +65,7 @@ __global__ __launch_bounds__(kThreads) void k_layer_fused(
     const __half* __restrict__ Fl, const float* __restrict__ b_inv_scale, const float* __restrict__ x_amax,
     float a1_mul, const float* __restrict__ bias, const float* __restrict__ mask, float* __restrict__ out,
     float* __restrict__ agg, int N, int R, int chunks, const uint32_t* __restrict__ tile_mask,
-    unsigned* __restrict__ amax_out, float out_scale) {
+    unsigned* __restrict__ amax_out, float out_scale, const float* __restrict__ a1_amax, int max_only) {
   constexpr int D_IN = 4 * G, KS = D_IN / 16, NG = kThreads / G, RPG = kRows / NG;
   constexpr int ROWB = D_IN * 2 + 16;            // bytes of one A row per image: + 16 keeps the fragment reads conflict-free
   constexpr int D_OUT = 32 * NT;
@@ -101,8 +101,11 @@ __global__ __launch_bounds__(kThreads) void k_layer_fused(
   rel_mask = __builtin_amdgcn_readfirstlane(rel_mask);
   const float xmax = rgcn_amax_value(x_amax, lane);
   const int ea2 = scale_exponent(xmax);                        // the table's own scale (last chunk; every chunk of a mean)
-  const int ea1 = WEIGHTED ? scale_exponent(xmax * a1_mul) : ea2;
-  const bool has_cols = NT == 4 * TNW || wave * TNW < NT;      // this wave multiplies (always, unless the output is 64 wide)
+  // weighted sums: scaled from their own maximum (a1_amax, left by this kernel's max_only pass) or by the bound a1_mul * xmax
+  const int ea1 = WEIGHTED ? scale_exponent(a1_amax ? rgcn_amax_value(a1_amax, lane) : xmax * a1_mul) : ea2;
+  // this wave multiplies (always, unless the output is 64 wide; never in the max_only pass)
+  const bool has_cols = (NT == 4 * TNW || wave * TNW < NT) && !max_only;
+  float sum_max = 0.f;                           // max_only: max |weighted sum| over this block's rows
 
   floatx16 acc[TNW];
 #pragma unroll
@@ -116,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void k_layer_fused(
 
   // the chunks this block multiplies: the relations some row of it has, then the rows themselves
   unsigned long long todo = (unsigned long long)rel_mask & ((1ull << R) - 1ull);
-  if (chunks > R) todo |= 1ull << R;
+  if (chunks > R && !max_only) todo |= 1ull << R;
 
   // the group's rows of the chunk being gathered: segment start / length and the ids of its edges (lane j: edge
   // j).  An id < 0 is row -id - 1 of hub_agg: the plan replaces every segment longer than its inline limit by ONE
@@ -233,8 +236,14 @@ __global__ __launch_bounds__(kThreads) void k_layer_fused(
         }
       }
     }
+    if (max_only) {                              // the rows' maximum only (rows past N gathered nothing: zero)
+#pragma unroll
+      for (int q = 0; q < RPG; ++q)
+        sum_max = fmaxf(sum_max, fmaxf(fmaxf(fabsf(a[q].x), fabsf(a[q].y)), fmaxf(fabsf(a[q].z), fabsf(a[q].w))));
+    }
 #pragma unroll
     for (int q = 0; q < RPG; ++q) {
+      if (max_only) break;
       const int i = grp * RPG + q;
       if (STORE_AGG && c < R && m0 + i < N)
         *reinterpret_cast<float4*>(agg + ((size_t)(m0 + i) * R + c) * D_IN + 4 * gl) = a[q];
@@ -253,6 +262,7 @@ __global__ __launch_bounds__(kThreads) void k_layer_fused(
       const int cn_ = __ffsll((long long)todo) - 1;
       if (cn_ < R) fetch_ids(cn_);
     }
+    if (max_only) continue;                      // no LDS images, no multiply
     __syncthreads();
 
     // ---- multiply: KS k-steps of this chunk ----
@@ -311,6 +321,11 @@ __global__ __launch_bounds__(kThreads) void k_layer_fused(
       }
     }
   }
+  if (max_only) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum_max = fmaxf(sum_max, __shfl_xor(sum_max, o));
+    cmax = sum_max;
+  }
   if (amax_out) rgcn_amax_publish(amax_out, cmax, seen);
 }
 
@@ -334,13 +349,15 @@ struct fused_args {
   const uint32_t* tile_mask;
   unsigned* amax_out;
   float out_scale;
+  const float* a1_amax;
+  int max_only;
 };
 
 template <int G, int TNW, int NT, int EPI, bool WIDE, bool STORE, bool WEIGHTED>
 void launch_one(const fused_args& a, hipStream_t stream) {
   k_layer_fused<G, TNW, NT, EPI, WIDE, STORE, WEIGHTED><<<(unsigned)ceil_div64(a.N, kRows), kThreads, 0, stream>>>(
       a.x, a.rowptr, a.col, a.wts, a.hub_agg, a.Fh, a.Fl, a.b_inv, a.x_amax, a.a1_mul, a.bias, a.mask, a.out, a.agg, a.N,
-      a.R, a.chunks, a.tile_mask, a.amax_out, a.out_scale);
+      a.R, a.chunks, a.tile_mask, a.amax_out, a.out_scale, a.a1_amax, a.max_only);
 }
 
 // forward (mean): EPI in {none, ReLU}, optional STORE; input gradient (weighted): EPI in {none, mask}
@@ -405,7 +422,7 @@ int rgcn_layer_bwd_input_fused(const int32_t* rowptr_t, const int32_t* col_t, co
                                const uint32_t* tile_mask_t, int64_t N, int64_t R, const float* hub_agg, const float* g,
                                const void* packed, int has_root, const float* relu_mask, int64_t d_in, int64_t d_out,
                                const float* g_amax, float gagg_amax_mul, float* grad_x, float* grad_x_amax,
-                               void* stream_, float out_scale) {
+                               void* stream_, float out_scale, float* gagg_amax) {
   if (N < 0 || !rowptr_t || !g || !packed || !g_amax || !grad_x || !(gagg_amax_mul > 0.f) || !(out_scale > 0.f))
     return RGCN_ERR_ARG;
   if (!supported(R, d_out, d_in, true)) return RGCN_ERR_UNSUPPORTED;
@@ -418,6 +435,18 @@ int rgcn_layer_bwd_input_fused(const int32_t* rowptr_t, const int32_t* col_t, co
   a.mask = relu_mask; a.out = grad_x;
   a.N = (int)N; a.R = (int)R; a.chunks = (int)R + (has_root ? 1 : 0);
   a.tile_mask = tile_mask_t; a.amax_out = reinterpret_cast<unsigned*>(grad_x_amax); a.out_scale = out_scale;
+  if (gagg_amax) {
+    // the weighted sums scaled from their own maximum: a first pass of the same kernel gathers them and publishes
+    // max |sum| only (no LDS images, no multiply); the second scales them by it - the rule of
+    // rgcn_aggregate(amax_out) -> rgcn_transform_bwd_input_split(gagg_amax, mul 1), same bits
+    fused_args m = a;
+    m.amax_out = reinterpret_cast<unsigned*>(gagg_amax);
+    m.chunks = (int)R;
+    m.max_only = 1;
+    const int rc = launch_fused<true>(m, d_out, d_in, relu_mask ? 2 : 0, (hipStream_t)stream_);
+    if (rc != RGCN_OK) return rc;
+    a.a1_amax = gagg_amax;
+  }
   return launch_fused<true>(a, d_out, d_in, relu_mask ? 2 : 0, (hipStream_t)stream_);
 }
 

@@ -13,6 +13,14 @@
 // MFMA cycles.  Elements far below the tensor's maximum keep an ABSOLUTE error of 2^-25 scaled units
 // (fp16 subnormal spacing; the MFMA honours subnormal operands - tools/split_probe.hip), i.e.
 // 2^-39 of the tensor's maximum.
+// Row-wise contract (tests/test_split_rows.py, against float64 of the same fp32 operands): with every operand scaled
+// from its own maximum, each output row of an NT kernel whose largest entry is within 2^16 of the tensor's keeps a
+// row-relative error <= max(4e-6, 2 x the exact-fp32 kernel's on the same inputs), every smaller row an absolute error
+// <= 2^-30 of the tensor's maximum, and each element of a TN output <= max(4e-6 (|A|^T|G|)_kn, 2 x fp32's).  Only a
+// scale whose maximum is within a small factor of the operand's real one keeps that: a BOUND b times too loose moves
+// every row log2(b) binades closer to the subnormal floor of the lo half: weight_bound * max|g| is ~800x the real
+// maximum of a transposed aggregate on a 200k-edge PrimeKG-shaped graph (rows 14-16 binades down: 5.4e-5), so the
+// layers scale that operand by its own maximum (rgcn_aggregate_amax; the fused input gradient's max-only pass).
 //
 // Replaces (reference call sites src/models/rgcn.py:123,128):
 //   rgcn_transform_fwd_split        out    = [agg | x]  * [W ; root] + bias              (+ ReLU)
@@ -962,6 +970,10 @@ __global__ __launch_bounds__(2 * kThreads) void k_gemm_tn_coop(const float* __re
   }
 
   RGCN_STAMP(2);
+  // The prologue stages three tiles whether or not they exist, so a workgroup whose row split has no live m-tile
+  // skips the loop with its DMAs still in flight into ring slots 0-2, which the transpose below overwrites: drain
+  // them first (free after a loop trip: its last trip already waited for vmcnt(0)).
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   const float ia = pow2f(-ea), ig = pow2f(-eg);
   float* out = slab + (size_t)split * Kc * N;
   if (kc0 + TKC <= Kc && n0 + 128 <= N) {

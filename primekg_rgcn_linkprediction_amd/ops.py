@@ -956,10 +956,14 @@ def layer_fwd_fused(graph: BucketedGraph, x: torch.Tensor, packed: SplitWeights,
 def layer_bwd_input_fused(graph: BucketedGraph, g: torch.Tensor, packed: SplitWeights,
                           relu_mask: Optional[torch.Tensor], amax: torch.Tensor,
                           amax_out: Optional[torch.Tensor] = None, inline_limit: int = 16,
-                          tail: Optional["PendingParamGrads"] = None, out_scale: float = 1.0) -> torch.Tensor:
+                          tail: Optional["PendingParamGrads"] = None, out_scale: float = 1.0,
+                          gagg_amax: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``grad_x = out_scale * [transposed-aggregate(g) | g] @ [W_r^T ; root^T]`` (``* (relu_mask > 0)``) in ONE kernel
     (``rgcn_layer_bwd_input_fused``): the weighted sums over out-edges are formed in LDS, no ``[N, R * d_out]``
-    tensor in HBM.  Bit-identical to ``aggregate(transposed=True)`` -> ``transform_bwd_input(precision="split")``.
+    tensor in HBM.  Bit-identical to ``aggregate(transposed=True)`` -> ``transform_bwd_input(precision="split")``
+    with the sums scaled by the bound ``weight_bound(True) * max |g|``; with ``gagg_amax`` (a ZEROED amax buffer) a first
+    pass of the kernel leaves ``max |sums|`` there and the sums are scaled by it - bit-identical to
+    ``aggregate(transposed=True, amax_out=gagg_amax)`` -> ``transform_bwd_input(amax=(gagg_amax, amax))``.
     ``amax``: amax buffer of ``g``; ``tail``: a pending parameter-gradient reduction that rides in the gather of
     the long segments (or is launched by itself if there is none)."""
     _need_gpu("g", g, torch.float32)
@@ -976,6 +980,7 @@ def layer_bwd_input_fused(graph: BucketedGraph, g: torch.Tensor, packed: SplitWe
     if amax is None:
         raise ValueError("amax (the amax buffer of g) is required")
     _check_amax("amax_out", amax_out, g.device)
+    _check_amax("gagg_amax", gagg_amax, g.device)
     plan = graph.fused_plan(min(int(inline_limit), d_out // 4), transposed=True)
     hub_agg = aggregate(plan.hub, g, tail=tail) if plan.hub is not None else None   # a pending slab reduction rides along
     if tail is not None and not tail.done:
@@ -991,7 +996,7 @@ def layer_bwd_input_fused(graph: BucketedGraph, g: torch.Tensor, packed: SplitWe
                                             graph.num_nodes, r, _ptr(hub_agg), _ptr(g), _ptr(packed.buf),
                                             int(packed.has_root), _ptr(relu_mask), d_in, d_out, _ptr(amax),
                                             float(graph.weight_bound(True)), _ptr(gx), _ptr(amax_out), _stream(),
-                                            float(out_scale))
+                                            float(out_scale), _ptr(gagg_amax))
         if FUSED_EVENTS is not None:
             end.record()
             FUSED_EVENTS.append(("bwd_input+mask" if relu_mask is not None else "bwd_input", graph.num_nodes,
