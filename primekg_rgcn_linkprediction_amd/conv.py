@@ -110,58 +110,97 @@ def _fused_backward(graph, g, r, d_in, d_out, g_amax, packed, precision) -> bool
             and ops.GEMM_PRECISION == "split" and ops.fused_bwd_supported(r, d_in, d_out))
 
 
-def _transform_first_applies(graph: "ops.BucketedGraph", weight: Tensor, root: Optional[Tensor], packed, precision) -> bool:
-    """does `_input_grad` take the transform-first order from the step's split weights for this layer?"""
+def _from_packed(weight: Tensor, packed, precision) -> bool:
+    """is the layer's transform-first product formed from the step's split images (``ops.transform_first``)?"""
+    return packed is not None and ops.GEMM_PRECISION == "split" and precision is None and weight.size(2) % 32 == 0
+
+
+def _transform_first(graph: "ops.BucketedGraph", weight: Tensor, root: Optional[Tensor], packed, precision) -> bool:
+    """does the layer's input gradient take the transform-first order (see _input_grad)?"""
     r, d_in, d_out = weight.shape
-    from_packed = packed is not None and ops.GEMM_PRECISION == "split" and precision is None and d_out % 32 == 0
-    return bool(from_packed and d_out >= _TRANSFORM_FIRST_RATIO * d_in and root is not None and not graph.bipartite)
+    ratio = _TRANSFORM_FIRST_RATIO if _from_packed(weight, packed, precision) else max(_TRANSFORM_FIRST_RATIO, 4.0)
+    return d_out >= ratio * d_in and root is not None and not graph.bipartite
+
+
+def _gagg_scale(graph: "ops.BucketedGraph", gagg_amax: Optional[Tensor], g_amax: Optional[Tensor]):
+    """``(amax, amax_mul)`` of the transform reading a transposed aggregate of ``g``: its OWN maximum, which its gather
+    publishes - the bound weight_bound * max |g| is hundreds of times looser on hub graphs and would cost its ordinary
+    rows that many binades of the lo half (tests/test_split_rows.py); the bound only without it (fp32: no slots)"""
+    if gagg_amax is not None:
+        return (gagg_amax, g_amax), 1.0
+    return (g_amax, g_amax), graph.weight_bound(True)
 
 
 def _input_grad(graph: "ops.BucketedGraph", g: Tensor, weight: Tensor, root: Optional[Tensor],
                 tail: Optional["ops.PendingParamGrads"] = None, g_amax: Optional[Tensor] = None,
                 scales: Optional[_Scales] = None, packed: Optional["ops.SplitWeights"] = None,
-                precision: Optional[str] = None, t_first: Optional[Tensor] = None) -> Tensor:
-    """``d loss / d x`` of one layer from ``g = d loss / d out``.
+                precision: Optional[str] = None, t_first: Optional[Tensor] = None, *,
+                relu_mask: Optional[Tensor] = None, out_scale: float = 1.0, amax_out: Optional[Tensor] = None,
+                lower=None):
+    """``d loss / d x`` of one layer (``weight``, ``root``, split images ``packed``) from ``g = d loss / d out``.
+    ``tail``: the pending slab reduction of the layer's parameter gradients (it rides in the gather launch); epilogue
+    extras (conv2 of the encoder): ``relu_mask``, ``out_scale`` (a dropout's 1 / (1 - p)), ``amax_out``; ``lower``: the
+    layer below ``(weight, root, split images)``, whose transform-first product ``T`` this layer's last launch may form:
+    the result is then ``(d loss / d x, T | None)``; ``t_first``: that product, when this is the layer below.  In order:
 
-    Default: gather first (``gagg = transposed aggregate of g``, then one GEMM with
-    K = (R+1) d_out) - the randomly read rows are d_out wide.
-    d_out >= 2 d_in (conv1 at 64 -> 128 and at hidden 256, BASELINE configs[1..2]): transform first -
-    ``T = g @ [W_r^T ... | root^T]`` is ``[N, (R+1) d_in]`` and the gather over the merged
-    structure reads d_in-wide rows (half / a quarter of the bytes per edge), adds the root
-    block as one more weighted row and writes ``grad_x`` directly.  Same flops.  Measured: the
-    step at 64 -> 256 -> 256 goes from 0.911 to 0.856 ms (round 1); at 64 -> 128 the short-K GEMM that writes
-    ``T`` cost what the narrower gather saved while it ran at the fp32 MFMA rate and split its own copy of the
-    weights - in split precision, from the step's split weights (``ops.transform_first``: their natural-order
-    image, no concatenation, no second split) the C2 step goes from 0.298 to 0.287 ms.  The fp32 and one-pass fp16
-    modes keep the threshold 4."""
+    1. transform first (no extras; d_out >= 2 d_in: conv1 at 64 -> 128 and at hidden 256, BASELINE configs[1..2]) -
+       ``T = g @ [W_r^T ... | root^T]`` is ``[N, (R+1) d_in]`` and the gather over the merged structure reads d_in-wide
+       rows (half / a quarter of the bytes per edge), adds the root block as one more weighted row and writes ``grad_x``
+       directly.  Same flops.  Measured: the step at 64 -> 256 -> 256 goes from 0.911 to 0.856 ms (round 1); at
+       64 -> 128 the short-K GEMM that writes ``T`` cost what the narrower gather saved while it ran at the fp32 MFMA
+       rate and split its own copy of the weights - in split precision, from the step's split weights
+       (``ops.transform_first``: their natural-order image, no concatenation, no second split) the C2 step goes from
+       0.298 to 0.287 ms.  The fp32 and one-pass fp16 modes keep the threshold 4;
+    2. the one-kernel input gradient (``_fused_backward``);
+    3. gather first - ``gagg``, then one GEMM with K = (R+1) d_out (the randomly read rows are d_out wide), which also
+       forms the ``T`` of ``lower`` from its own tiles where that layer goes transform first
+       (``ops.transform_bwd_input_chain``: one launch less, no re-read of the result).
+
+    The transposed aggregate is scaled by its own maximum (``_gagg_scale``), which its gather - or the fused kernel's
+    first pass - publishes into a slot of ``scales``.  No hub deferral: the maximum must be final."""
     r, d_in, d_out = weight.shape
-    from_packed = packed is not None and ops.GEMM_PRECISION == "split" and precision is None and d_out % 32 == 0
-    ratio = _TRANSFORM_FIRST_RATIO if from_packed else max(_TRANSFORM_FIRST_RATIO, 4.0)
+    extras = relu_mask is not None or amax_out is not None or out_scale != 1.0
     merged = (graph.merged_transposed()
-              if (d_out >= ratio * d_in and root is not None and not graph.bipartite) else None)
-    # `tail`: the pending slab reduction of this layer's parameter gradients rides in the gather launch
-    if merged is None:
-        # the transposed aggregate is scaled from its OWN maximum, which its gather (or the fused kernel's first pass)
-        # leaves: the bound weight_bound * max |g| is hundreds of times looser on hub graphs and would cost its ordinary
-        # rows that many binades of the lo half (tests/test_split_rows.py).  No hub deferral: the maximum must be final.
-        gagg_amax = scales.slot() if (scales is not None and g_amax is not None) else None
-        if _fused_backward(graph, g, r, d_in, d_out, g_amax, packed, precision):
-            return ops.layer_bwd_input_fused(graph, g, packed, None, g_amax, inline_limit=_EVAL_INLINE_LIMIT, tail=tail,
-                                             gagg_amax=gagg_amax)
-        gagg = ops.aggregate(graph, g, transposed=True, tail=tail, amax_out=gagg_amax)   # autograd of A3 + A4 (fp32 grads)
-        # without a slot (fp32 mode): |gagg| <= (largest sum of 1/cnt weights over a node's out-edges of one relation) * max |g|
-        a1, mul = (gagg_amax, 1.0) if gagg_amax is not None else (g_amax, graph.weight_bound(True))
-        return ops.transform_bwd_input(gagg, g, weight, root, graph=graph, amax=(a1, g_amax), amax_mul=mul, packed=packed,
-                                       precision=precision)                              # autograd of A6 wrt x
-    if t_first is not None:
-        t = t_first                              # (already formed behind conv2's input gradient: ops.transform_bwd_input_chain)
-    elif from_packed:
-        t = ops.transform_first(g.contiguous(), packed, g_amax)                   # from the step's split weights: no cat, no second split
+              if not extras and _transform_first(graph, weight, root, packed, precision) else None)
+    t = None                                     # the lower layer's T, when this launch forms it
+    if merged is not None:
+        if t_first is None and _from_packed(weight, packed, precision):
+            t_first = ops.transform_first(g.contiguous(), packed, g_amax)
+        elif t_first is None:
+            ops.guard_torch_op("weight concatenation of the transform-first input gradient")
+            wcat = torch.cat([weight.reshape(r * d_in, d_out), root]).view(1, (r + 1) * d_in, d_out)
+            t_first = ops.transform_bwd_input(g, g, wcat, None, amax=(g_amax, None), precision=precision)  # g @ wcat^T
+        gx = ops.aggregate(merged, t_first.view(-1, d_in), tail=tail)
     else:
-        ops.guard_torch_op("weight concatenation of the transform-first input gradient")
-        wcat = torch.cat([weight.reshape(r * d_in, d_out), root]).view(1, (r + 1) * d_in, d_out)
-        t = ops.transform_bwd_input(g, g, wcat, None, amax=(g_amax, None), precision=precision)   # [N, (R+1) d_in] = g @ wcat^T
-    return ops.aggregate(merged, t.view(-1, d_in), tail=tail)
+        gagg_amax = scales.slot() if scales is not None else None
+        if _fused_backward(graph, g, r, d_in, d_out, g_amax, packed, precision):
+            gx = ops.layer_bwd_input_fused(graph, g, packed, relu_mask, g_amax, amax_out=amax_out, tail=tail,
+                                           inline_limit=_EVAL_INLINE_LIMIT, out_scale=out_scale, gagg_amax=gagg_amax)
+        else:
+            gagg = ops.aggregate(graph, g, transposed=True, tail=tail, amax_out=gagg_amax)   # autograd of A3 + A4
+            amax, mul = _gagg_scale(graph, gagg_amax, g_amax)
+            if (lower is not None and packed is not None and g_amax is not None
+                    and _from_packed(lower[0], lower[2], precision) and _transform_first(graph, *lower, precision)
+                    and ops.chain_supported(weight, lower[0])):
+                gx, t = ops.transform_bwd_input_chain(gagg, g, weight, root, relu_mask, packed, lower[2], graph=graph,
+                                                      amax=amax, amax_mul=mul, amax_out=amax_out, out_scale=out_scale)
+            else:
+                gx = ops.transform_bwd_input(gagg, g, weight, root, relu_mask=relu_mask, graph=graph, amax=amax,
+                                             amax_mul=mul, amax_out=amax_out, packed=packed, precision=precision,
+                                             out_scale=out_scale)                   # autograd of A6 wrt x
+    return (gx, t) if lower is not None else gx
+
+
+def _backward_scales(g: Tensor, layers: int) -> _Scales:
+    """the operand scales of a backward pass through ``layers`` stacked layers, two per layer: the maximum of the gradient
+    it receives (max |g|, or the ``amax_out`` of the layer above) and the slot ``_input_grad`` takes for its aggregate"""
+    return _Scales(g, slots=2 * layers)
+
+
+def _deferred_params(graph: "ops.BucketedGraph", agg, x, g, x_amax, g_amax, has_root: bool, has_bias: bool, prec):
+    """a layer's parameter gradients, their slab reduction left pending: it rides in the gather that follows"""
+    return ops.transform_bwd_params(agg, x, g, graph.num_relations, want_root=has_root, want_bias=has_bias, graph=graph,
+                                    defer=True, amax=(x_amax, x_amax, g_amax), precision=prec)
 
 
 # Training forward of one layer: gather -> transform (two launches, the aggregate written by one and read by the
@@ -184,7 +223,6 @@ def _defer_hubs(half: bool, packed, amax, k: int, n_out: int) -> bool:
 
 
 _DEFER_HUBS = True
-_CHAIN = True          # conv1's transform-first product chained behind conv2's input-gradient GEMM (ops.transform_bwd_input_chain)
 
 
 def _train_fused(graph, n, r, d_in, d_out, half) -> bool:
@@ -230,25 +268,27 @@ def _conv_forward(x, weight, root, bias, *, graph, relu, gather_dtype, half):
 def _conv_backward(x, agg, weight, root, x_amax, pkbuf, g, *, graph, has_root, has_bias, need_x, need_p, prec):
     """one layer's backward as a pass -> (gx | None, gw | None, groot | None, gbias | None)"""
     packed = _packs([pkbuf], [(weight, root)])[0]
-    scales = _Scales(g, slots=2)                # max |g|; max |transposed aggregate of g|
-    g_amax = scales.first
-    pending = None
-    if need_p:
-        pending = ops.transform_bwd_params(agg, x, g, graph.num_relations, want_root=has_root, want_bias=has_bias,
-                                           graph=graph, defer=True, amax=(x_amax, x_amax, g_amax), precision=prec)
-    gx = None
-    if need_x:
-        gx = _input_grad(graph, g, weight, root, tail=pending, g_amax=g_amax, scales=scales, packed=packed,
-                         precision=prec)
-    gw = groot = gbias = None
-    if pending is not None:
-        pending.finish()                                                # no gather took it along
-        gw, groot, gbias = pending.grads
-    return gx, gw, groot, gbias
+    scales = _backward_scales(g, 1)
+    pending = _deferred_params(graph, agg, x, g, x_amax, scales.first, has_root, has_bias, prec) if need_p else None
+    gx = _input_grad(graph, g, weight, root, pending, scales.first, scales, packed, prec) if need_x else None
+    if pending is None:
+        return gx, None, None, None
+    pending.finish()                                                    # no gather took it along
+    return (gx, *pending.grads)
 
 
 _R_CONV_FORWARD = ops.Region("conv.forward", _conv_forward)
 _R_CONV_BACKWARD = ops.Region("conv.backward", _conv_backward)
+
+
+def _contiguous(*tensors):
+    return tuple(t.contiguous() if t is not None else None for t in tensors)
+
+
+def _bwd_precision(gather_dtype, half_backward: bool) -> Optional[str]:
+    """configs[4] backward: with the fp16 feature table the three gradient GEMMs per layer run as ONE fp16 pass (operands
+    rounded under per-tensor power-of-two scales = loss scaling per tensor, fp32 accumulate); gathers stay fp32"""
+    return "half" if (gather_dtype == torch.float16 and half_backward and ops.GEMM_PRECISION == "split") else None
 
 
 class _RGCNConvFunction(torch.autograd.Function):
@@ -262,27 +302,24 @@ class _RGCNConvFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: Tensor, weight: Tensor, root: Optional[Tensor], bias: Optional[Tensor],
                 graph: ops.BucketedGraph, relu: bool = False, gather_dtype=None, half_backward: bool = False) -> Tensor:
-        x = x.contiguous()
-        weight = weight.contiguous()
-        root_c = root.contiguous() if root is not None else None
-        bias_c = bias.contiguous() if bias is not None else None
-        half = gather_dtype == torch.float16
-        ctx.bwd_precision = "half" if (half and half_backward and ops.GEMM_PRECISION == "split") else None
+        x, weight, root, bias = _contiguous(x, weight, root, bias)
+        ctx.bwd_precision = _bwd_precision(gather_dtype, half_backward)
         key = (tuple(x.shape), tuple(weight.shape), root is not None, bias is not None, gather_dtype, bool(relu),
                _policy_key())
-        out, agg, x_amax, pkbuf = _R_CONV_FORWARD.run(graph, key, (x, weight, root_c, bias_c),
-                                                      dict(graph=graph, relu=relu, gather_dtype=gather_dtype, half=half),
-                                                      want={0})
+        out, agg, x_amax, pkbuf = _R_CONV_FORWARD.run(graph, key, (x, weight, root, bias),
+                                                      dict(graph=graph, relu=relu, gather_dtype=gather_dtype,
+                                                           half=gather_dtype == torch.float16), want={0})
         ctx.graph, ctx.relu, ctx.key = graph, relu, key
         ctx.has_root, ctx.has_bias = root is not None, bias is not None
-        ctx.save_for_backward(x, weight, root_c)             # the node's inputs (autograd checks their versions)
-        ctx.kept = (agg, x_amax, pkbuf, out if relu else None)   # tensors, or arena offsets of a replayed pass
+        # the node's inputs and, for the ReLU backward, its output (autograd checks their versions)
+        ctx.save_for_backward(x, weight, root, out if relu else None)
+        ctx.kept = (agg, x_amax, pkbuf)                      # tensors, or arena offsets of a replayed pass
         return out
 
     @staticmethod
     def backward(ctx, g: Tensor):
-        x, weight, root = ctx.saved_tensors
-        agg, x_amax, pkbuf, out = ctx.kept
+        x, weight, root, out = ctx.saved_tensors
+        agg, x_amax, pkbuf = ctx.kept
         if ctx.relu:
             g = g * (out > 0)                                               # ReLU backward (a torch op, outside the pass)
         g = g.contiguous()
@@ -326,46 +363,23 @@ def _enc2_forward(x, w1, root1, b1, w2, root2, b2, xa=None, w1a=None, r1a=None, 
 def _enc2_backward(x, agg1, h, agg2, w1, root1, w2, root2, x_amax, h_amax, pk1buf, pk2buf, g, *, graph, flags, p,
                    prec, need_x):
     """the whole backward of conv1 -> ReLU -> [dropout p] -> conv2 -> (gx | None, gw1, groot1, gb1, gw2, groot2, gb2)"""
-    r = graph.num_relations
     has_root1, has_b1, has_root2, has_b2 = flags
-    t_first = None
     pk1, pk2 = _packs([pk1buf, pk2buf], [(w1, root1), (w2, root2)])
-    scales = _Scales(g, slots=4)         # max |g|, |gz|, |transposed aggregate of g| and (gather-first conv1) of gz
-    g_amax, gz_amax, gagg2_amax = scales.first, scales.slot(), scales.slot()
-    wb = graph.weight_bound(True)        # |transposed aggregate| <= wb * max |gradient table|
+    scales = _backward_scales(g, 2)
+    g_amax, gz_amax = scales.first, scales.slot()
     # the slab reductions of the parameter gradients ride in the transposed gathers that follow them
-    red2 = ops.transform_bwd_params(agg2, h, g, r, want_root=has_root2, want_bias=has_b2, graph=graph,
-                                    defer=True, amax=(h_amax, h_amax, g_amax), precision=prec)
-    # dropout backward: the factor 1 / (1 - p) goes into the input-gradient epilogue as a scalar (the mask is h itself,
-    # positive exactly where a unit is active and kept) - the weights keep their split images
-    scale = 1.0 / (1.0 - p) if p > 0 else 1.0
-    # conv2's transposed aggregate is scaled from its own maximum (see _input_grad); wb only in fp32 mode (no slots)
-    a1, mul = (gagg2_amax, 1.0) if gagg2_amax is not None else (g_amax, wb)
-    if _fused_backward(graph, g, r, w2.size(1), w2.size(2), g_amax, pk2, prec):
-        gz = ops.layer_bwd_input_fused(graph, g, pk2, h, g_amax, amax_out=gz_amax, inline_limit=_EVAL_INLINE_LIMIT,
-                                       tail=red2, out_scale=scale, gagg_amax=gagg2_amax)
-    else:
-        gagg2 = ops.aggregate(graph, g, transposed=True, tail=red2, amax_out=gagg2_amax)
-        # conv1's input gradient is transform-first (T = gz [W1_r^T | root1^T], then one gather): T is formed by the SAME
-        # launch that forms gz, from the workgroup's own tile of it (round 4: one launch less, no re-read of gz)
-        if (_CHAIN and need_x and prec is None and pk1 is not None and pk2 is not None and g_amax is not None
-                and _transform_first_applies(graph, w1, root1, pk1, prec) and ops.chain_supported(w2, w1)):
-            gz, t_first = ops.transform_bwd_input_chain(gagg2, g, w2, root2, h, pk2, pk1, graph=graph, amax=(a1, g_amax),
-                                                        amax_mul=mul, amax_out=gz_amax, out_scale=scale)
-        else:
-            gz = ops.transform_bwd_input(gagg2, g, w2, root2, relu_mask=h, graph=graph, amax=(a1, g_amax),
-                                         amax_mul=mul, amax_out=gz_amax, packed=pk2, precision=prec,
-                                         out_scale=scale)   # d loss / d (pre-ReLU of conv1)
-    red1 = ops.transform_bwd_params(agg1, x, gz, r, want_root=has_root1, want_bias=has_b1, graph=graph,
-                                    defer=True, amax=(x_amax, x_amax, gz_amax), precision=prec)
-    gx = None
-    if need_x:
-        gx = _input_grad(graph, gz, w1, root1, tail=red1, g_amax=gz_amax, scales=scales, packed=pk1, precision=prec,
-                         t_first=t_first)
+    red2 = _deferred_params(graph, agg2, h, g, h_amax, g_amax, has_root2, has_b2, prec)
+    # gz = d loss / d (pre-ReLU of conv1): ReLU mask h (positive exactly where a unit is active and kept), the dropout
+    # factor 1 / (1 - p) one more epilogue scalar; where conv1's gradient is wanted, the launch may form its T too
+    gz = _input_grad(graph, g, w2, root2, red2, g_amax, scales, pk2, prec, relu_mask=h,
+                     out_scale=1.0 / (1.0 - p) if p > 0 else 1.0, amax_out=gz_amax,
+                     lower=(w1, root1, pk1) if need_x else None)
+    gz, t_first = gz if need_x else (gz, None)
+    red1 = _deferred_params(graph, agg1, x, gz, x_amax, gz_amax, has_root1, has_b1, prec)
+    gx = _input_grad(graph, gz, w1, root1, red1, gz_amax, scales, pk1, prec, t_first) if need_x else None
     red2.finish()
     red1.finish()
-    (gw2, groot2, gb2), (gw1, groot1, gb1) = red2.grads, red1.grads
-    return gx, gw1, groot1, gb1, gw2, groot2, gb2
+    return (gx, *red1.grads, *red2.grads)
 
 
 _R_LAYER1 = ops.Region("encoder2.layer1", _enc2_layer1)
@@ -375,7 +389,44 @@ _R_BACKWARD = ops.Region("encoder2.backward", _enc2_backward)
 
 
 def _policy_key():
-    return (_TRAIN_FUSED, _DEFER_HUBS, _TRANSFORM_FIRST_RATIO, _EVAL_INLINE_LIMIT, _TRAIN_FUSED_MIN_BYTES, _CHAIN)
+    return (_TRAIN_FUSED, _DEFER_HUBS, _TRANSFORM_FIRST_RATIO, _EVAL_INLINE_LIMIT, _TRAIN_FUSED_MIN_BYTES)
+
+
+def _enc2_train_forward(graph, params, gather_dtype, half_backward: bool, hints, p: float = 0.0):
+    """The forward of both training routes into the encoder (``_Encoder2Function``, ``rgcn_encoder2_step``): ``params``
+    = (x, w1, root1, b1, w2, root2, b2) -> (out, ``params`` made contiguous, the state ``_enc2_train_backward`` takes).
+    ``hints``: the maxima of x, w1, root1, w2, root2 the optimizer left (``_encoder_hints``).  One key: one plan."""
+    x, w1, root1, b1, w2, root2, b2 = params = _contiguous(*params)
+    hinted = hints is not None and ops.GEMM_PRECISION == "split"
+    hint_list = list(hints) if hinted else []
+    key = (tuple(x.shape), tuple(w1.shape), tuple(w2.shape), root1 is not None, b1 is not None, root2 is not None,
+           b2 is not None, gather_dtype, hinted, _policy_key())
+    static = dict(graph=graph, gather_dtype=gather_dtype, half=gather_dtype == torch.float16)
+    # A dense tensor's maximum is left behind by the launch that produces it (the first launch of the pass
+    # for x - or the optimizer step that wrote x -, the epilogue of conv1's transform for h); an aggregate is scaled
+    # by the bound its table's maximum gives (a mean of rows cannot exceed it), so the gathers publish nothing.
+    if p > 0:
+        h, agg1, x_amax, h_amax, pk1buf, pk2buf = _R_LAYER1.run(graph, key, [x, w1, root1, b1, w2, root2] + hint_list,
+                                                                static, want={0, 3})
+        h = torch.native_dropout(h, p, True)[0]
+        h_amax = ops.materialize(h_amax) * (1.0 / (1.0 - p)) if h_amax is not None else None   # kept units are scaled up
+        out, agg2 = _R_LAYER2.run(graph, key, (h, w2, root2, b2, h_amax, pk2buf), static, want={0})
+    else:
+        out, h, agg1, agg2, x_amax, h_amax, pk1buf, pk2buf = _R_FORWARD.run(graph, key, list(params) + hint_list, static,
+                                                                            want={0})
+    flags = (root1 is not None, b1 is not None, root2 is not None, b2 is not None)
+    kept = (agg1, h, agg2, x_amax, h_amax, pk1buf, pk2buf)      # tensors, or arena offsets of a replayed pass
+    return out, params, (graph, key, flags, p, _bwd_precision(gather_dtype, half_backward), kept)
+
+
+def _enc2_train_backward(state, inputs, g: Tensor, need_x: bool):
+    """the backward pass of both routes; ``inputs`` = (x, w1, root1, w2, root2) as ``_enc2_train_forward`` made them
+    -> (gx | None, gw1, groot1, gb1, gw2, groot2, gb2)"""
+    graph, key, flags, p, prec, (agg1, h, agg2, x_amax, h_amax, pk1buf, pk2buf) = state
+    x, w1, root1, w2, root2 = inputs
+    return _R_BACKWARD.run(graph, (key, p, need_x, prec),
+                           (x, agg1, h, agg2, w1, root1, w2, root2, x_amax, h_amax, pk1buf, pk2buf, g.contiguous()),
+                           dict(graph=graph, flags=flags, p=p, prec=prec, need_x=need_x), want={0, 1, 2, 3, 4, 5, 6})
 
 
 class _Encoder2Function(torch.autograd.Function):
@@ -397,50 +448,15 @@ class _Encoder2Function(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, root1, b1, w2, root2, b2, graph, gather_dtype=None, p: float = 0.0,
                 half_backward: bool = False, hints=None):
-        x, w1, w2 = x.contiguous(), w1.contiguous(), w2.contiguous()
-        root1 = root1.contiguous() if root1 is not None else None
-        root2 = root2.contiguous() if root2 is not None else None
-        b1 = b1.contiguous() if b1 is not None else None
-        b2 = b2.contiguous() if b2 is not None else None
-        half = gather_dtype == torch.float16          # configs[4]: fp16 operands on the fp16 matrix cores too
-        # configs[4] backward: the three gradient GEMMs per layer in ONE fp16 pass (operands rounded under their
-        # per-tensor power-of-two scales = loss scaling per tensor, fp32 accumulate); the gradient gathers stay fp32
-        ctx.bwd_precision = "half" if (half and half_backward and ops.GEMM_PRECISION == "split") else None
-        static = dict(graph=graph, gather_dtype=gather_dtype, half=half)
-        hinted = hints is not None and ops.GEMM_PRECISION == "split"
-        hint_list = list(hints) if hinted else []     # maxima of x, w1, root1, w2, root2 left by the optimizer
-        key = (tuple(x.shape), tuple(w1.shape), tuple(w2.shape), root1 is not None, b1 is not None, root2 is not None,
-               b2 is not None, gather_dtype, hinted, _policy_key())
-        # A dense tensor's maximum is left behind by the launch that produces it (the first launch of the pass
-        # for x - or the optimizer step that wrote x -, the epilogue of conv1's transform for h); an aggregate is scaled
-        # by the bound its table's maximum gives (a mean of rows cannot exceed it), so the gathers publish nothing.
-        if p > 0:
-            h, agg1, x_amax, h_amax, pk1buf, pk2buf = _R_LAYER1.run(graph, key, [x, w1, root1, b1, w2, root2] + hint_list,
-                                                                    static, want={0, 3})
-            h = torch.native_dropout(h, p, True)[0]
-            h_amax = ops.materialize(h_amax) * (1.0 / (1.0 - p)) if h_amax is not None else None   # kept units are scaled up
-            out, agg2 = _R_LAYER2.run(graph, key, (h, w2, root2, b2, h_amax, pk2buf), static, want={0})
-        else:
-            out, h, agg1, agg2, x_amax, h_amax, pk1buf, pk2buf = _R_FORWARD.run(
-                graph, key, [x, w1, root1, b1, w2, root2, b2] + hint_list, static, want={0})
-        ctx.graph, ctx.p, ctx.key = graph, p, key
-        ctx.flags = (root1 is not None, b1 is not None, root2 is not None, b2 is not None)
+        out, (x, w1, root1, _, w2, root2, _), ctx.state = _enc2_train_forward(
+            graph, (x, w1, root1, b1, w2, root2, b2), gather_dtype, half_backward, hints, p)
         ctx.save_for_backward(x, w1, root1, w2, root2)           # the node's inputs (autograd checks their versions)
-        ctx.kept = (agg1, h, agg2, x_amax, h_amax, pk1buf, pk2buf)   # tensors, or arena offsets of a replayed pass
         return out
 
     @staticmethod
     def backward(ctx, g):
-        x, w1, root1, w2, root2 = ctx.saved_tensors
-        agg1, h, agg2, x_amax, h_amax, pk1buf, pk2buf = ctx.kept
-        g = g.contiguous()
-        need_x = bool(ctx.needs_input_grad[0])
-        static = dict(graph=ctx.graph, flags=ctx.flags, p=ctx.p, prec=ctx.bwd_precision, need_x=need_x)
-        grads = _R_BACKWARD.run(ctx.graph, (ctx.key, ctx.p, need_x, ctx.bwd_precision),
-                                (x, agg1, h, agg2, w1, root1, w2, root2, x_amax, h_amax, pk1buf, pk2buf, g), static,
-                                want={0, 1, 2, 3, 4, 5, 6})
-        gx, gw1, groot1, gb1, gw2, groot2, gb2 = grads
-        return gx, gw1, groot1, gb1, gw2, groot2, gb2, None, None, None, None, None
+        grads = _enc2_train_backward(ctx.state, ctx.saved_tensors, g, bool(ctx.needs_input_grad[0]))
+        return (*grads, None, None, None, None, None)
 
 
 # No-grad encoder (``DrugDiseaseModel.get_embeddings / predict / predict_all_tails``, ``Trainer.validate``,
@@ -513,11 +529,7 @@ def encoder2_eval(x: Tensor, graph: "ops.BucketedGraph", w1, root1, b1, w2, root
     """conv2(relu(conv1(x))) with nothing kept for a backward and no whole-graph aggregate (see above); a Region:
     one native call per forward once recorded (``Trainer.validate`` re-runs it for every validation batch,
     src/train.py:389-395)"""
-    x, w1, w2 = x.contiguous(), w1.contiguous(), w2.contiguous()
-    root1 = root1.contiguous() if root1 is not None else None
-    root2 = root2.contiguous() if root2 is not None else None
-    b1 = b1.contiguous() if b1 is not None else None
-    b2 = b2.contiguous() if b2 is not None else None
+    x, w1, root1, b1, w2, root2, b2 = _contiguous(x, w1, root1, b1, w2, root2, b2)
     key = (tuple(x.shape), tuple(w1.shape), tuple(w2.shape), root1 is not None, b1 is not None, root2 is not None,
            b2 is not None, gather_dtype, _EVAL_FUSED, _EVAL_BLOCK_BYTES, _EVAL_INLINE_LIMIT)
     return _R_EVAL.run(graph, key, (x, w1, root1, b1, w2, root2, b2), dict(graph=graph, gather_dtype=gather_dtype), want={0})[0]
@@ -603,27 +615,13 @@ def rgcn_encoder2_step(x: Tensor, edge_index: Tensor, edge_type: Tensor, conv1: 
     _check_x(x)
     graph = ops.bucket(edge_index, edge_type, x.size(0), conv1.num_relations)
     basis1, basis2 = conv1.num_bases is not None, conv2.num_bases is not None
-    w1 = (ops.basis_compose(conv1.comp.contiguous(), conv1.weight.contiguous()) if basis1 else conv1.weight).contiguous()
-    w2 = (ops.basis_compose(conv2.comp.contiguous(), conv2.weight.contiguous()) if basis2 else conv2.weight).contiguous()
-    root1, b1, root2, b2 = conv1.root, conv1.bias, conv2.root, conv2.bias
-    x = x.contiguous()
-    gather_dtype = conv1.gather_dtype
-    half = gather_dtype == torch.float16
-    prec = "half" if (half and conv1.half_backward and ops.GEMM_PRECISION == "split") else None
-    key = (tuple(x.shape), tuple(w1.shape), tuple(w2.shape), root1 is not None, b1 is not None, root2 is not None,
-           b2 is not None, gather_dtype, _policy_key())
-    hints = None if (basis1 or basis2) else _encoder_hints(x, conv1, conv2)
-    hinted = hints is not None
-    key = key[:-1] + (hinted, key[-1])
-    out, h, agg1, agg2, x_amax, h_amax, pk1buf, pk2buf = _R_FORWARD.run(
-        graph, key, [x, w1, root1, b1, w2, root2, b2] + (list(hints) if hinted else []),
-        dict(graph=graph, gather_dtype=gather_dtype, half=half), want={0})
-    need_x = bool(need_input_grad)
-    flags = (root1 is not None, b1 is not None, root2 is not None, b2 is not None)
-    static = dict(graph=graph, flags=flags, p=0.0, prec=prec, need_x=need_x)
-    gx, gw1, groot1, gb1, gw2, groot2, gb2 = _R_BACKWARD.run(
-        graph, (key, 0.0, need_x, prec), (x, agg1, h, agg2, w1, root1, w2, root2, x_amax, h_amax, pk1buf, pk2buf,
-                                          cotangent.contiguous()), static, want={0, 1, 2, 3, 4, 5, 6})
+    w1 = ops.basis_compose(conv1.comp.contiguous(), conv1.weight.contiguous()) if basis1 else conv1.weight
+    w2 = ops.basis_compose(conv2.comp.contiguous(), conv2.weight.contiguous()) if basis2 else conv2.weight
+    out, (x, w1, root1, _, w2, root2, _), state = _enc2_train_forward(
+        graph, (x, w1, conv1.root, conv1.bias, w2, conv2.root, conv2.bias), conv1.gather_dtype, conv1.half_backward,
+        _encoder_hints(x, conv1, conv2))
+    gx, gw1, groot1, gb1, gw2, groot2, gb2 = _enc2_train_backward(state, (x, w1, root1, w2, root2), cotangent,
+                                                                  bool(need_input_grad))
     for conv, gw, groot, gb, basis in ((conv1, gw1, groot1, gb1, basis1), (conv2, gw2, groot2, gb2, basis2)):
         if basis:
             gcomp, gbasis = ops.basis_compose_bwd(gw, conv.comp.contiguous(), conv.weight.contiguous(),

@@ -68,12 +68,12 @@ class HipBackend:
     kernels shrink with 1 / N while the host cost of issuing them does not."""
 
     def __init__(self):
-        from . import ops
-        self.ops = ops
+        from . import conv, ops
+        self.ops, self.conv = ops, conv
         self._fwd = ops.Region("dist.layer_fwd", self._fwd_pass)
         self._fwd_rows = ops.Region("dist.layer_fwd_rows", self._fwd_rows_pass)
         self._bwd = ops.Region("dist.input_grad", self._bwd_pass)
-        self._bwd_rows = ops.Region("dist.input_grad_rows", self._bwd_rows_pass)
+        self._bwd_rows = ops.Region("dist.input_grad_rows", self._bwd_pass)
 
     def make_shard(self, key, other, etype, n_key, n_other, num_relations, edge_weight=None):
         return self.ops.BucketedGraph.from_shard(key, other, etype, n_key, n_other, num_relations,
@@ -82,24 +82,24 @@ class HipBackend:
     def aggregate(self, shard, x, out=None):
         return self.ops.aggregate(shard, x, out=out)
 
-    def _amax(self, table, shard):
-        """operand scales of the split-precision transforms: the aggregate is bounded by
-        (largest per-segment weight sum) * max |table it was gathered from|; the rank's own rows are
-        part of that table, so its maximum serves both operands - one launch, no collective"""
-        if table is None or self.ops.GEMM_PRECISION != "split":
-            return None, 1.0
-        t = self.ops.absmax(table)
-        return (t, t), (shard.weight_bound(False) if shard is not None else 1.0)
+    def _amax(self, table):
+        """max |table| in split precision (else None): the rank's own rows are part of the table an aggregate was
+        gathered from, so this one maximum scales the dense operand too - one launch, no collective"""
+        return self.ops.absmax(table) if table is not None and self.ops.GEMM_PRECISION == "split" else None
 
     # `shard` = the structure the aggregate operand was built over (its relation-occupancy mask
     # lets the kernels skip all-zero tiles), `table` = the rows it was gathered from; backends
     # without these notions ignore them
     def transform_fwd(self, agg, x, weight, root, bias, relu=False, shard=None, table=None, out=None):
-        amax, mul = self._amax(table, shard)
-        return self.ops.transform_fwd(agg, x, weight, root, bias, relu, shard, amax=amax, amax_mul=mul, out=out)
+        t = self._amax(table)                   # |agg| <= (largest per-segment weight sum) * max |table|
+        mul = shard.weight_bound(False) if t is not None and shard is not None else 1.0
+        return self.ops.transform_fwd(agg, x, weight, root, bias, relu, shard, amax=(t, t) if t is not None else None,
+                                      amax_mul=mul, out=out)
 
     def transform_bwd_input(self, gagg, g, weight, root, relu_mask=None, shard=None, table=None, out=None):
-        amax, mul = self._amax(table, shard)
+        """``gagg`` is finished: its own maximum is the one its gather would have published (the bits of input_grad)"""
+        t = self._amax(table)
+        amax, mul = self.conv._gagg_scale(shard, self.ops.absmax(gagg) if t is not None else None, t)
         gx = self.ops.transform_bwd_input(gagg, g, weight, root, relu_mask, shard, amax=amax, amax_mul=mul)
         if out is None:
             return gx
@@ -121,14 +121,15 @@ class HipBackend:
         self.transform_fwd(agg[lo:hi], x[lo:hi], weight, root, bias, relu, shard, table=tbl, out=out[lo:hi])
         return ()
 
-    def _bwd_pass(self, tbl, g, weight, root, mask, *, shard):
-        gagg = self.ops.aggregate(shard, tbl)
-        return (self.transform_bwd_input(gagg, g, weight, root, mask, shard, table=tbl),)
-
-    def _bwd_rows_pass(self, tbl, g, weight, root, mask, gagg, *, shard, lo, hi):
-        self.ops.aggregate(shard, tbl, out=gagg[lo:hi])
+    def _bwd_pass(self, tbl, g, weight, root, mask, gagg=None, *, shard, lo=0, hi=None):
+        """rows [lo, hi) of the input gradient (their aggregate into the caller's `gagg`, if given), the aggregate scaled
+        by its own maximum: the gather publishes it into a slot that the launch taking max |tbl| clears (conv._Scales)"""
+        scales = self.conv._Scales(tbl, slots=2)
+        slot = scales.slot()
+        gagg = self.ops.aggregate(shard, tbl, amax_out=slot, out=gagg[lo:hi] if gagg is not None else None)
+        amax, mul = self.conv._gagg_scale(shard, slot, scales.first)
         m = mask[lo:hi] if mask is not None else None
-        return (self.transform_bwd_input(gagg[lo:hi], g[lo:hi], weight, root, m, shard, table=tbl),)
+        return (self.ops.transform_bwd_input(gagg, g[lo:hi], weight, root, m, shard, amax=amax, amax_mul=mul),)
 
     @staticmethod
     def _key(*tensors, extra=()):

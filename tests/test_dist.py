@@ -537,9 +537,10 @@ def test_config_c4_node_partitioned_over_8_ranks_at_full_size(precision, monkeyp
     out1 = ops.transform_fwd(agg1, x, w, root, bias, amax=amax_x)
     gw1, groot1, gbias1 = ops.transform_bwd_params(agg1, x, g, r, graph=graph)
     del agg1
-    amax_g = (ops.absmax(g),) * 2 if precision == "split" else None
-    gagg1 = ops.aggregate(graph, g, transposed=True)
-    gx1 = ops.transform_bwd_input(gagg1, g, w, root, amax=amax_g, amax_mul=graph.weight_bound(True))
+    # the transposed aggregate scaled by the maximum its gather publishes, as the layers and the shards scale it
+    gagg_amax = ops.amax_buffer(dev)[0] if precision == "split" else None
+    gagg1 = ops.aggregate(graph, g, transposed=True, amax_out=gagg_amax)
+    gx1 = ops.transform_bwd_input(gagg1, g, w, root, amax=(gagg_amax, ops.absmax(g)) if precision == "split" else None)
     del gagg1
     graph.destroy()
     torch.cuda.synchronize()

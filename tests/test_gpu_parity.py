@@ -450,6 +450,25 @@ def test_layer_no_root_no_bias_and_frozen_input():
     assert_grad(conv.weight.grad, wr.grad)
 
 
+def test_fused_relu_layer_output_is_freed_without_the_cycle_collector():
+    """``activation='relu'`` keeps the layer's output for the ReLU backward through ``save_for_backward``: no reference
+    cycle out -> grad_fn -> ctx -> out, so the output (and its aggregate) is freed as soon as nothing refers to it"""
+    import gc
+    import weakref
+    dev = need_gpu()
+    ei, et, n, r = synth.uniform_graph(200, 3000, 4, seed=9)
+    x = torch.randn(n, 32, device=dev, requires_grad=True)
+    w = torch.randn(r, 32, 16, device=dev) * 0.1
+    gc.disable()
+    try:
+        out = rgcn_conv(x, ei.to(dev), et.to(dev), w, None, None, r, activation="relu")
+        ref = weakref.ref(out)
+        del out
+        assert ref() is None
+    finally:
+        gc.enable()
+
+
 # ------------------------------------------------------------------ model + head vs reference-run vectors
 def _load_ref_model(z, dev, **kw):
     sd = {k[4:].replace("__", "."): v for k, v in z.items() if k.startswith("sd__")}

@@ -410,9 +410,30 @@ def _cotangent(n, d, seed):
     return c.float()
 
 
-@pytest.mark.parametrize("mode", ["plain", "fused"])
+def _shard_input_grads(ei, et, n, r, w, root, cot, dev):
+    """grad_x of a two-rank partition through dist.HipBackend, each rank's halo exchange emulated from the full
+    cotangent: -> [(form, grad_x in node order)] for the one-pass shards and the interior / boundary halves"""
+    from types import SimpleNamespace
+    from primekg_rgcn_linkprediction_amd import dist as rdist
+    backend = rdist.HipBackend()
+    part = rdist.NodePartition(ei, n, 2)
+    results = []
+    for split in (False, True):
+        rows = []
+        for k in range(2):
+            shard = rdist.RankShard(part, ei, et, r, k, dev, backend, split=split)
+            assert shard.split == split
+            g_own = part.shard_rows(cot, k).to(dev)
+            halo = SimpleNamespace(table=lambda: shard.halo_out.emulate(g_own, cot.to(dev)))
+            rows.append(rdist._input_grad(g_own, w.to(dev), root.to(dev), None, shard, backend, None, halo))
+        results.append(("halves" if split else "one pass", part.unshard_rows(torch.cat(rows))))
+    return results
+
+
+@pytest.mark.parametrize("mode", ["plain", "fused", "shard"])
 def test_layer_input_gradient_rows_on_a_primekg_graph(mode, monkeypatch):
-    """rgcn_conv 128 -> 128 (gather first: the transposed aggregate feeds the transform) through autograd"""
+    """rgcn_conv 128 -> 128 (gather first: the transposed aggregate feeds the transform) through autograd; "shard": the
+    input gradient of each rank of a node partition (dist.HipBackend)"""
     from primekg_rgcn_linkprediction_amd import conv as C, rgcn_conv
     dev = need_gpu()
     monkeypatch.setattr(C, "_TRAIN_FUSED", "1" if mode == "fused" else "0")
@@ -421,12 +442,17 @@ def test_layer_input_gradient_rows_on_a_primekg_graph(mode, monkeypatch):
     w, root = weights(r, 128, 128, gen)
     x = torch.randn(n, 128, generator=gen).to(dev).requires_grad_(True)
     cot = _cotangent(n, 128, 4)
-    out = rgcn_conv(x, ei.to(dev), et.to(dev), w.to(dev), root.to(dev), None, r)
-    out.backward(cot.to(dev))
+    if mode == "shard":
+        got = _shard_input_grads(ei, et, n, r, w, root, cot, dev)
+    else:
+        out = rgcn_conv(x, ei.to(dev), et.to(dev), w.to(dev), root.to(dev), None, r)
+        out.backward(cot.to(dev))
+        got = [("autograd", x.grad)]
     wt = w.transpose(1, 2).reshape(r * 128, 128)
     refs = [_mean_agg64(cot, ei, et, n, r, True).to(dt) @ wt.to(dt) + cot.to(dt) @ root.t().to(dt)
             for dt in (torch.float64, torch.float32)]
-    assert_rows(x.grad, refs[0], refs[1], what=f"{mode} input gradient")
+    for form, gx in got:
+        assert_rows(gx, refs[0], refs[1], what=f"{mode} input gradient ({form})")
 
 
 def _encoder_ref(x, c1, c2, cot, ei, et, n, r, relu_mask, keep, p, dt):
