@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 25
+#define RGCN_ABI_VERSION 26
 
 enum {
   RGCN_OK = 0,
@@ -523,6 +523,35 @@ int rgcn_adam_clip_step(int num_tensors, float* const* params, const float* cons
 int distmult_rank_tails(const float* hr, const float* emb, const float* true_score,
                         const int64_t* tail, int64_t batch, int64_t num_entities, int64_t d,
                         int32_t* beaten_by, void* stream);
+
+/* Filtered and / or type-constrained ranking, either side of a triple (DistMult is symmetric: q = head_emb * rel_emb
+ * ranks tails, q = tail_emb * rel_emb ranks heads): the pass of distmult_rank_tails - same operands, tile walk and
+ * accumulation on the fp32 MFMA, so a score compared here, there and the one distmult_score_all_tails stores are
+ * the same bits - with a candidate filter in the counting epilogue:
+ *   beaten_by[b] += #{ n != target[b] : scores[b, n] > true_score[b]
+ *                                       and bit n of allow[query_class[b]] is set   (allow != NULL)
+ *                                       and bit n of exclude[b]            is clear (exclude != NULL) }
+ * Bit masks over the entities: W = ceil(num_entities / 32) uint32 words per row, entity n is bit (n & 31) of word
+ * (n >> 5); allow: [num_classes, W], query_class: int32[batch] (required with allow; a value outside
+ * [0, num_classes) allows no candidate), exclude: [batch, W].  Both NULL: exactly distmult_rank_tails.  Integer
+ * atomics into the caller-zeroed beaten_by, as there: two runs give the same counts.  d a multiple of 32. */
+int distmult_rank_masked(const float* q, const float* emb, const float* true_score, const int64_t* target,
+                         const uint32_t* allow, const int32_t* query_class, int64_t num_classes,
+                         const uint32_t* exclude, int64_t batch, int64_t num_entities, int64_t d,
+                         int32_t* beaten_by, void* stream);
+
+/* The masks of distmult_rank_masked (nothing rank-specific in them: any consumer of the [B, N] scores can take them).
+ * rgcn_rank_exclude_bits: row b of exclude[batch, W] = the ids of segment seg[b] of a CSR of known triples,
+ *   ids[ptr[seg[b]] .. ptr[seg[b] + 1]) - ptr: int64[num_segments + 1], ids: int64[nnz], seg: int64[batch], seg[b] < 0 =
+ *   nothing known.  Every row is cleared and then set by its own workgroup (no memset by the caller, the padding
+ *   bits of the last word are zero).  An id outside [0, num_entities), a segment >= num_segments or a ptr pair outside
+ *   [0, nnz] writes nothing and raises the index-error flag (rgcn_index_error_fetch).
+ * rgcn_rank_allow_bits: allow[num_classes, W], bit n of row c set iff class_of[n] == c (class_of: int32[num_entities];
+ *   negative = in no class; a class >= num_classes raises the index-error flag and is in no class).  Every word written. */
+int rgcn_rank_exclude_bits(const int64_t* ptr, const int64_t* ids, const int64_t* seg, int64_t num_segments, int64_t nnz,
+                           int64_t batch, int64_t num_entities, uint32_t* exclude, void* stream);
+int rgcn_rank_allow_bits(const int32_t* class_of, int64_t num_entities, int64_t num_classes, uint32_t* allow,
+                         void* stream);
 
 /* The [B, num_entities] score matrix itself (LinkPredictor.score_all_tails rgcn.py:215-243: (h * r) @ E^T; the callers
  * that want every candidate's score - predict_all_tails, the top-k consumers - rather than a rank):

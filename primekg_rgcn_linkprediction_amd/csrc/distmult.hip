@@ -299,6 +299,11 @@ int pick_group(int64_t d) {
 
 }  // namespace
 
+int* rgcn_index_error_flag() {
+  void* p = nullptr;
+  return hipGetSymbolAddress(&p, HIP_SYMBOL(g_index_error)) == hipSuccess ? static_cast<int*>(p) : nullptr;
+}
+
 extern "C" {
 
 int rgcn_index_error_fetch(int* host_flag, void* stream_) {

@@ -82,6 +82,10 @@ struct rgcn_graph {
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Device address of the current device's sticky index-error flag (distmult.hip; rgcn_index_error_fetch reads and
+// clears it) for kernels of other translation units that meet an id outside its table.  NULL if HIP fails.
+__attribute__((visibility("hidden"))) int* rgcn_index_error_flag();
+
 // ---------------------------------------------------------------------------------------------
 // "amax" buffers: max |tensor| as the split-precision transforms need it (rgcn_transform_split.hip).
 // A buffer is RGCN_AMAX_FLOATS floats, zeroed by the caller; its VALUE is the maximum over all entries.

@@ -30,7 +30,7 @@ constexpr int BK = 32;          // k-tile
 constexpr int LDS_S = 36;       // row stride (floats) of k-contiguous LDS tiles (144 B)
 
 enum { B_KN = 0, B_BLK = 1 };            // how the B operand is addressed (see k_gemm_nt)
-enum { EPI_NONE = 0, EPI_RELU = 1, EPI_MASK = 2, EPI_RANK = 3 };
+enum { EPI_NONE = 0, EPI_RELU = 1, EPI_MASK = 2, EPI_RANK = 3, EPI_RANK_MASKED = 4 };
 
 __device__ inline float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ inline float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -285,6 +285,8 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt_dma(const float* __restric
     }
   }
 
+  // (EPI_RANK_MASKED: A2 and Rt are not float data there - they carry the mask words; K2 == 0 and one B_BLK block
+  // of dk == K1 mean neither is ever staged.  A change that makes stage() read them must give the masks own slots.)
   auto stage = [&](int kt, int buf) {
     float* sA = lds + buf * BUF_FLOATS;
     float* sB = sA + A_FLOATS;
@@ -317,6 +319,7 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt_dma(const float* __restric
   }
   auto next_kt = [&](int kt) {                 // next active k-tile start after kt (K when none)
     kt += BK;
+    if (EPI == EPI_RANK_MASKED) return min(kt, K);   // no relation blocks there: kseg carries the number of allow rows
     while (kt < K1 && !((rel_mask >> (kt / kseg)) & 1u)) kt = (kt / kseg + 1) * kseg;
     return min(kt, K);
   };
@@ -415,6 +418,62 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt_dma(const float* __restric
         const unsigned long long hits = __ballot(in && (int64_t)n != tl && acc[b][r] > ts);
         if (li == 0 && m < M) {
           const int c = __popc(lh ? (unsigned)(hits >> 32) : (unsigned)hits);
+          if (c) atomicAdd(&counts[m], c);
+        }
+      }
+    }
+    return;
+  }
+  if (EPI == EPI_RANK_MASKED) {
+    // Filtered / type-constrained ranking: the EPI_RANK count with a candidate filter.  The ballot of an
+    // accumulator register is the 32 hits of columns nb .. nb+31 of two rows, and nb is a multiple of 32: exactly
+    // one word of a [rows, ceil(N/32)] bit mask per row, so the filter is hits & allow[class[m]][w] & ~exclude[m][w]
+    // before the popcount - two 4-byte loads per (row, 32-column group), all issued before the group's ballots.
+    // The operands a ranking launch does not use carry the masks: Rt = allow words, mask = query_class (int32),
+    // A2 = exclude words (K2 == 0: never staged), kseg = number of allow rows.  Either mask may be NULL.
+    const int64_t* tails = reinterpret_cast<const int64_t*>(aux);
+    const uint32_t* allow = reinterpret_cast<const uint32_t*>(Rt);
+    const int32_t* qcls = reinterpret_cast<const int32_t*>(mask);
+    const uint32_t* excl = reinterpret_cast<const uint32_t*>(A2);
+    int* counts = reinterpret_cast<int*>(C);
+    const int words = (N + 31) >> 5;
+    constexpr unsigned kNoRow = 0xffffffffu;
+    float ts[16];
+    int tl[16];
+    unsigned aoff[16];                     // first word of the row's allow row, kNoRow: nothing is allowed
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+      const bool ok = m < M;
+      ts[r] = ok ? bias[m] : 0.f;
+      const int64_t t64 = ok ? tails[m] : -1;
+      tl[r] = (t64 >= 0 && t64 < N) ? (int)t64 : -1;
+      aoff[r] = kNoRow;
+      if (allow && ok) {
+        const int c = qcls[m];
+        if (c >= 0 && c < kseg) aoff[r] = (unsigned)c * (unsigned)words;
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < TN; ++b) {
+      const int nb = n0 + (wn * TN + b) * 32, n = nb + li;
+      const int w = nb >> 5;
+      const bool wok = w < words;          // a column group wholly past N has no mask word (and no hit)
+      unsigned aw[16], ew[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        // only the lane that counts (li == 0 of each half) needs the words
+        aw[r] = allow ? ((li == 0 && wok && aoff[r] != kNoRow) ? allow[aoff[r] + (unsigned)w] : 0u) : 0xffffffffu;
+        ew[r] = (li == 0 && excl && wok && m < M) ? excl[(size_t)m * words + w] : 0u;
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const unsigned long long hits = __ballot(m < M && n < N && n != tl[r] && acc[b][r] > ts[r]);
+        if (li == 0 && m < M) {
+          const unsigned mine = lh ? (unsigned)(hits >> 32) : (unsigned)hits;
+          const int c = __popc(mine & aw[r] & ~ew[r]);
           if (c) atomicAdd(&counts[m], c);
         }
       }
@@ -947,6 +1006,27 @@ int distmult_rank_tails(const float* hr, const float* emb, const float* true_sco
   k_gemm_nt_dma<2, B_BLK, EPI_RANK><<<grid, kThreads, 0, stream>>>(hr, (int)d, hr, 0, emb, emb, (int)d, true_score,
                                                                     nullptr, reinterpret_cast<float*>(beaten_by),
                                                                     (int)batch, (int)num_entities, tail, nullptr, 0);
+  RGCN_HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+int distmult_rank_masked(const float* q, const float* emb, const float* true_score, const int64_t* target,
+                         const uint32_t* allow, const int32_t* query_class, int64_t num_classes, const uint32_t* exclude,
+                         int64_t batch, int64_t num_entities, int64_t d, int32_t* beaten_by, void* stream_) {
+  if (batch < 0 || num_entities <= 0 || d <= 0 || (d % BK)) return (d > 0 && (d % BK)) ? RGCN_ERR_UNSUPPORTED : RGCN_ERR_ARG;
+  if (num_classes < 0 || (allow && (num_classes == 0 || !query_class))) return RGCN_ERR_ARG;
+  if (batch == 0) return RGCN_OK;
+  if (!q || !emb || !true_score || !target || !beaten_by) return RGCN_ERR_ARG;
+  if (batch > INT32_MAX / 2 || num_entities > INT32_MAX / 2) return RGCN_ERR_UNSUPPORTED;
+  const int64_t words = ceil_div64(num_entities, 32);
+  if (allow && num_classes * words > INT32_MAX) return RGCN_ERR_UNSUPPORTED;   // 32-bit word offsets in the epilogue
+  hipStream_t stream = (hipStream_t)stream_;
+  // the ranking launch (same operands, tile walk and accumulation), the masks in the operand slots it leaves unused
+  dim3 grid((unsigned)ceil_div64(batch, 64), (unsigned)ceil_div64(num_entities, 128));
+  k_gemm_nt_dma<2, B_BLK, EPI_RANK_MASKED><<<grid, kThreads, 0, stream>>>(
+      q, (int)d, reinterpret_cast<const float*>(exclude), 0, emb, reinterpret_cast<const float*>(allow), (int)d, true_score,
+      reinterpret_cast<const float*>(query_class), reinterpret_cast<float*>(beaten_by), (int)batch, (int)num_entities,
+      target, nullptr, allow ? (int)num_classes : 0);
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }

@@ -71,6 +71,21 @@ def convert_to_pyg_format(df, node2idx: Dict, relation2idx: Dict) -> Dict:
             "num_nodes": num_nodes, "num_relations": len(relation2idx)}
 
 
+def node_classes(idx2node: Dict, num_nodes: int):
+    """-> (int32 [num_nodes] class id of every node, [class names]): the node types of ``idx2node``
+    ({idx: (id, name, type)}), class ids by sorted type name.  ``idx2node`` has more entries than the graph has
+    nodes (the key collision above: 30,968 triples for 30,926 nodes in PrimeKG); the rows past ``num_nodes`` name
+    no node of the graph and are dropped."""
+    num_nodes = int(num_nodes)
+    missing = [i for i in range(num_nodes) if i not in idx2node]
+    if missing:
+        raise ValueError(f"idx2node has no entry for node {missing[0]} (of {num_nodes})")
+    names = sorted({idx2node[i][2] for i in range(num_nodes)})
+    ids = {name: c for c, name in enumerate(names)}
+    classes = torch.tensor([ids[idx2node[i][2]] for i in range(num_nodes)], dtype=torch.int32)
+    return classes, names
+
+
 def save_graph(path, data: Dict) -> None:
     """The dict ``train.py:563-567`` / ``evaluate.py:744-746`` load; tensors and ints only."""
     out = {"edge_index": data["edge_index"].to(torch.int64).contiguous(),

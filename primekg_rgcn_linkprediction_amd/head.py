@@ -201,15 +201,59 @@ class LinkPredictor(nn.Module):
 
     @torch.no_grad()
     def rank_tails(self, head_embeddings: Tensor, relation_types: Tensor, all_tail_embeddings: Tensor,
-                   tail_indices: Tensor) -> Tensor:
+                   tail_indices: Tensor, *, known: Optional["ops.KnownTriples"] = None,
+                   head_indices: Optional[Tensor] = None, node_class: Optional[Tensor] = None,
+                   max_mask_bytes: int = 256 << 20) -> Tensor:
         """1-based rank of ``tail_indices[b]`` among all entities for ``(head, relation)``:
         ``argsort(score_all_tails(...)[b], descending=True)`` position + 1, as
         ``evaluate.py:266-274`` computes it, but from one fused MFMA pass that counts the
-        candidates beating the true tail's score (ties, measure zero in fp32, rank first)."""
+        candidates beating the true tail's score (ties, measure zero in fp32, rank first).
+
+        ``known`` (with ``head_indices``, the node ids of the heads): the filtered protocol - a candidate ``n`` with
+        ``(head, relation, n)`` among the known triples does not count.  ``node_class`` (int ``[N]``): the
+        type-constrained protocol - only candidates of the true tail's class count.  Both default to the raw
+        protocol above, through the same kernel as before."""
         hr = (head_embeddings * self.relation_embeddings(relation_types)).contiguous()
         emb = all_tail_embeddings.contiguous()
         true_score = (hr * emb[tail_indices]).sum(1)
-        return ops.distmult_rank_tails(hr, emb, true_score, tail_indices.contiguous())
+        if known is None and node_class is None:
+            return ops.distmult_rank_tails(hr, emb, true_score, tail_indices.contiguous())
+        return self._rank_filtered("tail", hr, emb, true_score, tail_indices.contiguous(), relation_types, known,
+                                   head_indices, node_class, max_mask_bytes)
+
+    @torch.no_grad()
+    def rank_heads(self, tail_embeddings: Tensor, relation_types: Tensor, all_head_embeddings: Tensor,
+                   head_indices: Tensor, *, known: Optional["ops.KnownTriples"] = None,
+                   tail_indices: Optional[Tensor] = None, node_class: Optional[Tensor] = None,
+                   max_mask_bytes: int = 256 << 20) -> Tensor:
+        """1-based rank of ``head_indices[b]`` among all entities for ``(?, relation, tail)``.  DistMult is symmetric
+        in head and tail, so this is ``rank_tails``'s pass with ``q = tail * rel``; ``known`` filters by the
+        ``(tail, relation)`` sets (``tail_indices``: the node ids of the tails), ``node_class`` restricts the
+        candidates to the true head's class."""
+        tr = (tail_embeddings * self.relation_embeddings(relation_types)).contiguous()
+        emb = all_head_embeddings.contiguous()
+        true_score = (tr * emb[head_indices]).sum(1)
+        return self._rank_filtered("head", tr, emb, true_score, head_indices.contiguous(), relation_types, known,
+                                   tail_indices, node_class, max_mask_bytes)
+
+    def _rank_filtered(self, side, q, emb, true_score, target, relation_types, known, anchor_indices, node_class,
+                       max_mask_bytes):
+        allow = query_class = None
+        if node_class is not None:
+            if node_class.shape != (emb.size(0),):
+                raise ValueError(f"node_class must hold one class per entity ([{emb.size(0)}])")
+            # the allow rows of a class vector are built once and kept while the caller passes the same, unmodified tensor
+            key = (node_class.data_ptr(), node_class._version, node_class.dtype, emb.device)
+            if getattr(self, "_allow_cache", (None,))[0] != key:
+                classes = node_class.to(device=emb.device, dtype=torch.int32).contiguous()
+                self._allow_cache = (key, node_class, classes, ops.class_allow_bits(classes, int(classes.max()) + 1))
+            _, _, node_class, allow = self._allow_cache
+            query_class = node_class[target].contiguous()
+        if known is not None and anchor_indices is None:
+            raise ValueError("filtered ranking needs the node ids of the given side "
+                             "(head_indices for rank_tails, tail_indices for rank_heads)")
+        return ops.distmult_rank_filtered(q, emb, true_score, target, known, side, anchor_indices, relation_types,
+                                          allow, query_class, max_mask_bytes)
 
     def score_all_tails(self, head_embeddings: Tensor, relation_types: Tensor,
                         all_tail_embeddings: Tensor) -> Tensor:

@@ -1669,6 +1669,163 @@ def distmult_rank_tails(hr: torch.Tensor, emb: torch.Tensor, true_score: torch.T
     return beaten.to(torch.int64) + 1
 
 
+# Candidate filters of the ranking pass: bit masks over the entities, W = ceil(N / 32) words per row, entity n = bit
+# (n & 31) of word (n >> 5), carried as int32 tensors (the words' bits; torch has no arithmetic on uint32).
+def mask_words(num_entities: int) -> int:
+    return (int(num_entities) + 31) // 32
+
+
+def class_allow_bits(class_of: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """``allow[c]`` has bit n set iff ``class_of[n] == c`` -> int32 ``[num_classes, W]`` (``rgcn_rank_allow_bits``);
+    a negative class is in no class, a class ``>= num_classes`` raises at the next ``check_indices``."""
+    _need_gpu("class_of", class_of, torch.int32)
+    if class_of.dim() != 1 or class_of.numel() == 0 or num_classes <= 0:
+        raise ValueError("class_of [N] (N > 0) and num_classes > 0 expected")
+    n = class_of.numel()
+    with _on(class_of.device):
+        allow = torch.empty((num_classes, mask_words(n)), dtype=torch.int32, device=class_of.device)
+        rc = _L().rgcn_rank_allow_bits(_ptr(class_of), n, num_classes, _ptr(allow), _stream())
+    _lib.check(rc, "rgcn_rank_allow_bits")
+    return allow
+
+
+class KnownTriples:
+    """The known-positive sets of a graph for filtered ranking: a CSR keyed by ``(head, relation)`` listing the known
+    tails (side ``"tail"``: what to skip when tails are ranked) and one keyed by ``(tail, relation)`` listing the
+    known heads (side ``"head"``).  Built once with torch sort / unique on whatever device the edges are on (CPU
+    tensors work: the logic is testable without a GPU); duplicates collapse.  Per side: ``keys`` (the sorted
+    ``anchor * R + relation`` that occur), ``ptr`` int64 ``[K + 1]``, ``ids`` int64 ``[nnz]`` ascending per segment."""
+
+    SIDES = ("tail", "head")
+
+    def __init__(self, edge_index: torch.Tensor, edge_type: torch.Tensor, num_nodes: int, num_relations: int):
+        if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_type.shape != (edge_index.size(1),):
+            raise ValueError("edge_index must be [2, E] and edge_type [E]")
+        self.num_nodes, self.num_relations = int(num_nodes), int(num_relations)
+        if self.num_nodes <= 0 or self.num_relations <= 0 or self.num_nodes * self.num_relations >= 2 ** 62 // self.num_nodes:
+            raise ValueError("num_nodes / num_relations out of range")
+        ei, et = edge_index.to(torch.int64), edge_type.to(torch.int64)
+        if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= self.num_nodes or int(et.min()) < 0
+                           or int(et.max()) >= self.num_relations):
+            raise IndexError("a node or relation id of the known triples is outside its range")
+        self.device = ei.device
+        self._csr = {"tail": self._build(ei[0], et, ei[1]), "head": self._build(ei[1], et, ei[0])}
+
+    def _build(self, anchor, rel, other):
+        n = self.num_nodes
+        triple = torch.unique((anchor * self.num_relations + rel) * n + other)      # sorted, duplicates gone
+        seg_key = torch.div(triple, n, rounding_mode="floor")
+        keys, counts = torch.unique_consecutive(seg_key, return_counts=True)
+        ptr = torch.zeros(keys.numel() + 1, dtype=torch.int64, device=triple.device)
+        ptr[1:] = torch.cumsum(counts, 0)
+        return keys.contiguous(), ptr, (triple - seg_key * n).contiguous()
+
+    def csr(self, side: str):
+        """``(keys, ptr, ids)`` of one side"""
+        if side not in self.SIDES:
+            raise ValueError(f"side must be one of {self.SIDES}")
+        return self._csr[side]
+
+    def segments(self, side: str, anchor_idx: torch.Tensor, rel_idx: torch.Tensor) -> torch.Tensor:
+        """int64 ``[B]``: the CSR segment of every ``(anchor, relation)`` query, -1 where nothing is known"""
+        keys = self.csr(side)[0]
+        anchor, rel = anchor_idx.to(torch.int64), rel_idx.to(torch.int64)
+        q = anchor * self.num_relations + rel
+        if keys.numel() == 0:
+            return torch.full_like(q, -1)
+        pos = torch.searchsorted(keys, q).clamp_(max=keys.numel() - 1)
+        # an id outside its range must not alias another anchor's key: nothing is known for it
+        ok = (keys[pos] == q) & (rel >= 0) & (rel < self.num_relations) & (anchor >= 0) & (anchor < self.num_nodes)
+        return torch.where(ok, pos, torch.full_like(pos, -1))
+
+    def exclude_bits(self, side: str, anchor_idx: torch.Tensor, rel_idx: torch.Tensor,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int32 ``[B, W]``: bit n of row b set iff ``(anchor[b], relation[b], n)`` is a known triple
+        (``rgcn_rank_exclude_bits``; the kernel clears the rows itself).  ``out``: a buffer of >= B rows to write into."""
+        keys, ptr, ids = self.csr(side)
+        seg = self.segments(side, anchor_idx, rel_idx).contiguous()
+        _need_gpu("segments", seg, torch.int64)
+        _need_gpu("ids", ids, torch.int64)
+        b, w = seg.numel(), mask_words(self.num_nodes)
+        if out is None:
+            out = torch.empty((b, w), dtype=torch.int32, device=seg.device)
+        elif out.dtype != torch.int32 or out.dim() != 2 or out.size(0) < b or out.size(1) != w or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int32 [>= {b}, {w}] buffer")
+        with _on(seg.device):
+            rc = _L().rgcn_rank_exclude_bits(_ptr(ptr), _ptr(ids), _ptr(seg), keys.numel(), ids.numel(), b,
+                                             self.num_nodes, _ptr(out), _stream())
+        _lib.check(rc, "rgcn_rank_exclude_bits")
+        return out[:b]
+
+
+def distmult_rank_masked(q: torch.Tensor, emb: torch.Tensor, true_score: torch.Tensor, target: torch.Tensor,
+                         allow: Optional[torch.Tensor] = None, query_class: Optional[torch.Tensor] = None,
+                         exclude: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``rank[b] = 1 + #{n != target[b] : <q[b], emb[n]> > true_score[b], n allowed, n not excluded}`` (int64 [B]):
+    ``distmult_rank_tails`` with the candidate filters in the epilogue (``distmult_rank_masked``).  ``allow`` int32
+    ``[C, W]`` with ``query_class`` int32 ``[B]`` in ``[0, C)``; ``exclude`` int32 ``[B, W]``; both ``None``: exactly
+    ``distmult_rank_tails``."""
+    _need_gpu("q", q, torch.float32)
+    _need_gpu("emb", emb, torch.float32)
+    _need_gpu("true_score", true_score, torch.float32)
+    _need_gpu("target", target, torch.int64)
+    b, d = q.shape
+    if emb.dim() != 2 or emb.size(1) != d or true_score.shape != (b,) or target.shape != (b,):
+        raise ValueError("q [B, d], emb [N, d], true_score [B], target [B] expected")
+    if d % 32:
+        raise ValueError("embedding dim must be a multiple of 32 for the fused ranking kernel")
+    w, classes = mask_words(emb.size(0)), 0
+    if (allow is None) != (query_class is None):
+        raise ValueError("allow and query_class go together")
+    if allow is not None:
+        _need_gpu("allow", allow, torch.int32)
+        _need_gpu("query_class", query_class, torch.int32)
+        classes = allow.size(0)
+        if allow.dim() != 2 or allow.size(1) != w or classes == 0 or query_class.shape != (b,):
+            raise ValueError(f"allow [C, {w}] and query_class [B] expected")
+    if exclude is not None:
+        _need_gpu("exclude", exclude, torch.int32)
+        if exclude.shape != (b, w):
+            raise ValueError(f"exclude [{b}, {w}] expected")
+    lib = _L()
+    with _on(q.device):
+        beaten = torch.zeros(b, dtype=torch.int32, device=q.device)
+        rc = lib.distmult_rank_masked(_ptr(q), _ptr(emb), _ptr(true_score), _ptr(target), _ptr(allow), _ptr(query_class),
+                                      classes, _ptr(exclude), b, emb.size(0), d, _ptr(beaten), _stream())
+    _lib.check(rc, "distmult_rank_masked")
+    return beaten.to(torch.int64) + 1
+
+
+def distmult_rank_filtered(q: torch.Tensor, emb: torch.Tensor, true_score: torch.Tensor, target: torch.Tensor,
+                           known: Optional[KnownTriples] = None, side: str = "tail",
+                           anchor_idx: Optional[torch.Tensor] = None, rel_idx: Optional[torch.Tensor] = None,
+                           allow: Optional[torch.Tensor] = None, query_class: Optional[torch.Tensor] = None,
+                           max_mask_bytes: int = 256 << 20) -> torch.Tensor:
+    """``distmult_rank_masked`` over all queries with the exclude mask of ``known`` built chunk by chunk: a mask row
+    costs ``W * 4`` bytes (62 KB per query at 500k nodes), so the queries are taken in chunks whose mask stays under
+    ``max_mask_bytes``, all through one buffer."""
+    b = q.size(0)
+    if known is None or b == 0:
+        return distmult_rank_masked(q, emb, true_score, target, allow, query_class)
+    if anchor_idx is None or rel_idx is None:
+        raise ValueError("filtered ranking needs the anchor node ids and relation ids of the queries")
+    if known.num_nodes != emb.size(0):
+        raise ValueError(f"known triples are over {known.num_nodes} nodes, the candidates are {emb.size(0)}")
+    w = mask_words(emb.size(0))
+    rows = max(1, int(max_mask_bytes) // (4 * w))
+    if rows >= 64:
+        rows -= rows % 64                                        # whole row tiles of the ranking pass
+    rows = min(rows, b)
+    ranks = torch.empty(b, dtype=torch.int64, device=q.device)
+    buf = torch.empty((rows, w), dtype=torch.int32, device=q.device)
+    for lo in range(0, b, rows):
+        hi = min(lo + rows, b)
+        excl = known.exclude_bits(side, anchor_idx[lo:hi], rel_idx[lo:hi], out=buf)
+        ranks[lo:hi] = distmult_rank_masked(q[lo:hi], emb, true_score[lo:hi], target[lo:hi], allow,
+                                            None if query_class is None else query_class[lo:hi], excl)
+    return ranks
+
+
 def distmult_score_all_tails(head: torch.Tensor, rel: torch.Tensor, rel_idx: Optional[torch.Tensor],
                              emb: torch.Tensor):
     """``((head * rel[rel_idx]) @ emb.T, head * rel[rel_idx])`` - the [B, N] score matrix of

@@ -68,6 +68,16 @@ def primekg_like(num_edges: int = PRIMEKG_EDGES, seed: int = 42,
     return edge_index, edge_type, PRIMEKG_NODES, 3
 
 
+def primekg_like_node_classes() -> torch.Tensor:
+    """int32 [PRIMEKG_NODES]: the node class of every id of the ``primekg_like`` layout, class ids by sorted type
+    name (0 = disease, 1 = drug, 2 = gene) - what ``graphio.node_classes`` gives for the real mapping."""
+    classes = torch.empty(PRIMEKG_NODES, dtype=torch.int32)
+    for c, kind in enumerate(sorted(_TYPE_RANGE)):
+        lo, hi = _TYPE_RANGE[kind]
+        classes[lo:hi] = c
+    return classes
+
+
 def uniform_graph(num_nodes: int, num_edges: int, num_relations: int,
                   seed: int = 42) -> Tuple[torch.Tensor, torch.Tensor, int, int]:
     gen = torch.Generator().manual_seed(seed)
