@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 26
+#define RGCN_ABI_VERSION 27
 
 enum {
   RGCN_OK = 0,
@@ -552,6 +552,28 @@ int rgcn_rank_exclude_bits(const int64_t* ptr, const int64_t* ids, const int64_t
                            int64_t batch, int64_t num_entities, uint32_t* exclude, void* stream);
 int rgcn_rank_allow_bits(const int32_t* class_of, int64_t num_entities, int64_t num_classes, uint32_t* allow,
                          void* stream);
+
+/* The k best candidates of every query from the same scores and masks (case_studies.predict_top_drugs,
+ * medical_validation.generate_predictions + _filter_known_associations; no [B, N] score matrix, no sort):
+ *   candidates of query b = { n in [0, num_entities) : bit n of allow[query_class[b]] set (allow != NULL), bit n of
+ *                             exclude[b] clear (exclude != NULL), scores[b, n] not NaN and >= min_score }
+ *   with scores[b, n] = <q[b], emb[n]>, the bits distmult_score_all_tails stores (same operands, tile walk and
+ *   accumulation on the fp32 MFMA).  There is no true target: nothing else is left out.  min_score = -INFINITY: none.
+ *   order = score descending, equal scores by entity id ascending (a total order: the result does not depend on
+ *   `slices` or on launch order, and two calls return the same bytes).
+ *   top_ids int64 [batch, k], top_scores float [batch, k]: the first k candidates in that order; the slots past the
+ *   number of candidates hold id -1 and score -INFINITY.  k > num_entities is legal.
+ * Masks: the layout and rules of distmult_rank_masked.  d a multiple of 32; 1 <= k <= 128 (larger:
+ * RGCN_ERR_UNSUPPORTED).  slices: into how many ranges the entities are cut, each walked by its own workgroups and
+ * merged afterwards (0: chosen from the batch so that a small batch still fills the device and a large one keeps
+ * the workspace at batch x k pairs); at most one per 128 entities and 256 are used.
+ * workspace: distmult_topk_workspace_bytes(batch, num_entities, k, slices) bytes (the same `slices`), 0 for an
+ * empty batch. */
+size_t distmult_topk_workspace_bytes(int64_t batch, int64_t num_entities, int64_t k, int64_t slices);
+int distmult_topk_masked(const float* q, const float* emb, const uint32_t* allow, const int32_t* query_class,
+                         int64_t num_classes, const uint32_t* exclude, float min_score, int64_t batch,
+                         int64_t num_entities, int64_t d, int64_t k, int64_t slices, int64_t* top_ids,
+                         float* top_scores, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The [B, num_entities] score matrix itself (LinkPredictor.score_all_tails rgcn.py:215-243: (h * r) @ E^T; the callers
  * that want every candidate's score - predict_all_tails, the top-k consumers - rather than a rank):

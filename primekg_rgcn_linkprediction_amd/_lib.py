@@ -13,7 +13,7 @@ from ctypes import c_float, POINTER, c_char_p, c_int, c_int64, c_size_t, c_void_
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 LIB_NAME = "librgcn_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -129,6 +129,9 @@ PROTOTYPES = {
     "distmult_rank_masked": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _P]),
     "rgcn_rank_exclude_bits": (c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "rgcn_rank_allow_bits": (c_int, [_P, _I64, _I64, _P, _P]),
+    "distmult_topk_workspace_bytes": (c_size_t, [_I64, _I64, _I64, _I64]),
+    "distmult_topk_masked": (c_int, [_P, _P, _P, _P, _I64, _P, c_float, _I64, _I64, _I64, _I64, _I64, _P, _P, _P,
+                                     c_size_t, _P]),
     "rgcn_basis_compose": (c_int, [_P, _P, _I64, _I64, _I64, _P, _P]),
     "rgcn_basis_compose_bwd_workspace_bytes": (c_size_t, [_I64, _I64, _I64]),
     "rgcn_basis_compose_bwd": (c_int, [_P, _P, _P, _I64, _I64, _I64, _P, _P, _P, c_size_t, _P]),

@@ -8,16 +8,20 @@ mapped to [0, 1]:
 * ``compare_methods.RGCNMethod.predict_all`` (``compare_methods.py:384-397``): the
   ``[n_drug, n_disease]`` matrix of the same;
 * ``case_studies.predict_top_drugs`` (``src/case_studies.py:236-284``): the top-k drugs of one
-  disease above a threshold, best first.
+  disease above a threshold, best first;
+* ``medical_validation.generate_predictions`` + ``_filter_known_associations``
+  (``src/medical_validation.py:191-280``): the best novel (drug, disease) pairs over many diseases.
 
 Here they stay on the device: rows are normalised once, the per-pair form reuses the DistMult
 kernel (relation factor = ones, so ``sum_d h*1*t`` of unit rows is the cosine), the matrix
 form is a plain library GEMM, the ranking a stable descending sort (ties keep candidate
-order, as the reference's ``list.sort(reverse=True)`` does).
+order, as the reference's ``list.sort(reverse=True)`` does).  The batched forms (``predict_top_drugs_batch``,
+``novel_drug_predictions``) select on the device instead: the fused top-k pass over unit rows, the drugs as its allow
+mask, the known associations as its exclude mask - no ``[diseases, drugs]`` matrix, no sort.
 """
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple, Union
+from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 from torch import Tensor
@@ -75,3 +79,46 @@ def predict_top_drugs(embeddings: Tensor, disease_idx: int, drug_indices: _Index
     cand, scores = cand[keep], scores[keep]
     order = torch.sort(scores, descending=True, stable=True).indices[:top_k]
     return list(zip(cand[order].tolist(), scores[order].tolist()))
+
+
+@torch.no_grad()
+def predict_top_drugs_batch(embeddings: Tensor, disease_indices: _Index, drug_indices: _Index, top_k: int = 10,
+                            known: Optional["ops.KnownTriples"] = None,
+                            normalized: bool = False) -> Tuple[Tensor, Tensor]:
+    """``predict_top_drugs`` for many diseases at once, on the device: ``(ids int64 [B, top_k], cosines [B, top_k])``,
+    row b the ``top_k`` drugs closest to ``disease_indices[b]``, cosine descending, equal cosines by node id
+    ascending (``predict_top_drugs`` keeps candidate order: the same for ascending ``drug_indices``), id -1 / -inf past
+    the number of candidates.  Unit rows are both operands of the fused top-k pass (relation factor = ones, as in
+    ``cosine_pair_scores``), the drugs its one allow row.  ``known``: a relation-free ``KnownTriples`` (edge type all
+    zero, one relation) - a drug linked to the disease in either direction is left out."""
+    unit = embeddings if normalized else normalize_rows(embeddings)
+    dis, drugs = _index(disease_indices, unit.device), _index(drug_indices, unit.device)
+    n = unit.size(0)
+    class_of = torch.full((n,), -1, dtype=torch.int32, device=unit.device)
+    class_of[drugs] = 0
+    allow = ops.class_allow_bits(class_of, 1)
+    query_class = torch.zeros(dis.numel(), dtype=torch.int32, device=unit.device)
+    exclude = None
+    if known is not None:
+        if known.num_relations != 1 or known.num_nodes != n:
+            raise ValueError("known must be relation-free (one relation, edge type all zero) over the same nodes")
+        zero = torch.zeros_like(dis)
+        exclude = known.exclude_bits("tail", dis, zero) | known.exclude_bits("head", dis, zero)
+    return ops.distmult_topk_masked(unit.index_select(0, dis), unit, top_k, allow, query_class, exclude)
+
+
+@torch.no_grad()
+def novel_drug_predictions(embeddings: Tensor, disease_indices: _Index, drug_indices: _Index,
+                           known: Optional["ops.KnownTriples"] = None, top_k: int = 100, threshold: float = 0.6,
+                           normalized: bool = False) -> List[Tuple[int, int, float]]:
+    """The device form of ``medical_validation.generate_predictions``: the best ``top_k`` ``(drug, disease, score)``
+    triples over all given diseases with ``score = (cos + 1) / 2 >= threshold`` (the threshold meets the mapped
+    score, as there) and no known drug-disease link, best first.  The global top-k of pairs lies inside the union of
+    the per-disease top-k, so one ``predict_top_drugs_batch`` and a sort of ``B x top_k`` values give it."""
+    ids, cos = predict_top_drugs_batch(embeddings, disease_indices, drug_indices, top_k, known, normalized)
+    dis = _index(disease_indices, ids.device).view(-1, 1).expand_as(ids)
+    scores = (cos + 1) / 2
+    keep = (ids >= 0) & (scores >= threshold)
+    ids, dis, scores = ids[keep], dis[keep], scores[keep]
+    order = torch.sort(scores, descending=True, stable=True).indices[:top_k]
+    return list(zip(ids[order].tolist(), dis[order].tolist(), scores[order].tolist()))

@@ -105,6 +105,40 @@ class ModelEvaluator:
         return self.model.decoder.rank_heads(emb[tail], rel, emb, head, tail_indices=tail,
                                              **self._protocol(filtered, type_constrained))
 
+    @torch.no_grad()
+    def top_candidates(self, side: str, anchors, relations, k: int, novel: bool = True, candidate_class=None,
+                       min_score: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(ids int64 [B, k], scores [B, k])``: the ``k`` best completions of every ``(anchor, relation)`` query on
+        the cached embeddings - tails of ``(anchor, relation, ?)`` for ``side="tail"``, heads of ``(?, relation,
+        anchor)`` for ``side="head"``; scores descending, equal scores by id ascending, id -1 / score -inf past the
+        number of candidates.  ``novel``: no returned id forms a known triple (``known_triples()``: full graph +
+        test set) with its query.  ``candidate_class`` (an int or one int per query; needs the node classes): only
+        entities of that class."""
+        if side not in ("tail", "head"):
+            raise ValueError("side must be 'tail' or 'head'")
+        if candidate_class is not None and self.node_class is None:
+            raise ValueError("candidate_class needs the node classes (ModelEvaluator(node_class=...), "
+                             "--node_types on the command line)")
+        emb = self.embeddings()
+        anchors = torch.as_tensor(anchors, dtype=torch.int64).to(self.device).view(-1)
+        relations = torch.as_tensor(relations, dtype=torch.int64).to(self.device).view(-1)
+        if relations.numel() == 1 and anchors.numel() != 1:
+            relations = relations.expand(anchors.numel()).contiguous()
+        if relations.shape != anchors.shape:
+            raise ValueError("one relation per anchor (or a single relation for all) expected")
+        if anchors.numel() and (int(anchors.min()) < 0 or int(anchors.max()) >= self.num_nodes):
+            raise IndexError("an anchor id is outside [0, num_nodes)")
+        if relations.numel() and (int(relations.min()) < 0 or int(relations.max()) >= self.model.decoder.num_relations):
+            raise IndexError("a relation id is outside [0, num_relations)")
+        if isinstance(candidate_class, torch.Tensor):
+            candidate_class = candidate_class.to(self.device)
+        kwargs = {"known": self.known_triples() if novel else None,
+                  "node_class": self.node_class if candidate_class is not None else None,
+                  "candidate_class": candidate_class, "min_score": min_score}
+        if side == "tail":
+            return self.model.decoder.top_tails(emb[anchors], relations, emb, k, head_indices=anchors, **kwargs)
+        return self.model.decoder.top_heads(emb[anchors], relations, emb, k, tail_indices=anchors, **kwargs)
+
     def compute_ranking_metrics(self, k_values: Sequence[int] = (10, 50), filtered: bool = False,
                                 type_constrained: bool = False, both_sides: bool = False) -> Dict:
         ranks = self.tail_ranks(filtered, type_constrained)

@@ -236,24 +236,76 @@ class LinkPredictor(nn.Module):
         return self._rank_filtered("head", tr, emb, true_score, head_indices.contiguous(), relation_types, known,
                                    tail_indices, node_class, max_mask_bytes)
 
+    def _allow_rows(self, node_class, emb):
+        """``(node_class int32 [N] on the device, allow [C, W])``: the allow rows of a class vector, built once and kept
+        while the caller passes the same, unmodified tensor"""
+        if node_class.shape != (emb.size(0),):
+            raise ValueError(f"node_class must hold one class per entity ([{emb.size(0)}])")
+        key = (node_class.data_ptr(), node_class._version, node_class.dtype, emb.device)
+        if getattr(self, "_allow_cache", (None,))[0] != key:
+            classes = node_class.to(device=emb.device, dtype=torch.int32).contiguous()
+            self._allow_cache = (key, node_class, classes, ops.class_allow_bits(classes, int(classes.max()) + 1))
+        return self._allow_cache[2], self._allow_cache[3]
+
     def _rank_filtered(self, side, q, emb, true_score, target, relation_types, known, anchor_indices, node_class,
                        max_mask_bytes):
         allow = query_class = None
         if node_class is not None:
-            if node_class.shape != (emb.size(0),):
-                raise ValueError(f"node_class must hold one class per entity ([{emb.size(0)}])")
-            # the allow rows of a class vector are built once and kept while the caller passes the same, unmodified tensor
-            key = (node_class.data_ptr(), node_class._version, node_class.dtype, emb.device)
-            if getattr(self, "_allow_cache", (None,))[0] != key:
-                classes = node_class.to(device=emb.device, dtype=torch.int32).contiguous()
-                self._allow_cache = (key, node_class, classes, ops.class_allow_bits(classes, int(classes.max()) + 1))
-            _, _, node_class, allow = self._allow_cache
+            node_class, allow = self._allow_rows(node_class, emb)
             query_class = node_class[target].contiguous()
         if known is not None and anchor_indices is None:
             raise ValueError("filtered ranking needs the node ids of the given side "
                              "(head_indices for rank_tails, tail_indices for rank_heads)")
         return ops.distmult_rank_filtered(q, emb, true_score, target, known, side, anchor_indices, relation_types,
                                           allow, query_class, max_mask_bytes)
+
+    @torch.no_grad()
+    def top_tails(self, head_embeddings: Tensor, relation_types: Tensor, all_tail_embeddings: Tensor, k: int, *,
+                  known: Optional["ops.KnownTriples"] = None, head_indices: Optional[Tensor] = None,
+                  node_class: Optional[Tensor] = None, candidate_class=None, min_score: Optional[float] = None,
+                  max_mask_bytes: int = 256 << 20):
+        """The ``k`` best tails of every ``(head, relation)`` query: ``(ids int64 [B, k], scores [B, k])``, scores
+        descending, equal scores by id ascending, id -1 / score -inf past the number of candidates - the first ``k``
+        columns of a stable descending sort of ``score_all_tails(...)`` restricted to the candidates, from one fused
+        pass that never stores the matrix (``case_studies.predict_top_drugs``, ``medical_validation.generate_predictions``).
+
+        ``known`` (with ``head_indices``): only novel tails - no ``n`` with ``(head, relation, n)`` among the known
+        triples.  ``node_class`` (int ``[N]``) with ``candidate_class`` (an int, or an int ``[B]`` tensor): only tails
+        of that class ("drugs").  ``min_score``: only scores ``>=`` it."""
+        hr = (head_embeddings * self.relation_embeddings(relation_types)).contiguous()
+        return self._top_filtered("tail", hr, all_tail_embeddings.contiguous(), k, relation_types, known, head_indices,
+                                  node_class, candidate_class, min_score, max_mask_bytes)
+
+    @torch.no_grad()
+    def top_heads(self, tail_embeddings: Tensor, relation_types: Tensor, all_head_embeddings: Tensor, k: int, *,
+                  known: Optional["ops.KnownTriples"] = None, tail_indices: Optional[Tensor] = None,
+                  node_class: Optional[Tensor] = None, candidate_class=None, min_score: Optional[float] = None,
+                  max_mask_bytes: int = 256 << 20):
+        """The ``k`` best heads of every ``(?, relation, tail)`` query.  DistMult is symmetric in head and tail, so
+        this is ``top_tails``'s pass with ``q = tail * rel``; ``known`` filters by the ``(tail, relation)`` sets."""
+        tr = (tail_embeddings * self.relation_embeddings(relation_types)).contiguous()
+        return self._top_filtered("head", tr, all_head_embeddings.contiguous(), k, relation_types, known, tail_indices,
+                                  node_class, candidate_class, min_score, max_mask_bytes)
+
+    def _top_filtered(self, side, q, emb, k, relation_types, known, anchor_indices, node_class, candidate_class,
+                      min_score, max_mask_bytes):
+        allow = query_class = None
+        if (node_class is None) != (candidate_class is None):
+            raise ValueError("node_class (the class of every entity) and candidate_class (the class the answers must "
+                             "have) go together")
+        if node_class is not None:
+            _, allow = self._allow_rows(node_class, emb)
+            if isinstance(candidate_class, Tensor):
+                if candidate_class.shape != (q.size(0),):
+                    raise ValueError(f"candidate_class must be an int or hold one class per query ([{q.size(0)}])")
+                query_class = candidate_class.to(device=emb.device, dtype=torch.int32).contiguous()
+            else:
+                query_class = torch.full((q.size(0),), int(candidate_class), dtype=torch.int32, device=emb.device)
+        if known is not None and anchor_indices is None:
+            raise ValueError("novel candidates need the node ids of the given side "
+                             "(head_indices for top_tails, tail_indices for top_heads)")
+        return ops.distmult_topk_filtered(q, emb, k, known, side, anchor_indices, relation_types, allow, query_class,
+                                          min_score, max_mask_bytes)
 
     def score_all_tails(self, head_embeddings: Tensor, relation_types: Tensor,
                         all_tail_embeddings: Tensor) -> Tensor:

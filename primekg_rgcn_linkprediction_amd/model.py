@@ -107,6 +107,25 @@ class DrugDiseaseModel(nn.Module):
             emb = self.encoder(edge_index, edge_type)
             return self.decoder.score_all_tails(emb[head_indices], relation_types, emb)
 
+    def predict_top_tails(self, edge_index: Tensor, edge_type: Tensor, anchor_indices: Tensor, relation_types: Tensor,
+                          k: int, **kwargs):
+        """``(ids [B, k], scores [B, k])``: the ``k`` best tails of every ``(anchor, relation)`` query - the first
+        ``k`` columns of a stable descending sort of ``predict_all_tails(...)`` restricted to the candidates, without
+        the ``[B, N]`` matrix.  ``kwargs``: ``known=`` (novel tails only), ``node_class=`` + ``candidate_class=``,
+        ``min_score=``, ``max_mask_bytes=`` of ``LinkPredictor.top_tails``."""
+        self.eval()
+        with torch.no_grad():
+            emb = self.encoder(edge_index, edge_type)
+            return self.decoder.top_tails(emb[anchor_indices], relation_types, emb, k, head_indices=anchor_indices, **kwargs)
+
+    def predict_top_heads(self, edge_index: Tensor, edge_type: Tensor, anchor_indices: Tensor, relation_types: Tensor,
+                          k: int, **kwargs):
+        """the ``k`` best heads of every ``(?, relation, anchor)`` query (``LinkPredictor.top_heads``)"""
+        self.eval()
+        with torch.no_grad():
+            emb = self.encoder(edge_index, edge_type)
+            return self.decoder.top_heads(emb[anchor_indices], relation_types, emb, k, tail_indices=anchor_indices, **kwargs)
+
     def get_embeddings(self, edge_index: Tensor, edge_type: Tensor) -> Tensor:
         self.eval()
         with torch.no_grad():

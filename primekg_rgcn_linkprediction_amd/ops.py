@@ -1826,6 +1826,95 @@ def distmult_rank_filtered(q: torch.Tensor, emb: torch.Tensor, true_score: torch
     return ranks
 
 
+TOPK_MAX_K = 128          # list length the select kernel is built for (csrc/rank_topk.hip)
+
+
+def distmult_topk_masked(q: torch.Tensor, emb: torch.Tensor, k: int, allow: Optional[torch.Tensor] = None,
+                         query_class: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None,
+                         min_score: Optional[float] = None, slices: int = 0):
+    """The ``k`` best candidates of every query, ``(ids int64 [B, k], scores float32 [B, k])``, from the ranking
+    pass's scores without the ``[B, N]`` matrix (``distmult_topk_masked``).  Candidates of query b: every entity that
+    ``allow[query_class[b]]`` admits and ``exclude[b]`` does not strike (the masks of ``distmult_rank_masked``), whose
+    score ``<q[b], emb[n]>`` - the bits ``distmult_score_all_tails`` stores - is not NaN and ``>= min_score``.  Order:
+    score descending, equal scores by id ascending; slots past the number of candidates hold id -1 and score -inf.
+    ``slices``: into how many ranges the entities are cut (0: chosen from the batch); the result does not depend on it."""
+    k, slices = int(k), int(slices)
+    if not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {TOPK_MAX_K}] (the top-k kernel keeps at most {TOPK_MAX_K} candidates per query), got {k}")
+    if slices < 0:
+        raise ValueError("slices must be >= 0 (0: chosen from the batch)")
+    _need_gpu("q", q, torch.float32)
+    _need_gpu("emb", emb, torch.float32)
+    if q.dim() != 2 or emb.dim() != 2 or emb.size(1) != q.size(1) or emb.size(0) == 0:
+        raise ValueError("q [B, d], emb [N, d] (N > 0) expected")
+    b, d = q.shape
+    if d % 32:
+        raise ValueError("embedding dim must be a multiple of 32 for the fused ranking kernel")
+    floor = float("-inf") if min_score is None else float(min_score)
+    if floor != floor:
+        raise ValueError("min_score must not be NaN")
+    w, classes = mask_words(emb.size(0)), 0
+    if (allow is None) != (query_class is None):
+        raise ValueError("allow and query_class go together")
+    if allow is not None:
+        _need_gpu("allow", allow, torch.int32)
+        _need_gpu("query_class", query_class, torch.int32)
+        classes = allow.size(0)
+        if allow.dim() != 2 or allow.size(1) != w or classes == 0 or query_class.shape != (b,):
+            raise ValueError(f"allow [C, {w}] and query_class [B] expected")
+    if exclude is not None:
+        _need_gpu("exclude", exclude, torch.int32)
+        if exclude.shape != (b, w):
+            raise ValueError(f"exclude [{b}, {w}] expected")
+    lib = _L()
+    with _on(q.device):
+        ids = torch.empty((b, k), dtype=torch.int64, device=q.device)
+        scores = torch.empty((b, k), dtype=torch.float32, device=q.device)
+        if b == 0:
+            return ids, scores
+        nbytes = int(lib.distmult_topk_workspace_bytes(b, emb.size(0), k, slices))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+        rc = lib.distmult_topk_masked(_ptr(q), _ptr(emb), _ptr(allow), _ptr(query_class), classes, _ptr(exclude), floor,
+                                      b, emb.size(0), d, k, slices, _ptr(ids), _ptr(scores), _ptr(ws), nbytes, _stream())
+    _lib.check(rc, "distmult_topk_masked")
+    return ids, scores
+
+
+def distmult_topk_filtered(q: torch.Tensor, emb: torch.Tensor, k: int, known: Optional[KnownTriples] = None,
+                           side: str = "tail", anchor_idx: Optional[torch.Tensor] = None,
+                           rel_idx: Optional[torch.Tensor] = None, allow: Optional[torch.Tensor] = None,
+                           query_class: Optional[torch.Tensor] = None, min_score: Optional[float] = None,
+                           max_mask_bytes: int = 256 << 20, slices: int = 0):
+    """``distmult_topk_masked`` over all queries with the exclude mask of ``known`` built chunk by chunk through one
+    buffer, exactly as ``distmult_rank_filtered`` does: the novel candidates - no returned id completes a known
+    triple with its query."""
+    b = q.size(0)
+    if known is None or b == 0:
+        return distmult_topk_masked(q, emb, k, allow, query_class, None, min_score, slices)
+    if anchor_idx is None or rel_idx is None:
+        raise ValueError("novel candidates need the anchor node ids and relation ids of the queries")
+    if known.num_nodes != emb.size(0):
+        raise ValueError(f"known triples are over {known.num_nodes} nodes, the candidates are {emb.size(0)}")
+    w = mask_words(emb.size(0))
+    rows = max(1, int(max_mask_bytes) // (4 * w))
+    if rows >= 64:
+        rows -= rows % 64                                        # whole row tiles of the select pass
+    rows = min(rows, b)
+    if rows >= b:
+        excl = known.exclude_bits(side, anchor_idx, rel_idx)
+        return distmult_topk_masked(q, emb, k, allow, query_class, excl, min_score, slices)
+    ids = torch.empty((b, int(k)), dtype=torch.int64, device=q.device)
+    scores = torch.empty((b, int(k)), dtype=torch.float32, device=q.device)
+    buf = torch.empty((rows, w), dtype=torch.int32, device=q.device)
+    for lo in range(0, b, rows):
+        hi = min(lo + rows, b)
+        excl = known.exclude_bits(side, anchor_idx[lo:hi], rel_idx[lo:hi], out=buf)
+        ids[lo:hi], scores[lo:hi] = distmult_topk_masked(q[lo:hi], emb, k, allow,
+                                                         None if query_class is None else query_class[lo:hi], excl,
+                                                         min_score, slices)
+    return ids, scores
+
+
 def distmult_score_all_tails(head: torch.Tensor, rel: torch.Tensor, rel_idx: Optional[torch.Tensor],
                              emb: torch.Tensor):
     """``((head * rel[rel_idx]) @ emb.T, head * rel[rel_idx])`` - the [B, N] score matrix of

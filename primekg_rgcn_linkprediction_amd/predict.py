@@ -1,0 +1,130 @@
+"""Use a trained model: the top-k candidates of ``(anchor, relation, ?)`` / ``(?, relation, anchor)`` queries.
+
+Counterpart of the question the reference's analysis scripts ask of a model - "which drugs, not already linked to
+this disease, does it rank highest?" (``case_studies.predict_top_drugs``, ``medical_validation.generate_predictions``
++ ``_filter_known_associations``, their ``--top_k``) - on the decoder's own scores: the encoder runs once, and
+``ModelEvaluator.top_candidates`` returns every query's list from one fused pass that keeps the k best allowed,
+not-known candidates while the score tiles are still in registers (no ``[B, N]`` matrix, no sort).
+
+    python -m primekg_rgcn_linkprediction_amd.predict --model_path results/models/best_model.pt \\
+        --data_dir data/processed --side tail --anchor_class 0 --relation 1 --top_k 20 --novel \\
+        --candidate_class 1 --node_types data/processed/mappings.pt --output_dir results/predictions
+
+writes ``predictions.json``: ``{"protocol": {...}, "queries": [{"anchor", "relation", "candidates": [[id, score],
+...]}]}``, best first, equal scores by id; with a ``mappings.pt`` as ``--node_types`` every query also carries
+``anchor_name`` and ``candidate_names``.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import logging
+from pathlib import Path
+from typing import Dict, Optional
+
+import torch
+
+from . import evaluate as E
+
+logger = logging.getLogger("primekg_rgcn_linkprediction_amd.predict")
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Top-k link predictions of a trained R-GCN link predictor on MI355X")
+    p.add_argument("--model_path", type=str, required=True)
+    p.add_argument("--data_dir", type=str, default="data/processed")
+    p.add_argument("--output_dir", type=str, default="results/predictions")
+    p.add_argument("--side", choices=("tail", "head"), default="tail",
+                   help="tail: complete (anchor, relation, ?); head: complete (?, relation, anchor)")
+    who = p.add_mutually_exclusive_group(required=True)
+    who.add_argument("--anchors", type=int, nargs="+", help="node ids of the queries")
+    who.add_argument("--anchor_class", type=int, help="every node of this class is a query (needs --node_types)")
+    p.add_argument("--relation", type=int, required=True, help="relation id of the queries")
+    p.add_argument("--top_k", type=int, default=10)
+    p.add_argument("--novel", action="store_true",
+                   help="leave out the candidates that form a known triple (full graph + test set) with their query")
+    p.add_argument("--candidate_class", type=int, default=None,
+                   help="only candidates of this node class (needs --node_types)")
+    p.add_argument("--node_types", type=str, default=None,
+                   help="the preprocessing's mappings.pt, or an .npz / .pt holding an int vector [num_nodes]")
+    p.add_argument("--min_score", type=float, default=None, help="only candidates with a score >= this")
+    p.add_argument("--device", type=str, default="cuda")
+    p.add_argument("--trust_checkpoint", action="store_true",
+                   help="allow the unrestricted pickle loader for --model_path (only for files you wrote yourself)")
+    return p
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if (args.anchor_class is not None or args.candidate_class is not None) and not args.node_types:
+        parser.error("--anchor_class / --candidate_class need --node_types PATH (mappings.pt, or an .npz / .pt int "
+                     "vector [num_nodes])")
+    if args.top_k < 1:
+        parser.error("--top_k must be >= 1")
+    return args
+
+
+def load_node_names(path: Optional[str]) -> Optional[Dict[int, str]]:
+    """``{node id: name}`` when ``path`` is a ``mappings.pt`` with ``idx2node`` ((id, name, type) per node), else None"""
+    if not path or str(path).endswith(".npz"):
+        return None
+    obj = torch.load(path, map_location="cpu", weights_only=True)
+    if not (isinstance(obj, dict) and "idx2node" in obj):
+        return None
+    return {int(i): str(v[1]) for i, v in obj["idx2node"].items()}
+
+
+def predict(evaluator, args: argparse.Namespace, names: Optional[Dict[int, str]] = None) -> Dict:
+    """the queries of ``args`` through ``evaluator.top_candidates`` -> the ``predictions.json`` dict"""
+    if args.anchor_class is not None:
+        if evaluator.node_class is None:
+            raise ValueError("--anchor_class needs the node classes (--node_types)")
+        anchors = torch.nonzero(evaluator.node_class.cpu() == args.anchor_class).view(-1)
+        if anchors.numel() == 0:
+            raise ValueError(f"no node has class {args.anchor_class}")
+    else:
+        anchors = torch.tensor(args.anchors, dtype=torch.int64)
+    relations = torch.full_like(anchors, args.relation)
+    ids, scores = evaluator.top_candidates(args.side, anchors, relations, args.top_k, novel=args.novel,
+                                           candidate_class=args.candidate_class, min_score=args.min_score)
+    ids, scores = ids.cpu().tolist(), scores.cpu().tolist()
+    queries = []
+    for anchor, row_ids, row_scores in zip(anchors.tolist(), ids, scores):
+        kept = [(i, s) for i, s in zip(row_ids, row_scores) if i >= 0]         # padding past the candidates dropped
+        q = {"anchor": anchor, "relation": args.relation, "candidates": [[i, s] for i, s in kept]}
+        if names is not None:
+            q["anchor_name"] = names.get(anchor)
+            q["candidate_names"] = [names.get(i) for i, _ in kept]
+        queries.append(q)
+    protocol = {"side": args.side, "top_k": args.top_k, "novel": bool(args.novel),
+                "candidate_class": args.candidate_class, "anchor_class": args.anchor_class, "min_score": args.min_score,
+                "order": "score descending, equal scores by id ascending"}
+    return {"protocol": protocol, "queries": queries}
+
+
+def save_predictions(result: Dict, output_dir) -> Path:
+    output_dir = Path(output_dir)
+    output_dir.mkdir(parents=True, exist_ok=True)
+    path = output_dir / "predictions.json"
+    with open(path, "w") as fh:
+        json.dump(result, fh, indent=2)
+    return path
+
+
+def main(argv=None) -> Dict:
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
+    args = parse_args(argv)
+    device = torch.device(args.device)
+    model, _ = E.load_model(args.model_path, device, trust_pickle=args.trust_checkpoint)
+    test_data, full_graph = E.load_test_data(args.data_dir)
+    node_class = E.load_node_classes(args.node_types, int(full_graph["num_nodes"])) if args.node_types else None
+    evaluator = E.ModelEvaluator(model, test_data, full_graph, device, node_class=node_class)
+    result = predict(evaluator, args, load_node_names(args.node_types))
+    path = save_predictions(result, args.output_dir)
+    logger.info("%d queries, top %d each, saved to: %s", len(result["queries"]), args.top_k, path)
+    return result
+
+
+if __name__ == "__main__":
+    main()
