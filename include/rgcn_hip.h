@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 27
+#define RGCN_ABI_VERSION 28
 
 enum {
   RGCN_OK = 0,
@@ -466,8 +466,10 @@ int distmult_bce_bwd(const float* grad_mean_loss, const float* scores, const flo
  * `predictions = sigmoid(scores) > 0.5`, `correct += (predictions == labels).sum()`, `total_loss += loss.item() * n` -
  * nine elementwise / reduce launches when written in torch): mean_loss[0] = mean(loss[0..batch)) in a fixed order (two
  * runs give the same bits); loss_sum[0] += (double)mean * batch and correct[0] += #{b : (scores[b] > 0) == (labels[b] >
- * 0.5)} - the epoch's running sums, device-resident, either may be NULL; cursor[0] += cursor_add - the position of the
- * next batch in the epoch's permutation (rgcn_sample_batch reads it), NULL to leave it alone. */
+ * 0.5)} (the sign of the score: the reference's expression for every score outside 0 < s < 2^-23; inside that window
+ * fp32 sigmoid may round to exactly 0.5, and where it does the reference predicts 0 and this kernel 1) - the epoch's
+ * running sums, device-resident, either may be NULL; cursor[0] += cursor_add - the position of the next batch in the
+ * epoch's permutation (rgcn_sample_batch reads it), NULL to leave it alone. */
 int distmult_bce_reduce(const float* loss, const float* scores, const float* labels, int64_t batch, float* mean_loss,
                         double* loss_sum, int64_t* correct, int64_t* cursor, int64_t cursor_add, void* stream);
 
@@ -502,6 +504,8 @@ int rgcn_sample_batch(const int64_t* edge_index, const int64_t* edge_type, int64
  * params / grads / exp_avg / exp_avg_sq / steps: HOST arrays of `num_tensors` DEVICE pointers (the
  * pointers travel in the launch arguments, so a captured HIP graph keeps working on them); steps[t]:
  * DEVICE float[1], torch's per-tensor step count, bumped by one per call on the device.
+ * beta1 / beta2 are doubles because torch rounds `1 - beta` to fp32 from the double difference (1.f - 0.999f is
+ * 1.3e-5 away from it, and exp_avg_sq would be too); every other scalar is used as fp32.
  * total_norm: DEVICE float[1] or NULL.  workspace: rgcn_adam_workspace_bytes(num_tensors, numels).
  * amax_out (round 4; HOST array of `num_tensors` DEVICE amax buffers, entries or the array itself may be NULL): the
  * update leaves max |params[t]| AFTER the step in amax_out[t] (the heads it publishes into are cleared by the first
@@ -511,7 +515,7 @@ int rgcn_sample_batch(const int64_t* edge_index, const int64_t* edge_type, int64
 size_t rgcn_adam_workspace_bytes(int num_tensors, const int64_t* numels);
 int rgcn_adam_clip_step(int num_tensors, float* const* params, const float* const* grads,
                         float* const* exp_avg, float* const* exp_avg_sq, float* const* steps,
-                        const int64_t* numels, float lr, float beta1, float beta2, float eps,
+                        const int64_t* numels, float lr, double beta1, double beta2, float eps,
                         float weight_decay, int adamw, float max_norm, float* total_norm,
                         float* const* amax_out, void* workspace, size_t workspace_bytes, void* stream);
 

@@ -249,6 +249,10 @@ __global__ __launch_bounds__(64) void k_segment_combine(const float* __restrict_
 // adds elements i, i + 1024, ... , then a fixed tree - two runs give the same bits), the epoch's running sums
 // (src/train.py:321-326: `predictions = sigmoid(scores) > 0.5`, `correct += (predictions == labels).sum()`,
 // `total_loss += loss.item() * labels.size(0)`) kept on the device, and the batch cursor moved on.
+// The prediction here is the SIGN of the score, `s > 0` (NaN and both zeros predict 0).  That is the reference's
+// expression for every score outside 0 < s < 2^-23.  Inside that window fp32 sigmoid(s) may round to exactly 0.5
+// (torch's does up to about 6e-8) and the reference then predicts 0: the kernel predicts 1 (it does not reproduce
+// the rounding of torch's expf).
 __global__ __launch_bounds__(1024) void k_bce_reduce(const float* __restrict__ loss, const float* __restrict__ scores,
                                                      const float* __restrict__ labels, int B, float* __restrict__ mean_loss,
                                                      double* __restrict__ loss_sum, long long* __restrict__ correct,

@@ -82,7 +82,8 @@ __global__ __launch_bounds__(kThreads) void k_sumsq(const AdamList L, float* __r
 
 __global__ __launch_bounds__(kThreads) void k_adam_update(const AdamList L, const float* __restrict__ partial,
                                                           int num_partials, float lr, float beta1, float beta2,
-                                                          float eps, float weight_decay, int adamw, float max_norm,
+                                                          float one_minus_beta1, float one_minus_beta2, float eps,
+                                                          float weight_decay, int adamw, float max_norm,
                                                           float* __restrict__ out_norm) {
   __shared__ float red[kThreads];
   float coef = 1.f;
@@ -107,8 +108,8 @@ __global__ __launch_bounds__(kThreads) void k_adam_update(const AdamList L, cons
     gg *= coef;
     if (adamw) pp *= 1.f - lr * weight_decay;
     else if (weight_decay != 0.f) gg += weight_decay * pp;
-    mm = mm + (gg - mm) * (1.f - beta1);                      // exp_avg.lerp_(grad, 1 - beta1)
-    vv = beta2 * vv + (1.f - beta2) * gg * gg;                // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    mm = mm + (gg - mm) * one_minus_beta1;                    // exp_avg.lerp_(grad, 1 - beta1)
+    vv = beta2 * vv + one_minus_beta2 * gg * gg;              // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
     const float denom = sqrtf(vv) / bc2_sqrt + eps;
     pp -= step_size * (mm / denom);
   };
@@ -167,13 +168,13 @@ size_t rgcn_adam_workspace_bytes(int num_tensors, const int64_t* numels) {
 }
 
 int rgcn_adam_clip_step(int num_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
-                        float* const* exp_avg_sq, float* const* steps, const int64_t* numels, float lr, float beta1,
-                        float beta2, float eps, float weight_decay, int adamw, float max_norm, float* total_norm,
+                        float* const* exp_avg_sq, float* const* steps, const int64_t* numels, float lr, double beta1,
+                        double beta2, float eps, float weight_decay, int adamw, float max_norm, float* total_norm,
                         float* const* amax_out, void* workspace, size_t workspace_bytes, void* stream_) {
   if (num_tensors < 0 || num_tensors > kMaxTensors) return num_tensors < 0 ? RGCN_ERR_ARG : RGCN_ERR_UNSUPPORTED;
   if (num_tensors == 0) return RGCN_OK;
   if (!params || !grads || !exp_avg || !exp_avg_sq || !steps || !numels) return RGCN_ERR_ARG;
-  if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f))
+  if (!(lr >= 0.f) || !(beta1 >= 0. && beta1 < 1.) || !(beta2 >= 0. && beta2 < 1.) || !(eps >= 0.f))
     return RGCN_ERR_ARG;
   AdamList L;
   int blocks = 0;
@@ -194,7 +195,10 @@ int rgcn_adam_clip_step(int num_tensors, float* const* params, const float* cons
   hipStream_t stream = (hipStream_t)stream_;
   float* partial = (float*)workspace;
   k_sumsq<<<blocks, kThreads, 0, stream>>>(L, partial);
-  k_adam_update<<<blocks, kThreads, 0, stream>>>(L, partial, blocks, lr, beta1, beta2, eps, weight_decay, adamw,
+  // torch forms `1 - beta` in double and rounds the difference to fp32 once: 1 - 0.999 becomes 0.0010000000475, where
+  // 1.f - 0.999f is 0.0009999871 (1.3e-5 off, and exp_avg_sq with it).  Hence betas in double up to here.
+  k_adam_update<<<blocks, kThreads, 0, stream>>>(L, partial, blocks, lr, (float)beta1, (float)beta2,
+                                                 (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, adamw,
                                                  max_norm, total_norm);
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;

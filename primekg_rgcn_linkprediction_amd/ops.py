@@ -1438,9 +1438,11 @@ def adam_clip_step(params, grads, exp_avgs, exp_avg_sqs, steps, lr: float, beta1
     ``torch.optim.Adam`` / ``AdamW`` step, in two launches (``rgcn_adam_clip_step``).  All lists
     are parallel, fp32, contiguous CUDA tensors; ``steps[t]`` is the one-element device step count of
     tensor t (bumped here).  Parameters and moments are updated in place; gradients are left as
-    they are (the clipped values are used, not stored).  ``amax_out``: per tensor an amax buffer (or None) that
-    receives ``max |param|`` after the update (its written heads are cleared by the first launch; allocate it with
-    ``amax_buffer``) - the scales the next step's transforms would otherwise scan for."""
+    they are (the clipped values are used, not stored).  The betas reach the library as doubles: like torch it
+    rounds ``1 - beta`` to fp32 from the double difference, so both moments follow torch's to rounding.
+    ``amax_out``: per tensor an amax buffer (or None) that receives ``max |param|`` after the update (its written
+    heads are cleared by the first launch; allocate it with ``amax_buffer``) - the scales the next step's transforms
+    would otherwise scan for."""
     n = len(params)
     if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(steps) == n):
         raise ValueError("params, grads, exp_avgs, exp_avg_sqs and steps must be equally long")
@@ -1584,7 +1586,12 @@ def distmult_bce_reduce(loss: torch.Tensor, scores: torch.Tensor, labels: torch.
                         cursor=None, cursor_add: int = 0) -> torch.Tensor:
     """-> ``mean(loss)`` as a one-element tensor, in ONE launch together with the epoch's device-resident running sums
     (``loss_sum`` float64 [] += mean * B, ``correct`` int64 [] += #{(scores > 0) == (labels > 0.5)}) and the batch cursor
-    (``cursor`` int64 [1] += cursor_add) - ``src/train.py:300, 321-326``; any of the three may be None."""
+    (``cursor`` int64 [1] += cursor_add) - ``src/train.py:300, 321-326``; any of the three may be None.
+
+    The hit rule is the sign of the score.  It equals the reference's ``(sigmoid(scores) > 0.5) == labels`` for every
+    score (zeros of both signs, infinities and NaN included) outside ``0 < s < 2**-23``.  Only inside that window can the
+    two differ: fp32 ``sigmoid`` may round to exactly 0.5 there (torch's does up to about 6e-8, no longer at 1e-7), and
+    where it does the reference predicts 0 while this kernel predicts 1."""
     _need_gpu("loss", loss, torch.float32)
     b = loss.numel()
     if correct is not None:

@@ -394,6 +394,9 @@ def test_fused_clip_adam_equals_torch(adamw, wd, clip):
     for a, b in zip(m, ref):
         st = opt.state[b]
         assert (a - st["exp_avg"]).abs().max().item() <= 1e-6 * max(1.0, st["exp_avg"].abs().max().item())
+    for a, b in zip(v, ref):
+        st = opt.state[b]
+        assert (a - st["exp_avg_sq"]).abs().max().item() <= 1e-6 * max(1.0, st["exp_avg_sq"].abs().max().item())
     with pytest.raises(ValueError):
         ops.adam_clip_step(got, grads[:-1], m, v, steps, 1e-2, 0.9, 0.999, 1e-8)
     with pytest.raises(ValueError):
