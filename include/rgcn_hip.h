@@ -615,6 +615,8 @@ int rgcn_basis_compose_bwd(const float* grad_weight, const float* comp, const fl
  * allocated, nothing synchronises: capturable like the calls it forwards to.
  * ---------------------------------------------------------------------------------- */
 enum { RGCN_SEQ_IMM = 0, RGCN_SEQ_FLOAT = 1, RGCN_SEQ_BASE = 2, RGCN_SEQ_JOB = 3, RGCN_SEQ_STREAM = 4, RGCN_SEQ_ARRAY = 5 };
+/* limits: arguments of one call, job slots of a run, HOST arrays of one call, entries of one such array */
+enum { RGCN_SEQ_MAX_ARGS = 32, RGCN_SEQ_MAX_JOBS = 8, RGCN_SEQ_MAX_ARRAYS = 12, RGCN_SEQ_MAX_ARRAY_ENTRIES = 8 };
 enum {
   RGCN_FN_ABSMAX = 0, RGCN_FN_ABSMAX_MULTI, RGCN_FN_ABSMAX_PACK, RGCN_FN_WEIGHTS_SPLIT_PACK_MULTI, RGCN_FN_AGGREGATE,
   RGCN_FN_AGGREGATE_AND_REDUCE, RGCN_FN_AGGREGATE_AMAX, RGCN_FN_AGGREGATE_DEFERRED, RGCN_FN_TRANSFORM_FWD_SPLIT,

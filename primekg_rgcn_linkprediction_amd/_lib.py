@@ -45,12 +45,15 @@ class SeqCall(ctypes.Structure):
 
 
 SEQ_IMM, SEQ_FLOAT, SEQ_BASE, SEQ_JOB, SEQ_STREAM, SEQ_ARRAY = range(6)
-# entry points rgcn_sequence_run can forward to (RGCN_FN_* of the header, in its order)
-SEQ_FUNCTIONS = ("rgcn_absmax", "rgcn_absmax_multi", "rgcn_absmax_pack", "rgcn_weights_split_pack_multi", "rgcn_aggregate",
-                 "rgcn_aggregate_and_reduce", "rgcn_aggregate_amax", "rgcn_aggregate_deferred", "rgcn_transform_fwd_split",
-                 "rgcn_transform_bwd_input_split", "rgcn_transform_first_split", "rgcn_transform_bwd_params_split_begin",
-                 "rgcn_slab_reduce", "rgcn_layer_fwd_fused", "rgcn_layer_bwd_input_fused",
-                 "rgcn_transform_bwd_input_chain_split")
+SEQ_MAX_JOBS = 8    # RGCN_SEQ_MAX_JOBS
+# entry points rgcn_sequence_run can forward to, in the header's RGCN_FN_* order: name -> position of `void* stream`
+SEQ_FUNCTIONS = {
+    "rgcn_absmax": 5, "rgcn_absmax_multi": 6, "rgcn_absmax_pack": 13, "rgcn_weights_split_pack_multi": 12,
+    "rgcn_aggregate": 7, "rgcn_aggregate_and_reduce": 8, "rgcn_aggregate_amax": 9, "rgcn_aggregate_deferred": 8,
+    "rgcn_transform_fwd_split": 20, "rgcn_transform_bwd_input_split": 19, "rgcn_transform_first_split": 12,
+    "rgcn_transform_bwd_params_split_begin": 18, "rgcn_slab_reduce": 1, "rgcn_layer_fwd_fused": 17,
+    "rgcn_layer_bwd_input_fused": 17, "rgcn_transform_bwd_input_chain_split": 18,
+}
 # their HOST array parameters: position -> (entries are device pointers?, position of the parameter holding the count)
 SEQ_HOST_ARRAYS = {
     "rgcn_absmax_multi": {1: (True, 0), 2: (False, 0), 3: (True, 0)},

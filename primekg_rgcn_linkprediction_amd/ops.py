@@ -1968,11 +1968,6 @@ class _NotRecordable(Exception):
 
 
 _SEQ_INDEX = {name: i for i, name in enumerate(_lib.SEQ_FUNCTIONS)}
-_SEQ_STREAM_POS = {"rgcn_absmax": 5, "rgcn_absmax_multi": 6, "rgcn_absmax_pack": 13, "rgcn_weights_split_pack_multi": 12,
-                   "rgcn_aggregate": 7, "rgcn_aggregate_and_reduce": 8, "rgcn_aggregate_amax": 9, "rgcn_aggregate_deferred": 8,
-                   "rgcn_transform_fwd_split": 20, "rgcn_transform_bwd_input_split": 19, "rgcn_transform_first_split": 12,
-                   "rgcn_transform_bwd_params_split_begin": 18, "rgcn_slab_reduce": 1, "rgcn_layer_fwd_fused": 17,
-                   "rgcn_layer_bwd_input_fused": 17, "rgcn_transform_bwd_input_chain_split": 18}
 _SEQ_PURE = ("rgcn_graph_tile_mask", "rgcn_graph_num_levels", "rgcn_graph_weight_bound", "rgcn_aggregate_deferrable",
              "rgcn_graph_num_edges", "rgcn_graph_num_nodes", "rgcn_graph_num_relations", "rgcn_abi_version", "rgcn_strerror")
 REGIONS = True      # False: always through the wrappers (tests, tools/host_profile.py)
@@ -1992,6 +1987,13 @@ def _strides(shape):
     return tuple(reversed(st))
 
 
+def _nbytes(shape, dtype) -> int:
+    n = 1
+    for s in shape:
+        n *= s
+    return n * torch.empty((), dtype=dtype).element_size()
+
+
 class Lazy:
     """a tensor of a replayed pass that nobody has looked at yet: arena + offset (``.tensor()`` makes the view - one
     ``as_strided`` on the arena's float32 alias, which the pass's outputs share)"""
@@ -2008,10 +2010,7 @@ class Lazy:
             if self.dtype == torch.float32 and self.alias is not None and self.offset % 4 == 0:
                 self._t = torch.as_strided(self.alias, self.shape, _strides(self.shape), self.offset // 4)
             else:
-                n = 1
-                for s in self.shape:
-                    n *= s
-                nbytes = n * torch.empty((), dtype=self.dtype).element_size() if n else 0
+                nbytes = _nbytes(self.shape, self.dtype)
                 self._t = self.arena[self.offset: self.offset + nbytes].view(self.dtype).view(self.shape)
         return self._t
 
@@ -2073,10 +2072,7 @@ class _Recorder:
 
     def alloc(self, shape, dtype, device):
         shape = tuple(int(s) for s in shape)
-        n = 1
-        for s in shape:
-            n *= s
-        nbytes = n * torch.empty((), dtype=dtype).element_size()
+        nbytes = _nbytes(shape, dtype)
         if not self.recording:
             self.sizes.append(nbytes)
             t = torch.empty(shape, dtype=dtype, device=device)
@@ -2116,7 +2112,7 @@ class _Recorder:
         arrays = _lib.SEQ_HOST_ARRAYS.get(name, {})
         descs = []
         for i, (a, ty) in enumerate(zip(args, proto)):
-            if i == _SEQ_STREAM_POS[name]:
+            if i == _lib.SEQ_FUNCTIONS[name]:
                 descs.append((_lib.SEQ_STREAM, 0, 0))
             elif i in arrays:
                 is_ptr, cnt_pos = arrays[i]
@@ -2159,10 +2155,7 @@ class _Plan:
             if spec is None or spec[0] != "arena":
                 continue
             off, shape, dtype = spec[1], spec[2], spec[3]
-            n = 1
-            for d in shape:
-                n *= d
-            nbytes = n * torch.empty((), dtype=dtype).element_size()
+            nbytes = _nbytes(shape, dtype)
             if nbytes and spans.get(off) == nbytes:
                 if off not in ext_of:
                     ext_of[off] = len(self.external)
@@ -2217,14 +2210,7 @@ class _Plan:
                 self._small_off.append(None)
         self._small = sum(o is not None for o in self._small_off) >= 2
         self._small_f32 = all(dt == torch.float32 for o, (_, _, _, dt) in zip(self._small_off, self.external) if o is not None)
-
-        def dense_strides(shape):
-            st, acc = [], 1
-            for dim in reversed(shape):
-                st.append(acc)
-                acc *= dim
-            return tuple(reversed(st))
-        self._small_strides = [dense_strides(shape) for _, _, shape, _ in self.external]
+        self._small_strides = [_strides(shape) for _, _, shape, _ in self.external]
         # what the recorded addresses stand for: a later call whose inputs differ in type, shape or place must not be
         # replayed (the wrappers would have refused it; the native list would read the wrong bytes)
         self.signature = rec.input_signature
@@ -2369,7 +2355,7 @@ class Region:
             else:
                 store[full_key] = self.DISABLED              # an output the record cannot place
                 return outs
-        if rec.cursor != len(rec.sizes) or len(rec.jobs) > 8:
+        if rec.cursor != len(rec.sizes) or len(rec.jobs) > _lib.SEQ_MAX_JOBS:
             store[full_key] = self.DISABLED
             return outs
         plan = _Plan(rec, specs, want)

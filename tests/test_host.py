@@ -12,11 +12,20 @@ from primekg_rgcn_linkprediction_amd import (DrugDiseaseModel, DrugDiseaseRGCN, 
 
 
 # ------------------------------------------------------------------ C ABI surface
-def _declared_functions():
+def _header_text():
     text = open(os.path.join(ROOT, "include", "rgcn_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    names = re.findall(r"\b([a-z_0-9]+)\s*\([^;{]*\)\s*;", text)
-    return sorted(set(n for n in names if n.startswith(("rgcn_", "distmult_"))))
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+def _declared_prototypes():
+    """name -> list of parameter declarations, for every function include/rgcn_hip.h declares"""
+    found = re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", _header_text())
+    return {name: [] if params.strip() == "void" else [" ".join(p.split()) for p in params.split(",")]
+            for name, params in found if name.startswith(("rgcn_", "distmult_"))}
+
+
+def _declared_functions():
+    return sorted(_declared_prototypes())
 
 
 def test_library_loads_and_exports_every_declared_symbol():
@@ -73,6 +82,79 @@ def test_null_handle_and_bad_args_return_codes_without_a_gpu():
     assert lib.rgcn_sample_batch(None, None, 10, None, None, 4, 1, 0, None, None, None, None, None, None) == E
     assert lib.rgcn_sample_batch(None, None, 10, None, None, 4, 1, 100, None, None, None, None, None, None) == E
     assert lib.rgcn_sample_batch(None, None, 10, None, None, 0, 1, 100, None, None, None, None, None, None) == _lib.RGCN_OK
+
+
+def _kind_in_header(param):
+    if "*" in param:
+        return "pointer"
+    return next(k for k in ("float", "double", "size_t", "int64_t", "int") if re.search(rf"\b{k}\b", param))
+
+
+def _kind_in_ctypes(ty):
+    import ctypes
+    kinds = {ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_size_t: "size_t", ctypes.c_int64: "int64_t",
+             ctypes.c_int: "int"}
+    if ty in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ty, ctypes._Pointer):
+        return "pointer"
+    return kinds[ty]
+
+
+def test_ctypes_prototypes_match_the_header_parameter_by_parameter():
+    """count and, position by position, kind (pointer / float / double / size_t / int64_t / int) of EVERY declared
+    function: a ctypes prototype that drifts from the header passes a wrong pointer or size without any error"""
+    declared = _declared_prototypes()
+    assert len(declared) >= 71 and sorted(declared) == sorted(_lib.PROTOTYPES)
+    for name, params in declared.items():
+        argtypes = _lib.PROTOTYPES[name][1]
+        assert len(argtypes) == len(params), name
+        for i, (param, ty) in enumerate(zip(params, argtypes)):
+            assert _kind_in_ctypes(ty) == _kind_in_header(param), f"{name}: parameter {i} ({param})"
+
+
+def test_sequence_tables_match_the_header():
+    """what rgcn_sequence_run's host side still writes down by hand, held to include/rgcn_hip.h: the forwarded
+    functions in RGCN_FN_* order, each one's `void* stream` position, which HOST arrays hold device pointers, and
+    the job limit"""
+    text, declared = _header_text(), _declared_prototypes()
+    fns = re.search(r"enum\s*\{\s*(RGCN_FN_ABSMAX\b[^}]*)\}", text).group(1)
+    fns = [f.split("=")[0].strip() for f in fns.split(",")]
+    assert fns[-1] == "RGCN_FN_COUNT" and len(fns) == 17
+    assert list(_lib.SEQ_FUNCTIONS) == ["rgcn_" + f[len("RGCN_FN_"):].lower() for f in fns[:-1]]
+    for name, stream_pos in _lib.SEQ_FUNCTIONS.items():
+        assert [i for i, p in enumerate(declared[name]) if p == "void* stream"] == [stream_pos], name
+    assert set(_lib.SEQ_HOST_ARRAYS) <= set(_lib.SEQ_FUNCTIONS)
+    for name, arrays in _lib.SEQ_HOST_ARRAYS.items():
+        params = declared[name]
+        for pos, (is_ptr, cnt_pos) in arrays.items():
+            assert "*" in params[pos] and is_ptr == (params[pos].count("*") == 2), f"{name}: parameter {pos} ({params[pos]})"
+            assert _kind_in_header(params[cnt_pos]) == "int", f"{name}: parameter {cnt_pos} ({params[cnt_pos]})"
+    assert int(re.search(r"RGCN_SEQ_MAX_JOBS\s*=\s*(\d+)", text).group(1)) == _lib.SEQ_MAX_JOBS
+
+
+def test_sequence_run_forwards_every_entry_point_with_its_own_argument_count():
+    """the REAL library, no device needed: one recorded call per forwarded function with all-zero arguments (null
+    pointers, a job slot where the prototype takes a job) is refused or accepted by the entry point exactly as the
+    direct call is - so it arrived there - and one argument less or more never reaches it"""
+    import ctypes
+    lib = _lib.load()
+    job_ptr = ctypes.POINTER(_lib.SlabJob)
+    direct_codes = {}
+    for fn, (name, stream_pos) in enumerate(_lib.SEQ_FUNCTIONS.items()):
+        proto = _lib.PROTOTYPES[name][1]
+        direct = getattr(lib, name)(*[ctypes.byref(_lib.SlabJob()) if ty is job_ptr else
+                                      None if _kind_in_ctypes(ty) == "pointer" else 0 for ty in proto])
+        direct_codes[name] = direct
+        args = (_lib.SeqArg * (len(proto) + 1))()
+        for i, ty in enumerate(proto):
+            args[i].kind = (_lib.SEQ_JOB if ty is job_ptr else _lib.SEQ_STREAM if i == stream_pos else
+                            _lib.SEQ_FLOAT if ty is ctypes.c_float else _lib.SEQ_IMM)
+        for n, expected in ((len(proto), direct), (len(proto) - 1, _lib.RGCN_ERR_ARG), (len(proto) + 1, _lib.RGCN_ERR_ARG)):
+            call = _lib.SeqCall(fn, n, 0)
+            got = lib.rgcn_sequence_run(ctypes.byref(call), 1, args, len(args), None, 0, None)
+            assert got == expected, f"{name} with {n} of {len(proto)} arguments"
+    assert sorted(direct_codes.values()) == [_lib.RGCN_ERR_UNSUPPORTED] + [_lib.RGCN_ERR_ARG] * 14 + [_lib.RGCN_OK]
+    call = _lib.SeqCall(len(_lib.SEQ_FUNCTIONS), 0, 0)
+    assert lib.rgcn_sequence_run(ctypes.byref(call), 1, args, len(args), None, 0, None) == _lib.RGCN_ERR_UNSUPPORTED
 
 
 def test_missing_library_fails_loudly(monkeypatch):
