@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 28
+#define RGCN_ABI_VERSION 29
 
 enum {
   RGCN_OK = 0,
@@ -121,7 +121,7 @@ int rgcn_graph_import(int64_t num_edges, int64_t num_nodes, int64_t num_relation
                       const float* w_t, void* stream, rgcn_graph** out);
 
 /* A pending fixed-order reduction of parameter-gradient slabs (filled by
- * rgcn_transform_bwd_params_begin, consumed by rgcn_slab_reduce or rgcn_aggregate_and_reduce). */
+ * rgcn_transform_bwd_params_begin, consumed by rgcn_slab_reduce or rgcn_aggregate_ex). */
 typedef struct rgcn_slab_job {
   const float* slab;
   const float* bias_part;
@@ -144,21 +144,26 @@ typedef struct rgcn_slab_job {
  * 64 edges, four runs to a pack, packs reduced in order), so the result is run-to-run
  * deterministic.  `workspace` holds one partial row per pack of the segments longer than 256
  * edges: rgcn_aggregate_workspace_bytes(g, t, d).
+ *
+ * rgcn_aggregate_ex is the same gather with options; rgcn_aggregate is it with none of them (fp32 table, all
+ * levels, no job, no amax):
+ *   x_f16 != 0   the gathered table is IEEE fp16 (x: half[N, d], d % 8 == 0): half the bytes per gathered row
+ *                (BASELINE.json configs[4], "fp16 features + fp32 accumulate").  Sums, agg and the workspace stay
+ *                fp32.  amax must be NULL (RGCN_ERR_UNSUPPORTED otherwise).
+ *   first_level, last_level
+ *                only the launches (tree levels) [first_level, last_level) of rgcn_graph_num_levels are issued;
+ *                last_level < 0: all from first_level on.  The levels called in order equal one call, which lets a
+ *                profiler bracket the level-0 gather kernel by itself.  Levels [0, 1) alone leave the segments longer
+ *                than 256 edges as partial rows in `workspace` (which the caller keeps alive), to be summed by the
+ *                split-precision transform that consumes the aggregate (hub_graph / hub_partial of
+ *                rgcn_transform_fwd_split / _bwd_input_split): one launch less per gather.  That transform needs
+ *                rgcn_aggregate_deferrable: exactly one reduce level (every segment <= 131,072 edges) and d 64, 128 or 256.
+ *   job          NULL or a pending slab reduction (see rgcn_transform_bwd_params_begin; slab == NULL: nothing pending;
+ *                a malformed one: RGCN_ERR_ARG).  It rides in the level-0 launch as extra workgroups when that launch
+ *                is the fp32 gather's 1-D grid (fp32 table, first_level == 0 < last_level, d <= 256, level 0 not
+ *                empty); otherwise it is launched by itself first, also where there is nothing to gather.
+ *   amax         NULL or an amax buffer (below) zeroed by the caller: every level launched publishes max |agg| there.
  * ---------------------------------------------------------------------------------- */
-size_t rgcn_aggregate_workspace_bytes(const rgcn_graph* g, int transposed, int64_t d);
-int rgcn_aggregate(const rgcn_graph* g, int transposed, const float* x, int64_t d, float* agg,
-                   void* workspace, size_t workspace_bytes, void* stream);
-/* rgcn_aggregate whose level-0 launch also performs a pending slab reduction (see
- * rgcn_transform_bwd_params_begin) as extra workgroups; `job` may be NULL.  For row widths the
- * gather splits over a second grid dimension (d > 256) the reduction is launched by itself first. */
-int rgcn_aggregate_and_reduce(const rgcn_graph* g, int transposed, const float* x, int64_t d,
-                              float* agg, void* workspace, size_t workspace_bytes,
-                              const rgcn_slab_job* job, void* stream);
-/* The same with the gathered table stored as IEEE fp16 (x_f16: half[N, d], d % 8 == 0) and fp32
- * accumulation / output: half the bytes per gathered row (BASELINE.json configs[4], "fp16
- * features + fp32 accumulate").  agg and the workspace stay fp32. */
-int rgcn_aggregate_f16(const rgcn_graph* g, int transposed, const void* x_f16, int64_t d, float* agg,
-                       void* workspace, size_t workspace_bytes, void* stream);
 /* "amax buffer": DEVICE float[RGCN_AMAX_FLOATS]; its VALUE, max |tensor|, is the maximum over its 256 "heads"
  * (entries 0, 8, 16, ...; the other entries are never touched).  Kernels that produce a tensor publish wave
  * maxima into 64 of the heads, 128 bytes apart, with an atomic max on the bit pattern (order-free, so the value
@@ -166,23 +171,13 @@ int rgcn_aggregate_f16(const rgcn_graph* g, int transposed, const void* x_f16, i
  * such a producer runs (rgcn_absmax clears buffers on the side).  The split-precision transforms below scale
  * their operands by it. */
 #define RGCN_AMAX_FLOATS 2048
-/* rgcn_aggregate_and_reduce that also leaves max |agg| in the amax buffer `amax` (zeroed by the caller). */
-int rgcn_aggregate_amax(const rgcn_graph* g, int transposed, const float* x, int64_t d, float* agg,
-                        void* workspace, size_t workspace_bytes, const rgcn_slab_job* job, float* amax,
-                        void* stream);
-/* The gather WITHOUT its hub-tail launch: segments longer than 256 edges are left as partial rows in `workspace`
- * (which the caller keeps alive), to be summed by the split-precision transform that consumes the aggregate
- * (hub_graph / hub_partial arguments of rgcn_transform_fwd_split / _bwd_input_split) - one launch less per
- * gather.  deferrable: 1 if the structure has exactly one reduce level (every segment <= 131,072 edges) and d is
- * 64, 128 or 256.  job: as rgcn_aggregate_and_reduce (NULL: none). */
+size_t rgcn_aggregate_workspace_bytes(const rgcn_graph* g, int transposed, int64_t d);
 int rgcn_aggregate_deferrable(const rgcn_graph* g, int transposed, int64_t d);
-int rgcn_aggregate_deferred(const rgcn_graph* g, int transposed, const float* x, int64_t d, float* agg,
-                            void* workspace, size_t workspace_bytes, const rgcn_slab_job* job, void* stream);
-/* One launch of the above (level in [0, rgcn_graph_num_levels)); calling the levels in order
- * equals rgcn_aggregate.  Lets a profiler bracket the level-0 gather kernel by itself. */
-int rgcn_aggregate_level(const rgcn_graph* g, int transposed, int level, const float* x, int64_t d,
-                         float* agg, void* workspace, size_t workspace_bytes, float* amax /* or NULL */,
-                         void* stream);
+int rgcn_aggregate(const rgcn_graph* g, int transposed, const float* x, int64_t d, float* agg,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int rgcn_aggregate_ex(const rgcn_graph* g, int transposed, const void* x, int x_f16, int64_t d, float* agg,
+                      void* workspace, size_t workspace_bytes, int first_level, int last_level /* < 0: all */,
+                      const rgcn_slab_job* job /* or NULL */, float* amax /* or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Per-relation transform + root + bias (row A6), fp32 MFMA (v_mfma_f32_32x32x2_f32):
@@ -236,7 +231,7 @@ int rgcn_transform_bwd_params(const float* agg, const float* x, const float* g,
  * launch boundaries: `_begin` launches the slab GEMM and describes the pending reduction in `*job`
  * (plain pointers into `workspace` and the three outputs; nothing is owned); the reduction then
  * either runs by itself (rgcn_slab_reduce) or rides as extra workgroups of the transposed gather
- * that follows in a layer's backward and does not depend on it (rgcn_aggregate_and_reduce).
+ * that follows in a layer's backward and does not depend on it (rgcn_aggregate_ex's job).
  * `workspace` and the outputs must stay alive until that launch. */
 int rgcn_transform_bwd_params_begin(const float* agg, const float* x, const float* g,
                                     const uint32_t* tile_mask, int64_t num_nodes, int64_t num_relations,
@@ -256,11 +251,11 @@ int rgcn_slab_reduce(const rgcn_slab_job* job, void* stream);
  * The aggregate operand (agg / gagg) is scaled by a BOUND on its magnitude, agg_amax_mul * value(agg_amax):
  * pass the amax buffer of the table the aggregate was gathered FROM and the structure's
  * rgcn_graph_weight_bound (1 for a mean: a mean of rows cannot exceed the table's maximum) - no pass over
- * the aggregate, no atomics in the gather; or the aggregate's own maximum (rgcn_aggregate_amax) and 1.
+ * the aggregate, no atomics in the gather; or the aggregate's own maximum (rgcn_aggregate_ex's amax) and 1.
  * The second operand (x / g) is scaled by its own maximum; the accumulator is carried from the one scale
  * to the other where the k loop passes between the operands (powers of two: exact).
- * *_amax arguments: an amax buffer (see rgcn_aggregate_amax) holding max |operand| as left by the operand's producer
- * (rgcn_aggregate_amax, rgcn_absmax, or the out_amax / grad_x_amax of a previous transform); NULL makes
+ * *_amax arguments: an amax buffer (see RGCN_AMAX_FLOATS) holding max |operand| as left by the operand's producer
+ * (rgcn_aggregate_ex, rgcn_absmax, or the out_amax / grad_x_amax of a previous transform); NULL makes
  * the call scan that operand itself (one extra pass over it).  out_amax / grad_x_amax (or NULL):
  * receives max |result| (zeroed by the caller).  Shapes outside the kernels' tiling (d_in resp. d_out
  * not a multiple of 32; 64 for the parameter gradients) return RGCN_ERR_UNSUPPORTED: use the fp32 calls.
@@ -304,7 +299,7 @@ int rgcn_absmax_pack(const float* x, int64_t numel, float* x_amax, float* zero_b
                      void* stream);
 size_t rgcn_transform_split_workspace_bytes(int64_t num_relations, int64_t d_in, int64_t d_out);
 /* hub_graph / hub_transposed / hub_partial (NULL / 0 / NULL: the aggregate operand is complete): the operand came
- * from rgcn_aggregate_deferred over that structure and direction, with hub_partial its workspace - the transform
+ * from rgcn_aggregate_ex stopped at level 1 over that structure and direction, with hub_partial its workspace - the transform
  * finishes the hub rows of each 64-row tile itself before reading it (and writes them into the aggregate, which
  * is therefore complete once the call has run).  Needs agg_amax / gagg_amax (an unfinished operand cannot be
  * scanned). */
@@ -355,7 +350,7 @@ int rgcn_transform_first_split(const float* g, const void* packed, int has_root,
 size_t rgcn_transform_bwd_params_split_workspace_bytes(int64_t num_nodes, int64_t num_relations,
                                                        int64_t d_in, int64_t d_out);
 /* slab GEMM in split precision; the pending fixed-order reduction is consumed exactly like the one of
- * rgcn_transform_bwd_params_begin (rgcn_slab_reduce / rgcn_aggregate_and_reduce / rgcn_aggregate_amax) */
+ * rgcn_transform_bwd_params_begin (rgcn_slab_reduce / rgcn_aggregate_ex) */
 int rgcn_transform_bwd_params_split_begin(const float* agg, const float* x, const float* g,
                                           const uint32_t* tile_mask, int64_t num_nodes, int64_t num_relations,
                                           int64_t d_in, int64_t d_out, const float* agg_amax,
@@ -619,7 +614,7 @@ enum { RGCN_SEQ_IMM = 0, RGCN_SEQ_FLOAT = 1, RGCN_SEQ_BASE = 2, RGCN_SEQ_JOB = 3
 enum { RGCN_SEQ_MAX_ARGS = 32, RGCN_SEQ_MAX_JOBS = 8, RGCN_SEQ_MAX_ARRAYS = 12, RGCN_SEQ_MAX_ARRAY_ENTRIES = 8 };
 enum {
   RGCN_FN_ABSMAX = 0, RGCN_FN_ABSMAX_MULTI, RGCN_FN_ABSMAX_PACK, RGCN_FN_WEIGHTS_SPLIT_PACK_MULTI, RGCN_FN_AGGREGATE,
-  RGCN_FN_AGGREGATE_AND_REDUCE, RGCN_FN_AGGREGATE_AMAX, RGCN_FN_AGGREGATE_DEFERRED, RGCN_FN_TRANSFORM_FWD_SPLIT,
+  RGCN_FN_AGGREGATE_EX, RGCN_FN_TRANSFORM_FWD_SPLIT,
   RGCN_FN_TRANSFORM_BWD_INPUT_SPLIT, RGCN_FN_TRANSFORM_FIRST_SPLIT, RGCN_FN_TRANSFORM_BWD_PARAMS_SPLIT_BEGIN,
   RGCN_FN_SLAB_REDUCE, RGCN_FN_LAYER_FWD_FUSED, RGCN_FN_LAYER_BWD_INPUT_FUSED, RGCN_FN_TRANSFORM_BWD_INPUT_CHAIN_SPLIT, RGCN_FN_COUNT
 };

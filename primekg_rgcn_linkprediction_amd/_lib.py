@@ -13,7 +13,7 @@ from ctypes import c_double, c_float, POINTER, c_char_p, c_int, c_int64, c_size_
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 LIB_NAME = "librgcn_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -49,7 +49,7 @@ SEQ_MAX_JOBS = 8    # RGCN_SEQ_MAX_JOBS
 # entry points rgcn_sequence_run can forward to, in the header's RGCN_FN_* order: name -> position of `void* stream`
 SEQ_FUNCTIONS = {
     "rgcn_absmax": 5, "rgcn_absmax_multi": 6, "rgcn_absmax_pack": 13, "rgcn_weights_split_pack_multi": 12,
-    "rgcn_aggregate": 7, "rgcn_aggregate_and_reduce": 8, "rgcn_aggregate_amax": 9, "rgcn_aggregate_deferred": 8,
+    "rgcn_aggregate": 7, "rgcn_aggregate_ex": 12,
     "rgcn_transform_fwd_split": 20, "rgcn_transform_bwd_input_split": 19, "rgcn_transform_first_split": 12,
     "rgcn_transform_bwd_params_split_begin": 18, "rgcn_slab_reduce": 1, "rgcn_layer_fwd_fused": 17,
     "rgcn_layer_bwd_input_fused": 17, "rgcn_transform_bwd_input_chain_split": 18,
@@ -81,8 +81,7 @@ PROTOTYPES = {
     "rgcn_graph_import": (c_int, [_I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(c_void_p)]),
     "rgcn_aggregate_workspace_bytes": (c_size_t, [c_void_p, c_int, _I64]),
     "rgcn_aggregate": (c_int, [c_void_p, c_int, _P, _I64, _P, _P, c_size_t, _P]),
-    "rgcn_aggregate_f16": (c_int, [c_void_p, c_int, _P, _I64, _P, _P, c_size_t, _P]),
-    "rgcn_aggregate_level": (c_int, [c_void_p, c_int, c_int, _P, _I64, _P, _P, c_size_t, _P, _P]),
+    "rgcn_aggregate_ex": (c_int, [c_void_p, c_int, _P, c_int, _I64, _P, _P, c_size_t, c_int, c_int, POINTER(SlabJob), _P, _P]),
     "rgcn_graph_tile_mask": (c_void_p, [c_void_p, c_int, POINTER(c_int64)]),
     "rgcn_transform_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "rgcn_transform_fwd_f16_workspace_bytes": (c_size_t, [_I64, _I64, _I64]),
@@ -94,8 +93,6 @@ PROTOTYPES = {
     "rgcn_transform_bwd_params_begin": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, c_size_t, _P,
                                                 POINTER(SlabJob)]),
     "rgcn_slab_reduce": (c_int, [POINTER(SlabJob), _P]),
-    "rgcn_aggregate_and_reduce": (c_int, [c_void_p, c_int, _P, _I64, _P, _P, c_size_t, POINTER(SlabJob), _P]),
-    "rgcn_aggregate_amax": (c_int, [c_void_p, c_int, _P, _I64, _P, _P, c_size_t, POINTER(SlabJob), _P, _P]),
     "rgcn_absmax": (c_int, [_P, _I64, _P, _P, c_int, _P]),
     "rgcn_absmax_multi": (c_int, [c_int, _P, _P, _P, _P, c_int, _P]),
     "rgcn_absmax_pack": (c_int, [_P, _I64, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -112,7 +109,6 @@ PROTOTYPES = {
                                                      _P, _P, c_size_t, _P, c_void_p, c_int, _P, c_float, _P, c_int, _I64,
                                                      _I64, _P]),
     "rgcn_aggregate_deferrable": (c_int, [c_void_p, c_int, _I64]),
-    "rgcn_aggregate_deferred": (c_int, [c_void_p, c_int, _P, _I64, _P, _P, c_size_t, POINTER(SlabJob), _P]),
     "rgcn_transform_first_split": (c_int, [_P, _P, c_int, _I64, _I64, _I64, _I64, _P, c_int, _P, _P, c_size_t, _P]),
     "rgcn_transform_bwd_params_split_workspace_bytes": (c_size_t, [_I64, _I64, _I64, _I64]),
     "rgcn_transform_bwd_params_split_begin": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, c_float, _P, _P, c_int,

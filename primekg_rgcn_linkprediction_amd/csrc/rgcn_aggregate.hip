@@ -372,10 +372,20 @@ void launch_level0_h(const rgcn_csr* c, bool weighted, const __half* x, const fl
 }
 
 int aggregate_levels(const rgcn_graph* g, int transposed, int first, int last, const float* x, int64_t d,
-                     float* agg, void* workspace, size_t workspace_bytes, void* stream_, bool half_in = false,
-                     const rgcn_slab_job* tail = nullptr, float* amax = nullptr) {
-  if (!g || !agg || d <= 0 || (d & 3) || (half_in && (d & 7))) return RGCN_ERR_ARG;
+                     float* agg, void* workspace, size_t workspace_bytes, void* stream_, bool half_in,
+                     const rgcn_slab_job* tail, float* amax) {
+  if (!g) return RGCN_ERR_ARG;
   const rgcn_csr* c = &g->dir[transposed ? 1 : 0];
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!tail || !tail->slab) tail = nullptr;     // nothing pending
+  if (tail && (!tail->grad_weight || tail->splits <= 0 || tail->Kc <= 0 || tail->N <= 0 || (tail->N & 3)))
+    return RGCN_ERR_ARG;
+  if (tail && c->rowptr && c->n_key == 0) {     // nothing to gather: the reduction still has to run
+    k_slab_reduce<<<(unsigned)rgcn_slab_reduce_blocks(*tail), 256, 0, stream>>>(*tail);
+    RGCN_HIP_TRY(hipGetLastError());
+    return RGCN_OK;
+  }
+  if (!agg || d <= 0 || (d & 3) || (half_in && (d & 7))) return RGCN_ERR_ARG;
   if (!c->rowptr) return RGCN_ERR_ARG;   // direction not built
   if (c->n_key == 0) return RGCN_OK;
   if (!x) return RGCN_ERR_ARG;
@@ -384,7 +394,6 @@ int aggregate_levels(const rgcn_graph* g, int transposed, int first, int last, c
   if (c->num_partials > 0 &&
       (!workspace || workspace_bytes < (size_t)c->num_partials * (size_t)d * sizeof(float)))
     return RGCN_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
   float* partial = (float*)workspace;
   unsigned* amax_out = reinterpret_cast<unsigned*>(amax);
   if (amax && half_in) return RGCN_ERR_UNSUPPORTED;            // the fp16-table gather feeds the fp16 transform: no scale needed
@@ -393,13 +402,9 @@ int aggregate_levels(const rgcn_graph* g, int transposed, int first, int last, c
   const int q = (int)(d / 4);
   // a pending slab reduction rides in the level-0 launch when that launch is a plain 1-D grid of the
   // fp32 gather with work of its own; otherwise it is launched by itself, first
-  if (tail && tail->slab) {
-    const bool can_ride = !half_in && first == 0 && last > 0 && d <= 256 && c->num_items[0] > 0;
-    if (!can_ride) {
-      k_slab_reduce<<<(unsigned)rgcn_slab_reduce_blocks(*tail), 256, 0, stream>>>(*tail);
-      tail = nullptr;
-    }
-  } else {
+  const bool can_ride = !half_in && first == 0 && last > 0 && d <= 256 && c->num_items[0] > 0;
+  if (tail && !can_ride) {
+    k_slab_reduce<<<(unsigned)rgcn_slab_reduce_blocks(*tail), 256, 0, stream>>>(*tail);
     tail = nullptr;
   }
   for (int l = first; l < last; ++l) {
@@ -437,67 +442,24 @@ size_t rgcn_aggregate_workspace_bytes(const rgcn_graph* g, int transposed, int64
   return (size_t)g->dir[transposed ? 1 : 0].num_partials * (size_t)d * sizeof(float);
 }
 
+int rgcn_aggregate_ex(const rgcn_graph* g, int transposed, const void* x, int x_f16, int64_t d, float* agg,
+                      void* workspace, size_t workspace_bytes, int first_level, int last_level, const rgcn_slab_job* job,
+                      float* amax, void* stream) {
+  if (!g) return RGCN_ERR_ARG;
+  return aggregate_levels(g, transposed, first_level, last_level < 0 ? g->dir[transposed ? 1 : 0].num_levels : last_level,
+                          reinterpret_cast<const float*>(x), d, agg, workspace, workspace_bytes, stream, x_f16 != 0, job,
+                          amax);
+}
+
 int rgcn_aggregate(const rgcn_graph* g, int transposed, const float* x, int64_t d, float* agg,
                    void* workspace, size_t workspace_bytes, void* stream) {
-  if (!g) return RGCN_ERR_ARG;
-  return aggregate_levels(g, transposed, 0, g->dir[transposed ? 1 : 0].num_levels, x, d, agg, workspace,
-                          workspace_bytes, stream);
+  return rgcn_aggregate_ex(g, transposed, x, 0, d, agg, workspace, workspace_bytes, 0, -1, nullptr, nullptr, stream);
 }
 
 int rgcn_aggregate_deferrable(const rgcn_graph* g, int transposed, int64_t d) {
   if (!g) return 0;
   const rgcn_csr& c = g->dir[transposed ? 1 : 0];
   return (c.num_levels == 2 && c.fin_ptr && (d == 64 || d == 128 || d == 256)) ? 1 : 0;
-}
-
-int rgcn_aggregate_deferred(const rgcn_graph* g, int transposed, const float* x, int64_t d, float* agg,
-                            void* workspace, size_t workspace_bytes, const rgcn_slab_job* job, void* stream) {
-  if (!rgcn_aggregate_deferrable(g, transposed, d)) return RGCN_ERR_UNSUPPORTED;
-  return aggregate_levels(g, transposed, 0, 1, x, d, agg, workspace, workspace_bytes, stream, false, job);
-}
-
-int rgcn_aggregate_and_reduce(const rgcn_graph* g, int transposed, const float* x, int64_t d, float* agg,
-                              void* workspace, size_t workspace_bytes, const rgcn_slab_job* job, void* stream) {
-  if (!g) return RGCN_ERR_ARG;
-  if (job && job->slab &&
-      (!job->grad_weight || job->splits <= 0 || job->Kc <= 0 || job->N <= 0 || (job->N & 3)))
-    return RGCN_ERR_ARG;
-  const rgcn_csr* c = &g->dir[transposed ? 1 : 0];
-  if (job && job->slab && c->rowptr && c->n_key == 0) {      // nothing to gather: the reduction still has to run
-    k_slab_reduce<<<(unsigned)rgcn_slab_reduce_blocks(*job), 256, 0, (hipStream_t)stream>>>(*job);
-    RGCN_HIP_TRY(hipGetLastError());
-    return RGCN_OK;
-  }
-  return aggregate_levels(g, transposed, 0, c->num_levels, x, d, agg, workspace, workspace_bytes, stream, false, job);
-}
-
-int rgcn_aggregate_amax(const rgcn_graph* g, int transposed, const float* x, int64_t d, float* agg,
-                        void* workspace, size_t workspace_bytes, const rgcn_slab_job* job, float* amax, void* stream) {
-  if (!g || !amax) return RGCN_ERR_ARG;
-  if (job && job->slab &&
-      (!job->grad_weight || job->splits <= 0 || job->Kc <= 0 || job->N <= 0 || (job->N & 3)))
-    return RGCN_ERR_ARG;
-  const rgcn_csr* c = &g->dir[transposed ? 1 : 0];
-  if (job && job->slab && c->rowptr && c->n_key == 0) {      // nothing to gather: the reduction still has to run
-    k_slab_reduce<<<(unsigned)rgcn_slab_reduce_blocks(*job), 256, 0, (hipStream_t)stream>>>(*job);
-    RGCN_HIP_TRY(hipGetLastError());
-    return RGCN_OK;
-  }
-  return aggregate_levels(g, transposed, 0, c->num_levels, x, d, agg, workspace, workspace_bytes, stream, false, job,
-                          amax);
-}
-
-int rgcn_aggregate_f16(const rgcn_graph* g, int transposed, const void* x_f16, int64_t d, float* agg,
-                       void* workspace, size_t workspace_bytes, void* stream) {
-  if (!g) return RGCN_ERR_ARG;
-  return aggregate_levels(g, transposed, 0, g->dir[transposed ? 1 : 0].num_levels,
-                          reinterpret_cast<const float*>(x_f16), d, agg, workspace, workspace_bytes, stream, true);
-}
-
-int rgcn_aggregate_level(const rgcn_graph* g, int transposed, int level, const float* x, int64_t d, float* agg,
-                         void* workspace, size_t workspace_bytes, float* amax, void* stream) {
-  return aggregate_levels(g, transposed, level, level + 1, x, d, agg, workspace, workspace_bytes, stream, false,
-                          nullptr, amax);
 }
 
 }  // extern "C"

@@ -19,9 +19,7 @@ const rgcn_seq::entry kTable[] = {                   // in RGCN_FN_* order
     RGCN_SEQ_ENTRY(rgcn_absmax_pack),
     RGCN_SEQ_ENTRY(rgcn_weights_split_pack_multi),
     RGCN_SEQ_ENTRY(rgcn_aggregate),
-    RGCN_SEQ_ENTRY(rgcn_aggregate_and_reduce),
-    RGCN_SEQ_ENTRY(rgcn_aggregate_amax),
-    RGCN_SEQ_ENTRY(rgcn_aggregate_deferred),
+    RGCN_SEQ_ENTRY(rgcn_aggregate_ex),
     RGCN_SEQ_ENTRY(rgcn_transform_fwd_split),
     RGCN_SEQ_ENTRY(rgcn_transform_bwd_input_split),
     RGCN_SEQ_ENTRY(rgcn_transform_first_split),

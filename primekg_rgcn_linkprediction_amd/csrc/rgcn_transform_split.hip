@@ -20,7 +20,7 @@
 // scale whose maximum is within a small factor of the operand's real one keeps that: a BOUND b times too loose moves
 // every row log2(b) binades closer to the subnormal floor of the lo half: weight_bound * max|g| is ~800x the real
 // maximum of a transposed aggregate on a 200k-edge PrimeKG-shaped graph (rows 14-16 binades down: 5.4e-5), so the
-// layers scale that operand by its own maximum (rgcn_aggregate_amax; the fused input gradient's max-only pass).
+// layers scale that operand by its own maximum (rgcn_aggregate_ex's amax; the fused input gradient's max-only pass).
 //
 // Replaces (reference call sites src/models/rgcn.py:123,128):
 //   rgcn_transform_fwd_split        out    = [agg | x]  * [W ; root] + bias              (+ ReLU)
@@ -1158,7 +1158,7 @@ int launch_nt_split(const float* A1, int K1, const float* A2, int K2, const __ha
   return RGCN_OK;
 }
 
-// the hub tails a gather left to this transform (rgcn_aggregate_deferred): 0 = none, < 0 = error code
+// the hub tails a gather left to this transform (rgcn_aggregate_ex stopped at level 1): 0 = none, < 0 = error code
 int make_hub_fin(const rgcn_graph* g, int transposed, float* partial, int64_t N, int64_t R, int64_t d, hub_fin* out) {
   *out = hub_fin{};
   if (!g) return 0;

@@ -819,16 +819,10 @@ class PendingParamGrads:
         self.done, self._workspace = True, None        # stream-ordered allocator: safe to release after the launch
 
 
-def aggregate(graph: BucketedGraph, x: torch.Tensor, transposed: bool = False,
-              tail: Optional[PendingParamGrads] = None, amax_out: Optional[torch.Tensor] = None,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``[N, R*d]``: per-(dst, rel) mean of source rows (``transposed=False``) or the
-    1/cnt-weighted sum over out-edges per (src, rel) (``transposed=True``).  For a shard
-    (``BucketedGraph.from_shard``) x holds the gathered rows of all ranks and the result has
-    the rank's own rows.  ``x`` may be float16 (BASELINE configs[4]: fp16 feature table, half
-    the bytes per gathered row); sums and the result are fp32 either way.  ``amax_out`` (a ZEROED amax
-    buffer, fp32 table only): receives ``max |result|``, the scale the split-precision
-    transforms need for this operand."""
+def _gather(graph: BucketedGraph, x: torch.Tensor, transposed: bool, tail: Optional[PendingParamGrads],
+            amax_out: Optional[torch.Tensor], out: Optional[torch.Tensor], levels=(0, -1)):
+    """The one ``rgcn_aggregate_ex`` call behind ``aggregate`` and ``aggregate_deferred``: launches ``levels`` =
+    [first, last) of the gather (last < 0: all) -> (agg, workspace).  A pending ``tail`` goes along as the call's job."""
     half_in = isinstance(x, torch.Tensor) and x.dtype == torch.float16
     _need_gpu("x", x, torch.float16 if half_in else torch.float32)
     if graph.bipartite and transposed:
@@ -848,47 +842,47 @@ def aggregate(graph: BucketedGraph, x: torch.Tensor, transposed: bool = False,
         _need_gpu("out", out, torch.float32)
         if tuple(out.shape) != (graph.num_nodes, graph.num_relations * d) or out.device != x.device:
             raise ValueError(f"out must be [{graph.num_nodes}, {graph.num_relations * d}] on x's device")
+    # measurement mode (bench.py): same launches, one call per level, level 0 (the gather kernel proper) bracketed
+    # by HIP events on the stream it is launched on - so no ride: the reduction is launched by itself
+    measure = GATHER_EVENTS is not None and not half_in
     with _on(x.device):
         if out is None:
             out = _empty(graph.num_nodes, graph.num_relations * d, dtype=torch.float32, device=x.device)
         nbytes = graph.workspace_bytes(transposed, d)
         ws = _workspace(nbytes, x.device)
-        if tail is not None and not tail.done and (half_in or GATHER_EVENTS is not None):
-            tail.finish()                       # no ride in these modes: launch the reduction by itself
-        if half_in:
-            rc = lib.rgcn_aggregate_f16(graph.handle, int(transposed), _ptr(x), d, _ptr(out), _ptr(ws), nbytes,
-                                        _stream())
-        elif GATHER_EVENTS is None and amax_out is not None:
-            job = tail.job if (tail is not None and not tail.done) else None
-            rc = lib.rgcn_aggregate_amax(graph.handle, int(transposed), _ptr(x), d, _ptr(out), _ptr(ws), nbytes,
-                                         ctypes.byref(job) if job is not None else None, _ptr(amax_out), _stream())
-            if rc == 0 and job is not None:
-                tail._launched()
-        elif GATHER_EVENTS is None and tail is not None and not tail.done:
-            rc = lib.rgcn_aggregate_and_reduce(graph.handle, int(transposed), _ptr(x), d, _ptr(out), _ptr(ws), nbytes,
-                                               ctypes.byref(tail.job), _stream())
-            if rc == 0:
-                tail._launched()
-        elif GATHER_EVENTS is None:
-            rc = lib.rgcn_aggregate(graph.handle, int(transposed), _ptr(x), d, _ptr(out), _ptr(ws), nbytes,
-                                    _stream())
-        else:
-            # measurement mode (bench.py): same launches, level 0 (the gather kernel proper)
-            # bracketed by HIP events on the stream it is launched on
-            rc = 0
-            for level in range(graph.num_levels(transposed)):
-                if level == 0:
-                    beg, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    beg.record()
-                rc = rc or lib.rgcn_aggregate_level(graph.handle, int(transposed), level, _ptr(x), d,
-                                                    _ptr(out), _ptr(ws), nbytes, _ptr(amax_out), _stream())
-                if level == 0:
-                    end.record()
-                    weighted = bool(transposed) or (graph.bipartite and graph.weighted_shard)
-                    GATHER_EVENTS.append((weighted, d, graph.num_edges, graph.num_nodes * graph.num_relations,
-                                          graph.num_other_nodes, beg, end))
+        if measure and tail is not None:
+            tail.finish()
+        job = tail.job if tail is not None and not tail.done else None
+        rc = 0
+        for first, last in ([(l, l + 1) for l in range(graph.num_levels(transposed))] if measure else [levels]):
+            if measure and first == 0:
+                beg, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                beg.record()
+            rc = rc or lib.rgcn_aggregate_ex(graph.handle, int(transposed), _ptr(x), int(half_in), d, _ptr(out), _ptr(ws),
+                                             nbytes, first, last, ctypes.byref(job) if job is not None else None,
+                                             _ptr(amax_out), _stream())
+            if measure and first == 0:
+                end.record()
+                weighted = bool(transposed) or (graph.bipartite and graph.weighted_shard)
+                GATHER_EVENTS.append((weighted, d, graph.num_edges, graph.num_nodes * graph.num_relations,
+                                      graph.num_other_nodes, beg, end))
+        if rc == 0 and job is not None:
+            tail._launched()
     _lib.check(rc, "rgcn_aggregate")
-    return out
+    return out, ws
+
+
+def aggregate(graph: BucketedGraph, x: torch.Tensor, transposed: bool = False,
+              tail: Optional[PendingParamGrads] = None, amax_out: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``[N, R*d]``: per-(dst, rel) mean of source rows (``transposed=False``) or the
+    1/cnt-weighted sum over out-edges per (src, rel) (``transposed=True``).  For a shard
+    (``BucketedGraph.from_shard``) x holds the gathered rows of all ranks and the result has
+    the rank's own rows.  ``x`` may be float16 (BASELINE configs[4]: fp16 feature table, half
+    the bytes per gathered row); sums and the result are fp32 either way.  ``amax_out`` (a ZEROED amax
+    buffer, fp32 table only): receives ``max |result|``, the scale the split-precision
+    transforms need for this operand."""
+    return _gather(graph, x, transposed, tail, amax_out, out)[0]
 
 
 def fused_bwd_supported(num_relations: int, d_in: int, d_out: int) -> bool:
@@ -1020,33 +1014,15 @@ def aggregate_deferred(graph: BucketedGraph, x: torch.Tensor, transposed: bool =
     rows of the long segments tile by tile itself (same order, same bits) and completes ``agg`` in passing.
     ``hubs`` is None (and ``agg`` complete) where nothing can be deferred: no long segment, a structure with more
     than one reduce level, a width other than 64 / 128 / 256, an fp16 table, measurement mode."""
-    lib = _L()
     d = x.size(1) if x.dim() == 2 else 0
     deferrable = (x.dtype == torch.float32 and GATHER_EVENTS is None and graph.num_levels(transposed) == 2
                   and graph.deferrable(transposed, d))
     if not deferrable:
         return aggregate(graph, x, transposed, tail=tail), None
-    _need_gpu("x", x, torch.float32)
-    if graph.bipartite and transposed:
-        raise ValueError("a shard structure has one direction only (transposed=False)")
-    if x.size(0) != graph.num_other_nodes or x.device != graph.device:
-        raise ValueError(f"x must be [{graph.num_other_nodes}, d] on the graph's device, got {tuple(x.shape)}")
-    with _on(x.device):
-        out = _empty(graph.num_nodes, graph.num_relations * d, dtype=torch.float32, device=x.device)
-        nbytes = graph.workspace_bytes(transposed, d)
-        ws = _workspace(nbytes, x.device)
-        job = tail.job if (tail is not None and not tail.done) else None
-        rc = lib.rgcn_aggregate_deferred(graph.handle, int(transposed), _ptr(x), d, _ptr(out), _ptr(ws), nbytes,
-                                         ctypes.byref(job) if job is not None else None, _stream())
-        if rc == 0 and job is not None:
-            tail._launched()
-    _lib.check(rc, "rgcn_aggregate_deferred")
+    out, ws = _gather(graph, x, transposed, tail, None, None, levels=(0, 1))
     return out, DeferredHubs(graph, transposed, ws)
 
 
-# 1: the pass's first launch rides in conv1's gather (rgcn_aggregate_prep).  OFF by default: measured on the MI355X the
-# step gets 5 us SLOWER (0.286 against 0.281 ms, profiles/r03_prep_rides.txt) - in 256-thread workgroups the riders' scan
-# of the weights takes 8 rounds of loads instead of 2 and outlasts the gather it was meant to hide behind.
 def _hub_args(hubs: Optional[DeferredHubs], n: int, r: int):
     if hubs is None:
         return None, 0, None

@@ -1358,8 +1358,8 @@ def test_c_abi_error_codes_with_real_handles():
     assert lib.rgcn_aggregate(g.handle, 0, P(x), d, P(agg), None, 0, stream) == _lib.RGCN_ERR_WORKSPACE
     assert lib.rgcn_aggregate(g.handle, 0, P(x), 6, P(agg), P(ws), need, stream) == _lib.RGCN_ERR_ARG
     assert lib.rgcn_aggregate(g.handle, 0, None, d, P(agg), P(ws), need, stream) == _lib.RGCN_ERR_ARG
-    assert lib.rgcn_aggregate_f16(g.handle, 0, P(x), 68, P(agg), P(ws), need * 2, stream) == _lib.RGCN_ERR_ARG   # d % 8
-    assert lib.rgcn_aggregate_level(g.handle, 0, 7, P(x), d, P(agg), P(ws), need, None, stream) == _lib.RGCN_ERR_ARG
+    assert lib.rgcn_aggregate_ex(g.handle, 0, P(x), 1, 68, P(agg), P(ws), need * 2, 0, -1, None, None, stream) == _lib.RGCN_ERR_ARG   # d % 8
+    assert lib.rgcn_aggregate_ex(g.handle, 0, P(x), 0, d, P(agg), P(ws), need, 7, 8, None, None, stream) == _lib.RGCN_ERR_ARG
     assert lib.rgcn_aggregate(g.handle, 0, P(x), d, P(agg), P(ws), need, stream) == _lib.RGCN_OK
     torch.cuda.synchronize()
     assert_fwd(agg.view(50, -1), O.mean_aggregate_ref(x.cpu(), ei, torch.zeros(500, dtype=torch.int64), 2).view(50, -1))
@@ -2096,7 +2096,7 @@ def test_fused_layers_on_degenerate_graphs(monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize("d_in,d_out", [(64, 128), (128, 128), (128, 256), (256, 64)])
 def test_hub_tails_left_to_the_transform_change_no_bit(d_in, d_out, monkeypatch):
-    """rgcn_aggregate_deferred: the gather skips its hub-tail launch and the split-precision transform that reads the
+    """ops.aggregate_deferred: the gather skips its hub-tail launch and the split-precision transform that reads the
     aggregate sums the partial rows of its own row tiles (the same function k_reduce_partials runs): outputs, the
     completed aggregate and - through the training node with the switch on and off - every gradient are bit-equal;
     forward and transposed direction, several column blocks finishing the same rows (d_out = 256), ReLU mask."""
@@ -2151,3 +2151,73 @@ def test_hub_tails_left_to_the_transform_change_no_bit(d_in, d_out, monkeypatch)
         res[on] = [out.detach(), e.grad.clone()] + [p.grad.clone() for c in convs for p in c.parameters()]
     for a, b in zip(res[False], res[True]):
         assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("transposed", [False, True])
+@pytest.mark.parametrize("d", [8, 64, 264])
+def test_gather_options_are_bit_for_bit_one_gather(d, transposed, monkeypatch):
+    """every option of the gather (a pending tail, amax_out, both - the training route -, measurement mode, the levels
+    left to the consuming transform, the fp16 table) issues the launches of the plain ``aggregate`` in the same order:
+    rows, the tail's three gradients and the published maximum are bit-equal.  A hub segment in either direction (610
+    edges: partial rows and a reduce level); d = 8 (every lane loads its ids), 64 (deferrable), 264 (past the riding
+    limit of 256, second grid dimension; still a multiple of 8 for the fp16 table)."""
+    dev = need_gpu()
+    n, r = 64, 3
+    gen = torch.Generator().manual_seed(29)
+    spokes, hub = torch.arange(600) % n, torch.zeros(600, dtype=torch.int64)
+    rnd = torch.randint(0, n, (2, 200), generator=gen)
+    ei = torch.cat([torch.stack([spokes, hub]), torch.stack([hub + 1, spokes]), rnd], dim=1)
+    et = torch.cat([torch.zeros(1200, dtype=torch.int64), torch.ones(200, dtype=torch.int64)])      # relation 2: empty
+    graph = ops.BucketedGraph(ei.to(dev), et.to(dev), n, r)
+    assert graph.num_levels(False) == 2 and graph.num_levels(True) == 2
+    x = torch.randn(n, d, generator=gen).to(dev)
+    base = ops.aggregate(graph, x, transposed)
+    if not transposed:
+        assert_fwd(base.view(n, r, d), O.mean_aggregate_ref(x.cpu(), ei, et, r))
+    # the tail: parameter gradients of a 64 x (64 -> 64) layer, their slab reduction pending
+    pa, px, pg = (torch.randn(n, w, generator=gen).to(dev) for w in (r * 64, 64, 64))
+
+    def pending():
+        return ops.transform_bwd_params(pa, px, pg, r, defer=True)
+    alone = pending()
+    alone.finish()
+
+    def check(rows, want, tail=None, slot=None):
+        assert torch.equal(rows, want)
+        if tail is not None:
+            assert tail.done and all(torch.equal(a, b) for a, b in zip(tail.grads, alone.grads))
+        if slot is not None:
+            assert ops.amax_value(slot).item() == rows.abs().max().item() > 0
+
+    def options():
+        for with_tail in (True, False):
+            for with_amax in (False, True):
+                if with_tail or with_amax:
+                    yield (pending() if with_tail else None), (ops.amax_buffer(dev)[0] if with_amax else None)
+
+    for tail, slot in options():                     # riding (or launched first: d = 264), amax_out, both
+        check(ops.aggregate(graph, x, transposed, tail=tail, amax_out=slot), base, tail, slot)
+    # measurement mode: one call per level, level 0 between events, a pending tail finished first
+    events = []
+    monkeypatch.setattr(ops, "GATHER_EVENTS", events)
+    for k, (tail, slot) in enumerate([(None, None)] + list(options())):
+        check(ops.aggregate(graph, x, transposed, tail=tail, amax_out=slot), base, tail, slot)
+        assert len(events) == k + 1 and events[-1][:5] == (transposed, d, 1400, n * r, n)
+    monkeypatch.setattr(ops, "GATHER_EVENTS", None)
+    # the reduce level left to the transform that consumes the rows (d = 64 only), a tail riding all the same
+    tail = pending()
+    rows, hubs = ops.aggregate_deferred(graph, x, transposed, tail=tail)
+    assert (hubs is not None) == (d == 64)
+    if hubs is not None:
+        weight, root = torch.randn(r, d, d, generator=gen).to(dev) / 8, torch.randn(d, d, generator=gen).to(dev) / 8
+        x_amax = ops.absmax(x)
+        if transposed:
+            ops.transform_bwd_input(rows, x, weight, root, graph=graph, amax=(x_amax, x_amax),
+                                    amax_mul=graph.weight_bound(True), hubs=hubs)
+        else:
+            ops.transform_fwd(rows, x, weight, root, graph=graph, amax=(x_amax, x_amax), hubs=hubs)
+    check(rows, base, tail)
+    # fp16 table: against its own plain gather, the tail launched by itself first
+    tail = pending()
+    check(ops.aggregate(graph, x.half(), transposed, tail=tail), ops.aggregate(graph, x.half(), transposed), tail)

@@ -59,6 +59,12 @@ def test_null_handle_and_bad_args_return_codes_without_a_gpu():
     assert lib.rgcn_transform_bwd_params_workspace_bytes(30926, 3, 128, 128) > 0
     # every entry point rejects bad sizes / null pointers before it touches the device
     import ctypes
+    assert lib.rgcn_aggregate_ex(None, 0, None, 0, 64, None, None, 0, 0, -1, None, None, None) == _lib.RGCN_ERR_ARG
+    for grad_weight in (None, 256):          # a job with a slab, malformed (no grad_weight) or not: no graph, no launch
+        job = _lib.SlabJob(slab=256, splits=1, Kc=64, N=64, grad_weight=grad_weight)
+        for x_f16 in (0, 1):
+            assert lib.rgcn_aggregate_ex(None, 0, None, x_f16, 64, None, None, 0, 0, -1, ctypes.byref(job), None,
+                                         None) == _lib.RGCN_ERR_ARG
     out = ctypes.c_void_p()
     E, A, U = _lib.RGCN_ERR_ARG, _lib.RGCN_ERR_ARG, _lib.RGCN_ERR_UNSUPPORTED
     assert lib.rgcn_graph_create(None, None, -1, 5, 3, None, ctypes.byref(out)) == E
@@ -103,7 +109,7 @@ def test_ctypes_prototypes_match_the_header_parameter_by_parameter():
     """count and, position by position, kind (pointer / float / double / size_t / int64_t / int) of EVERY declared
     function: a ctypes prototype that drifts from the header passes a wrong pointer or size without any error"""
     declared = _declared_prototypes()
-    assert len(declared) >= 71 and sorted(declared) == sorted(_lib.PROTOTYPES)
+    assert len(declared) == 67 and sorted(declared) == sorted(_lib.PROTOTYPES)
     for name, params in declared.items():
         argtypes = _lib.PROTOTYPES[name][1]
         assert len(argtypes) == len(params), name
@@ -118,7 +124,7 @@ def test_sequence_tables_match_the_header():
     text, declared = _header_text(), _declared_prototypes()
     fns = re.search(r"enum\s*\{\s*(RGCN_FN_ABSMAX\b[^}]*)\}", text).group(1)
     fns = [f.split("=")[0].strip() for f in fns.split(",")]
-    assert fns[-1] == "RGCN_FN_COUNT" and len(fns) == 17
+    assert fns[-1] == "RGCN_FN_COUNT" and len(fns) == 15
     assert list(_lib.SEQ_FUNCTIONS) == ["rgcn_" + f[len("RGCN_FN_"):].lower() for f in fns[:-1]]
     for name, stream_pos in _lib.SEQ_FUNCTIONS.items():
         assert [i for i, p in enumerate(declared[name]) if p == "void* stream"] == [stream_pos], name
@@ -152,7 +158,7 @@ def test_sequence_run_forwards_every_entry_point_with_its_own_argument_count():
             call = _lib.SeqCall(fn, n, 0)
             got = lib.rgcn_sequence_run(ctypes.byref(call), 1, args, len(args), None, 0, None)
             assert got == expected, f"{name} with {n} of {len(proto)} arguments"
-    assert sorted(direct_codes.values()) == [_lib.RGCN_ERR_UNSUPPORTED] + [_lib.RGCN_ERR_ARG] * 14 + [_lib.RGCN_OK]
+    assert sorted(direct_codes.values()) == [_lib.RGCN_ERR_ARG] * 13 + [_lib.RGCN_OK]
     call = _lib.SeqCall(len(_lib.SEQ_FUNCTIONS), 0, 0)
     assert lib.rgcn_sequence_run(ctypes.byref(call), 1, args, len(args), None, 0, None) == _lib.RGCN_ERR_UNSUPPORTED
 
