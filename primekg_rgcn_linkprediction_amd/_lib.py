@@ -13,7 +13,7 @@ from ctypes import c_double, c_float, POINTER, c_char_p, c_int, c_int64, c_size_
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-ABI_VERSION = 29
+ABI_VERSION = 30
 LIB_NAME = "librgcn_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -146,6 +146,16 @@ PROTOTYPES = {
                                  c_size_t, c_int, _P]),
 }
 
+# include/rgcn_sampling.h, one to one: the same library's protocol-aware sampler (not part of rgcn_hip.h, never forwarded by
+# rgcn_sequence_run - the trainer samples outside any recorded Region)
+SAMPLING_PROTOTYPES = {
+    "rgcn_sample_batch_constrained": (c_int, [_P, _P, _I64, _P, _P, _I64, _I64, _I64, _P,          # slice, cursor, rng
+                                              _P, _P, _P, _I64,                                    # classes
+                                              _P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _I64, _I64,   # known triples
+                                              c_int, _P,                                           # max_tries, stats
+                                              _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -167,7 +177,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise RGCNLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -36,7 +36,7 @@ class ModelEvaluator:
                  batch_size: int = 1024, node_class: Optional[torch.Tensor] = None):
         self.model = model.to(device).eval()
         self.node_class = None if node_class is None else torch.as_tensor(node_class).to(device=device, dtype=torch.int32)
-        self._known = None
+        self._known = self._classes = None
         self.device, self.batch_size = device, batch_size
         self.test_edge_index = test_data["edge_index"].to(device)
         self.test_edge_type = test_data["edge_type"].to(device)
@@ -54,9 +54,15 @@ class ModelEvaluator:
         return self._emb
 
     @torch.no_grad()
-    def compute_scores_and_labels(self, num_neg_samples: int = 1) -> Tuple[np.ndarray, np.ndarray]:
-        """-> (sigmoid scores, labels): every test column + ``num_neg_samples`` corruptions."""
+    def compute_scores_and_labels(self, num_neg_samples: int = 1, filtered: bool = False,
+                                  type_constrained: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (sigmoid scores, labels): every test column + ``num_neg_samples`` corruptions.  ``filtered``: no
+        corruption is a known triple (``known_triples()``; up to ``NEGATIVE_TRIES`` draws each); ``type_constrained``:
+        a node is replaced by one of its own class.  Either one draws from the constrained device sampler (cursor =
+        the batch start, key = torch's seed): the same negatives every time."""
         emb = self.embeddings()
+        if filtered or type_constrained:
+            return self._constrained_scores_and_labels(emb, num_neg_samples, **self._protocol(filtered, type_constrained))
         sampler = NegativeSampler(self.num_nodes, num_neg_samples)
         head, tail, rel = self.test_edge_index[0], self.test_edge_index[1], self.test_edge_type
         scores, labels = [], []
@@ -67,6 +73,31 @@ class ModelEvaluator:
             scores.append(torch.sigmoid(s))
             labels.append(torch.cat([torch.ones(h.numel(), device=self.device),
                                      torch.zeros(nh.numel(), device=self.device)]))
+        return torch.cat(scores).cpu().numpy(), torch.cat(labels).cpu().numpy()
+
+    NEGATIVE_TRIES = 16          # draws per filtered negative before the last one is kept
+    NEGATIVE_STREAM = (1 << 55) + 1   # Philox stream of these negatives: no training epoch, not validate()'s
+
+    def _constrained_scores_and_labels(self, emb, num_neg_samples: int, known, node_class):
+        from . import ops
+        classes = None
+        if node_class is not None:
+            if self._classes is None:
+                self._classes = ops.NodeClasses(node_class, max(int(node_class.max()) + 1, 1))
+            classes = self._classes
+        starts = torch.arange(0, max(self.num_test_edges, 1), self.batch_size, device=self.device, dtype=torch.int64)
+        rng = torch.tensor([torch.initial_seed() & 0x7FFFFFFFFFFFFFFF, self.NEGATIVE_STREAM], dtype=torch.int64).to(self.device)
+        self.negative_stats = torch.zeros(2, dtype=torch.int64, device=self.device)
+        scores, labels, triples = [], [], []
+        for i, lo in enumerate(range(0, self.num_test_edges, self.batch_size)):
+            h, t, r, y = ops.sample_batch_constrained(
+                self.test_edge_index, self.test_edge_type, None, starts[i:i + 1], min(self.batch_size, self.num_test_edges - lo),
+                num_neg_samples, self.num_nodes, rng, classes=classes, known=known, max_tries=self.NEGATIVE_TRIES,
+                stats=self.negative_stats)
+            triples.append((h, t, r))
+            scores.append(torch.sigmoid(self.model.decoder.score_triples(emb, h, t, r)))
+            labels.append(y)
+        self.scored_triples = tuple(torch.cat(p) for p in zip(*triples))     # (heads, tails, rels) in score order
         return torch.cat(scores).cpu().numpy(), torch.cat(labels).cpu().numpy()
 
     def known_triples(self):
@@ -165,7 +196,7 @@ class ModelEvaluator:
                  type_constrained: bool = False, both_sides: bool = False) -> Dict:
         """the reference's four keys; with any of the three protocol options one more, ``"ranking_filtered"``: the
         same metric names under that protocol plus ``"protocol"`` saying which it was"""
-        scores, labels = self.compute_scores_and_labels(num_neg_samples)
+        scores, labels = self.compute_scores_and_labels(num_neg_samples, filtered, type_constrained)
         self.scores, self.labels = scores, labels          # kept for plotting code, as the reference does
         metrics = {"classification": self.compute_classification_metrics(scores, labels),
                    "ranking": self.compute_ranking_metrics(k_values),

@@ -1741,6 +1741,115 @@ class KnownTriples:
         return out[:b]
 
 
+class NodeClasses:
+    """The nodes of every class for type-constrained negatives: ``class_of`` int32 ``[N]`` (negative: no class),
+    ``ptr`` int64 ``[C + 1]``, ``members`` int64 (the node ids of class c are ``members[ptr[c] : ptr[c + 1]]``,
+    ascending) and ``sizes`` int64 ``[C]``.  Built once with a torch sort on whatever device ``class_of`` is on (CPU
+    tensors work: the logic is testable without a GPU).  A class ``>= num_classes`` raises ``IndexError``."""
+
+    def __init__(self, class_of: torch.Tensor, num_classes: int):
+        class_of = torch.as_tensor(class_of)
+        if class_of.dim() != 1 or class_of.numel() == 0 or int(num_classes) <= 0:
+            raise ValueError("class_of [N] (N > 0) and num_classes > 0 expected")
+        if class_of.dtype.is_floating_point or class_of.dtype == torch.bool:
+            raise TypeError(f"class_of must hold integers, got {class_of.dtype}")
+        self.num_nodes, self.num_classes = class_of.numel(), int(num_classes)
+        if int(class_of.max()) >= self.num_classes:
+            raise IndexError(f"a node's class is outside [0, {self.num_classes})")
+        self.class_of = class_of.to(torch.int32).contiguous()
+        self.device = self.class_of.device
+        sorted_class, by_class = torch.sort(self.class_of, stable=True)        # stable: ids ascend within a class
+        self.members = by_class[sorted_class >= 0].contiguous()
+        self.sizes = torch.bincount(sorted_class[sorted_class >= 0].to(torch.int64), minlength=self.num_classes)
+        self.ptr = torch.zeros(self.num_classes + 1, dtype=torch.int64, device=self.device)
+        self.ptr[1:] = torch.cumsum(self.sizes, 0)
+
+
+def sample_batch_constrained(edge_index: torch.Tensor, edge_type: torch.Tensor, order: Optional[torch.Tensor],
+                             cursor: Optional[torch.Tensor], batch: int, num_neg: int, num_nodes: int,
+                             rng: Optional[torch.Tensor], classes: Optional[NodeClasses] = None,
+                             known: Optional[KnownTriples] = None, max_tries: int = 8,
+                             stats: Optional[torch.Tensor] = None):
+    """``sample_batch`` under the evaluation protocol (``rgcn_sample_batch_constrained``, ``include/rgcn_sampling.h``):
+    with ``classes`` a replacement comes from the class of the node it replaces, with ``known`` it is redrawn - up to
+    ``max_tries`` draws, 1..16 - while it forms a known triple with the kept endpoint and the relation; the last
+    draw is kept if all are rejected.  ``stats`` (DEVICE int64[2]) is ADDED to: {rejected draws, negatives that gave
+    up}.  Same positives, labels and first Philox block as ``sample_batch``; with neither structure and
+    ``max_tries=1`` the same bits.  ``rng[1]`` (the epoch) must stay below 2**56.
+    -> (heads, tails, rels int64[B(1+k)], labels f32)."""
+    _need_gpu("edge_index", edge_index, torch.int64)
+    _need_gpu("edge_type", edge_type, torch.int64)
+    if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_type.shape != (edge_index.size(1),):
+        raise ValueError("edge_index must be [2, E] and edge_type [E]")
+    dev, e = edge_index.device, edge_index.size(1)
+    if order is not None:
+        _need_gpu("order", order, torch.int64)
+        if order.shape != (e,):
+            raise ValueError(f"order must be [{e}]")
+    if cursor is not None:
+        _need_gpu("cursor", cursor, torch.int64)
+        if cursor.numel() != 1:
+            raise ValueError("cursor must hold one int64")
+    if num_neg > 0:
+        if rng is None:
+            raise ValueError("rng (int64[2]: seed, epoch) is needed to draw negatives")
+        _need_gpu("rng", rng, torch.int64)
+        if rng.numel() != 2:
+            raise ValueError("rng must hold two int64 (seed, epoch)")
+    if batch < 0 or num_neg < 0 or (batch > 0 and e == 0):
+        raise ValueError("batch / num_neg must be >= 0 and the graph must have columns")
+    if not 1 <= int(max_tries) <= 16:
+        raise ValueError(f"max_tries must be in 1..16, got {max_tries}")
+    class_args = (None, None, None, 0)
+    if classes is not None:
+        if not isinstance(classes, NodeClasses):
+            raise TypeError("classes must be an ops.NodeClasses")
+        if classes.num_nodes != int(num_nodes):
+            raise ValueError(f"classes describe {classes.num_nodes} nodes, num_nodes is {num_nodes}")
+        _need_gpu("classes.class_of", classes.class_of, torch.int32)
+        _need_gpu("classes.ptr", classes.ptr, torch.int64)
+        _need_gpu("classes.members", classes.members, torch.int64)
+        if classes.members.numel():               # (no node has a class: every draw is uniform, as without classes)
+            class_args = (_ptr(classes.class_of), _ptr(classes.ptr), _ptr(classes.members), classes.num_classes)
+    known_args = (None, None, None, 0, 0) * 2 + (0,)
+    if known is not None:
+        if not isinstance(known, KnownTriples):
+            raise TypeError("known must be an ops.KnownTriples")
+        if known.num_nodes != int(num_nodes):
+            raise ValueError(f"known triples are over {known.num_nodes} nodes, num_nodes is {num_nodes}")
+        sides = []
+        for side in KnownTriples.SIDES:           # "tail", then "head": the order of the C signature
+            keys, ptr, ids = known.csr(side)
+            for name, t in (("keys", keys), ("ptr", ptr), ("ids", ids)):
+                _need_gpu(f"known.csr({side!r}) {name}", t, torch.int64)
+            if ptr.numel() != keys.numel() + 1:
+                raise ValueError(f"known.csr({side!r}): ptr must hold one entry more than keys")
+            sides += [_ptr(keys), _ptr(ptr), _ptr(ids), keys.numel(), ids.numel()]
+        if sides[4]:                              # (no known triple at all: nothing to reject)
+            known_args = tuple(sides) + (known.num_relations,)
+    for name, t in (("order", order), ("cursor", cursor), ("rng", rng if num_neg > 0 else None), ("stats", stats),
+                    ("classes", None if classes is None else classes.class_of),
+                    ("known", None if known is None else known.csr("tail")[0])):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, edge_index on {dev}")
+    if stats is not None:
+        _need_gpu("stats", stats, torch.int64)
+        if stats.numel() != 2:
+            raise ValueError("stats must hold two int64 (rejected draws, negatives that gave up)")
+    total = batch * (1 + num_neg)
+    lib = _L()
+    with _on(dev):
+        heads = _empty(total, dtype=torch.int64, device=dev)
+        tails, rels = torch.empty_like(heads), torch.empty_like(heads)
+        labels = _empty(total, dtype=torch.float32, device=dev)
+        rc = lib.rgcn_sample_batch_constrained(
+            _ptr(edge_index), _ptr(edge_type), e, _ptr(order), _ptr(cursor), batch, num_neg, int(num_nodes), _ptr(rng),
+            *class_args, *known_args, int(max_tries), _ptr(stats), _ptr(heads), _ptr(tails), _ptr(rels), _ptr(labels),
+            _stream())
+    _lib.check(rc, "rgcn_sample_batch_constrained")
+    return heads, tails, rels, labels
+
+
 def distmult_rank_masked(q: torch.Tensor, emb: torch.Tensor, true_score: torch.Tensor, target: torch.Tensor,
                          allow: Optional[torch.Tensor] = None, query_class: Optional[torch.Tensor] = None,
                          exclude: Optional[torch.Tensor] = None) -> torch.Tensor:

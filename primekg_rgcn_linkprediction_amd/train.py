@@ -60,6 +60,11 @@ class NegativeSampler:
         return torch.where(flip_head, entity, head), torch.where(flip_head, tail, entity), rel
 
 
+# Philox stream (the "epoch" word of the device sampler's counter) of validate()'s negatives under a constraint: no
+# training epoch gets there, and it is below the sampler's 2^56 limit
+VALIDATION_STREAM = 1 << 55
+
+
 def group_has_extras(optimizer: torch.optim.Optimizer) -> bool:
     """options of torch's Adam the two-launch update does not implement"""
     g = optimizer.param_groups
@@ -72,6 +77,21 @@ class Trainer:
 
     def __init__(self, model: DrugDiseaseModel, train_data: Dict, val_data: Dict, full_graph: Dict,
                  device: torch.device, args: argparse.Namespace):
+        # negatives under the evaluation protocol (off by default): filtered against the known triples and / or drawn
+        # from the class of the node they replace, by the constrained device sampler - there is no other path to them
+        self.filtered_negatives = bool(getattr(args, "filtered_negatives", False))
+        self.type_constrained_negatives = bool(getattr(args, "type_constrained_negatives", False))
+        self.constrained_negatives = self.filtered_negatives or self.type_constrained_negatives
+        if self.constrained_negatives:
+            if getattr(args, "torch_sampler", False):
+                raise ValueError("--filtered_negatives / --type_constrained_negatives need the device sampler: drop --torch_sampler")
+            if device.type != "cuda":
+                raise ValueError("--filtered_negatives / --type_constrained_negatives run on the GPU only (no CPU sampler)")
+            if self.type_constrained_negatives and not getattr(args, "node_types", None):
+                raise ValueError("--type_constrained_negatives needs --node_types PATH (mappings.pt, or an .npz / .pt "
+                                 "int vector [num_nodes])")
+            if not 1 <= int(getattr(args, "negative_tries", 8)) <= 16:
+                raise ValueError("--negative_tries must be in 1..16")
         self.model = model.to(device)
         self.device, self.args = device, args
         self.train_data, self.val_data, self.full_graph = train_data, val_data, full_graph
@@ -108,6 +128,21 @@ class Trainer:
         self.device_sampler = device.type == "cuda" and not getattr(args, "torch_sampler", False)
         self.criterion = nn.BCEWithLogitsLoss()
         self.neg_sampler = NegativeSampler(train_data["num_nodes"], args.num_neg_samples)
+        self._neg_classes = self._neg_known = self._neg_known_full = self._neg_stats = None
+        self.negative_stats = (0, 0)       # (rejected draws, negatives that gave up) of the last training epoch
+        if self.constrained_negatives:
+            n, r = train_data["num_nodes"], train_data["num_relations"]
+            self.negative_tries = int(getattr(args, "negative_tries", 8))
+            if self.type_constrained_negatives:
+                from .evaluate import load_node_classes
+                class_of = load_node_classes(args.node_types, n)
+                self._neg_classes = ops.NodeClasses(class_of.to(device), max(int(class_of.max()) + 1, 1))
+            if self.filtered_negatives:
+                # what training may know: the train graph - not the validation or test triples (no leakage);
+                # validate() scores over the full graph and filters against it
+                self._neg_known = ops.KnownTriples(self.train_edge_index, self.train_edge_type, n, r)
+                self._neg_known_full = ops.KnownTriples(self.full_edge_index, self.full_edge_type, n, r)
+            self._neg_stats = torch.zeros(2, dtype=torch.int64, device=device)
         self.best_val_loss, self.best_val_acc = float("inf"), 0.0
         self.train_losses, self.val_losses, self.train_accs, self.val_accs = [], [], [], []
         self.output_dir = Path(args.output_dir)
@@ -142,6 +177,12 @@ class Trainer:
         """(heads, tails, rels, labels) of train columns ``order[lo : lo + size]`` plus their
         negatives.  Device sampler: one launch reading the position from ``self._cursor``;
         ``--torch_sampler``: the reference's op sequence on torch's RNG stream."""
+        if self.constrained_negatives:
+            from . import ops
+            return ops.sample_batch_constrained(self.train_edge_index, self.train_edge_type, self._order, self._cursor, size,
+                                                self.neg_sampler.num_neg_samples, self.neg_sampler.num_nodes, self._rng,
+                                                classes=self._neg_classes, known=self._neg_known,
+                                                max_tries=self.negative_tries, stats=self._neg_stats)
         if self.device_sampler:
             from . import ops
             return ops.sample_batch(self.train_edge_index, self.train_edge_type, self._order, self._cursor, size,
@@ -252,6 +293,8 @@ class Trainer:
         self._correct.zero_()
         self._cursor.zero_()
         self._rng[1] += 1
+        if self._neg_stats is not None:
+            self._neg_stats.zero_()
         # the permutation is drawn on the host like the reference's torch.randperm(num_edges)
         self._order.copy_(torch.randperm(e))
         steps = -(-e // bsz)
@@ -278,6 +321,8 @@ class Trainer:
             if on_step is not None:
                 on_step(*out)
         result = (self._loss_sum / max(seen, 1)).item(), self._correct.item() / max(seen, 1)
+        if self._neg_stats is not None:      # read back once per epoch, with the loss
+            self.negative_stats = tuple(self._neg_stats.tolist())
         ops.check_indices(self.device)       # an id outside the embedding table anywhere in the epoch: IndexError, here
         return result
 
@@ -294,8 +339,7 @@ class Trainer:
         # sampler on torch's RNG stream, as there.
         fused = self._fused_bookkeeping and hasattr(self.model, "encoder") and hasattr(self.model, "decoder")
         emb = self.model.encoder(self.full_edge_index, self.full_edge_type) if fused else None
-        for head, tail, rel in self._batches(self.val_edge_index, self.val_edge_type, shuffle=False):
-            heads, tails, rels, labels = self._with_negatives(head, tail, rel)
+        for heads, tails, rels, labels in self._validation_batches():
             if fused:
                 self.model.decoder.bce_loss(emb, heads, tails, rels, labels, stats=(loss_sum, correct, None, 0))
             else:
@@ -306,6 +350,23 @@ class Trainer:
         result = (loss_sum / max(seen, 1)).item(), correct.item() / max(seen, 1)
         ops.check_indices(self.device)
         return result
+
+    def _validation_batches(self):
+        """(heads, tails, rels, labels) of every validation batch.  Default: the reference's sampler on torch's RNG
+        stream.  Under a constraint: the constrained device sampler at cursor = the batch start, keyed by the run's
+        seed on a stream of its own, filtered against the FULL graph - the same negatives every time it is called."""
+        if not self.constrained_negatives:
+            for head, tail, rel in self._batches(self.val_edge_index, self.val_edge_type, shuffle=False):
+                yield self._with_negatives(head, tail, rel)
+            return
+        e, bsz = self.val_edge_index.size(1), self.args.batch_size
+        starts = torch.arange(0, max(e, 1), bsz, device=self.device, dtype=torch.int64)
+        rng = torch.tensor([torch.initial_seed() & 0x7FFFFFFFFFFFFFFF, VALIDATION_STREAM], dtype=torch.int64).to(self.device)
+        for i, lo in enumerate(range(0, e, bsz)):
+            yield ops.sample_batch_constrained(self.val_edge_index, self.val_edge_type, None, starts[i:i + 1],
+                                               min(bsz, e - lo), self.neg_sampler.num_neg_samples,
+                                               self.neg_sampler.num_nodes, rng, classes=self._neg_classes,
+                                               known=self._neg_known_full, max_tries=self.negative_tries)
 
     # -- checkpoints (same keys as train.py:431-442) --------------------------------------
     def save_checkpoint(self, epoch: int, is_best: bool = False, is_final: bool = False,
@@ -333,8 +394,11 @@ class Trainer:
             va_loss, va_acc = self.validate()
             self.train_losses.append(tr_loss); self.train_accs.append(tr_acc)
             self.val_losses.append(va_loss); self.val_accs.append(va_acc)
+            negatives = ("" if not self.constrained_negatives else
+                         " | Neg Rejected: %d | Neg Gave Up: %d" % self.negative_stats)
             logger.info("Epoch %d/%d | Time: %.2fs | Train Loss: %.4f | Train Acc: %.4f | Val Loss: %.4f | "
-                        "Val Acc: %.4f", epoch, self.args.epochs, time.time() - t0, tr_loss, tr_acc, va_loss, va_acc)
+                        "Val Acc: %.4f%s", epoch, self.args.epochs, time.time() - t0, tr_loss, tr_acc, va_loss, va_acc,
+                        negatives)
             is_best = va_loss < self.best_val_loss
             if is_best:
                 self.best_val_loss = va_loss
@@ -442,6 +506,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--torch_sampler", action="store_true",
                    help="draw negatives with the reference's torch.rand/randint sequence instead of the "
                         "one-kernel device sampler")
+    p.add_argument("--filtered_negatives", action="store_true",
+                   help="redraw a training negative that is a known triple of the train graph (validation: of the full "
+                        "graph); needs the device sampler")
+    p.add_argument("--type_constrained_negatives", action="store_true",
+                   help="replace a node only by a node of its own type (needs --node_types and the device sampler)")
+    p.add_argument("--node_types", type=str, default=None,
+                   help="the preprocessing's mappings.pt, or an .npz / .pt holding an int vector [num_nodes]")
+    p.add_argument("--negative_tries", type=int, default=8,
+                   help="draws per filtered negative before the last one is kept (1..16)")
     p.add_argument("--no_hip_graph", action="store_true",
                    help="launch every training step eagerly instead of replaying one captured HIP graph")
     p.add_argument("--synthetic", action="store_true",
