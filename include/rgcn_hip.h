@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 30
+#define RGCN_ABI_VERSION 31
 
 enum {
   RGCN_OK = 0,

@@ -13,7 +13,7 @@ from ctypes import c_double, c_float, POINTER, c_char_p, c_int, c_int64, c_size_
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 LIB_NAME = "librgcn_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -156,6 +156,16 @@ SAMPLING_PROTOTYPES = {
                                               _P, _P, _P, _P, _P]),
 }
 
+# include/rgcn_paths.h, one to one: score-ranked connecting paths between node pairs (csrc/paths.hip; not part of
+# rgcn_hip.h, never forwarded by rgcn_sequence_run - an analysis call, outside any recorded Region)
+PATHS_PROTOTYPES = {
+    "rgcn_edge_cosine": (c_int, [_P, _I64, c_int, _P, _P, _I64, _P, _P]),
+    "rgcn_paths_workspace_bytes": (c_size_t, [_I64, c_int, c_int]),
+    "rgcn_paths_topk": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64,            # structure, edge scores
+                                _P, _P, _I64, c_int, c_int, c_int,             # queries, max_len, k, slices
+                                _P, _P, _P, _P, _P, c_size_t, _P]),            # outputs, workspace, stream
+}
+
 _lib = None
 
 
@@ -177,7 +187,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise RGCNLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -18,6 +18,11 @@ form is a plain library GEMM, the ranking a stable descending sort (ties keep ca
 order, as the reference's ``list.sort(reverse=True)`` does).  The batched forms (``predict_top_drugs_batch``,
 ``novel_drug_predictions``) select on the device instead: the fused top-k pass over unit rows, the drugs as its allow
 mask, the known associations as its exclude mask - no ``[diseases, drugs]`` matrix, no sort.
+
+``connecting_paths`` answers the "why" the scripts ask next (``explain_predictions.find_paths`` / ``score_path`` /
+``rank_paths``, ``case_studies.py:319-351``, ``analyze_failures.py:345-366``: ``networkx.all_simple_paths(cutoff=4)``
+scored by the mean cosine of consecutive nodes times a length penalty): the k best of ALL simple paths between a
+pair, enumerated on the device (``ops.paths_topk``).
 """
 from __future__ import annotations
 
@@ -122,3 +127,32 @@ def novel_drug_predictions(embeddings: Tensor, disease_indices: _Index, drug_ind
     ids, dis, scores = ids[keep], dis[keep], scores[keep]
     order = torch.sort(scores, descending=True, stable=True).indices[:top_k]
     return list(zip(ids[order].tolist(), dis[order].tolist(), scores[order].tolist()))
+
+
+@torch.no_grad()
+def connecting_paths(embeddings: Tensor, graph: "ops.PathGraph", pairs, k: int = 5, max_len: int = 4,
+                     return_counts: bool = False, edge_score: Optional[Tensor] = None):
+    """For every ``(source, target)`` of ``pairs`` the ``k`` best-scoring simple paths of at most ``max_len`` edges,
+    best first: a list per pair of ``{"nodes": [...], "relations": [...], "length": L, "score": s}`` (the content of the
+    reference's ``get_path_details``; ``relations[i]`` is the relation of hop i in ``graph``).  The score is the mean
+    cosine of consecutive nodes times ``1 / (1 + 0.2 * (L - 1))`` (``ops.paths_topk`` over ``ops.edge_cosine``; pass
+    ``edge_score`` to reuse or replace the per-edge scores).  ``return_counts``: also the exact number of simple paths of
+    length 1..4 per pair, ``(paths, counts)``."""
+    dev = embeddings.device
+    p = torch.as_tensor(pairs, dtype=torch.int64).reshape(-1, 2).to(dev)
+    graph = graph.to(dev)
+    if edge_score is None:
+        edge_score = ops.edge_cosine(embeddings.contiguous(), graph)
+    nodes, length, score, count = ops.paths_topk(graph, edge_score, p[:, 0].contiguous(), p[:, 1].contiguous(), k, max_len)
+    # the relation of every hop: its position among the (src, dst)-sorted unique pairs
+    u, v = nodes[:, :, :-1].to(torch.int64), nodes[:, :, 1:].to(torch.int64)
+    hop = (u >= 0) & (v >= 0)
+    rel = torch.full(u.shape, -1, dtype=torch.int32, device=dev)
+    if graph.nnz:
+        keys = graph.out_src * graph.num_nodes + graph.out_dst.to(torch.int64)
+        pos = torch.searchsorted(keys, (u * graph.num_nodes + v)[hop])
+        rel[hop] = graph.out_rel[pos.clamp_(max=graph.nnz - 1)]
+    nodes, rel, length, score = nodes.cpu().tolist(), rel.cpu().tolist(), length.cpu().tolist(), score.cpu().tolist()
+    paths = [[{"nodes": nodes[q][j][:length[q][j] + 1], "relations": rel[q][j][:length[q][j]], "length": length[q][j],
+               "score": score[q][j]} for j in range(len(length[q])) if length[q][j] > 0] for q in range(len(length))]
+    return (paths, count.cpu().tolist()) if return_counts else paths

@@ -36,7 +36,7 @@ class ModelEvaluator:
                  batch_size: int = 1024, node_class: Optional[torch.Tensor] = None):
         self.model = model.to(device).eval()
         self.node_class = None if node_class is None else torch.as_tensor(node_class).to(device=device, dtype=torch.int32)
-        self._known = self._classes = None
+        self._known = self._classes = self._path_graph = self._edge_cosine = None
         self.device, self.batch_size = device, batch_size
         self.test_edge_index = test_data["edge_index"].to(device)
         self.test_edge_type = test_data["edge_type"].to(device)
@@ -169,6 +169,21 @@ class ModelEvaluator:
         if side == "tail":
             return self.model.decoder.top_tails(emb[anchors], relations, emb, k, head_indices=anchors, **kwargs)
         return self.model.decoder.top_heads(emb[anchors], relations, emb, k, tail_indices=anchors, **kwargs)
+
+    @torch.no_grad()
+    def explain(self, pairs, k: int = 5, max_len: int = 4):
+        """why a pair is predicted: for every ``(source, target)`` of ``pairs`` the ``k`` best-scoring simple paths of at
+        most ``max_len`` edges through the full graph (``consumers.connecting_paths`` on the cached embeddings) and the
+        exact number of such paths of length 1..4 -> ``(paths, counts)``.  The full graph's ``PathGraph`` and the cosine
+        of every edge are built on first use and kept."""
+        from . import consumers, ops
+        if self._path_graph is None:
+            self._path_graph = ops.PathGraph(self.full_edge_index, self.full_edge_type, self.num_nodes)
+        emb = self.embeddings()
+        if self._edge_cosine is None:
+            self._edge_cosine = ops.edge_cosine(emb.contiguous(), self._path_graph)
+        return consumers.connecting_paths(emb, self._path_graph, pairs, k, max_len, return_counts=True,
+                                          edge_score=self._edge_cosine)
 
     def compute_ranking_metrics(self, k_values: Sequence[int] = (10, 50), filtered: bool = False,
                                 type_constrained: bool = False, both_sides: bool = False) -> Dict:

@@ -2007,6 +2007,134 @@ def distmult_topk_filtered(q: torch.Tensor, emb: torch.Tensor, k: int, known: Op
     return ids, scores
 
 
+PATHS_MAX_K = 64          # one list entry per lane of the inserting wave (csrc/paths.hip)
+PATHS_MAX_LEN = 4         # edges of the longest path
+PATHS_LDS_IDS = 2048      # in-neighbours of a target the enumeration stages in LDS; more are read from global memory
+
+
+class PathGraph:
+    """The node-level digraph of a relational graph for the path search (``include/rgcn_paths.h``) - what
+    ``networkx.DiGraph.add_edge`` in a loop over the columns builds: the UNIQUE ``(src, dst)`` pairs, each with the
+    relation of the LAST column that names it.  Built once with a torch sort on whatever device the edges are on (CPU
+    tensors work: the logic is testable without a GPU).  ``out_ptr`` int64 ``[N + 1]``, ``out_dst`` int32 ``[nnz]``
+    (by src, then dst ascending), ``out_rel`` int32 ``[nnz]``; ``in_ptr`` / ``in_src`` the same pairs by dst, then src;
+    ``in_pos`` int64 ``[nnz]`` the position of every in-entry in the out arrays.  Self loops are kept."""
+
+    def __init__(self, edge_index: torch.Tensor, edge_type: torch.Tensor, num_nodes: int):
+        if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_type.shape != (edge_index.size(1),):
+            raise ValueError("edge_index must be [2, E] and edge_type [E]")
+        self.num_nodes = n = int(num_nodes)
+        if n <= 0 or n >= 2 ** 31:
+            raise ValueError("num_nodes must be in [1, 2^31)")
+        ei = edge_index.to(torch.int64)
+        if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= n):
+            raise IndexError("a node id of the path graph is outside [0, num_nodes)")
+        self.device = dev = ei.device
+        order = torch.argsort(ei[0] * n + ei[1], stable=True)                   # equal pairs stay in column order
+        pair, counts = torch.unique_consecutive((ei[0] * n + ei[1])[order], return_counts=True)
+        last = order[torch.cumsum(counts, 0) - 1]                              # the last column of every pair
+        src = torch.div(pair, n, rounding_mode="floor")
+        dst = pair - src * n
+        self.nnz = int(pair.numel())
+        self.out_dst = dst.to(torch.int32).contiguous()
+        self.out_rel = edge_type[last].to(torch.int32).contiguous()
+        self.out_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        self.out_ptr[1:] = torch.cumsum(torch.bincount(src, minlength=n), 0)
+        self.in_pos = torch.argsort(dst * n + src).contiguous()                # (the keys are distinct)
+        self.in_src = src[self.in_pos].to(torch.int32).contiguous()
+        self.in_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        self.in_ptr[1:] = torch.cumsum(torch.bincount(dst, minlength=n), 0)
+        self.out_src = src                                                     # int64 [nnz]: the source of every out-entry
+
+    def to(self, device) -> "PathGraph":
+        """the same structure with its arrays on ``device`` (a copy of the handle; ``self`` when already there)"""
+        device = torch.device(device)
+        if device == self.device:
+            return self
+        other = object.__new__(PathGraph)
+        other.__dict__.update({k: v.to(device) if isinstance(v, torch.Tensor) else v for k, v in self.__dict__.items()})
+        other.device = other.out_ptr.device
+        return other
+
+    def _arrays(self):
+        return (("out_ptr", self.out_ptr, torch.int64), ("out_dst", self.out_dst, torch.int32),
+                ("in_ptr", self.in_ptr, torch.int64), ("in_src", self.in_src, torch.int32),
+                ("in_pos", self.in_pos, torch.int64))
+
+
+def edge_cosine(emb: torch.Tensor, graph: PathGraph) -> torch.Tensor:
+    """float32 ``[nnz]``: the cosine of the two embedding rows of every unique edge of ``graph``, in the order of its
+    out arrays (``rgcn_edge_cosine``); a zero row gives 0.0.  The embedding dim must be a multiple of 32."""
+    if not isinstance(graph, PathGraph):
+        raise TypeError("graph must be an ops.PathGraph")
+    _need_gpu("emb", emb, torch.float32)
+    if emb.dim() != 2 or emb.size(0) != graph.num_nodes:
+        raise ValueError(f"emb [{graph.num_nodes}, d] expected")
+    for name, t, dtype in graph._arrays()[:2]:
+        _need_gpu(f"graph.{name}", t, dtype)
+        if t.device != emb.device:
+            raise ValueError(f"graph.{name} is on {t.device}, emb on {emb.device}")
+    with _on(emb.device):
+        out = torch.empty(graph.nnz, dtype=torch.float32, device=emb.device)
+        rc = _L().rgcn_edge_cosine(_ptr(emb), graph.num_nodes, emb.size(1), _ptr(graph.out_ptr), _ptr(graph.out_dst),
+                                   graph.nnz, _ptr(out), _stream())
+    _lib.check(rc, "rgcn_edge_cosine")
+    return out
+
+
+def paths_topk(graph: PathGraph, edge_score: torch.Tensor, sources: torch.Tensor, targets: torch.Tensor, k: int,
+               max_len: int = 4, slices: int = 0):
+    """The ``k`` best-scoring simple paths of at most ``max_len`` edges from ``sources[q]`` to ``targets[q]``, out of
+    ALL of them, and their exact number per length (``rgcn_paths_topk``, ``include/rgcn_paths.h``) ->
+    ``(nodes int32 [Q, k, 5], length int32 [Q, k], score float32 [Q, k], count int64 [Q, 4])``.  A path's score is
+    ``(((c1 + c2) + c3) + c4)[first L terms] * float32(1 / (L * (1 + 0.2 * (L - 1))))`` in fp32, ``c_i`` the
+    ``edge_score`` (one float per out-entry of ``graph``, e.g. ``edge_cosine``) of hop i.  Order: score descending, then
+    fewer edges, then the interior nodes lexicographically; a NaN score is counted and never listed.  Empty slots:
+    nodes -1, length 0, score -inf.  ``slices``: workgroups per query (0: chosen from Q); the result does not depend on
+    it."""
+    k, max_len, slices = int(k), int(max_len), int(slices)
+    if not 1 <= k <= PATHS_MAX_K:
+        raise ValueError(f"k must be in [1, {PATHS_MAX_K}] (the path kernel keeps at most {PATHS_MAX_K} paths per query), got {k}")
+    if not 1 <= max_len <= PATHS_MAX_LEN:
+        raise ValueError(f"max_len must be in [1, {PATHS_MAX_LEN}], got {max_len}")
+    if slices < 0:
+        raise ValueError("slices must be >= 0 (0: chosen from the number of queries)")
+    if not isinstance(graph, PathGraph):
+        raise TypeError("graph must be an ops.PathGraph")
+    _need_gpu("edge_score", edge_score, torch.float32)
+    _need_gpu("sources", sources, torch.int64)
+    _need_gpu("targets", targets, torch.int64)
+    dev = edge_score.device
+    for name, t, dtype in graph._arrays():
+        _need_gpu(f"graph.{name}", t, dtype)
+        if t.device != dev:
+            raise ValueError(f"graph.{name} is on {t.device}, edge_score on {dev}")
+    if edge_score.shape != (graph.nnz,):
+        raise ValueError(f"edge_score [{graph.nnz}] (one per unique edge) expected")
+    if sources.dim() != 1 or sources.shape != targets.shape or sources.device != dev or targets.device != dev:
+        raise ValueError("sources [Q] and targets [Q] on the graph's device expected")
+    q = sources.numel()
+    if q and (int(torch.minimum(sources.min(), targets.min())) < 0
+              or int(torch.maximum(sources.max(), targets.max())) >= graph.num_nodes):
+        raise IndexError("a source or target id is outside [0, num_nodes)")
+    lib = _L()
+    with _on(dev):
+        nodes = torch.empty((q, k, PATHS_MAX_LEN + 1), dtype=torch.int32, device=dev)
+        length = torch.empty((q, k), dtype=torch.int32, device=dev)
+        score = torch.empty((q, k), dtype=torch.float32, device=dev)
+        count = torch.empty((q, PATHS_MAX_LEN), dtype=torch.int64, device=dev)
+        if q == 0:
+            return nodes, length, score, count
+        nbytes = int(lib.rgcn_paths_workspace_bytes(q, k, slices))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rc = lib.rgcn_paths_topk(_ptr(graph.out_ptr), _ptr(graph.out_dst), _ptr(edge_score), _ptr(graph.in_ptr),
+                                 _ptr(graph.in_src), _ptr(graph.in_pos), graph.num_nodes, graph.nnz, _ptr(sources),
+                                 _ptr(targets), q, max_len, k, slices, _ptr(nodes), _ptr(length), _ptr(score), _ptr(count),
+                                 _ptr(ws), nbytes, _stream())
+    _lib.check(rc, "rgcn_paths_topk")
+    return nodes, length, score, count
+
+
 def distmult_score_all_tails(head: torch.Tensor, rel: torch.Tensor, rel_idx: Optional[torch.Tensor],
                              emb: torch.Tensor):
     """``((head * rel[rel_idx]) @ emb.T, head * rel[rel_idx])`` - the [B, N] score matrix of

@@ -12,7 +12,9 @@ not-known candidates while the score tiles are still in registers (no ``[B, N]``
 
 writes ``predictions.json``: ``{"protocol": {...}, "queries": [{"anchor", "relation", "candidates": [[id, score],
 ...]}]}``, best first, equal scores by id; with a ``mappings.pt`` as ``--node_types`` every query also carries
-``anchor_name`` and ``candidate_names``.
+``anchor_name`` and ``candidate_names``.  ``--explain K`` adds to every query ``"paths"`` - per candidate the K
+best-scoring simple paths of at most ``--max_path_length`` edges between anchor and candidate through the full graph
+(``ModelEvaluator.explain``) - and ``"path_counts"``, per candidate the exact number of such paths of length 1..4.
 """
 from __future__ import annotations
 
@@ -48,6 +50,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--node_types", type=str, default=None,
                    help="the preprocessing's mappings.pt, or an .npz / .pt holding an int vector [num_nodes]")
     p.add_argument("--min_score", type=float, default=None, help="only candidates with a score >= this")
+    p.add_argument("--explain", type=int, default=0, metavar="K",
+                   help="also list the K best-scoring connecting paths of every (anchor, candidate) (0: off)")
+    p.add_argument("--max_path_length", type=int, default=4, help="edges of the longest connecting path, 1..4")
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--trust_checkpoint", action="store_true",
                    help="allow the unrestricted pickle loader for --model_path (only for files you wrote yourself)")
@@ -62,6 +67,10 @@ def parse_args(argv=None) -> argparse.Namespace:
                      "vector [num_nodes])")
     if args.top_k < 1:
         parser.error("--top_k must be >= 1")
+    if args.explain < 0:
+        parser.error("--explain must be >= 0")
+    if not 1 <= args.max_path_length <= 4:
+        parser.error("--max_path_length must be in 1..4")
     return args
 
 
@@ -100,6 +109,26 @@ def predict(evaluator, args: argparse.Namespace, names: Optional[Dict[int, str]]
     protocol = {"side": args.side, "top_k": args.top_k, "novel": bool(args.novel),
                 "candidate_class": args.candidate_class, "anchor_class": args.anchor_class, "min_score": args.min_score,
                 "order": "score descending, equal scores by id ascending"}
+    explain = int(getattr(args, "explain", 0) or 0)
+    if explain > 0:
+        # the triple reads (anchor, relation, candidate) for tails and (candidate, relation, anchor) for heads
+        pairs = [(q["anchor"], c) if args.side == "tail" else (c, q["anchor"]) for q in queries for c, _ in q["candidates"]]
+        max_len = int(getattr(args, "max_path_length", 4))
+        paths, counts = evaluator.explain(pairs, explain, max_len) if pairs else ([], [])
+        at = 0
+        for q in queries:
+            n = len(q["candidates"])
+            q["paths"], q["path_counts"] = paths[at:at + n], counts[at:at + n]
+            at += n
+            if names is not None:
+                for per_candidate in q["paths"]:
+                    for path in per_candidate:
+                        path["node_names"] = [names.get(i) for i in path["nodes"]]
+        protocol["paths"] = {"per_candidate": explain, "max_length": max_len,
+                             "pair": "(anchor, candidate)" if args.side == "tail" else "(candidate, anchor)",
+                             "score": "mean cosine of consecutive nodes * 1 / (1 + 0.2 * (edges - 1)), float32",
+                             "order": "score descending, then fewer edges, then interior nodes ascending",
+                             "path_counts": "simple paths of 1, 2, 3, 4 edges, all of them"}
     return {"protocol": protocol, "queries": queries}
 
 
