@@ -518,15 +518,16 @@ int rgcn_adam_clip_step(int num_tensors, float* const* params, const float* cons
  * compute_ranking_metrics evaluate.py:260-276, without materialising the [B, N] score matrix
  * or sorting it): hr = head_emb * rel_emb rows [B, d]; scores[b, n] = <hr[b], emb[n]> on the
  * fp32 MFMA; beaten_by[b] += #{ n != tail[b] : scores[b, n] > true_score[b] } (int atomics into
- * a caller-zeroed buffer), so rank[b] = 1 + beaten_by[b].  d must be a multiple of 32. */
+ * a caller-zeroed buffer), so rank[b] = 1 + beaten_by[b].  d must be a multiple of 32.  The launch of
+ * distmult_rank_masked with no mask; a tail outside [0, num_entities) leaves no candidate out. */
 int distmult_rank_tails(const float* hr, const float* emb, const float* true_score,
                         const int64_t* tail, int64_t batch, int64_t num_entities, int64_t d,
                         int32_t* beaten_by, void* stream);
 
 /* Filtered and / or type-constrained ranking, either side of a triple (DistMult is symmetric: q = head_emb * rel_emb
- * ranks tails, q = tail_emb * rel_emb ranks heads): the pass of distmult_rank_tails - same operands, tile walk and
- * accumulation on the fp32 MFMA, so a score compared here, there and the one distmult_score_all_tails stores are
- * the same bits - with a candidate filter in the counting epilogue:
+ * ranks tails, q = tail_emb * rel_emb ranks heads): the kernel of distmult_rank_tails - one k-tile definition with
+ * distmult_score_all_tails on the fp32 MFMA, so a score compared here, there and the one that entry point stores are
+ * the same bits - with a candidate filter, typed parameters of the kernel, in the counting epilogue:
  *   beaten_by[b] += #{ n != target[b] : scores[b, n] > true_score[b]
  *                                       and bit n of allow[query_class[b]] is set   (allow != NULL)
  *                                       and bit n of exclude[b]            is clear (exclude != NULL) }

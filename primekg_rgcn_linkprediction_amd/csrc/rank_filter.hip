@@ -1,5 +1,5 @@
-// Candidate filters of the masked ranking pass (distmult_rank_masked, the EPI_RANK_MASKED epilogue of
-// k_gemm_nt_dma in rgcn_transform.hip) as bit masks over the entities: bit (n & 31) of word (n >> 5), W = ceil(N / 32)
+// Candidate filters of the masked ranking pass (distmult_rank_masked: k_rank_count in rank_count.hip) and of the
+// top-k pass (rank_topk.hip) as bit masks over the entities: bit (n & 31) of word (n >> 5), W = ceil(N / 32)
 // words per row - the layout in which one ballot word of the ranking epilogue meets exactly one mask word.
 //   exclude[b] : the known positives of query b (filtered ranking, Bordes et al.), from a CSR of known triples
 //   allow[c]   : the entities of class c (type-constrained ranking), from a node-class vector

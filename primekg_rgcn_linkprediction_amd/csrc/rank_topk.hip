@@ -2,10 +2,10 @@
 // (case_studies.predict_top_drugs / medical_validation.generate_predictions + _filter_known_associations of the
 // reference: "which entities, allowed and not already linked, does the model score highest for this query?").
 //
-//   score[b, n] = <q[b], emb[n]>   - the k loop of k_gemm_nt_dma<2, B_BLK> (rgcn_transform.hip) restated: the same
-//                                    LDS-DMA ring, fragment reads and v_mfma_f32_32x32x2_f32 sequence per output
-//                                    element, so a score here and the one distmult_score_all_tails stores are the
-//                                    same bits
+//   score[b, n] = <q[b], emb[n]>   - the k-tile of k_gemm_nt_dma<2, B_BLK> (rgcn_transform.hip), shared
+//                                    (rgcn_mma_f32_dma.h): the same LDS-DMA ring, fragment reads and
+//                                    v_mfma_f32_32x32x2_f32 sequence per output element, so a score here and the one
+//                                    distmult_score_all_tails stores are the same bits
 //   candidates  = allowed (allow[query_class[b]]), not excluded (exclude[b]), not NaN, >= min_score
 //   order       = score descending, equal scores by entity id ascending
 //
@@ -13,7 +13,7 @@
 // the entity range, ids ascending.  The (column tile, k-tile) pairs form ONE stream through the three-buffer ring,
 // so the DMA pipeline never drains between column tiles.  After the last k-tile of a column tile the accumulators
 // are tested against the row's current k-th best score (one ballot per accumulator register, filtered by one mask
-// word per row and 32-column group exactly as EPI_RANK_MASKED does) and the survivors - about k ln(N / k) per row
+// word per row and 32-column group exactly as k_rank_count does) and the survivors - about k ln(N / k) per row
 // over the whole walk - are inserted by the whole wave into the row's sorted list in LDS.
 //   One list per ROW: the two waves that share a row (wave columns 0 and 1) insert one after the other - wave
 //   column 0, a barrier, wave column 1 - so every row sees ONE stream of candidates with ascending ids, and
@@ -24,25 +24,19 @@
 #include <algorithm>
 
 #include "rgcn_common.h"
+#include "rgcn_mma_f32_dma.h"
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace mma_f32_dma;    // kThreads (256: 4 waves, 2 (m) x 2 (n)), BK, BM, NBUF, glds16, the vector types
 
-constexpr int kThreads = 256;   // 4 waves, arranged 2 (m) x 2 (n)
-constexpr int BK = 32, BM = 64, BN = 128, NBUF = 3;
-constexpr int A_FLOATS = BM * BK, B_FLOATS = BN * BK, BUF_FLOATS = A_FLOATS + B_FLOATS;
-constexpr int A_PW = BM / 32, B_PW = BN / 32, P = A_PW + B_PW;   // LDS-DMA instructions per thread and k-tile
+typedef KTile<2, B_BLK> Tile;   // 64 x 128 outputs per workgroup, B = embedding rows
+constexpr int BN = Tile::BN, A_FLOATS = Tile::A_FLOATS, BUF_FLOATS = Tile::BUF_FLOATS;
+constexpr int A_PW = Tile::A_PW, B_PW = Tile::B_PW, P = Tile::P;
 constexpr int STAGE_BYTES = NBUF * BUF_FLOATS * 4;               // 73,728
 constexpr int kMaxK = 128;      // list length the select pass is built for (two entries per lane of the inserting wave)
 constexpr int kMaxSlices = 256; // one list per thread of the merge workgroup
 constexpr int kCUs = 256;       // MI355X
-
-__device__ inline void glds16(const float* src, float* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 // dynamic LDS of the select pass: [ring 73,728 B][thr f32 x 64][cnt i32 x 64][scores f32 x 64 k][ids i32 x 64 k]
 __host__ __device__ inline size_t select_lds_bytes(int k) { return (size_t)STAGE_BYTES + 2 * BM * 4 + (size_t)BM * k * 8; }
@@ -119,19 +113,19 @@ __global__ __launch_bounds__(kThreads) void k_topk_select(const float* __restric
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
 
-  // per-lane source offsets of the LDS-DMAs (see k_gemm_nt_dma: 16-byte chunks XOR-swizzled with (row >> 1) & 7)
+  // per-lane source offsets of the LDS-DMAs
   size_t a_off[A_PW];
 #pragma unroll
   for (int j = 0; j < A_PW; ++j) {
-    const int row = (wave * A_PW + j) * 8 + (lane >> 3);
+    const int row = dma_row(wave * A_PW + j, lane);
     const int m = min(m0 + row, M - 1);                        // rows past M read a valid row; never selected
-    a_off[j] = (size_t)m * d + (((lane & 7) ^ ((row >> 1) & 7)) << 2);
+    a_off[j] = (size_t)m * d + dma_col(row, lane);
   }
   int b_row[B_PW], b_chunk[B_PW];
 #pragma unroll
   for (int j = 0; j < B_PW; ++j) {
-    b_row[j] = (wave * B_PW + j) * 8 + (lane >> 3);
-    b_chunk[j] = ((lane & 7) ^ ((b_row[j] >> 1) & 7)) << 2;
+    b_row[j] = dma_row(wave * B_PW + j, lane);
+    b_chunk[j] = dma_col(b_row[j], lane);
   }
   auto stage = [&](int ct, int kt, int buf) {
     float* sA = lds + buf * BUF_FLOATS;
@@ -158,28 +152,7 @@ __global__ __launch_bounds__(kThreads) void k_topk_select(const float* __restric
   }
   const uint32_t* erow_p = excl ? excl + (size_t)min(mrow, M - 1) * words : nullptr;
 
-  // fragment reads: inline asm with hand-counted waits (see k_gemm_nt_dma)
-  const int arow = wm * 32 + li;
-  unsigned a_addr[4], b_addr[2][4];
-#pragma unroll
-  for (int s4 = 0; s4 < 4; ++s4) {
-    a_addr[s4] = (unsigned)(arow * BK + (((2 * s4 + lh) ^ ((arow >> 1) & 7)) << 2)) * 4u;
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int brow = (wn * 2 + b) * 32 + li;
-      b_addr[b][s4] = (unsigned)(A_FLOATS + brow * BK + (((2 * s4 + lh) ^ ((brow >> 1) & 7)) << 2)) * 4u;
-    }
-  }
-  f32x4 fa[2];
-  f32x4 fb[2][2];
-  auto read_frags = [&](int set, int s4, unsigned buf_bytes) {
-    asm volatile("ds_read_b128 %0, %1" : "=v"(fa[set]) : "v"(a_addr[s4] + buf_bytes));
-#pragma unroll
-    for (int b = 0; b < 2; ++b) asm volatile("ds_read_b128 %0, %1" : "=v"(fb[set][b]) : "v"(b_addr[b][s4] + buf_bytes));
-  };
-  auto wait_frags = [&](int set) {       // lgkmcnt(0), tied to the registers the MFMAs will read
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[set]), "+v"(fb[set][0]), "+v"(fb[set][1]));
-  };
+  Tile tile(wm, wn, li, lh);
 
   // Selection epilogue of column tile ct (the accumulators hold its 64 x 128 scores).  Fast part, straight-line:
   // every lane tests its 32 scores against the rows' thresholds and keeps the outcomes as 32 bits.  Once the lists
@@ -260,8 +233,8 @@ __global__ __launch_bounds__(kThreads) void k_topk_select(const float* __restric
     if (t + 1 < total) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    const unsigned buf_bytes = (unsigned)(buf * BUF_FLOATS) * 4u;
-    read_frags(0, 0, buf_bytes);
+    const unsigned buf_bytes = Tile::buf_bytes(buf);
+    tile.read_first(buf_bytes);
     if (cur_kt == 0) {
       // the column tile's mask words, one (row, 32-column group) per lane, a column tile ahead of their use
       const int w = min((cur_ct * BN + (wn * 2 + lh) * 32) >> 5, words - 1);
@@ -269,21 +242,7 @@ __global__ __launch_bounds__(kThreads) void k_topk_select(const float* __restric
       if (excl) ew_raw = erow_p[w];
     }
     if (t + 2 < total) stage_next(buf2);
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) {
-      const int cur = s4 & 1;
-      wait_frags(cur);
-      if (s4 + 1 < 4) read_frags(cur ^ 1, s4 + 1, buf_bytes);   // in flight behind this step's MFMAs
-      __builtin_amdgcn_sched_barrier(0);                        // keep the MFMAs below the reads just issued
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].x, fb[cur][b].x, acc[b], 0, 0, 0);
-        acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].y, fb[cur][b].y, acc[b], 0, 0, 0);
-        acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].z, fb[cur][b].z, acc[b], 0, 0, 0);
-        acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].w, fb[cur][b].w, acc[b], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);                        // ... and above the next step's wait
-    }
+    tile.finish(acc, buf_bytes);
     buf = buf == NBUF - 1 ? 0 : buf + 1;
     buf2 = buf2 == NBUF - 1 ? 0 : buf2 + 1;
     cur_kt += BK;

@@ -18,19 +18,18 @@
 #include <cstdlib>
 
 #include "rgcn_common.h"
+#include "rgcn_mma_f32_dma.h"
 #include "rgcn_slab_reduce.h"
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// kThreads (256: 4 waves, 2 (m) x 2 (n)), BK (k-tile 32), B_KN / B_BLK (how the B operand is addressed, see
+// k_gemm_nt), glds16 and the vector types
+using namespace mma_f32_dma;
 
-constexpr int kThreads = 256;   // 4 waves, arranged 2 (m) x 2 (n)
-constexpr int BK = 32;          // k-tile
 constexpr int LDS_S = 36;       // row stride (floats) of k-contiguous LDS tiles (144 B)
 
-enum { B_KN = 0, B_BLK = 1 };            // how the B operand is addressed (see k_gemm_nt)
-enum { EPI_NONE = 0, EPI_RELU = 1, EPI_MASK = 2, EPI_RANK = 3, EPI_RANK_MASKED = 4 };
+enum { EPI_NONE = 0, EPI_RELU = 1, EPI_MASK = 2 };
 
 __device__ inline float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ inline float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -216,16 +215,10 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt(const float* __restrict__ 
 // staging VGPRs, no ds_write, no address recomputation beyond one add), through a ring of
 // three LDS buffers with ONE raw s_barrier per k-tile and a counted vmcnt, so the loads of
 // k-tile t+2 are issued before the MFMAs of k-tile t and have two MFMA phases to land.
-// An LDS-DMA wave instruction writes 64 x 16 B linearly, so the 128-byte-row tiles (A, and B
-// in B_BLK mode) are stored unpadded and bank conflicts are removed by XOR-swizzling the
-// 16-byte chunk index with (row >> 1) & 7 - applied to the per-lane SOURCE address on the way
-// in and to the ds_read_b128 address on the way out.
+// The tile layout, its swizzle, the fragment reads and the MFMA steps of a k-tile are KTile
+// (rgcn_mma_f32_dma.h), shared with the ranking and top-k kernels; what is staged when - two A
+// operands, relation blocks of B, k-tiles of absent relations skipped - is this kernel's.
 // ---------------------------------------------------------------------------------------
-__device__ inline void glds16(const float* src, float* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 template <int TN, int BMODE, int EPI>
 __global__ __launch_bounds__(kThreads) void k_gemm_nt_dma(const float* __restrict__ A1, int K1,
                                                           const float* __restrict__ A2, int K2,
@@ -234,13 +227,10 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt_dma(const float* __restric
                                                           const float* __restrict__ bias,
                                                           const float* __restrict__ mask,
                                                           float* __restrict__ C, int M, int N,
-                                                          const void* __restrict__ aux,
                                                           const uint32_t* __restrict__ tile_mask, int kseg) {
-  constexpr int BM = 64, BN = 64 * TN, NBUF = 3;
-  constexpr int A_FLOATS = BM * BK, B_FLOATS = BN * BK, BUF_FLOATS = A_FLOATS + B_FLOATS;
-  constexpr int A_PW = BM / 32;                 // A wave-instructions per wave and k-tile (8 rows each)
-  constexpr int B_PW = BN / 32;                 // B wave-instructions per wave and k-tile
-  constexpr int P = A_PW + B_PW;                // LDS-DMA instructions per thread and k-tile
+  typedef KTile<TN, BMODE> Tile;                // the shared k-tile (rgcn_mma_f32_dma.h)
+  constexpr int BN = Tile::BN, A_FLOATS = Tile::A_FLOATS, BUF_FLOATS = Tile::BUF_FLOATS;
+  constexpr int A_PW = Tile::A_PW, B_PW = Tile::B_PW, P = Tile::P;
   __shared__ __attribute__((aligned(16))) float lds[NBUF * BUF_FLOATS];   // the ONLY LDS object
 
   const int K = K1 + K2;
@@ -260,11 +250,10 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt_dma(const float* __restric
   size_t a_off1[A_PW], a_off2[A_PW];
 #pragma unroll
   for (int j = 0; j < A_PW; ++j) {
-    const int row = (wave * A_PW + j) * 8 + (lane >> 3);
+    const int row = dma_row(wave * A_PW + j, lane);
     const int m = min(m0 + row, M - 1);                        // rows past M read a valid row; never stored
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-    a_off1[j] = (size_t)m * K1 + chunk * 4;
-    a_off2[j] = (size_t)m * K2 + chunk * 4;
+    a_off1[j] = (size_t)m * K1 + dma_col(row, lane);
+    a_off2[j] = (size_t)m * K2 + dma_col(row, lane);
   }
   size_t b_off[B_PW];
   bool b_ok[B_PW];
@@ -277,16 +266,13 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt_dma(const float* __restric
       b_ok[j] = n < N;
       b_off[j] = (size_t)krow * N + n;
     } else {                                                   // [n][32 k], swizzled like A
-      const int row = (wave * B_PW + j) * 8 + (lane >> 3);
+      const int row = dma_row(wave * B_PW + j, lane);
       const int n = min(n0 + row, N - 1);
-      const int chunk = (lane & 7) ^ ((row >> 1) & 7);
       b_ok[j] = true;
-      b_off[j] = (size_t)n * dk + chunk * 4;
+      b_off[j] = (size_t)n * dk + dma_col(row, lane);
     }
   }
 
-  // (EPI_RANK_MASKED: A2 and Rt are not float data there - they carry the mask words; K2 == 0 and one B_BLK block
-  // of dk == K1 mean neither is ever staged.  A change that makes stage() read them must give the masks own slots.)
   auto stage = [&](int kt, int buf) {
     float* sA = lds + buf * BUF_FLOATS;
     float* sB = sA + A_FLOATS;
@@ -319,7 +305,6 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt_dma(const float* __restric
   }
   auto next_kt = [&](int kt) {                 // next active k-tile start after kt (K when none)
     kt += BK;
-    if (EPI == EPI_RANK_MASKED) return min(kt, K);   // no relation blocks there: kseg carries the number of allow rows
     while (kt < K1 && !((rel_mask >> (kt / kseg)) & 1u)) kt = (kt / kseg + 1) * kseg;
     return min(kt, K);
   };
@@ -327,46 +312,7 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt_dma(const float* __restric
   if (kt_a < K) stage(kt_a, 0);
   if (kt_b < K) stage(kt_b, 1);
 
-  // Fragment reads are inline asm: hipcc cannot tell a ds_read from the in-flight LDS-DMA
-  // destinations apart and would drain vmcnt(0) before the first read of every k-tile.
-  // Byte addresses inside one buffer, fixed over the k loop (the XOR swizzle is not additive,
-  // so the four kb steps get one address register each):
-  const int arow = wm * 32 + li;
-  unsigned a_addr[4], b_addr[TN][4];
-#pragma unroll
-  for (int s4 = 0; s4 < 4; ++s4) {
-    a_addr[s4] = (unsigned)(arow * BK + (((2 * s4 + lh) ^ ((arow >> 1) & 7)) << 2)) * 4u;
-#pragma unroll
-    for (int b = 0; b < TN; ++b) {
-      if (BMODE == B_KN) {
-        b_addr[b][s4] = (unsigned)(A_FLOATS + (8 * s4 + 4 * lh) * BN + (wn * TN + b) * 32 + li) * 4u;
-      } else {
-        const int brow = (wn * TN + b) * 32 + li;
-        b_addr[b][s4] = (unsigned)(A_FLOATS + brow * BK + (((2 * s4 + lh) ^ ((brow >> 1) & 7)) << 2)) * 4u;
-      }
-    }
-  }
-  f32x4 fa[2];
-  f32x4 fb[2][TN];
-  auto read_frags = [&](int set, int s4, unsigned buf_bytes) {
-    asm volatile("ds_read_b128 %0, %1" : "=v"(fa[set]) : "v"(a_addr[s4] + buf_bytes));
-#pragma unroll
-    for (int b = 0; b < TN; ++b) {
-      if (BMODE == B_KN) {
-        const unsigned ad = b_addr[b][s4] + buf_bytes;
-        asm volatile("ds_read_b32 %0, %1" : "=v"(fb[set][b].x) : "v"(ad));
-        asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(fb[set][b].y) : "v"(ad), "n"(BN * 4));
-        asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(fb[set][b].z) : "v"(ad), "n"(BN * 8));
-        asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(fb[set][b].w) : "v"(ad), "n"(BN * 12));
-      } else {
-        asm volatile("ds_read_b128 %0, %1" : "=v"(fb[set][b]) : "v"(b_addr[b][s4] + buf_bytes));
-      }
-    }
-  };
-  auto wait_frags = [&](int set) {       // lgkmcnt(0), tied to the registers the MFMAs will read
-    if (TN == 2) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[set]), "+v"(fb[set][0]), "+v"(fb[set][TN - 1]));
-    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[set]), "+v"(fb[set][0]));
-  };
+  Tile tile(wm, wn, li, lh);
 
   for (int t = 0; kt_a < K; ++t) {
     // k-tile kt_a landed for this wave (all but the newest P DMAs are done), then for all waves;
@@ -376,110 +322,15 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt_dma(const float* __restric
     __builtin_amdgcn_s_barrier();
     // first fragments of this k-tile go out before the DMA issue below, whose ~40 instructions then
     // cover their LDS latency
-    const unsigned buf_bytes = (unsigned)((t % NBUF) * BUF_FLOATS) * 4u;
-    read_frags(0, 0, buf_bytes);
+    const unsigned buf_bytes = Tile::buf_bytes(t % NBUF);
+    tile.read_first(buf_bytes);
     kt_c = kt_b < K ? next_kt(kt_b) : K;
     if (kt_c < K) stage(kt_c, (t + 2) % NBUF);
     kt_a = kt_b;
     kt_b = kt_c;
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) {
-      const int cur = s4 & 1;
-      wait_frags(cur);
-      if (s4 + 1 < 4) read_frags(cur ^ 1, s4 + 1, buf_bytes);   // in flight behind this step's MFMAs
-      __builtin_amdgcn_sched_barrier(0);                        // keep the MFMAs below the reads just issued
-#pragma unroll
-      for (int b = 0; b < TN; ++b) {
-        acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].x, fb[cur][b].x, acc[b], 0, 0, 0);
-        acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].y, fb[cur][b].y, acc[b], 0, 0, 0);
-        acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].z, fb[cur][b].z, acc[b], 0, 0, 0);
-        acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur].w, fb[cur][b].w, acc[b], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);                        // ... and above the next step's wait
-    }
+    tile.finish(acc, buf_bytes);
   }
 
-  if (EPI == EPI_RANK) {
-    // Ranking epilogue (evaluate.py:260-276 without the [B, N] score matrix): row m is a test
-    // triple, column n a candidate tail; count the candidates that beat the true tail's score
-    // (bias[m]), the true tail itself (aux[m]) excluded.  One ballot per accumulator register:
-    // lanes 0-31 / 32-63 hold 32 columns of two rows.
-    const int64_t* tails = reinterpret_cast<const int64_t*>(aux);
-    int* counts = reinterpret_cast<int*>(C);
-#pragma unroll
-    for (int b = 0; b < TN; ++b) {
-      const int n = n0 + (wn * TN + b) * 32 + li;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const bool in = (m < M) && (n < N);
-        const float ts = in ? bias[m] : 0.f;
-        const int64_t tl = in ? tails[m] : -1;
-        const unsigned long long hits = __ballot(in && (int64_t)n != tl && acc[b][r] > ts);
-        if (li == 0 && m < M) {
-          const int c = __popc(lh ? (unsigned)(hits >> 32) : (unsigned)hits);
-          if (c) atomicAdd(&counts[m], c);
-        }
-      }
-    }
-    return;
-  }
-  if (EPI == EPI_RANK_MASKED) {
-    // Filtered / type-constrained ranking: the EPI_RANK count with a candidate filter.  The ballot of an
-    // accumulator register is the 32 hits of columns nb .. nb+31 of two rows, and nb is a multiple of 32: exactly
-    // one word of a [rows, ceil(N/32)] bit mask per row, so the filter is hits & allow[class[m]][w] & ~exclude[m][w]
-    // before the popcount - two 4-byte loads per (row, 32-column group), all issued before the group's ballots.
-    // The operands a ranking launch does not use carry the masks: Rt = allow words, mask = query_class (int32),
-    // A2 = exclude words (K2 == 0: never staged), kseg = number of allow rows.  Either mask may be NULL.
-    const int64_t* tails = reinterpret_cast<const int64_t*>(aux);
-    const uint32_t* allow = reinterpret_cast<const uint32_t*>(Rt);
-    const int32_t* qcls = reinterpret_cast<const int32_t*>(mask);
-    const uint32_t* excl = reinterpret_cast<const uint32_t*>(A2);
-    int* counts = reinterpret_cast<int*>(C);
-    const int words = (N + 31) >> 5;
-    constexpr unsigned kNoRow = 0xffffffffu;
-    float ts[16];
-    int tl[16];
-    unsigned aoff[16];                     // first word of the row's allow row, kNoRow: nothing is allowed
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      const bool ok = m < M;
-      ts[r] = ok ? bias[m] : 0.f;
-      const int64_t t64 = ok ? tails[m] : -1;
-      tl[r] = (t64 >= 0 && t64 < N) ? (int)t64 : -1;
-      aoff[r] = kNoRow;
-      if (allow && ok) {
-        const int c = qcls[m];
-        if (c >= 0 && c < kseg) aoff[r] = (unsigned)c * (unsigned)words;
-      }
-    }
-#pragma unroll
-    for (int b = 0; b < TN; ++b) {
-      const int nb = n0 + (wn * TN + b) * 32, n = nb + li;
-      const int w = nb >> 5;
-      const bool wok = w < words;          // a column group wholly past N has no mask word (and no hit)
-      unsigned aw[16], ew[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        // only the lane that counts (li == 0 of each half) needs the words
-        aw[r] = allow ? ((li == 0 && wok && aoff[r] != kNoRow) ? allow[aoff[r] + (unsigned)w] : 0u) : 0xffffffffu;
-        ew[r] = (li == 0 && excl && wok && m < M) ? excl[(size_t)m * words + w] : 0u;
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const unsigned long long hits = __ballot(m < M && n < N && n != tl[r] && acc[b][r] > ts[r]);
-        if (li == 0 && m < M) {
-          const unsigned mine = lh ? (unsigned)(hits >> 32) : (unsigned)hits;
-          const int c = __popc(mine & aw[r] & ~ew[r]);
-          if (c) atomicAdd(&counts[m], c);
-        }
-      }
-    }
-    return;
-  }
   if (m0 + BM <= M && n0 + BN <= N) {
     // Interior tile (all but the last row of tiles): no per-element bounds branches, so the
     // epilogue loads (bias, mask) are waited for ONCE and the 16 x TN stores of a lane go out
@@ -907,11 +758,11 @@ void launch_nt(const float* A1, int K1, const float* A2, int K2, const float* W,
     if (N <= 64) {
       dim3 grid((unsigned)ceil_div64(M, 64), (unsigned)ceil_div64(N, 64));
       k_gemm_nt_dma<1, BMODE, EPI><<<grid, kThreads, 0, stream>>>(A1, K1, A2, K2, W, Rt, dk, bias, mask, C, M, N,
-                                                                  nullptr, tile_mask, kseg);
+                                                                  tile_mask, kseg);
     } else {
       dim3 grid((unsigned)ceil_div64(M, 64), (unsigned)ceil_div64(N, 128));
       k_gemm_nt_dma<2, BMODE, EPI><<<grid, kThreads, 0, stream>>>(A1, K1, A2, K2, W, Rt, dk, bias, mask, C, M, N,
-                                                                  nullptr, tile_mask, kseg);
+                                                                  tile_mask, kseg);
     }
     return;
   }
@@ -994,43 +845,6 @@ int rgcn_transform_bwd_input(const float* gagg, const float* g, const float* wei
   return RGCN_OK;
 }
 
-int distmult_rank_tails(const float* hr, const float* emb, const float* true_score, const int64_t* tail,
-                        int64_t batch, int64_t num_entities, int64_t d, int32_t* beaten_by, void* stream_) {
-  if (batch < 0 || num_entities <= 0 || d <= 0 || (d % BK)) return (d > 0 && (d % BK)) ? RGCN_ERR_UNSUPPORTED : RGCN_ERR_ARG;
-  if (batch == 0) return RGCN_OK;
-  if (!hr || !emb || !true_score || !tail || !beaten_by) return RGCN_ERR_ARG;
-  if (batch > INT32_MAX / 2 || num_entities > INT32_MAX / 2) return RGCN_ERR_UNSUPPORTED;
-  hipStream_t stream = (hipStream_t)stream_;
-  // scores[b, n] = sum_k hr[b, k] * emb[n, k]: the B_BLK addressing with one block (r = 0, dk = d)
-  dim3 grid((unsigned)ceil_div64(batch, 64), (unsigned)ceil_div64(num_entities, 128));
-  k_gemm_nt_dma<2, B_BLK, EPI_RANK><<<grid, kThreads, 0, stream>>>(hr, (int)d, hr, 0, emb, emb, (int)d, true_score,
-                                                                    nullptr, reinterpret_cast<float*>(beaten_by),
-                                                                    (int)batch, (int)num_entities, tail, nullptr, 0);
-  RGCN_HIP_TRY(hipGetLastError());
-  return RGCN_OK;
-}
-
-int distmult_rank_masked(const float* q, const float* emb, const float* true_score, const int64_t* target,
-                         const uint32_t* allow, const int32_t* query_class, int64_t num_classes, const uint32_t* exclude,
-                         int64_t batch, int64_t num_entities, int64_t d, int32_t* beaten_by, void* stream_) {
-  if (batch < 0 || num_entities <= 0 || d <= 0 || (d % BK)) return (d > 0 && (d % BK)) ? RGCN_ERR_UNSUPPORTED : RGCN_ERR_ARG;
-  if (num_classes < 0 || (allow && (num_classes == 0 || !query_class))) return RGCN_ERR_ARG;
-  if (batch == 0) return RGCN_OK;
-  if (!q || !emb || !true_score || !target || !beaten_by) return RGCN_ERR_ARG;
-  if (batch > INT32_MAX / 2 || num_entities > INT32_MAX / 2) return RGCN_ERR_UNSUPPORTED;
-  const int64_t words = ceil_div64(num_entities, 32);
-  if (allow && num_classes * words > INT32_MAX) return RGCN_ERR_UNSUPPORTED;   // 32-bit word offsets in the epilogue
-  hipStream_t stream = (hipStream_t)stream_;
-  // the ranking launch (same operands, tile walk and accumulation), the masks in the operand slots it leaves unused
-  dim3 grid((unsigned)ceil_div64(batch, 64), (unsigned)ceil_div64(num_entities, 128));
-  k_gemm_nt_dma<2, B_BLK, EPI_RANK_MASKED><<<grid, kThreads, 0, stream>>>(
-      q, (int)d, reinterpret_cast<const float*>(exclude), 0, emb, reinterpret_cast<const float*>(allow), (int)d, true_score,
-      reinterpret_cast<const float*>(query_class), reinterpret_cast<float*>(beaten_by), (int)batch, (int)num_entities,
-      target, nullptr, allow ? (int)num_classes : 0);
-  RGCN_HIP_TRY(hipGetLastError());
-  return RGCN_OK;
-}
-
 int distmult_score_all_tails(const float* head, const float* rel, const int64_t* rel_idx, int64_t num_relations,
                              const float* emb, int64_t batch, int64_t num_entities, int64_t d, float* hr, float* scores,
                              void* stream_) {
@@ -1043,11 +857,11 @@ int distmult_score_all_tails(const float* head, const float* rel, const int64_t*
   k_head_times_relation<<<(unsigned)ceil_div64(quads, 256), 256, 0, stream>>>(head, rel, rel_idx, (int)num_relations,
                                                                               (int)(d / 4), (int)quads, hr);
   RGCN_HIP_TRY(hipGetLastError());
-  // scores[b, n] = sum_k hr[b, k] * emb[n, k]: the ranking launch's operands, the plain store epilogue
+  // scores[b, n] = sum_k hr[b, k] * emb[n, k]: the B_BLK addressing with one block (r = 0, dk = d) - the k-tile of
+  // k_rank_count and k_topk_select, the plain store epilogue
   dim3 grid((unsigned)ceil_div64(batch, 64), (unsigned)ceil_div64(num_entities, 128));
   k_gemm_nt_dma<2, B_BLK, EPI_NONE><<<grid, kThreads, 0, stream>>>(hr, (int)d, hr, 0, emb, emb, (int)d, nullptr, nullptr,
-                                                                    scores, (int)batch, (int)num_entities, nullptr,
-                                                                    nullptr, 0);
+                                                                    scores, (int)batch, (int)num_entities, nullptr, 0);
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }

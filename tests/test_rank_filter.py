@@ -134,9 +134,36 @@ def test_masked_ranks_ragged_shapes(batch, entities, d):
         got = ops.distmult_rank_masked(q, emb, true, target.to(dev), a, None if a is None else qcls.to(dev), e)
         want = _host_rank(scores.cpu(), true.cpu(), target, None if a is None else allowed, None if e is None else known)
         assert torch.equal(got.cpu(), want)
+    if (batch, entities, d) in ((1, 100, 32), (63, 127, 128), (65, 129, 32), (64, 128, 128)):
+        # the raw entry point is the same launch with no mask: one row, a ragged last row tile, a ragged last column
+        # group, a column group wholly past N, exact tiles
+        assert torch.equal(ops.distmult_rank_tails(q, emb, true, target.to(dev)).cpu(), _host_rank(scores.cpu(), true.cpu(), target))
     # a query class outside the allow rows allows nothing: rank 1
     bad = torch.full((batch,), 7, dtype=torch.int32, device=dev)
     assert bool((ops.distmult_rank_masked(q, emb, true, target.to(dev), allow, bad, None) == 1).all())
+
+
+def test_targets_outside_the_entity_range_exclude_nothing():
+    """A target outside ``[0, N)`` is compared, never used as an index: rows 0 and 1 (targets -1 and N) count over all N
+    candidates, row 2 leaves candidate 5 out - in both entry points, equal to the host count."""
+    dev = need_gpu()
+    g = torch.Generator().manual_seed(40)
+    b, n, d = 3, 40, 32
+    dec = LinkPredictor(4, d, dropout=0.0).to(dev)
+    head, emb = torch.randn(b, d, generator=g).to(dev), torch.randn(n, d, generator=g).to(dev)
+    rel = torch.randint(0, 4, (b,), generator=g).to(dev)
+    scores, q = ops.distmult_score_all_tails(head, dec.relation_embeddings.weight.detach(), rel, emb)
+    s_cpu = scores.cpu()
+    true = s_cpu.median(1).values                                  # a score of the row: about half the candidates beat it
+    true[2] = s_cpu[2, 5] - 1.0                                    # ... and one that candidate 5 beats
+    target = torch.tensor([-1, n, 5])
+    beat = s_cpu > true.view(-1, 1)
+    assert bool(beat[2, 5])                                        # the excluded candidate would have counted
+    beat[2, 5] = False
+    want = beat.sum(1) + 1
+    assert torch.equal(ops.distmult_rank_tails(q, emb, true.to(dev), target.to(dev)).cpu(), want)
+    assert torch.equal(ops.distmult_rank_masked(q, emb, true.to(dev), target.to(dev)).cpu(), want)
+    ops.check_indices(dev)
 
 
 def test_mask_builders(case6):
