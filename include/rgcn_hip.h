@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 31
+#define RGCN_ABI_VERSION 32
 
 enum {
   RGCN_OK = 0,

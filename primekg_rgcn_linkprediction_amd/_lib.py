@@ -13,7 +13,7 @@ from ctypes import c_double, c_float, POINTER, c_char_p, c_int, c_int64, c_size_
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 LIB_NAME = "librgcn_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -166,6 +166,19 @@ PATHS_PROTOTYPES = {
                                 _P, _P, _P, _P, _P, c_size_t, _P]),            # outputs, workspace, stream
 }
 
+# include/rgcn_cluster.h, one to one: k-means and silhouette analysis of embedding rows (csrc/cluster.hip; not part of
+# rgcn_hip.h, never forwarded by rgcn_sequence_run - an analysis call, outside any recorded Region)
+CLUSTER_PROTOTYPES = {
+    "rgcn_kmeans_workspace_bytes": (c_size_t, [_I64, _I64, _I64, _I64]),
+    "rgcn_kmeans_assign": (c_int, [_P, _I64, _I64, _P, _I64, _I64,                # rows, centroids
+                                   _P, _P, _P, _P, _P, c_size_t, _P]),            # labels, counters, flags, workspace, stream
+    "rgcn_kmeans_update": (c_int, [_P, _I64, _I64, _P, _I64, _I64,
+                                   _P, _P, _P, _P, _P, _P, c_float, _P, c_size_t, _P]),
+    "rgcn_kmeans_inertia": (c_int, [_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, c_size_t, _P]),
+    "rgcn_silhouette_workspace_bytes": (c_size_t, [_I64, _I64, _I64, _I64]),
+    "rgcn_silhouette_samples": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, c_size_t, _P]),
+}
+
 _lib = None
 
 
@@ -187,7 +200,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise RGCNLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -23,15 +23,23 @@ mask, the known associations as its exclude mask - no ``[diseases, drugs]`` matr
 ``rank_paths``, ``case_studies.py:319-351``, ``analyze_failures.py:345-366``: ``networkx.all_simple_paths(cutoff=4)``
 scored by the mean cosine of consecutive nodes times a length penalty): the k best of ALL simple paths between a
 pair, enumerated on the device (``ops.paths_topk``).
+
+``cluster_analysis`` is ``visualize_embeddings.cluster_analysis`` (``src/visualize_embeddings.py:651-777``): per node
+type ``KMeans(n_clusters, n_init=10, random_state=42)`` and ``silhouette_score`` on that type's rows, the cluster sizes
+and members - ``ops.kmeans`` and ``ops.silhouette_score``, the table never leaves the device.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import Dict, List, Mapping, Optional, Sequence, Tuple, Union
+
+import logging
 
 import torch
 from torch import Tensor
 
 from . import ops
+
+logger = logging.getLogger("primekg_rgcn_linkprediction_amd.consumers")
 
 _Index = Union[Tensor, Sequence[int]]
 
@@ -156,3 +164,38 @@ def connecting_paths(embeddings: Tensor, graph: "ops.PathGraph", pairs, k: int =
     paths = [[{"nodes": nodes[q][j][:length[q][j] + 1], "relations": rel[q][j][:length[q][j]], "length": length[q][j],
                "score": score[q][j]} for j in range(len(length[q])) if length[q][j] > 0] for q in range(len(length))]
     return (paths, count.cpu().tolist()) if return_counts else paths
+
+
+@torch.no_grad()
+def cluster_analysis(embeddings: Tensor, node_class: Tensor, class_names: Union[Mapping[str, int], Sequence[Optional[str]]],
+                     n_clusters: int = 10, **kmeans_kw) -> Dict[str, Dict]:
+    """K-means and silhouette of every named node type's embedding rows, on the device.  ``node_class`` int ``[N]`` is
+    the class of every node, ``class_names`` says which classes to analyse and what to call them: ``{name: class id}``,
+    or a sequence of names indexed by class id (``None``: skip).  Per name ``{"labels": int64 [n_type] (the cluster of
+    the type's nodes, node id ascending), "silhouette": float, "cluster_sizes": int64 [n_clusters], "members": a list
+    per cluster of its node ids, ascending}`` - the reference's ``results`` dict plus what its
+    ``*_cluster_examples.txt`` lists.  The silhouette is 0.0 when fewer than two clusters are populated, as there.
+    A type with fewer nodes than ``n_clusters`` is left out of the result with a logged warning.
+    ``kmeans_kw`` goes to ``ops.kmeans`` (``n_init``, ``seed``, ``max_iter``, ``tol``, ``init``, ``poll_every``)."""
+    if embeddings.dim() != 2:
+        raise ValueError("embeddings must be [N, d]")
+    classes = torch.as_tensor(node_class).to(embeddings.device)
+    if classes.shape != (embeddings.size(0),):
+        raise ValueError(f"node_class must be [{embeddings.size(0)}]")
+    named = class_names.items() if isinstance(class_names, Mapping) else [(n, c) for c, n in enumerate(class_names) if n is not None]
+    results = {}
+    for name, cls in named:
+        nodes = torch.nonzero(classes == int(cls)).view(-1)                    # ascending
+        if nodes.numel() < max(2, n_clusters):                                # one small type must not end the others' analysis
+            logger.warning("node type %r (class %s) has %d nodes: %d clusters need at least as many - left out",
+                           name, cls, nodes.numel(), n_clusters)
+            continue
+        rows = embeddings.index_select(0, nodes).to(torch.float32).contiguous()
+        fit = ops.kmeans(rows, n_clusters, **kmeans_kw)
+        populated = int((fit.sizes > 0).sum())
+        silhouette = ops.silhouette_score(rows, fit.labels, n_clusters) if populated > 1 else 0.0
+        order = torch.argsort(fit.labels, stable=True)                         # by cluster, node ids stay ascending
+        members = [m.tolist() for m in torch.split(nodes[order].cpu(), fit.sizes.cpu().tolist())]
+        results[name] = {"labels": fit.labels.cpu(), "silhouette": float(silhouette), "cluster_sizes": fit.sizes.cpu(),
+                         "members": members}
+    return results

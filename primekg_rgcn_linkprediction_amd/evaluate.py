@@ -185,6 +185,17 @@ class ModelEvaluator:
         return consumers.connecting_paths(emb, self._path_graph, pairs, k, max_len, return_counts=True,
                                           edge_score=self._edge_cosine)
 
+    @torch.no_grad()
+    def cluster_analysis(self, class_names, n_clusters: int = 10, **kmeans_kw):
+        """which nodes of a type the model groups together, and how well separated the groups are:
+        ``consumers.cluster_analysis`` (k-means + silhouette per node type, on the device) on the cached embeddings and
+        the evaluator's node classes"""
+        from . import consumers
+        if self.node_class is None:
+            raise ValueError("cluster_analysis needs the node classes (ModelEvaluator(node_class=...), e.g. "
+                             "graphio.node_classes(mappings['idx2node'], num_nodes)[0])")
+        return consumers.cluster_analysis(self.embeddings(), self.node_class, class_names, n_clusters, **kmeans_kw)
+
     def compute_ranking_metrics(self, k_values: Sequence[int] = (10, 50), filtered: bool = False,
                                 type_constrained: bool = False, both_sides: bool = False) -> Dict:
         ranks = self.tail_ranks(filtered, type_constrained)

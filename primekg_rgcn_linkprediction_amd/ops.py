@@ -15,7 +15,7 @@ import ctypes
 import os
 import pickle
 from collections import OrderedDict
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -2133,6 +2133,277 @@ def paths_topk(graph: PathGraph, edge_score: torch.Tensor, sources: torch.Tensor
                                  _ptr(ws), nbytes, _stream())
     _lib.check(rc, "rgcn_paths_topk")
     return nodes, length, score, count
+
+
+CLUSTER_MAX_K = 64            # RGCN_CLUSTER_MAX_K: two 32-column blocks per restart, 32 KB of sums per update workgroup
+CLUSTER_MAX_RESTARTS = 1024   # RGCN_CLUSTER_MAX_RESTARTS
+
+
+class KMeansResult(NamedTuple):
+    labels: torch.Tensor      # int64 [M]: the assignment against `centers`
+    centers: torch.Tensor     # float32 [k, d]
+    inertia: float
+    n_iter: int
+    sizes: torch.Tensor       # int64 [k]
+    restart: int              # the winning restart
+
+
+def _cluster_shape(x: torch.Tensor, k) -> int:
+    """the checks ``include/rgcn_cluster.h`` makes on (M, d, k), by name and before any device is looked at"""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch.Tensor")
+    if x.dim() != 2:
+        raise ValueError("x must be [M, d]")
+    if x.size(0) < 2:
+        raise ValueError(f"x must have at least 2 rows (M >= 2), got M = {x.size(0)}")
+    if x.size(1) == 0 or x.size(1) % 32:
+        raise ValueError(f"the row width d must be a positive multiple of 32 (the matrix-core k-tile), got d = {x.size(1)}")
+    k = int(k)
+    if not 2 <= k <= CLUSTER_MAX_K:
+        raise ValueError(f"k must be in [2, {CLUSTER_MAX_K}] (CLUSTER_MAX_K), got {k}")
+    return k
+
+
+def _cluster_centers(x: torch.Tensor, centers: torch.Tensor, name: str = "centers") -> Tuple[int, int]:
+    if not isinstance(centers, torch.Tensor) or centers.dim() != 3 or centers.size(2) != x.size(1):
+        raise ValueError(f"{name} must be [R, k, {x.size(1)}]")
+    r = centers.size(0)
+    if not 1 <= r <= CLUSTER_MAX_RESTARTS:
+        raise ValueError(f"the number of restarts R must be in [1, {CLUSTER_MAX_RESTARTS}], got {r}")
+    k = _cluster_shape(x, centers.size(1))
+    _need_gpu("x", x, torch.float32)
+    _need_gpu(name, centers, torch.float32)
+    if centers.device != x.device:
+        raise ValueError(f"{name} is on {centers.device}, x on {x.device}")
+    return r, k
+
+
+def _kmeans_workspace(x: torch.Tensor, r: int, k: int) -> torch.Tensor:
+    nbytes = int(_lib.load().rgcn_kmeans_workspace_bytes(x.size(0), x.size(1), r, k))
+    return torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+
+
+def _flags(name: str, t: Optional[torch.Tensor], r: int, device) -> None:
+    if t is not None:
+        _need_gpu(name, t, torch.int32)
+        if t.shape != (r,) or t.device != device:
+            raise ValueError(f"{name} must be int32 [{r}] on {device}")
+
+
+def kmeans_assign(x: torch.Tensor, centers: torch.Tensor, labels_prev: Optional[torch.Tensor] = None,
+                  done: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+                  num_changed: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
+    """One assignment step of all ``R`` restarts in one pass over the rows (``rgcn_kmeans_assign``): ``centers``
+    ``[R, k, d]`` -> ``(labels int32 [R, M], num_changed int32 [R])``, the label of a row the centroid of least
+    ``|c|^2 - 2 <x, c>``, equal keys to the lower id, a NaN key never chosen over a number; ``num_changed`` counts the
+    rows whose label differs from ``labels_prev`` (None: all).  A restart whose ``done`` flag (int32 ``[R]``) is set is
+    left as it is in ``labels`` / ``num_changed`` when those are passed in."""
+    r, k = _cluster_centers(x, centers)
+    m, dev = x.size(0), x.device
+    _flags("done", done, r, dev)
+    for name, t in (("labels_prev", labels_prev), ("labels", labels)):
+        if t is not None:
+            _need_gpu(name, t, torch.int32)
+            if t.shape != (r, m) or t.device != dev:
+                raise ValueError(f"{name} must be int32 [{r}, {m}] on {dev}")
+    _flags("num_changed", num_changed, r, dev)
+    with _on(dev):
+        if labels is None:
+            labels = torch.full((r, m), -1, dtype=torch.int32, device=dev) if labels_prev is None else labels_prev.clone()
+        if num_changed is None:
+            num_changed = torch.zeros(r, dtype=torch.int32, device=dev)
+        ws = _kmeans_workspace(x, r, k) if ws is None else ws
+        rc = _lib.load().rgcn_kmeans_assign(_ptr(x), m, x.size(1), _ptr(centers), r, k, _ptr(labels_prev), _ptr(labels),
+                                            _ptr(num_changed), _ptr(done), _ptr(ws), ws.numel(), _stream())
+    _lib.check(rc, "rgcn_kmeans_assign")
+    return labels, num_changed
+
+
+def kmeans_update(x: torch.Tensor, centers: torch.Tensor, labels: torch.Tensor, num_changed: torch.Tensor,
+                  tol_abs: float = 0.0, done: Optional[torch.Tensor] = None, num_iter: Optional[torch.Tensor] = None,
+                  counts: Optional[torch.Tensor] = None, shift2: Optional[torch.Tensor] = None,
+                  ws: Optional[torch.Tensor] = None):
+    """One update step (``rgcn_kmeans_update``): every centroid of ``centers`` ``[R, k, d]`` is REPLACED, in place, by
+    the mean of its members under ``labels`` (sums in a fixed order: the same bits on every call); a cluster without
+    members keeps its centroid and has count 0 (scikit-learn relocates it; this does not).  -> ``(counts int32 [R, k],
+    shift2 float32 [R])``, ``shift2`` the squared movement of the restart's centroids.  ``done`` (int32 ``[R]``): set
+    restarts are frozen, and a restart is set when ``num_changed`` is 0 or ``shift2 <= tol_abs``; ``num_iter`` (int32
+    ``[R]``) counts the updates of every restart that was not done."""
+    r, k = _cluster_centers(x, centers)
+    m, dev = x.size(0), x.device
+    if not float(tol_abs) >= 0.0:
+        raise ValueError(f"tol_abs must be >= 0, got {tol_abs}")
+    _need_gpu("labels", labels, torch.int32)
+    if labels.shape != (r, m) or labels.device != dev:
+        raise ValueError(f"labels must be int32 [{r}, {m}] on {dev}")
+    _flags("num_changed", num_changed, r, dev)
+    _flags("done", done, r, dev)
+    _flags("num_iter", num_iter, r, dev)
+    with _on(dev):
+        counts = torch.zeros((r, k), dtype=torch.int32, device=dev) if counts is None else counts
+        shift2 = torch.zeros(r, dtype=torch.float32, device=dev) if shift2 is None else shift2
+        num_iter = torch.zeros(r, dtype=torch.int32, device=dev) if num_iter is None else num_iter
+        ws = _kmeans_workspace(x, r, k) if ws is None else ws
+        rc = _lib.load().rgcn_kmeans_update(_ptr(x), m, x.size(1), _ptr(centers), r, k, _ptr(labels), _ptr(num_changed),
+                                            _ptr(counts), _ptr(shift2), _ptr(num_iter), _ptr(done), float(tol_abs), _ptr(ws),
+                                            ws.numel(), _stream())
+    _lib.check(rc, "rgcn_kmeans_update")
+    return counts, shift2
+
+
+def kmeans_inertia(x: torch.Tensor, centers: torch.Tensor, labels: torch.Tensor, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float64 ``[R]``: ``sum_i |x_i - centers[r, labels[r, i]]|^2``, from the rows (``rgcn_kmeans_inertia``)"""
+    r, k = _cluster_centers(x, centers)
+    m, dev = x.size(0), x.device
+    _need_gpu("labels", labels, torch.int32)
+    if labels.shape != (r, m) or labels.device != dev:
+        raise ValueError(f"labels must be int32 [{r}, {m}] on {dev}")
+    with _on(dev):
+        out = torch.empty(r, dtype=torch.float64, device=dev)
+        ws = _kmeans_workspace(x, r, k) if ws is None else ws
+        rc = _lib.load().rgcn_kmeans_inertia(_ptr(x), m, x.size(1), _ptr(centers), r, k, _ptr(labels), _ptr(out), _ptr(ws),
+                                             ws.numel(), _stream())
+    _lib.check(rc, "rgcn_kmeans_inertia")
+    return out
+
+
+def kmeans_plusplus(x: torch.Tensor, k: int, n_init: int, seed: int) -> torch.Tensor:
+    """``[n_init, k, d]`` starts by k-means++ (every next centre a row drawn with probability proportional to its squared
+    distance from the nearest centre so far), all restarts side by side in torch ops.  The random numbers come from a
+    CPU ``torch.Generator(seed)``: the same seed gives the same starts; they are NOT scikit-learn's draws."""
+    gen = torch.Generator().manual_seed(int(seed))
+    u = torch.rand(k, n_init, generator=gen, dtype=torch.float64).to(x.device)
+    m = x.size(0)
+    idx = (u[0] * m).to(torch.int64).clamp_(max=m - 1)
+    chosen = [idx]
+    d2 = None
+    for c in range(1, k):
+        step = torch.cdist(x[chosen[-1]], x, compute_mode="donot_use_mm_for_euclid_dist").to(torch.float64).square_()   # [R, M]
+        d2 = step if d2 is None else torch.minimum(d2, step)
+        cum = torch.cumsum(d2, 1)
+        target = (u[c] * cum[:, -1]).unsqueeze(1)
+        idx = torch.searchsorted(cum, target, right=True).view(-1).clamp_(max=m - 1)  # the first row past the target: d2 > 0
+        chosen.append(idx)
+    return x[torch.stack(chosen, 1)].contiguous()                                      # [R, k, d]
+
+
+def kmeans(x: torch.Tensor, k: int, *, init: Optional[torch.Tensor] = None, n_init: int = 10, max_iter: int = 300,
+           tol: float = 1e-4, seed: int = 42, poll_every: int = 8, return_restarts: bool = False):
+    """Lloyd's k-means of the rows of ``x`` (float32 ``[M, d]``, ``d % 32 == 0``) with ``n_init`` restarts run side by
+    side on the device - the reference's ``KMeans(n_clusters, n_init=10, random_state=42)``.  Per iteration one
+    assignment pass over all restarts (``kmeans_assign``) and one deterministic update (``kmeans_update``); a restart
+    stops when no label changed or its centroids moved by ``<= tol * mean(var(x, dim 0))`` squared, as scikit-learn
+    defines ``tol`` (``tol = 0``: until no label changes), and is then frozen on the device - the host looks at the flags
+    every ``poll_every`` iterations, which changes no result bit.  The winner is the restart of least inertia (computed
+    from the rows against the final centroids; ties to the lower index); its labels are the assignment against the
+    returned centers.  ``init`` ``[R, k, d]`` (or ``[k, d]``) replaces the k-means++ starts drawn from ``seed`` and makes
+    the run a function of its inputs alone.  An emptied cluster keeps its centroid (scikit-learn relocates it).
+    ``return_restarts``: ``(result, restarts)`` with every restart's final state, ``{"labels" int32 [R, M], "centers"
+    [R, k, d], "inertia" float64 [R], "n_iter" int32 [R], "sizes" int64 [R, k]}``."""
+    k = _cluster_shape(x, k)
+    n_init, max_iter, poll_every = int(n_init), int(max_iter), int(poll_every)
+    if max_iter < 1:
+        raise ValueError(f"max_iter must be >= 1, got {max_iter}")
+    if poll_every < 1:
+        raise ValueError(f"poll_every must be >= 1, got {poll_every}")
+    if not float(tol) >= 0.0:
+        raise ValueError(f"tol must be >= 0, got {tol}")
+    if k > x.size(0):
+        raise ValueError(f"k = {k} clusters need at least as many rows, got M = {x.size(0)}")
+    if init is not None:
+        if not isinstance(init, torch.Tensor):
+            raise TypeError("init must be a torch.Tensor")
+        init = init.unsqueeze(0) if init.dim() == 2 else init
+        if init.dim() != 3 or init.shape[1:] != (k, x.size(1)):
+            raise ValueError(f"init must be [R, {k}, {x.size(1)}] (or [{k}, {x.size(1)}])")
+        n_init = init.size(0)
+    if not 1 <= n_init <= CLUSTER_MAX_RESTARTS:
+        raise ValueError(f"n_init must be in [1, {CLUSTER_MAX_RESTARTS}], got {n_init}")
+    _need_gpu("x", x, torch.float32)
+    dev, m = x.device, x.size(0)
+    with _on(dev):
+        centers = kmeans_plusplus(x, k, n_init, seed) if init is None else init.to(device=dev, dtype=torch.float32).clone().contiguous()
+        tol_abs = float(tol) * float(x.var(dim=0, unbiased=False).mean())
+        labels = torch.full((n_init, m), -1, dtype=torch.int32, device=dev)
+        num_changed, num_iter, done = (torch.zeros(n_init, dtype=torch.int32, device=dev) for _ in range(3))
+        counts = torch.zeros((n_init, k), dtype=torch.int32, device=dev)
+        shift2 = torch.zeros(n_init, dtype=torch.float32, device=dev)
+        ws = _kmeans_workspace(x, n_init, k)
+        for it in range(max_iter):
+            kmeans_assign(x, centers, labels, done, labels, num_changed, ws)
+            kmeans_update(x, centers, labels, num_changed, tol_abs, done, num_iter, counts, shift2, ws)
+            if (it + 1) % poll_every == 0 and bool(done.all()):
+                break
+        # the labels that go with the final centroids (a restart stopped by `tol` has moved them once more)
+        kmeans_assign(x, centers, labels, None, labels, torch.zeros_like(num_changed), ws)
+        inertia_all = kmeans_inertia(x, centers, labels, ws)
+        inertia = inertia_all.cpu().numpy()
+        best = int(inertia.argmin())                                                   # the first of equal minima
+        final = labels[best].to(torch.int64)
+        result = KMeansResult(final, centers[best].clone(), float(inertia[best]), int(num_iter[best]),
+                              torch.bincount(final, minlength=k), best)
+        if not return_restarts:
+            return result
+        sizes = torch.stack([torch.bincount(row.to(torch.int64), minlength=k) for row in labels])
+        return result, {"labels": labels, "centers": centers, "inertia": inertia_all, "n_iter": num_iter, "sizes": sizes}
+
+
+def _silhouette(x: torch.Tensor, labels: torch.Tensor, k: int, slices: int = 0):
+    k, slices = _cluster_shape(x, k), int(slices)
+    if slices < 0:
+        raise ValueError("slices must be >= 0 (0: chosen from the number of rows)")
+    if not isinstance(labels, torch.Tensor) or labels.shape != (x.size(0),) or labels.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"labels must be an int32 / int64 tensor [{x.size(0)}]")
+    _need_gpu("x", x, torch.float32)
+    if labels.device != x.device:
+        raise ValueError(f"labels is on {labels.device}, x on {x.device}")
+    dev, m, d = x.device, x.size(0), x.size(1)
+    with _on(dev):
+        lab = labels.to(torch.int64)
+        if int(lab.min()) < 0 or int(lab.max()) >= k:
+            raise ValueError(f"a label is outside [0, {k})")
+        xc = (x - x.mean(dim=0, keepdim=True)).contiguous()                    # distances unchanged, less cancellation
+        counts = torch.bincount(lab, minlength=k)
+        padded = (counts + 31) // 32 * 32                                      # every label's segment: whole 32-row blocks
+        mp = (int(padded.sum()) + 127) // 128 * 128
+        order = torch.argsort(lab, stable=True)
+        first = torch.cumsum(counts, 0) - counts                               # of every label among the sorted rows ...
+        pfirst = torch.cumsum(padded, 0) - padded                              # ... and among the padded ones
+        slab = lab[order]
+        dest = pfirst[slab] + (torch.arange(m, device=dev) - first[slab])
+        col_row = torch.full((mp,), -1, dtype=torch.int32, device=dev)
+        col_row[dest] = order.to(torch.int32)
+        xs = torch.zeros((mp, d), dtype=torch.float32, device=dev)
+        xs[dest] = xc[order]
+        blk_cluster = torch.full((mp // 32,), -1, dtype=torch.int32, device=dev)
+        real = torch.repeat_interleave(torch.arange(k, dtype=torch.int32, device=dev), padded // 32)
+        blk_cluster[:real.numel()] = real
+        lab32, counts32 = lab.to(torch.int32), counts.to(torch.int32)
+        s = torch.empty(m, dtype=torch.float32, device=dev)
+        mean = torch.empty(1, dtype=torch.float64, device=dev)
+        lib = _lib.load()
+        nbytes = int(lib.rgcn_silhouette_workspace_bytes(m, mp, k, slices))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rc = lib.rgcn_silhouette_samples(_ptr(xc), _ptr(xs), _ptr(col_row), _ptr(blk_cluster), _ptr(counts32), _ptr(lab32),
+                                         m, mp, d, k, slices, _ptr(s), _ptr(mean), _ptr(ws), nbytes, _stream())
+    _lib.check(rc, "rgcn_silhouette_samples")
+    return s, mean
+
+
+def silhouette_samples(x: torch.Tensor, labels: torch.Tensor, k: int, slices: int = 0) -> torch.Tensor:
+    """float32 ``[M]``: the silhouette coefficient of every row of ``x`` (float32 ``[M, d]``, ``d % 32 == 0``) under
+    ``labels`` in ``[0, k)`` with Euclidean distances - scikit-learn's ``silhouette_samples`` without the ``[M, M]``
+    distance matrix (``rgcn_silhouette_samples``): ``(b - a) / max(a, b)``, ``a`` the mean distance to the other members
+    of the row's own cluster, ``b`` the least mean distance to another populated cluster; 0 for the only member of a
+    cluster and where ``max(a, b)`` is 0; a label nobody carries is skipped.  The rows are centred at their mean, grouped
+    by label (stable sort) and padded per label to 32 here; the distances come from the fp32 matrix-core tile.
+    ``slices``: workgroups per 64-row tile (0: chosen from M); the same bits on every call for a given value."""
+    return _silhouette(x, labels, k, slices)[0]
+
+
+def silhouette_score(x: torch.Tensor, labels: torch.Tensor, k: int, slices: int = 0) -> float:
+    """the mean of ``silhouette_samples``, summed on the device in a fixed order in double"""
+    return float(_silhouette(x, labels, k, slices)[1])
 
 
 def distmult_score_all_tails(head: torch.Tensor, rel: torch.Tensor, rel_idx: Optional[torch.Tensor],

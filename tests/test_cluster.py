@@ -1,0 +1,362 @@
+"""K-means and silhouette analysis on the GPU (``csrc/cluster.hip``, ``include/rgcn_cluster.h``) against the float64
+restatement of the header (``cluster_reference.py``).
+
+Labels, counts, iteration numbers and everything "same bits" are compared exactly.  The two tolerances of this file are
+not chosen: each is 4 x the largest error the fp32 HOST restatement of the device arithmetic (Gram-trick distances of
+centred rows, fp32 sums, numpy's order) shows against float64 over this file's own inputs; the factor covers the matrix
+core's different summation order.  Measured on the inputs below (CPU, numpy):
+
+    silhouette, per sample   restatement <= 9.15e-06 (the duplicated rows)   ->  gate 3.66e-05   (``_sil_gates``)
+    silhouette, mean         restatement <= 1.30e-07 (M = 65, k = 33)        ->  gate 5.22e-07
+    inertia, relative        restatement <= 9.95e-08                         ->  gate 3.98e-07   (``_inertia_gate``)
+
+(the constants are recomputed from the restatement whenever the tests run, so they cannot drift from the inputs).
+"""
+import functools
+import json
+
+import numpy as np
+import pytest
+import torch
+
+import cluster_reference as R
+from conftest import need_gpu
+from primekg_rgcn_linkprediction_amd import consumers, ops, synth
+from primekg_rgcn_linkprediction_amd import evaluate as E, train as T
+
+pytestmark = pytest.mark.gpu
+
+# (M, d, k): every M in {2, 63, 64, 65, 129, 700}, d in {32, 96, 128}, k in {2, 5, 10, 33} (33 crosses the 32-column pad)
+KM_CASES = [(2, 32, 2), (63, 96, 5), (64, 128, 10), (65, 32, 33), (129, 96, 33), (129, 128, 2), (700, 32, 5), (700, 128, 10),
+            (700, 96, 33)]
+RESTARTS = 3
+# name -> (M, d, k, blobs keywords): the plain blobs at every M and d, and the four special inputs
+SIL_CASES = {
+    "m2": (2, 32, 2, {}), "m63": (63, 96, 5, {}), "m64": (64, 128, 10, {}), "m65": (65, 32, 33, {}),
+    "m129": (129, 96, 33, {}), "m700": (700, 128, 10, {}), "m700_k33": (700, 96, 33, {}),
+    "duplicates": (700, 128, 10, {"duplicates": 8}), "offset3": (700, 128, 10, {"offset": 3.0}),
+    "singleton": (129, 128, 5, {}), "unused_id": (129, 96, 5, {}),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _km(m, d, k):
+    """rows, ``RESTARTS`` starts, and the float64 / fp32 host runs of every start (tol = 0), computed once"""
+    x = R.blobs(m, d, seed=1000 + m + d + k)
+    init = R.starts(x, k, RESTARTS, seed=7)
+    best, runs = R.kmeans(x, init)
+    best32, runs32 = R.kmeans(x, init, dtype=np.float32)
+    return x, init, best, runs, best32, runs32
+
+
+@functools.lru_cache(maxsize=None)
+def _sil(name):
+    """rows, labels in [0, k), k, and the float64 / fp32 host silhouettes, computed once"""
+    m, d, k, kw = SIL_CASES[name]
+    x = R.blobs(m, d, seed=2000 + m + d + k, **kw)
+    labels = R.lloyd(x, R.starts(x, k, 1, seed=3)[0])["labels"] if m > k else np.arange(m)
+    if name == "singleton":                                    # the last row alone in a cluster of its own
+        labels = np.where(labels == k - 1, 0, labels)
+        labels[-1] = k - 1
+    if name == "unused_id":                                    # nobody carries id 2
+        labels = np.where(labels == 2, 3, labels)
+    s64 = R.silhouette_samples(x, labels, k)
+    s32 = R.silhouette_samples(x, labels, k, np.float32)
+    return x, labels, k, s64, s32
+
+
+@functools.lru_cache(maxsize=None)
+def _sil_gates():
+    """(per sample, mean): 4 x the restatement's largest error over SIL_CASES"""
+    per, mean = 0.0, 0.0
+    for name in SIL_CASES:
+        _, _, _, s64, s32 = _sil(name)
+        per = max(per, float(np.abs(s32.astype(np.float64) - s64).max()))
+        mean = max(mean, abs(R.silhouette_mean(s32) - R.silhouette_mean(s64)))
+    print(f"silhouette restatement errors: per sample {per:.3e}, mean {mean:.3e}")
+    return 4 * per, 4 * mean
+
+
+@functools.lru_cache(maxsize=None)
+def _inertia_gate():
+    """relative: 4 x the restatement's largest error over the restarts of KM_CASES"""
+    worst = 0.0
+    for case in KM_CASES:
+        _, _, _, runs, _, runs32 = _km(*case)
+        for a, b in zip(runs, runs32):
+            if a["inertia"] > 0:
+                worst = max(worst, abs(b["inertia"] - a["inertia"]) / a["inertia"])
+    print(f"inertia restatement error: {worst:.3e} relative")
+    return 4 * worst
+
+
+def _t(a, dev, dtype=None):
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    return t.to(device=dev, dtype=dtype) if dtype is not None else t.to(dev)
+
+
+# ---------------------------------------------------------------------------------- one assignment step
+@pytest.mark.parametrize("m,d,k", KM_CASES)
+def test_one_assignment_step_is_the_float64_argmin(m, d, k):
+    dev = need_gpu()
+    x, init, *_ = _km(m, d, k)
+    labels, changed = ops.kmeans_assign(_t(x, dev), _t(init, dev))
+    assert labels.dtype == torch.int32 and labels.shape == (RESTARTS, m) and changed.tolist() == [m] * RESTARTS
+    got = labels.cpu().numpy()
+    for r in range(RESTARTS):
+        want, margin = R.assign(x, init[r])
+        x2 = (x.astype(np.float64) ** 2).sum(1)
+        c2 = (init[r].astype(np.float64) ** 2).sum(1).max()
+        sure = margin >= 1e-5 * (x2 + c2)
+        print(f"restart {r}: {int((~sure).sum())} of {m} rows below the margin, {int((got[r] != want).sum())} differ")
+        assert (~sure).mean() <= 0.01                          # a condition on the inputs, not a tolerance
+        assert np.array_equal(got[r][sure], want[sure])
+        assert got[r].min() >= 0 and got[r].max() < k
+    # the same step again: nothing changes, the count says so
+    again, changed = ops.kmeans_assign(_t(x, dev), _t(init, dev), labels_prev=labels)
+    assert torch.equal(again, labels) and changed.tolist() == [0] * RESTARTS
+
+
+def test_equal_keys_go_to_the_lower_id_and_an_empty_cluster_keeps_its_centroid():
+    dev = need_gpu()
+    for m, d, k, twin in ((700, 128, 10, (1, 3)), (129, 96, 33, (4, 32)), (65, 32, 33, (31, 32))):
+        x, init, *_ = _km(m, d, k)
+        c = init.copy()
+        c[:, twin[1]] = c[:, twin[0]]                          # two identical centroids: every tie to the lower id
+        xd, cd = _t(x, dev), _t(c, dev)
+        before = cd.clone()
+        labels, changed = ops.kmeans_assign(xd, cd)
+        counts, shift2 = ops.kmeans_update(xd, cd, labels, changed)
+        got = labels.cpu().numpy()
+        for r in range(RESTARTS):
+            want, _ = R.assign(x, c[r])
+            assert not (got[r] == twin[1]).any() and (want == twin[0]).sum() > 0
+            assert np.array_equal(got[r] == twin[0], want == twin[0])
+            assert counts[r, twin[1]].item() == 0 and torch.equal(cd[r, twin[1]], before[r, twin[1]])   # bits unchanged
+            new, cnt = R.update(x, c[r], want)
+            assert counts[r].tolist() == cnt.tolist()
+            assert np.abs(cd[r].cpu().numpy() - new).max() <= 1e-5 * max(1.0, np.abs(new).max())
+            assert abs(shift2[r].item() - ((new - c[r]) ** 2).sum()) <= 1e-4 * max(1.0, ((new - c[r]) ** 2).sum())
+
+
+def test_a_nan_centroid_never_wins_a_point():
+    dev = need_gpu()
+    for m, d, k, bad in ((700, 128, 10, 0), (129, 96, 33, 32), (65, 32, 33, 5)):
+        x, init, *_ = _km(m, d, k)
+        c = init.copy()
+        c[:, bad] = np.nan
+        labels, _ = ops.kmeans_assign(_t(x, dev), _t(c, dev))
+        got = labels.cpu().numpy()
+        for r in range(RESTARTS):
+            want, _ = R.assign(x, c[r])
+            assert not (got[r] == bad).any() and not (want == bad).any()
+            assert (got[r] != want).mean() <= 0.01
+        fit = ops.kmeans(_t(x, dev), k, init=_t(c, dev), tol=0.0)
+        assert fit.sizes[bad].item() == 0 and not (fit.labels == bad).any() and bool(torch.isnan(fit.centers[bad]).all())
+        assert int(fit.sizes.sum()) == m and np.isfinite(fit.inertia)
+
+
+# ---------------------------------------------------------------------------------- full runs
+def _same_fit(a, b):
+    return (torch.equal(a.labels, b.labels) and torch.equal(a.centers, b.centers) and a.inertia == b.inertia
+            and a.n_iter == b.n_iter and torch.equal(a.sizes, b.sizes) and a.restart == b.restart)
+
+
+@pytest.mark.parametrize("m,d,k", KM_CASES)
+def test_full_run_from_given_starts(m, d, k):
+    dev = need_gpu()
+    x, init, best, runs, best32, runs32 = _km(m, d, k)
+    # a condition on the inputs: the fp32 host restatement follows the float64 one label for label
+    assert best32 == best and all(np.array_equal(a["labels"], b["labels"]) for a, b in zip(runs, runs32))
+    gate = _inertia_gate()
+    xd = _t(x, dev)
+    fit = ops.kmeans(xd, k, init=_t(init, dev), tol=0.0, poll_every=1)
+    want = runs[best]
+    print(f"inertia {fit.inertia!r} vs {want['inertia']!r}: relative error "
+          f"{abs(fit.inertia - want['inertia']) / max(want['inertia'], 1e-300):.3e}, gate {gate:.3e}")
+    assert fit.restart == best and fit.labels.dtype == torch.int64 and fit.labels.device.type == "cuda"
+    assert np.array_equal(fit.labels.cpu().numpy(), want["labels"])
+    assert fit.sizes.tolist() == want["counts"].tolist() and fit.n_iter == want["n_iter"]
+    assert abs(fit.inertia - want["inertia"]) <= gate * want["inertia"]
+    assert np.abs(fit.centers.cpu().numpy() - want["centers"]).max() <= 1e-5 * max(1.0, np.abs(want["centers"]).max())
+    # the interval at which the host looks at the flags changes no bit, nor does a second call
+    assert _same_fit(fit, ops.kmeans(xd, k, init=_t(init, dev), tol=0.0, poll_every=7))
+    assert _same_fit(fit, ops.kmeans(xd, k, init=_t(init, dev), tol=0.0, poll_every=1))
+    # every restart on its own (R = 1) ends where it ended among the three
+    alone = ops.kmeans(xd, k, init=_t(init[best:best + 1], dev), tol=0.0)
+    assert torch.equal(alone.labels, fit.labels) and torch.equal(alone.centers, fit.centers) and alone.inertia == fit.inertia
+
+
+def test_tolerance_stops_a_run_as_the_restatement_does():
+    dev = need_gpu()
+    m, d, k = 700, 128, 10
+    x, init, *_ = _km(m, d, k)
+    tol_abs = R.tol_abs(x, 1e-2)
+    best, runs = R.kmeans(x, init, tol_abs)
+    fit = ops.kmeans(_t(x, dev), k, init=_t(init, dev), tol=1e-2)
+    assert fit.restart == best and fit.n_iter == runs[best]["n_iter"]
+    assert np.array_equal(fit.labels.cpu().numpy(), runs[best]["labels"])
+    one = ops.kmeans(_t(x, dev), k, init=_t(init, dev), tol=0.0, max_iter=1)
+    best1, runs1 = R.kmeans(x, init, 0.0, max_iter=1)
+    assert one.n_iter == 1 and one.restart == best1 and np.array_equal(one.labels.cpu().numpy(), runs1[best1]["labels"])
+
+
+def test_a_done_restart_is_frozen():
+    dev = need_gpu()
+    m, d, k = 700, 128, 10
+    x, init, best, runs, *_ = _km(m, d, k)
+    xd = _t(x, dev)
+    # restart 1 is the converged answer already: the run returns it bit for bit
+    ended = ops.kmeans(xd, k, init=_t(init[1:2], dev), tol=0.0)
+    c = init.copy()
+    c[1] = ended.centers.cpu().numpy()
+    fit = ops.kmeans(xd, k, init=_t(c[1:2], dev), tol=0.0)
+    assert torch.equal(fit.centers, ended.centers) and torch.equal(fit.labels, ended.labels) and fit.inertia == ended.inertia
+    # ... and so does a run of three restarts of which it is the second: its centroids keep their bits, it is done after one
+    # iteration (every label is new, nothing moves) and stays frozen while the other two go on
+    three, per = ops.kmeans(xd, k, init=_t(c, dev), tol=0.0, poll_every=1, return_restarts=True)
+    assert torch.equal(per["centers"][1], _t(c[1], dev)) and per["n_iter"].tolist()[1] == 1
+    assert torch.equal(per["labels"][1].to(torch.int64), ended.labels) and per["inertia"][1].item() == ended.inertia
+    assert per["sizes"][1].tolist() == ended.sizes.tolist() and min(per["n_iter"].tolist()[0], per["n_iter"].tolist()[2]) > 1
+    assert [per["n_iter"].tolist()[r] for r in (0, 2)] == [runs[r]["n_iter"] for r in (0, 2)]
+    assert three.restart == int(np.argmin(per["inertia"].cpu().numpy())) and three.inertia == per["inertia"][three.restart].item()
+    # with its flag set, no call writes anything of restart 1 - whatever its arrays hold
+    cd = _t(c, dev)
+    done = torch.tensor([0, 1, 0], dtype=torch.int32, device=dev)
+    labels = torch.full((RESTARTS, m), -7, dtype=torch.int32, device=dev)
+    changed = torch.full((RESTARTS,), 123, dtype=torch.int32, device=dev)
+    ops.kmeans_assign(xd, cd, labels, done, labels, changed)
+    assert (labels[1] == -7).all() and changed[1].item() == 123 and changed[0].item() == m == changed[2].item()
+    assert labels[0].min().item() >= 0 and labels[2].min().item() >= 0
+    labels[1] = ended.labels.to(torch.int32)
+    counts = torch.full((RESTARTS, k), -5, dtype=torch.int32, device=dev)
+    shift2 = torch.full((RESTARTS,), -1.0, device=dev)
+    num_iter = torch.full((RESTARTS,), 40, dtype=torch.int32, device=dev)
+    before = cd.clone()
+    ops.kmeans_update(xd, cd, labels, changed, 0.0, done, num_iter, counts, shift2)
+    assert torch.equal(cd[1], before[1]) and (counts[1] == -5).all() and shift2[1].item() == -1.0
+    assert num_iter.tolist() == [41, 40, 41] and done.tolist() == [0, 1, 0]
+    assert not torch.equal(cd[0], before[0]) and int(counts[0].sum()) == m == int(counts[2].sum())
+
+
+def test_starts_drawn_from_a_seed():
+    dev = need_gpu()
+    x = _t(_km(700, 128, 10)[0], dev)
+    a, b = ops.kmeans(x, 10, n_init=4, seed=11), ops.kmeans(x, 10, n_init=4, seed=11)
+    assert _same_fit(a, b) and int(a.sizes.sum()) == 700 and 0 <= a.restart < 4
+    starts = ops.kmeans_plusplus(x, 10, 4, 11)
+    assert starts.shape == (4, 10, 128) and torch.equal(starts, ops.kmeans_plusplus(x, 10, 4, 11))
+    assert not torch.equal(starts, ops.kmeans_plusplus(x, 10, 4, 12))
+    is_row = (starts.reshape(-1, 1, 128) == x.unsqueeze(0)).all(2).any(1)          # every start is a row of x
+    assert bool(is_row.all())
+    for r in range(4):                                                             # ... and k distinct ones
+        assert len({tuple(row) for row in starts[r].cpu().tolist()}) == 10
+    # the returned labels are the assignment against the returned centers
+    labels, _ = ops.kmeans_assign(x, a.centers.unsqueeze(0))
+    assert torch.equal(labels[0].to(torch.int64), a.labels)
+
+
+# ---------------------------------------------------------------------------------- silhouette
+@pytest.mark.parametrize("name", list(SIL_CASES))
+def test_silhouette_samples_and_mean(name):
+    dev = need_gpu()
+    x, labels, k, s64, _ = _sil(name)
+    gate, mean_gate = _sil_gates()
+    xd, ld = _t(x, dev), _t(labels, dev, torch.int64)
+    worst = worst_mean = 0.0
+    results = {}
+    for slices in (0, 1, 2, 7):
+        s = ops.silhouette_samples(xd, ld, k, slices)
+        mean = ops.silhouette_score(xd, ld, k, slices)
+        assert s.dtype == torch.float32 and s.shape == (len(labels),)
+        assert torch.equal(s, ops.silhouette_samples(xd, ld, k, slices)) and mean == ops.silhouette_score(xd, ld, k, slices)
+        got = s.cpu().numpy().astype(np.float64)
+        assert mean == R.silhouette_mean(got)                  # the mean of exactly these samples, summed in double
+        worst = max(worst, float(np.abs(got - s64).max()))
+        worst_mean = max(worst_mean, abs(mean - R.silhouette_mean(s64)))
+        results[slices] = got
+    print(f"{name}: per sample {worst:.3e} (gate {gate:.3e}), mean {worst_mean:.3e} (gate {mean_gate:.3e})")
+    assert worst <= gate and worst_mean <= mean_gate
+    for slices in (1, 2, 7):
+        assert np.abs(results[slices] - results[0]).max() <= gate
+    counts = np.bincount(labels, minlength=k)
+    alone = counts[labels] == 1
+    assert (results[0][alone] == 0).all() and (s64[alone] == 0).all()
+    if name == "singleton":
+        assert alone.sum() == 1 and alone[-1]
+    if name == "duplicates":                                   # equal rows, equal labels: a distance of (nearly) 0 each
+        assert np.array_equal(labels[-8:], labels[:8]) and np.array_equal(x[-8:], x[:8])
+        print(f"duplicates: the two of a pair differ by at most {np.abs(results[0][-8:] - results[0][:8]).max():.3e}")
+        assert np.abs(results[0][-8:] - results[0][:8]).max() <= gate
+    if name == "unused_id":
+        assert counts[2] == 0 and counts.sum() == len(labels)
+        # the id nobody carries changes nothing: the same labels with the gap closed give the same bits
+        closed = np.where(labels > 2, labels - 1, labels)
+        s = ops.silhouette_samples(xd, _t(closed, dev, torch.int64), k - 1)
+        assert np.array_equal(s.cpu().numpy().astype(np.float64), results[0])
+        one = ops.silhouette_samples(xd, torch.zeros_like(ld), k)                  # one populated cluster: all 0
+        assert not one.any()
+
+
+# ---------------------------------------------------------------------------------- end to end
+def test_cluster_analysis_on_a_three_type_table():
+    dev = need_gpu()
+    sizes = {"drug": 300, "disease": 129, "gene": 700}
+    rows = [R.blobs(n, 128, seed=50 + i, centres=4) for i, n in enumerate(sizes.values())]
+    gen = torch.Generator().manual_seed(0)
+    perm = torch.randperm(sum(sizes.values()), generator=gen)                      # the types interleaved in the table
+    table = torch.from_numpy(np.concatenate(rows))[perm]
+    cls = torch.repeat_interleave(torch.arange(3), torch.tensor(list(sizes.values())))[perm]
+    names = {name: c for c, name in enumerate(sizes)}
+    res = consumers.cluster_analysis(table.to(dev), cls, names, n_clusters=4, n_init=3, seed=5)
+    assert list(res) == list(sizes)
+    for c, (name, n) in enumerate(sizes.items()):
+        r = res[name]
+        assert set(r) == {"labels", "silhouette", "cluster_sizes", "members"}
+        nodes = torch.nonzero(cls == c).view(-1)
+        assert r["labels"].shape == (n,) and r["cluster_sizes"].tolist() == torch.bincount(r["labels"], minlength=4).tolist()
+        assert int(r["cluster_sizes"].sum()) == n and len(r["members"]) == 4
+        for j, members in enumerate(r["members"]):
+            assert members == sorted(members) and members == nodes[r["labels"] == j].tolist()
+        # four well separated blobs, four clusters
+        want = R.silhouette_mean(R.silhouette_samples(table[nodes].numpy(), r["labels"].numpy(), 4))
+        assert isinstance(r["silhouette"], float) and abs(r["silhouette"] - want) <= _sil_gates()[0]
+    by_list = consumers.cluster_analysis(table.to(dev), cls, [None, "disease", None], n_clusters=4, n_init=3, seed=5)
+    assert list(by_list) == ["disease"] and torch.equal(by_list["disease"]["labels"], res["disease"]["labels"])
+    # a type with fewer nodes than clusters is left out; the others are analysed as before
+    few = cls.clone()
+    few[torch.nonzero(cls == 1).view(-1)[3:]] = 9                                  # class 1 keeps 3 nodes
+    small = consumers.cluster_analysis(table.to(dev), few, names, n_clusters=4, n_init=3, seed=5)
+    assert list(small) == ["drug", "gene"] and torch.equal(small["gene"]["labels"], res["gene"]["labels"])
+
+
+def test_cluster_cli_round_trip(tmp_path):
+    """train one epoch -> ``final_model.pt`` -> ``cluster.main`` on files in the reference's on-disk format ->
+    ``clustering_summary.json`` equal to ``ModelEvaluator.cluster_analysis``"""
+    dev = need_gpu()
+    from primekg_rgcn_linkprediction_amd import cluster as C
+    tr, va, full, te = T.synthetic_data(num_edges=20000, seed=4)
+    data_dir = tmp_path / "processed"
+    data_dir.mkdir()
+    for name, d in (("train_data.pt", tr), ("val_data.pt", va), ("test_data.pt", te), ("full_graph.pt", full)):
+        torch.save(d, data_dir / name)
+    cls = synth.primekg_like_node_classes()
+    np.savez(data_dir / "node_types.npz", node_class=cls.numpy())
+    T.main(["--data_dir", str(data_dir), "--output_dir", str(tmp_path / "out"), "--epochs", "1", "--lr", "0.01"])
+    model_path = str(tmp_path / "out" / "models" / "final_model.pt")
+    summary = C.main(["--model_path", model_path, "--data_dir", str(data_dir), "--node_types", str(data_dir / "node_types.npz"),
+                      "--classes", "0", "1", "--n_clusters", "4", "--n_init", "2", "--max_iter", "20", "--seed", "3",
+                      "--output_dir", str(tmp_path / "emb")])
+    saved = json.loads((tmp_path / "emb" / "clustering_summary.json").read_text())
+    assert saved == summary and set(saved) == {"protocol", "types"} and list(saved["types"]) == ["class_0", "class_1"]
+    model, _ = E.load_model(model_path, dev)
+    test_data, full_graph = E.load_test_data(str(data_dir))
+    ev = E.ModelEvaluator(model, test_data, full_graph, dev, node_class=cls)
+    res = ev.cluster_analysis({"class_0": 0, "class_1": 1}, 4, n_init=2, max_iter=20, seed=3)
+    for name, n in (("class_0", synth.N_DISEASE), ("class_1", synth.N_DRUG)):
+        entry = saved["types"][name]
+        assert set(entry) == {"num_nodes", "silhouette", "cluster_sizes", "mean_cluster_size", "std_cluster_size", "first_members"}
+        assert entry["num_nodes"] == n == sum(entry["cluster_sizes"]) and entry["cluster_sizes"] == res[name]["cluster_sizes"].tolist()
+        assert entry["silhouette"] == res[name]["silhouette"] and -1.0 <= entry["silhouette"] <= 1.0
+        assert entry["first_members"] == [m[:10] for m in res[name]["members"]]
+        assert entry["mean_cluster_size"] == n / 4

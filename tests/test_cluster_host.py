@@ -1,0 +1,326 @@
+"""CPU tier of the cluster analysis (``csrc/cluster.hip``, ``include/rgcn_cluster.h``): the C surface and every argument
+check that runs before a launch, the Python wrappers' checks by name, the float64 restatement (``cluster_reference.py``)
+the GPU tier holds the device to against scikit-learn, and the CLI's parser and JSON shape on a stubbed evaluator."""
+import argparse
+import ctypes
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import cluster_reference as R
+from conftest import ROOT
+from primekg_rgcn_linkprediction_amd import _lib, consumers, evaluate, ops
+from primekg_rgcn_linkprediction_amd import cluster as C
+
+NAMES = ["rgcn_kmeans_assign", "rgcn_kmeans_inertia", "rgcn_kmeans_update", "rgcn_kmeans_workspace_bytes",
+         "rgcn_silhouette_samples", "rgcn_silhouette_workspace_bytes"]
+
+
+# ---------------------------------------------------------------------------------- C surface
+def _declared(header):
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+    found = re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", text)
+    return {name: [" ".join(p.split()) for p in params.split(",")] for name, params in found}
+
+
+def _kind_in_header(param):
+    if "*" in param:
+        return "pointer"
+    return next(k for k in ("float", "double", "size_t", "int64_t", "int") if re.search(rf"\b{k}\b", param))
+
+
+def _kind_in_ctypes(ty):
+    kinds = {ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_size_t: "size_t", ctypes.c_int64: "int64_t",
+             ctypes.c_int: "int"}
+    if ty in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ty, ctypes._Pointer):
+        return "pointer"
+    return kinds[ty]
+
+
+def test_cluster_header_table_and_library_agree():
+    declared = _declared("rgcn_cluster.h")
+    assert sorted(declared) == sorted(_lib.CLUSTER_PROTOTYPES) == NAMES
+    lib = _lib.load()
+    for name, params in declared.items():
+        restype, argtypes = _lib.CLUSTER_PROTOTYPES[name]
+        assert restype is (ctypes.c_size_t if name.endswith("_bytes") else ctypes.c_int) and len(argtypes) == len(params), name
+        for i, (param, ty) in enumerate(zip(params, argtypes)):
+            assert _kind_in_ctypes(ty) == _kind_in_header(param), f"{name}: parameter {i} ({param})"
+        assert hasattr(lib, name) and getattr(lib, name).argtypes == argtypes
+        assert name not in _lib.PROTOTYPES and name not in _lib.SAMPLING_PROTOTYPES and name not in _lib.PATHS_PROTOTYPES
+        assert name not in _lib.SEQ_FUNCTIONS
+    main_header = open(os.path.join(ROOT, "include", "rgcn_hip.h")).read()
+    assert "rgcn_kmeans" not in main_header and "rgcn_silhouette" not in main_header
+    assert f"#define RGCN_ABI_VERSION {_lib.ABI_VERSION}\n" in main_header and lib.rgcn_abi_version() == _lib.ABI_VERSION >= 32
+    for other in ("rgcn_sampling.h", "rgcn_paths.h"):
+        assert not set(declared) & set(_declared(other))
+    text = open(os.path.join(ROOT, "include", "rgcn_cluster.h")).read()
+    assert '#include "rgcn_hip.h"' in text
+    assert f"#define RGCN_CLUSTER_MAX_K {ops.CLUSTER_MAX_K}\n" in text and ops.CLUSTER_MAX_K >= 33
+    assert f"#define RGCN_CLUSTER_MAX_RESTARTS {ops.CLUSTER_MAX_RESTARTS}\n" in text
+    assert "relocate" in text                                  # the empty-cluster rule and how scikit-learn differs
+
+
+def test_cluster_header_is_plain_c(tmp_path):
+    import shutil
+    import subprocess
+    if shutil.which("gcc") is None:
+        pytest.skip("no gcc")
+    src = tmp_path / "c.c"
+    src.write_text('#include "include/rgcn_cluster.h"\nint main(void) { return RGCN_CLUSTER_MAX_K > 32 ? RGCN_OK : 1; }\n')
+    for cc, std, lang in (("gcc", "-std=c99", "c"), ("g++", "-std=c++17", "c++")):
+        subprocess.run([cc, std, "-Wall", "-Wextra", "-pedantic", "-fsyntax-only", "-x", lang, "-I", ROOT, str(src)], check=True)
+
+
+def test_cluster_entry_points_reject_bad_arguments_without_a_gpu():
+    lib = _lib.load()
+    A, U = _lib.RGCN_ERR_ARG, _lib.RGCN_ERR_UNSUPPORTED
+    size = lib.rgcn_kmeans_workspace_bytes
+    need = size(700, 128, 3, 10)
+    assert need > 0 and size(700, 128, 3, 10) <= size(701, 128, 3, 10) <= size(701, 128, 4, 10) <= size(701, 128, 4, 33)
+    for bad in ((1, 128, 3, 10), (700, 0, 3, 10), (700, 48, 3, 10), (700, 128, 0, 10), (700, 128, 3, 1),
+                (700, 128, 3, ops.CLUSTER_MAX_K + 1), (700, 128, ops.CLUSTER_MAX_RESTARTS + 1, 10), (1 << 30, 128, 3, 10)):
+        assert size(*bad) == 0, bad
+    assert size(2, 32, 1, 2) > 0 and size(700, 128, ops.CLUSTER_MAX_RESTARTS, ops.CLUSTER_MAX_K) > 0
+
+    # rgcn_kmeans_assign(x, M, d, centroids, R, k, labels_prev, labels, num_changed, done, ws, ws_bytes, stream)
+    def assign(m=700, d=128, r=3, k=10, x=8, c=8, prev=None, labels=8, changed=8, done=None, ws=8, ws_bytes=need):
+        return lib.rgcn_kmeans_assign(x, m, d, c, r, k, prev, labels, changed, done, ws, ws_bytes, None)
+
+    # rgcn_kmeans_update(x, M, d, centroids, R, k, labels, num_changed, counts, shift2, num_iter, done, tol_abs, ws, ws_bytes, stream)
+    def update(m=700, d=128, r=3, k=10, x=8, c=8, labels=8, changed=8, counts=8, shift2=8, num_iter=8, done=None, tol=0.0,
+               ws=8, ws_bytes=need):
+        return lib.rgcn_kmeans_update(x, m, d, c, r, k, labels, changed, counts, shift2, num_iter, done, tol, ws, ws_bytes, None)
+
+    # rgcn_kmeans_inertia(x, M, d, centroids, R, k, labels, inertia, ws, ws_bytes, stream)
+    def inertia(m=700, d=128, r=3, k=10, x=8, c=8, labels=8, out=8, ws=8, ws_bytes=need):
+        return lib.rgcn_kmeans_inertia(x, m, d, c, r, k, labels, out, ws, ws_bytes, None)
+
+    for call in (assign, update, inertia):
+        assert call(m=1) == A and call(m=0) == A and call(d=0) == A and call(d=-32) == A and call(r=0) == A and call(k=1) == A
+        assert call(d=48) == U and call(d=100) == U and call(k=ops.CLUSTER_MAX_K + 1) == U
+        assert call(r=ops.CLUSTER_MAX_RESTARTS + 1) == U and call(m=1 << 30) == U
+        assert call(ws=None) == A and call(ws_bytes=need - 1) == A and call(ws_bytes=0) == A
+        assert call(x=None) == A and call(c=None) == A and call(labels=None) == A
+    assert assign(changed=None) == A
+    for hole in ("changed", "counts", "shift2", "num_iter"):
+        assert update(**{hole: None}) == A, hole
+    assert update(tol=-1.0) == A and update(tol=float("nan")) == A
+    assert inertia(out=None) == A
+
+    # rgcn_silhouette_samples(x, xs, col_row, blk_cluster, counts, labels, M, Mp, d, k, slices, s, mean, ws, ws_bytes, stream)
+    ssize = lib.rgcn_silhouette_workspace_bytes
+    sneed = ssize(700, 1024, 10, 0)
+    assert sneed > 0 and ssize(700, 1024, 10, 1) <= ssize(700, 1024, 10, 2) <= ssize(700, 1024, 10, 7)
+    assert ssize(700, 1024, 10, 1000) == ssize(700, 1024, 10, 8)               # no more slices than column tiles
+    assert ssize(70000, 70016, 10, 0) == ssize(70000, 70016, 10, 1) < ssize(20000, 20480, 10, 0)   # 1,024 row tiles and more: one slice
+    for bad in ((1, 128, 2, 0), (700, 640, 10, 0), (700, 1000, 10, 0), (700, 1024, 1, 0), (700, 1024, ops.CLUSTER_MAX_K + 1, 0),
+                (700, 1024, 10, -1)):
+        assert ssize(*bad) == 0, bad
+    arrays = ("x", "xs", "col_row", "blk_cluster", "counts", "labels", "s", "mean")
+
+    def sil(m=700, mp=1024, d=128, k=10, slices=0, ws=8, ws_bytes=sneed, **holes):
+        p = {name: 8 for name in arrays}
+        p.update(holes)
+        return lib.rgcn_silhouette_samples(p["x"], p["xs"], p["col_row"], p["blk_cluster"], p["counts"], p["labels"], m, mp, d, k,
+                                           slices, p["s"], p["mean"], ws, ws_bytes, None)
+
+    assert sil(m=1) == A and sil(d=0) == A and sil(k=1) == A and sil(slices=-1) == A and sil(mp=640) == A and sil(mp=1000) == A
+    assert sil(d=48) == U and sil(k=ops.CLUSTER_MAX_K + 1) == U and sil(m=1 << 30, mp=1 << 30) == U
+    for name in arrays:
+        assert sil(**{name: None}) == A, name
+    assert sil(ws=None) == A and sil(ws_bytes=sneed - 1) == A
+
+
+# ---------------------------------------------------------------------------------- the wrappers
+def test_python_wrappers_raise_by_name_and_have_no_cpu_path():
+    x = torch.zeros(40, 32)
+    for bad_x, what in ((torch.zeros(1, 32), "M >= 2"), (torch.zeros(40, 48), "multiple of 32"), (torch.zeros(40, 0), "multiple of 32"),
+                        (torch.zeros(40), r"\[M, d\]")):
+        with pytest.raises(ValueError, match=what):
+            ops.kmeans(bad_x, 3)
+        with pytest.raises(ValueError, match=what):
+            ops.silhouette_samples(bad_x, torch.zeros(bad_x.size(0), dtype=torch.int64), 3)
+    for k in (1, 0, -2, ops.CLUSTER_MAX_K + 1):
+        with pytest.raises(ValueError, match="CLUSTER_MAX_K"):
+            ops.kmeans(x, k)
+        with pytest.raises(ValueError, match="CLUSTER_MAX_K"):
+            ops.silhouette_score(x, torch.zeros(40, dtype=torch.int64), k)
+    with pytest.raises(ValueError, match="at least as many rows"):
+        ops.kmeans(x, 41)
+    for kw, what in (({"max_iter": 0}, "max_iter"), ({"poll_every": 0}, "poll_every"), ({"tol": -1.0}, "tol"),
+                     ({"tol": float("nan")}, "tol"), ({"n_init": 0}, "n_init"), ({"n_init": ops.CLUSTER_MAX_RESTARTS + 1}, "n_init"),
+                     ({"init": torch.zeros(2, 4, 32)}, "init"), ({"init": torch.zeros(3, 64)}, "init")):
+        with pytest.raises(ValueError, match=what):
+            ops.kmeans(x, 3, **kw)
+    with pytest.raises(TypeError):
+        ops.kmeans([[0.0] * 32] * 4, 2)
+    with pytest.raises(ValueError, match="slices"):
+        ops.silhouette_samples(x, torch.zeros(40, dtype=torch.int64), 3, slices=-1)
+    with pytest.raises(ValueError, match="labels"):
+        ops.silhouette_samples(x, torch.zeros(39, dtype=torch.int64), 3)
+    with pytest.raises(ValueError, match="labels"):
+        ops.silhouette_samples(x, torch.zeros(40), 3)
+    with pytest.raises(ValueError, match=r"\[R, k, 32\]"):
+        ops.kmeans_assign(x, torch.zeros(3, 32))
+    with pytest.raises(ValueError, match="restarts"):
+        ops.kmeans_assign(x, torch.zeros(0, 3, 32))
+    # CPU tensors: every range check came first; then there is no CPU path
+    for call in (lambda: ops.kmeans(x, 3), lambda: ops.kmeans(x, 3, init=torch.zeros(2, 3, 32)),
+                 lambda: ops.silhouette_samples(x, torch.zeros(40, dtype=torch.int64), 3),
+                 lambda: ops.silhouette_score(x, torch.zeros(40, dtype=torch.int64), 3),
+                 lambda: ops.kmeans_assign(x, torch.zeros(2, 3, 32)),
+                 lambda: ops.kmeans_inertia(x, torch.zeros(2, 3, 32), torch.zeros(2, 40, dtype=torch.int32)),
+                 lambda: consumers.cluster_analysis(torch.zeros(40, 32), torch.zeros(40, dtype=torch.int32), {"a": 0}, 3)):
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            call()
+    # a class with fewer nodes than clusters (here: none) is left out, not an error
+    assert consumers.cluster_analysis(torch.zeros(40, 32), torch.zeros(40, dtype=torch.int32), {"b": 1}, 3) == {}
+    assert "cluster_analysis" in dir(evaluate.ModelEvaluator)
+    assert ops.KMeansResult._fields == ("labels", "centers", "inertia", "n_iter", "sizes", "restart")
+
+
+# ---------------------------------------------------------------------------------- the restatement against scikit-learn
+# (M, d, k, seed of the starts): seeds under which the float64 run never empties a cluster (asserted below)
+SK_CASES = [(700, 128, 10, 1), (700, 96, 33, 1), (129, 32, 5, 4), (65, 128, 2, 3)]
+
+
+@pytest.mark.parametrize("m,d,k,seed", SK_CASES)
+def test_restatement_is_scikit_learns_lloyd(m, d, k, seed):
+    """``KMeans(init=C0, n_init=1, algorithm="lloyd", tol=0)``: the same labels, the inertia to 1e-9 relative - on inputs
+    where no cluster ever empties (asserted per iteration: scikit-learn relocates an empty cluster, the header keeps it)"""
+    pytest.importorskip("sklearn")
+    from sklearn.cluster import KMeans
+    x = R.blobs(m, d, seed=300 + m + d + k)
+    init = R.starts(x, k, 1, seed=seed)[0]
+    mine = R.lloyd(x, init)
+    assert all(counts.min() > 0 for counts in mine["history"]) and len(mine["history"]) == mine["n_iter"] >= 2
+    theirs = KMeans(n_clusters=k, init=init.astype(np.float64), n_init=1, algorithm="lloyd", tol=0).fit(x.astype(np.float64))
+    assert np.array_equal(theirs.labels_, mine["labels"]) and theirs.n_iter_ == mine["n_iter"]
+    assert abs(theirs.inertia_ - mine["inertia"]) <= 1e-9 * theirs.inertia_
+    assert np.abs(theirs.cluster_centers_ - mine["centers"]).max() <= 1e-9 * np.abs(mine["centers"]).max()
+    # the fp32 restatement of the device arithmetic ends at the same labels (measured: inertia to ~1e-7 relative)
+    low = R.lloyd(x, init, dtype=np.float32)
+    assert np.array_equal(low["labels"], mine["labels"]) and abs(low["inertia"] - mine["inertia"]) <= 1e-6 * mine["inertia"]
+    # the winner of several starts has the least inertia, the first of equals
+    starts = np.stack([init, R.starts(x, k, 1, seed=seed + 50)[0], init])
+    best, runs = R.kmeans(x, starts)
+    assert runs[0]["inertia"] == runs[2]["inertia"] and best == int(np.argmin([r["inertia"] for r in runs])) and best != 2
+
+
+def test_restatement_rules_scikit_learn_does_not_have():
+    x = R.blobs(129, 32, seed=9)
+    init = R.starts(x, 5, 1, seed=1)[0]
+    twin = init.copy()
+    twin[3] = twin[1]                                          # equal keys: the lower id; the other cluster stays empty
+    labels, _ = R.assign(x, twin)
+    new, counts = R.update(x, twin, labels)
+    assert not (labels == 3).any() and (labels == 1).any() and counts[3] == 0 and counts.sum() == 129
+    assert np.array_equal(new[3], twin[3].astype(np.float64)) and not np.array_equal(new[1], twin[1].astype(np.float64))
+    run = R.lloyd(x, twin, max_iter=1)
+    assert run["history"][0][3] == 0 and np.array_equal(run["centers"], new) and run["n_iter"] == 1
+    bad = init.copy()
+    bad[2] = np.nan                                            # a NaN key never wins
+    run = R.lloyd(x, bad)
+    assert not (run["labels"] == 2).any() and np.isnan(run["centers"][2]).all() and np.isfinite(run["inertia"])
+    # tol_abs stops a run early; the labels are then the assignment against the final centroids
+    full = R.lloyd(x, init)
+    early = R.lloyd(x, init, R.tol_abs(x, 10.0))
+    assert 1 <= early["n_iter"] < full["n_iter"]
+    assert np.array_equal(early["labels"], R.assign(x, early["centers"])[0])
+    assert R.tol_abs(x, 1e-4) == pytest.approx(1e-4 * x.astype(np.float64).var(0).mean())
+
+
+@pytest.mark.parametrize("m,d,k", [(700, 128, 10), (129, 96, 33), (65, 32, 5)])
+def test_restated_silhouette_is_scikit_learns(m, d, k):
+    pytest.importorskip("sklearn")
+    from sklearn.metrics import silhouette_samples, silhouette_score
+    x = R.blobs(m, d, seed=400 + m)        # (no equal rows: scikit-learn's own float64 Gram trick is 1e-9 off at distance 0)
+    labels = R.lloyd(x, R.starts(x, k, 1, seed=3)[0])["labels"]
+    labels[-1] = labels[0] if m == 65 else labels[-1]
+    present = np.unique(labels)
+    mine = R.silhouette_samples(x, labels, k)
+    # scikit-learn wants consecutive labels; an id nobody carries must not matter to the restatement
+    compact = np.searchsorted(present, labels)
+    theirs = silhouette_samples(x.astype(np.float64), compact, metric="euclidean")
+    assert np.abs(mine - theirs).max() <= 1e-12
+    assert abs(R.silhouette_mean(mine) - silhouette_score(x.astype(np.float64), compact)) <= 1e-12
+    assert np.array_equal(R.silhouette_samples(x, compact, len(present)), mine)
+    assert np.array_equal(R.silhouette_samples(x, labels + 1, k + 1)[1:], mine[1:])       # id 0 unused
+    counts = np.bincount(labels, minlength=k)
+    assert (mine[counts[labels] == 1] == 0).all()                                         # singletons are exactly 0
+    lonely = labels.copy()
+    lonely[5] = k                                                                         # one more cluster, one member
+    out = R.silhouette_samples(x, lonely, k + 1)
+    assert out[5] == 0 and np.abs(out - silhouette_samples(x.astype(np.float64), np.searchsorted(np.unique(lonely), lonely))).max() <= 1e-12
+    assert not R.silhouette_samples(x, np.zeros(m, dtype=np.int64), k).any()              # one populated cluster
+    # what the device arithmetic costs, for scale (the GPU tier measures its own inputs): well under 1e-4 per sample
+    low = R.silhouette_samples(x, labels, k, np.float32)
+    assert low.dtype == np.float32 and np.abs(low - mine).max() <= 1e-4
+
+
+# ---------------------------------------------------------------------------------- cluster.py
+class _StubEvaluator:
+    """``cluster_analysis`` from fixed labels, on the CPU"""
+
+    def __init__(self):
+        self.calls = []
+
+    def cluster_analysis(self, class_names, n_clusters=10, **kw):
+        self.calls.append((dict(class_names), n_clusters, kw))
+        out = {}
+        for name, cls in class_names.items():
+            nodes = torch.arange(100 * cls, 100 * cls + 37)
+            labels = (nodes * 7 + cls) % n_clusters
+            sizes = torch.bincount(labels, minlength=n_clusters)
+            out[name] = {"labels": labels, "silhouette": 0.25 + 0.1 * cls, "cluster_sizes": sizes,
+                         "members": [nodes[labels == j].tolist() for j in range(n_clusters)]}
+        return out
+
+
+def test_cluster_cli_flags_and_json_shape_on_a_stubbed_evaluator(tmp_path):
+    base = ["--model_path", "m.pt", "--node_types", "types.npz"]
+    args = C.parse_args(base)
+    assert (args.n_clusters, args.n_init, args.seed, args.max_iter, args.tol) == (10, 10, 42, 300, 1e-4)
+    assert args.data_dir == "data/processed" and args.output_dir == "results/embeddings" and args.node_names is None and args.classes is None
+    args = C.parse_args(base + ["--n_clusters", "3", "--n_init", "2", "--seed", "7", "--classes", "0", "2", "--node_names", "mappings.pt"])
+    assert (args.n_clusters, args.n_init, args.seed, args.classes, args.node_names) == (3, 2, 7, [0, 2], "mappings.pt")
+    for bad in (["--n_clusters", "1"], ["--n_init", "0"], ["--max_iter", "0"], ["--tol", "-1"], ["--n_clusters", "x"]):
+        with pytest.raises(SystemExit):
+            C.parse_args(base + bad)
+    with pytest.raises(SystemExit):
+        C.parse_args(["--model_path", "m.pt"])                                             # --node_types is required
+    node_class = torch.tensor([0, 0, 2, 2, 2, -1, 1], dtype=torch.int32)
+    assert C.class_names("types.npz", node_class) == {"class_0": 0, "class_1": 1, "class_2": 2}
+    assert C.class_names(None, node_class, only=[2, 0]) == {"class_2": 2, "class_0": 0}
+    idx2node = {i: (f"id{i}", f"name{i}", ("drug", "disease", "gene/protein")[c]) for i, c in enumerate([0, 0, 2, 2, 2, 1, 1])}
+    torch.save({"idx2node": idx2node}, tmp_path / "mappings.pt")
+    classes = evaluate.load_node_classes(str(tmp_path / "mappings.pt"), 7)
+    assert C.class_names(str(tmp_path / "mappings.pt"), classes) == {"disease": 0, "drug": 1, "gene/protein": 2}
+    ev = _StubEvaluator()
+    which = {"disease": 0, "gene/protein": 2}
+    names = {i: f"node{i}" for i in range(300)}
+    summary = C.analyse(ev, args, which, names)
+    assert ev.calls == [(which, 3, {"n_init": 2, "seed": 7, "max_iter": 300, "tol": 1e-4})]
+    assert set(summary) == {"protocol", "types"} and list(summary["types"]) == ["disease", "gene/protein"]
+    assert {"n_clusters", "n_init", "seed", "max_iter", "tol", "first_members", "kmeans", "silhouette", "left_out"} == set(summary["protocol"])
+    assert summary["protocol"]["left_out"] == []
+    assert summary["protocol"]["n_clusters"] == 3 and summary["protocol"]["first_members"] == 10
+    for name, cls in which.items():
+        entry = summary["types"][name]
+        assert set(entry) == {"num_nodes", "silhouette", "cluster_sizes", "mean_cluster_size", "std_cluster_size", "first_members",
+                              "first_member_names"}
+        sizes = np.array(entry["cluster_sizes"])
+        assert entry["num_nodes"] == 37 == sizes.sum() and entry["silhouette"] == 0.25 + 0.1 * cls
+        assert entry["mean_cluster_size"] == sizes.mean() and entry["std_cluster_size"] == sizes.std()   # numpy's, as the reference prints
+        assert len(entry["first_members"]) == 3 and all(len(m) == 10 and m == sorted(m) for m in entry["first_members"])
+        assert entry["first_member_names"] == [[f"node{i}" for i in m] for m in entry["first_members"]]
+    plain = C.analyse(ev, args, which, None)
+    assert all("first_member_names" not in entry for entry in plain["types"].values())
+    saved = C.save_summary(summary, tmp_path / "out")
+    assert saved.name == "clustering_summary.json" and json.loads(saved.read_text()) == summary
+    assert isinstance(C.parse_args(base), argparse.Namespace)
