@@ -1489,7 +1489,8 @@ def sample_batch(edge_index: torch.Tensor, edge_type: torch.Tensor, order: Optio
     lib = _L()
     with _on(edge_index.device):
         heads = _empty(total, dtype=torch.int64, device=edge_index.device)
-        tails, rels = torch.empty_like(heads), torch.empty_like(heads)
+        tails = _empty(total, dtype=torch.int64, device=edge_index.device)
+        rels = _empty(total, dtype=torch.int64, device=edge_index.device)
         labels = _empty(total, dtype=torch.float32, device=edge_index.device)
         rc = lib.rgcn_sample_batch(_ptr(edge_index), _ptr(edge_type), e, _ptr(order), _ptr(cursor), batch, num_neg,
                                    int(num_nodes), _ptr(rng), _ptr(heads), _ptr(tails), _ptr(rels), _ptr(labels),
@@ -1645,7 +1646,7 @@ def distmult_rank_tails(hr: torch.Tensor, emb: torch.Tensor, true_score: torch.T
         raise ValueError("embedding dim must be a multiple of 32 for the fused ranking kernel")
     lib = _L()
     with _on(hr.device):
-        beaten = torch.zeros(b, dtype=torch.int32, device=hr.device)
+        beaten = _empty(b, dtype=torch.int32, device=hr.device).zero_()
         rc = lib.distmult_rank_tails(_ptr(hr), _ptr(emb), _ptr(true_score), _ptr(tail), b, emb.size(0), d,
                                      _ptr(beaten), _stream())
     _lib.check(rc, "distmult_rank_tails")
@@ -1666,7 +1667,7 @@ def class_allow_bits(class_of: torch.Tensor, num_classes: int) -> torch.Tensor:
         raise ValueError("class_of [N] (N > 0) and num_classes > 0 expected")
     n = class_of.numel()
     with _on(class_of.device):
-        allow = torch.empty((num_classes, mask_words(n)), dtype=torch.int32, device=class_of.device)
+        allow = _empty((num_classes, mask_words(n)), dtype=torch.int32, device=class_of.device)
         rc = _L().rgcn_rank_allow_bits(_ptr(class_of), n, num_classes, _ptr(allow), _stream())
     _lib.check(rc, "rgcn_rank_allow_bits")
     return allow
@@ -1731,7 +1732,7 @@ class KnownTriples:
         _need_gpu("ids", ids, torch.int64)
         b, w = seg.numel(), mask_words(self.num_nodes)
         if out is None:
-            out = torch.empty((b, w), dtype=torch.int32, device=seg.device)
+            out = _empty((b, w), dtype=torch.int32, device=seg.device)
         elif out.dtype != torch.int32 or out.dim() != 2 or out.size(0) < b or out.size(1) != w or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous int32 [>= {b}, {w}] buffer")
         with _on(seg.device):
@@ -1840,7 +1841,8 @@ def sample_batch_constrained(edge_index: torch.Tensor, edge_type: torch.Tensor, 
     lib = _L()
     with _on(dev):
         heads = _empty(total, dtype=torch.int64, device=dev)
-        tails, rels = torch.empty_like(heads), torch.empty_like(heads)
+        tails = _empty(total, dtype=torch.int64, device=dev)
+        rels = _empty(total, dtype=torch.int64, device=dev)
         labels = _empty(total, dtype=torch.float32, device=dev)
         rc = lib.rgcn_sample_batch_constrained(
             _ptr(edge_index), _ptr(edge_type), e, _ptr(order), _ptr(cursor), batch, num_neg, int(num_nodes), _ptr(rng),
@@ -1881,7 +1883,7 @@ def distmult_rank_masked(q: torch.Tensor, emb: torch.Tensor, true_score: torch.T
             raise ValueError(f"exclude [{b}, {w}] expected")
     lib = _L()
     with _on(q.device):
-        beaten = torch.zeros(b, dtype=torch.int32, device=q.device)
+        beaten = _empty(b, dtype=torch.int32, device=q.device).zero_()
         rc = lib.distmult_rank_masked(_ptr(q), _ptr(emb), _ptr(true_score), _ptr(target), _ptr(allow), _ptr(query_class),
                                       classes, _ptr(exclude), b, emb.size(0), d, _ptr(beaten), _stream())
     _lib.check(rc, "distmult_rank_masked")
@@ -1908,8 +1910,8 @@ def distmult_rank_filtered(q: torch.Tensor, emb: torch.Tensor, true_score: torch
     if rows >= 64:
         rows -= rows % 64                                        # whole row tiles of the ranking pass
     rows = min(rows, b)
-    ranks = torch.empty(b, dtype=torch.int64, device=q.device)
-    buf = torch.empty((rows, w), dtype=torch.int32, device=q.device)
+    ranks = _empty(b, dtype=torch.int64, device=q.device)
+    buf = _empty((rows, w), dtype=torch.int32, device=q.device)
     for lo in range(0, b, rows):
         hi = min(lo + rows, b)
         excl = known.exclude_bits(side, anchor_idx[lo:hi], rel_idx[lo:hi], out=buf)
@@ -1960,12 +1962,12 @@ def distmult_topk_masked(q: torch.Tensor, emb: torch.Tensor, k: int, allow: Opti
             raise ValueError(f"exclude [{b}, {w}] expected")
     lib = _L()
     with _on(q.device):
-        ids = torch.empty((b, k), dtype=torch.int64, device=q.device)
-        scores = torch.empty((b, k), dtype=torch.float32, device=q.device)
+        ids = _empty((b, k), dtype=torch.int64, device=q.device)
+        scores = _empty((b, k), dtype=torch.float32, device=q.device)
         if b == 0:
             return ids, scores
         nbytes = int(lib.distmult_topk_workspace_bytes(b, emb.size(0), k, slices))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+        ws = _empty(nbytes, dtype=torch.uint8, device=q.device)
         rc = lib.distmult_topk_masked(_ptr(q), _ptr(emb), _ptr(allow), _ptr(query_class), classes, _ptr(exclude), floor,
                                       b, emb.size(0), d, k, slices, _ptr(ids), _ptr(scores), _ptr(ws), nbytes, _stream())
     _lib.check(rc, "distmult_topk_masked")
@@ -1995,9 +1997,9 @@ def distmult_topk_filtered(q: torch.Tensor, emb: torch.Tensor, k: int, known: Op
     if rows >= b:
         excl = known.exclude_bits(side, anchor_idx, rel_idx)
         return distmult_topk_masked(q, emb, k, allow, query_class, excl, min_score, slices)
-    ids = torch.empty((b, int(k)), dtype=torch.int64, device=q.device)
-    scores = torch.empty((b, int(k)), dtype=torch.float32, device=q.device)
-    buf = torch.empty((rows, w), dtype=torch.int32, device=q.device)
+    ids = _empty((b, int(k)), dtype=torch.int64, device=q.device)
+    scores = _empty((b, int(k)), dtype=torch.float32, device=q.device)
+    buf = _empty((rows, w), dtype=torch.int32, device=q.device)
     for lo in range(0, b, rows):
         hi = min(lo + rows, b)
         excl = known.exclude_bits(side, anchor_idx[lo:hi], rel_idx[lo:hi], out=buf)
@@ -2075,7 +2077,7 @@ def edge_cosine(emb: torch.Tensor, graph: PathGraph) -> torch.Tensor:
         if t.device != emb.device:
             raise ValueError(f"graph.{name} is on {t.device}, emb on {emb.device}")
     with _on(emb.device):
-        out = torch.empty(graph.nnz, dtype=torch.float32, device=emb.device)
+        out = _empty(graph.nnz, dtype=torch.float32, device=emb.device)
         rc = _L().rgcn_edge_cosine(_ptr(emb), graph.num_nodes, emb.size(1), _ptr(graph.out_ptr), _ptr(graph.out_dst),
                                    graph.nnz, _ptr(out), _stream())
     _lib.check(rc, "rgcn_edge_cosine")
@@ -2119,14 +2121,14 @@ def paths_topk(graph: PathGraph, edge_score: torch.Tensor, sources: torch.Tensor
         raise IndexError("a source or target id is outside [0, num_nodes)")
     lib = _L()
     with _on(dev):
-        nodes = torch.empty((q, k, PATHS_MAX_LEN + 1), dtype=torch.int32, device=dev)
-        length = torch.empty((q, k), dtype=torch.int32, device=dev)
-        score = torch.empty((q, k), dtype=torch.float32, device=dev)
-        count = torch.empty((q, PATHS_MAX_LEN), dtype=torch.int64, device=dev)
+        nodes = _empty((q, k, PATHS_MAX_LEN + 1), dtype=torch.int32, device=dev)
+        length = _empty((q, k), dtype=torch.int32, device=dev)
+        score = _empty((q, k), dtype=torch.float32, device=dev)
+        count = _empty((q, PATHS_MAX_LEN), dtype=torch.int64, device=dev)
         if q == 0:
             return nodes, length, score, count
         nbytes = int(lib.rgcn_paths_workspace_bytes(q, k, slices))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _empty(nbytes, dtype=torch.uint8, device=dev)
         rc = lib.rgcn_paths_topk(_ptr(graph.out_ptr), _ptr(graph.out_dst), _ptr(edge_score), _ptr(graph.in_ptr),
                                  _ptr(graph.in_src), _ptr(graph.in_pos), graph.num_nodes, graph.nnz, _ptr(sources),
                                  _ptr(targets), q, max_len, k, slices, _ptr(nodes), _ptr(length), _ptr(score), _ptr(count),
@@ -2180,7 +2182,7 @@ def _cluster_centers(x: torch.Tensor, centers: torch.Tensor, name: str = "center
 
 def _kmeans_workspace(x: torch.Tensor, r: int, k: int) -> torch.Tensor:
     nbytes = int(_lib.load().rgcn_kmeans_workspace_bytes(x.size(0), x.size(1), r, k))
-    return torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    return _empty(nbytes, dtype=torch.uint8, device=x.device)
 
 
 def _flags(name: str, t: Optional[torch.Tensor], r: int, device) -> None:
@@ -2209,9 +2211,10 @@ def kmeans_assign(x: torch.Tensor, centers: torch.Tensor, labels_prev: Optional[
     _flags("num_changed", num_changed, r, dev)
     with _on(dev):
         if labels is None:
-            labels = torch.full((r, m), -1, dtype=torch.int32, device=dev) if labels_prev is None else labels_prev.clone()
+            labels = _empty((r, m), dtype=torch.int32, device=dev)
+            labels = labels.fill_(-1) if labels_prev is None else labels.copy_(labels_prev)
         if num_changed is None:
-            num_changed = torch.zeros(r, dtype=torch.int32, device=dev)
+            num_changed = _empty(r, dtype=torch.int32, device=dev).zero_()
         ws = _kmeans_workspace(x, r, k) if ws is None else ws
         rc = _lib.load().rgcn_kmeans_assign(_ptr(x), m, x.size(1), _ptr(centers), r, k, _ptr(labels_prev), _ptr(labels),
                                             _ptr(num_changed), _ptr(done), _ptr(ws), ws.numel(), _stream())
@@ -2240,9 +2243,9 @@ def kmeans_update(x: torch.Tensor, centers: torch.Tensor, labels: torch.Tensor, 
     _flags("done", done, r, dev)
     _flags("num_iter", num_iter, r, dev)
     with _on(dev):
-        counts = torch.zeros((r, k), dtype=torch.int32, device=dev) if counts is None else counts
-        shift2 = torch.zeros(r, dtype=torch.float32, device=dev) if shift2 is None else shift2
-        num_iter = torch.zeros(r, dtype=torch.int32, device=dev) if num_iter is None else num_iter
+        counts = _empty((r, k), dtype=torch.int32, device=dev).zero_() if counts is None else counts
+        shift2 = _empty(r, dtype=torch.float32, device=dev).zero_() if shift2 is None else shift2
+        num_iter = _empty(r, dtype=torch.int32, device=dev).zero_() if num_iter is None else num_iter
         ws = _kmeans_workspace(x, r, k) if ws is None else ws
         rc = _lib.load().rgcn_kmeans_update(_ptr(x), m, x.size(1), _ptr(centers), r, k, _ptr(labels), _ptr(num_changed),
                                             _ptr(counts), _ptr(shift2), _ptr(num_iter), _ptr(done), float(tol_abs), _ptr(ws),
@@ -2259,7 +2262,7 @@ def kmeans_inertia(x: torch.Tensor, centers: torch.Tensor, labels: torch.Tensor,
     if labels.shape != (r, m) or labels.device != dev:
         raise ValueError(f"labels must be int32 [{r}, {m}] on {dev}")
     with _on(dev):
-        out = torch.empty(r, dtype=torch.float64, device=dev)
+        out = _empty(r, dtype=torch.float64, device=dev)
         ws = _kmeans_workspace(x, r, k) if ws is None else ws
         rc = _lib.load().rgcn_kmeans_inertia(_ptr(x), m, x.size(1), _ptr(centers), r, k, _ptr(labels), _ptr(out), _ptr(ws),
                                              ws.numel(), _stream())
@@ -2324,10 +2327,10 @@ def kmeans(x: torch.Tensor, k: int, *, init: Optional[torch.Tensor] = None, n_in
     with _on(dev):
         centers = kmeans_plusplus(x, k, n_init, seed) if init is None else init.to(device=dev, dtype=torch.float32).clone().contiguous()
         tol_abs = float(tol) * float(x.var(dim=0, unbiased=False).mean())
-        labels = torch.full((n_init, m), -1, dtype=torch.int32, device=dev)
-        num_changed, num_iter, done = (torch.zeros(n_init, dtype=torch.int32, device=dev) for _ in range(3))
-        counts = torch.zeros((n_init, k), dtype=torch.int32, device=dev)
-        shift2 = torch.zeros(n_init, dtype=torch.float32, device=dev)
+        labels = _empty((n_init, m), dtype=torch.int32, device=dev).fill_(-1)
+        num_changed, num_iter, done = (_empty(n_init, dtype=torch.int32, device=dev).zero_() for _ in range(3))
+        counts = _empty((n_init, k), dtype=torch.int32, device=dev).zero_()
+        shift2 = _empty(n_init, dtype=torch.float32, device=dev).zero_()
         ws = _kmeans_workspace(x, n_init, k)
         for it in range(max_iter):
             kmeans_assign(x, centers, labels, done, labels, num_changed, ws)
@@ -2335,7 +2338,7 @@ def kmeans(x: torch.Tensor, k: int, *, init: Optional[torch.Tensor] = None, n_in
             if (it + 1) % poll_every == 0 and bool(done.all()):
                 break
         # the labels that go with the final centroids (a restart stopped by `tol` has moved them once more)
-        kmeans_assign(x, centers, labels, None, labels, torch.zeros_like(num_changed), ws)
+        kmeans_assign(x, centers, labels, None, labels, _empty(n_init, dtype=torch.int32, device=dev).zero_(), ws)
         inertia_all = kmeans_inertia(x, centers, labels, ws)
         inertia = inertia_all.cpu().numpy()
         best = int(inertia.argmin())                                                   # the first of equal minima
@@ -2371,19 +2374,19 @@ def _silhouette(x: torch.Tensor, labels: torch.Tensor, k: int, slices: int = 0):
         pfirst = torch.cumsum(padded, 0) - padded                              # ... and among the padded ones
         slab = lab[order]
         dest = pfirst[slab] + (torch.arange(m, device=dev) - first[slab])
-        col_row = torch.full((mp,), -1, dtype=torch.int32, device=dev)
+        col_row = _empty((mp,), dtype=torch.int32, device=dev).fill_(-1)
         col_row[dest] = order.to(torch.int32)
-        xs = torch.zeros((mp, d), dtype=torch.float32, device=dev)
+        xs = _empty((mp, d), dtype=torch.float32, device=dev).zero_()
         xs[dest] = xc[order]
-        blk_cluster = torch.full((mp // 32,), -1, dtype=torch.int32, device=dev)
+        blk_cluster = _empty((mp // 32,), dtype=torch.int32, device=dev).fill_(-1)
         real = torch.repeat_interleave(torch.arange(k, dtype=torch.int32, device=dev), padded // 32)
         blk_cluster[:real.numel()] = real
         lab32, counts32 = lab.to(torch.int32), counts.to(torch.int32)
-        s = torch.empty(m, dtype=torch.float32, device=dev)
-        mean = torch.empty(1, dtype=torch.float64, device=dev)
+        s = _empty(m, dtype=torch.float32, device=dev)
+        mean = _empty(1, dtype=torch.float64, device=dev)
         lib = _lib.load()
         nbytes = int(lib.rgcn_silhouette_workspace_bytes(m, mp, k, slices))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _empty(nbytes, dtype=torch.uint8, device=dev)
         rc = lib.rgcn_silhouette_samples(_ptr(xc), _ptr(xs), _ptr(col_row), _ptr(blk_cluster), _ptr(counts32), _ptr(lab32),
                                          m, mp, d, k, slices, _ptr(s), _ptr(mean), _ptr(ws), nbytes, _stream())
     _lib.check(rc, "rgcn_silhouette_samples")
