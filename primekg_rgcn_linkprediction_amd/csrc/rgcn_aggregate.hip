@@ -169,23 +169,28 @@ __device__ inline void aggregate_block(
       }
     }
   }
+  // Lanes that write nothing (members and padding of a pack, lanes past the row end) stay to the end with a maximum
+  // of 0: rgcn_amax_publish wants the wave's lanes from 0 up to the last one with an item, not a subset with holes.
+  bool writes = live;
   if (has_packs) {                               // the runs of a pack meet in LDS; its leader adds them in slot order
     red[threadIdx.x] = acc;
     __syncthreads();
-    if (it.flags & (RGCN_ITEM_MEMBER | RGCN_ITEM_SKIP)) return;
-    const int followers = (it.flags >> RGCN_ITEM_FOLLOW_SHIFT) & (RGCN_PACK - 1);
-    for (int f = 1; f <= followers; ++f) f4add(acc, red[threadIdx.x + f * G]);
+    if (it.flags & (RGCN_ITEM_MEMBER | RGCN_ITEM_SKIP)) {
+      writes = false;
+    } else {
+      const int followers = (it.flags >> RGCN_ITEM_FOLLOW_SHIFT) & (RGCN_PACK - 1);
+      for (int f = 1; f <= followers; ++f) f4add(acc, red[threadIdx.x + f * G]);
+    }
   }
-  if (!live) return;
   float lmax = 0.f;
-  if (it.flags & RGCN_ITEM_FINAL) {
+  if (writes && (it.flags & RGCN_ITEM_FINAL)) {
     if (cnt) {  // mean: true division by max(1, segment size), as `sum / count` does
       const float c = cnt[it.dst];
       acc.x /= c; acc.y /= c; acc.z /= c; acc.w /= c;
     }
     *reinterpret_cast<float4*>(agg + (size_t)it.dst * d + c4) = acc;
     lmax = f4amax(acc);
-  } else {
+  } else if (writes) {
     *reinterpret_cast<float4*>(partial + (size_t)it.dst * d + c4) = acc;
   }
   if (amax_out) rgcn_amax_publish(amax_out, lmax, seen);

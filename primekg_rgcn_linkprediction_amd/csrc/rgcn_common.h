@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/rgcn_hip.h"
+#include "rgcn_plan.h"
 
 #define RGCN_HIP_TRY(expr)                       \
   do {                                           \
@@ -10,36 +11,9 @@
     if (err__ != hipSuccess) return RGCN_ERR_HIP; \
   } while (0)
 
-// Longest run of source rows one lane group sums sequentially.  At ~1 us per dependent
-// round trip and 8 rows in flight per group this bounds a work item to a few us, which is
-// what keeps a 25-50 us gather launch free of a straggler tail under Zipf-like degree skew.
-constexpr int RGCN_CHUNK = 64;
-// Fan-in of the levels above: partial rows are contiguous and a whole workgroup sums one run.
-constexpr int RGCN_CHUNK_UP = 512;
-constexpr int RGCN_MAX_LEVELS = 8;
+// The work plan's constants and item record live in rgcn_plan.h (plain host code, shared with the host check).
 // Edges of an item whose ids travel with the item (= rows a lane group keeps in flight).
 constexpr int RGCN_HEAD = 8;
-
-// One unit of aggregate work: sum source rows [begin, end) into row `dst`.
-//   level 0 : source rows are x[col[e]] for e in [begin, end)
-//   level>0 : source rows are partial[begin .. end) (contiguous)
-//   flags & RGCN_ITEM_FINAL : `dst` is a final segment row of agg (apply the mean divide), otherwise
-//             a row of the partial-sum workspace.
-// Level 0 only - packs: a segment longer than RGCN_CHUNK edges is cut into runs of RGCN_CHUNK, and
-// up to RGCN_PACK consecutive runs form a pack that sits in RGCN_PACK consecutive, RGCN_PACK-aligned
-// item slots - hence inside one gather workgroup for every row width - whose lane groups combine
-// their sums through LDS: the pack's first item (the leader) adds the `followers` after it in slot
-// order and writes ONE row (final if the whole segment is this pack, a partial row otherwise).
-//   RGCN_ITEM_PACK   : slot belongs to a pack (leader, member or padding)
-//   RGCN_ITEM_MEMBER : not the leader: contributes through LDS, writes nothing
-//   RGCN_ITEM_SKIP   : padding slot of a short pack: nothing to do
-//   bits 8..9        : leader only - number of members that follow (0..RGCN_PACK-1)
-struct rgcn_item {
-  int32_t begin, end, dst, flags;
-};
-constexpr int RGCN_PACK = 4;
-enum : int32_t { RGCN_ITEM_FINAL = 1, RGCN_ITEM_PACK = 2, RGCN_ITEM_MEMBER = 4, RGCN_ITEM_SKIP = 8 };
-constexpr int RGCN_ITEM_FOLLOW_SHIFT = 8;
 
 struct rgcn_csr {
   int32_t* rowptr = nullptr;  // [N*R+1]
@@ -80,8 +54,6 @@ struct rgcn_graph {
   rgcn_csr dir[2];  // [0] forward (dst,rel), [1] transposed (src,rel)
 };
 
-static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 // Device address of the current device's sticky index-error flag (distmult.hip; rgcn_index_error_fetch reads and
 // clears it) for kernels of other translation units that meet an id outside its table.  NULL if HIP fails.
 __attribute__((visibility("hidden"))) int* rgcn_index_error_flag();
@@ -107,7 +79,10 @@ static_assert(RGCN_AMAX_HEADS * RGCN_AMAX_HEAD_STRIDE == RGCN_AMAX_FLOATS && RGC
 
 #if defined(__HIPCC__)
 extern "C" __device__ unsigned __ockl_wfred_max_u32(unsigned);
-// called by any subset of a wave's lanes (the reduction runs over the active ones)
+// Called by lanes 0 .. k of a wave, for any k (a last wave that is not full) - NOT by a subset with holes: the DPP
+// reduction behind __ockl_wfred_max_u32 gathers a row of 16 lanes in the row's lane 0 and hands rows 1 and 3 on
+// through lanes 15 and 47, so a maximum held by a row whose lane 0, or whose neighbour's lane 15, has left is lost
+// (the gather at d = 4 published 1.64 for rows whose maximum was 7).  Lanes with nothing to report pass 0.
 // `seen`: what the slot showed when the wave started (rgcn_amax_peek) - read early so that the tail of a
 // wave does not wait for a dependent load; a stale value only costs an atomic that changes nothing
 __device__ inline unsigned rgcn_amax_peek(const unsigned* __restrict__ amax) {

@@ -566,14 +566,15 @@ class BucketedGraph:
 
     def arrays(self, transposed: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """Copies of (rowptr int32[N*R+1], col int32[E], perm int64[E], val float32) on the
-        device: val = cnt[N*R] (forward) or w_t[E] (transposed).  For parity tests."""
+        device: val = cnt[N*R] (forward; a weighted shard: its w[E]) or w_t[E] (transposed).  For parity tests."""
         lib = _L()
         nr, e = self.num_nodes * self.num_relations, self.num_edges
         with _on(self.device):
             rowptr = _empty(nr + 1, dtype=torch.int32, device=self.device)
             col = _empty(e, dtype=torch.int32, device=self.device)
             perm = _empty(e, dtype=torch.int64, device=self.device)
-            val = _empty(e if transposed else nr, dtype=torch.float32, device=self.device)
+            # rgcn_graph_export copies E floats out of a weighted structure, N * R out of a mean one
+            val = _empty(e if transposed or self.weighted_shard else nr, dtype=torch.float32, device=self.device)
             rc = lib.rgcn_graph_export(self.handle, int(transposed), _ptr(rowptr), _ptr(col), _ptr(perm),
                                        _ptr(val), _stream())
         _lib.check(rc, "rgcn_graph_export")

@@ -257,6 +257,51 @@ def test_gathers_fp16_table(d, monkeypatch):
     protocol(monkeypatch, [x], fn)
 
 
+@pytest.mark.parametrize("d", [4, 64, 264])
+def test_gathers_three_levels_deep(d, monkeypatch):
+    """the boundary graph of ``test_hub_levels.py`` (segments of 131,072 / 131,073 / 262,444 edges): the mean and the
+    weighted gather whose plan has a reduce level that reads what another reduce level wrote.  The workspace is exactly
+    ``num_partials * d`` floats, so a partial row written past the plan lands in a band; integer tables, so the rows are
+    also the exact segment sums."""
+    import hub_graphs as H
+    dev = need_gpu()
+    key, other, rel = H.boundary_edges()
+    lens = H.segment_lengths()
+    gen = torch.Generator().manual_seed(d)
+    w8 = (2 ** torch.randint(0, 4, key.shape, generator=gen)) * (2 * torch.randint(0, 2, key.shape, generator=gen) - 1)
+    weight = (w8.float() / 8).to(dev)
+    mean = ops.BucketedGraph(torch.stack([other, key]).to(dev), rel.to(dev), H.N, H.R)
+    weighted = ops.BucketedGraph.from_shard(key.to(dev), other.to(dev), rel.to(dev), H.N, H.N, H.R, edge_weight=weight)
+    assert mean.num_levels(False) == weighted.num_levels(False) == 3
+    assert mean.workspace_bytes(False, d) == weighted.workspace_bytes(False, d) == H.plan_partials(lens) * d * 4
+    table = H.int_table(d, 4, seed=d)
+    x = table.float().to(dev)
+    want_mean = H.mean_expected(key, other, rel, table).to(dev)
+    want_weighted = ((H.segment_matrix(key, other, rel, weight=w8) @ table.long()).float() / 8).view(H.N, -1).to(dev)
+
+    def fn(ctx):
+        out = {}
+        for name, g, want in (("mean", mean, want_mean), ("weighted", weighted, want_weighted)):
+            out[name] = ops.aggregate(g, x)
+            assert torch.equal(out[name], want)
+            am = ctx.amax(dev)
+            out[name, "amax"] = (ops.aggregate(g, x, amax_out=am), Amax(am))
+            given = ctx.empty(H.N, H.R * d, device=dev)
+            ops.aggregate(g, x, out=given)
+            out[name, "into out"] = given
+            agg, hubs = ops.aggregate_deferred(g, x)
+            assert hubs is None                                  # three levels: nothing is left to a transform
+            out[name, "not deferred"] = agg
+            if d % 8 == 0:
+                out[name, "fp16 table"] = ops.aggregate(g, x.half())
+        out["arrays of the weighted shard"] = weighted.arrays(False)          # val holds E weights, not N * R counts
+        return out
+
+    protocol(monkeypatch, [x, weight], fn)
+    mean.destroy()
+    weighted.destroy()
+
+
 @pytest.mark.parametrize("precision", ["fp32", "split", "half"])
 def test_deferred_parameter_gradient_tail_rides_in_the_gather(precision, monkeypatch):
     dev = need_gpu()
