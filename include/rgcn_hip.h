@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 32
+#define RGCN_ABI_VERSION 33
 
 enum {
   RGCN_OK = 0,

@@ -13,7 +13,7 @@ from ctypes import c_double, c_float, POINTER, c_char_p, c_int, c_int64, c_size_
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-ABI_VERSION = 32
+ABI_VERSION = 33
 LIB_NAME = "librgcn_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -179,6 +179,17 @@ CLUSTER_PROTOTYPES = {
     "rgcn_silhouette_samples": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, c_size_t, _P]),
 }
 
+# include/rgcn_tsne.h, one to one: t-SNE projection of embedding rows to the plane (csrc/tsne.hip; not part of
+# rgcn_hip.h, never forwarded by rgcn_sequence_run - an analysis call, outside any recorded Region)
+TSNE_PROTOTYPES = {
+    "rgcn_knn_refine": (c_int, [_P, _I64, _I64, _P, _I64, _P, _P, _P]),
+    "rgcn_tsne_affinities": (c_int, [_P, _I64, _I64, c_double, _P, _P, _P]),
+    "rgcn_tsne_workspace_bytes": (c_size_t, [_I64, _I64]),
+    "rgcn_tsne_gradient": (c_int, [_P, _I64, _P, _P, _P, _I64, c_float, _I64, c_int,       # layout, P, options
+                                   _P, _P, _P, _P, c_size_t, _P]),                         # outputs, workspace, stream
+    "rgcn_tsne_update": (c_int, [_P, _I64, c_float, c_float, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
+}
+
 _lib = None
 
 
@@ -200,7 +211,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise RGCNLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -27,6 +27,10 @@ pair, enumerated on the device (``ops.paths_topk``).
 ``cluster_analysis`` is ``visualize_embeddings.cluster_analysis`` (``src/visualize_embeddings.py:651-777``): per node
 type ``KMeans(n_clusters, n_init=10, random_state=42)`` and ``silhouette_score`` on that type's rows, the cluster sizes
 and members - ``ops.kmeans`` and ``ops.silhouette_score``, the table never leaves the device.
+
+``reduce_dimensions`` is ``visualize_embeddings.reduce_dimensions`` (``src/visualize_embeddings.py:176-236``): the
+optional node sample and ``TSNE(n_components=2, perplexity=min(30, n - 1), max_iter=1000)`` - ``ops.tsne``, with exact
+repulsion instead of scikit-learn's Barnes-Hut approximation.
 """
 from __future__ import annotations
 
@@ -34,6 +38,7 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
 import logging
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -199,3 +204,36 @@ def cluster_analysis(embeddings: Tensor, node_class: Tensor, class_names: Union[
         results[name] = {"labels": fit.labels.cpu(), "silhouette": float(silhouette), "cluster_sizes": fit.sizes.cpu(),
                          "members": members}
     return results
+
+
+def sample_indices(n: int, sample_size: Optional[int] = None, random_state: int = 42) -> np.ndarray:
+    """the reference's node sample: ``np.random.seed(random_state); np.random.choice(n, sample_size, replace=False)`` when
+    ``sample_size`` is given and below ``n``, else every node in order (a private ``RandomState``: the same draw, the
+    global generator left alone)"""
+    if sample_size and sample_size < n:
+        return np.random.RandomState(random_state).choice(n, size=int(sample_size), replace=False)
+    return np.arange(n)
+
+
+@torch.no_grad()
+def reduce_dimensions(embeddings: Tensor, method: str = "tsne", sample_size: Optional[int] = None, random_state: int = 42,
+                      return_result: bool = False, **tsne_kw):
+    """The 2-D projection of (a sample of) the embedding rows, on the device: ``(xy float32 [n, 2], sample_indices int64
+    [n])`` - the reference's ``embeddings_2d`` and ``sample_indices``.  ``method="tsne"``: ``ops.tsne`` at perplexity
+    ``min(30, n - 1)`` with ``seed=random_state``; ``tsne_kw`` goes to ``ops.tsne`` (``perplexity``, ``max_iter``, ``init``,
+    ``slices``, ...).  The default needs at least 32 rows: ``ops.tsne`` searches among ``k = min(n - 1, int(3 perplexity + 1))``
+    neighbours and requires ``perplexity < k``, so for ``n <= 31`` pass a ``perplexity`` below ``n - 1`` (scikit-learn, which only
+    asks for ``perplexity < n``, accepts ``n - 1`` there).  ``return_result``: ``(xy, sample_indices, ops.TSNEResult)``.  ``method="umap"`` is not built (the reference itself falls back to t-SNE when ``umap`` is missing)."""
+    if not isinstance(method, str) or method.lower() not in ("tsne", "umap"):
+        raise ValueError(f"Unknown method: {method}. Use 'tsne' or 'umap'")
+    if method.lower() == "umap":
+        raise NotImplementedError("method='umap' is not built: only method='tsne' runs on the device")
+    if embeddings.dim() != 2:
+        raise ValueError("embeddings must be [N, d]")
+    idx = sample_indices(embeddings.size(0), sample_size, random_state)
+    rows = embeddings.index_select(0, torch.as_tensor(idx, dtype=torch.int64, device=embeddings.device))
+    rows = rows.to(torch.float32).contiguous()
+    kw = {"perplexity": float(min(30, rows.size(0) - 1)), "seed": random_state}
+    kw.update(tsne_kw)
+    result = ops.tsne(rows, **kw)
+    return (result.y, idx, result) if return_result else (result.y, idx)

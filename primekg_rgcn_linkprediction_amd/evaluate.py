@@ -196,6 +196,14 @@ class ModelEvaluator:
                              "graphio.node_classes(mappings['idx2node'], num_nodes)[0])")
         return consumers.cluster_analysis(self.embeddings(), self.node_class, class_names, n_clusters, **kmeans_kw)
 
+    @torch.no_grad()
+    def reduce_dimensions(self, method: str = "tsne", sample_size: Optional[int] = None, random_state: int = 42, **tsne_kw):
+        """the 2-D t-SNE projection of (a sample of) the cached embeddings, on the device:
+        ``consumers.reduce_dimensions`` -> ``(xy float32 [n, 2], sample_indices [n])`` (and the ``ops.TSNEResult`` with
+        ``return_result=True``)"""
+        from . import consumers
+        return consumers.reduce_dimensions(self.embeddings(), method, sample_size, random_state, **tsne_kw)
+
     def compute_ranking_metrics(self, k_values: Sequence[int] = (10, 50), filtered: bool = False,
                                 type_constrained: bool = False, both_sides: bool = False) -> Dict:
         ranks = self.tail_ranks(filtered, type_constrained)

@@ -14,6 +14,7 @@ from __future__ import annotations
 import ctypes
 import os
 import pickle
+import time
 from collections import OrderedDict
 from typing import NamedTuple, Optional, Tuple
 
@@ -2408,6 +2409,327 @@ def silhouette_samples(x: torch.Tensor, labels: torch.Tensor, k: int, slices: in
 def silhouette_score(x: torch.Tensor, labels: torch.Tensor, k: int, slices: int = 0) -> float:
     """the mean of ``silhouette_samples``, summed on the device in a fixed order in double"""
     return float(_silhouette(x, labels, k, slices)[1])
+
+
+KNN_MAX_K = 127               # RGCN_KNN_MAX_K: k + 1 candidates per row from the top-k pass (TOPK_MAX_K = 128)
+TSNE_EXPLORATION_ITERS = 250  # scikit-learn's _EXPLORATION_MAX_ITER: the stage with early exaggeration
+TSNE_CHECK_EVERY = 50         # scikit-learn's _N_ITER_CHECK: convergence is looked at every so many iterations
+
+
+class TSNEResult(NamedTuple):
+    y: torch.Tensor           # float32 [M, 2]
+    kl_divergence: float      # of the last iteration (without exaggeration once stage two has run)
+    n_iter: int               # iterations performed
+
+
+def _rows_2d(name: str, x: torch.Tensor) -> None:
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if x.dim() != 2:
+        raise ValueError(f"{name} must be [M, d]")
+    if x.size(0) < 2:
+        raise ValueError(f"{name} must have at least 2 rows (M >= 2), got M = {x.size(0)}")
+    if x.size(0) >= 1 << 24:
+        raise ValueError(f"{name} must have fewer than 2^24 rows, got M = {x.size(0)}")
+
+
+def knn(x: torch.Tensor, k: int, slices: int = 0):
+    """The ``k`` nearest OTHER rows of every row of ``x`` (float32 ``[M, d]``, ``d % 32 == 0``) in squared Euclidean
+    distance: ``(ids int32 [M, k], sqdist float32 [M, k])``, every row ordered by ``(sqdist, id)`` ascending.  The
+    selection is the fused top-k pass (``distmult_topk_masked``) on mean-centred, augmented rows - queries
+    ``[xc_i, 1, 0 x 31]``, entities ``[xc_j, -|xc_j|^2 / 2, 0 x 31]``, so that descending score is ascending distance - asked
+    for ``k + 1`` candidates; ``rgcn_knn_refine`` drops the row itself (or, among more than ``k`` duplicates of it, the last
+    candidate), recomputes the distances from the differences (duplicates are at exactly 0) and orders the row.  Rows whose
+    distances differ by less than the fp32 rounding of the selection key (relative to ``|xc|^2``) may swap places at the
+    k-th position.  ``2 <= k + 1 <= min(M, 128)``."""
+    _rows_2d("x", x)
+    m, d = x.shape
+    if d == 0 or d % 32:
+        raise ValueError(f"the row width d must be a positive multiple of 32 (the matrix-core k-tile), got d = {d}")
+    k = int(k)
+    if not 1 <= k <= min(KNN_MAX_K, m - 1):
+        raise ValueError(f"k must be in [1, min(KNN_MAX_K = {KNN_MAX_K}, M - 1 = {m - 1})], got {k}")
+    _need_gpu("x", x, torch.float32)
+    dev = x.device
+    with _on(dev):
+        xc = (x - x.mean(dim=0, keepdim=True)).contiguous()
+        q = _empty((m, d + 32), dtype=torch.float32, device=dev).zero_()
+        e = _empty((m, d + 32), dtype=torch.float32, device=dev).zero_()
+        q[:, :d] = xc
+        q[:, d] = 1.0
+        e[:, :d] = xc
+        e[:, d] = (xc * xc).sum(dim=1) * -0.5
+        cand, _ = distmult_topk_masked(q, e, k + 1, slices=slices)
+        ids = _empty((m, k), dtype=torch.int32, device=dev)
+        sqdist = _empty((m, k), dtype=torch.float32, device=dev)
+        rc = _lib.load().rgcn_knn_refine(_ptr(xc), m, d, _ptr(cand), k, _ptr(ids), _ptr(sqdist), _stream())
+    _lib.check(rc, "rgcn_knn_refine")
+    return ids, sqdist
+
+
+def tsne_affinities(sqdist: torch.Tensor, perplexity: float):
+    """``(cond_p float32 [M, k], beta float32 [M])``: the conditional neighbour probabilities of every row at the given
+    perplexity - scikit-learn's ``_binary_search_perplexity`` in double, one wave per row (``rgcn_tsne_affinities``).
+    ``sqdist`` float32 ``[M, k]`` (``ops.knn``'s), ``2 <= k <= KNN_MAX_K``, ``0 < perplexity < k``."""
+    if not isinstance(sqdist, torch.Tensor):
+        raise TypeError("sqdist must be a torch.Tensor")
+    if sqdist.dim() != 2 or sqdist.size(0) < 1:
+        raise ValueError("sqdist must be [M, k] with M >= 1")
+    m, k = sqdist.shape
+    if not 2 <= k <= KNN_MAX_K:
+        raise ValueError(f"the number of neighbours k must be in [2, KNN_MAX_K = {KNN_MAX_K}], got {k}")
+    perplexity = float(perplexity)
+    if not 0.0 < perplexity < k:
+        raise ValueError(f"perplexity must be in (0, k = {k}), got {perplexity}")
+    _need_gpu("sqdist", sqdist, torch.float32)
+    dev = sqdist.device
+    with _on(dev):
+        cond_p = _empty((m, k), dtype=torch.float32, device=dev)
+        beta = _empty(m, dtype=torch.float32, device=dev)
+        rc = _lib.load().rgcn_tsne_affinities(_ptr(sqdist), m, k, perplexity, _ptr(cond_p), _ptr(beta), _stream())
+    _lib.check(rc, "rgcn_tsne_affinities")
+    return cond_p, beta
+
+
+def tsne_joint(ids: torch.Tensor, cond_p: torch.Tensor):
+    """The symmetric joint probabilities ``P = (C + C^T) / max(sum, eps)`` of the conditional ones ``C[i, ids[i, j]] =
+    cond_p[i, j]`` as CSR over the union pattern: ``(rowptr int32 [M + 1], col int32 [nnz] ascending per row, val float32
+    [nnz])``.  Runs once per projection and has no hot path: torch ops - the doubled coordinate list sorted by
+    ``row * M + col``, equal keys merged (at most two addends meet, in float64: no order to depend on), normalised by the
+    float64 sum."""
+    if not isinstance(ids, torch.Tensor) or not isinstance(cond_p, torch.Tensor):
+        raise TypeError("ids and cond_p must be torch.Tensors")
+    if ids.dim() != 2 or ids.shape != cond_p.shape or ids.dtype != torch.int32:
+        raise ValueError("ids int32 [M, k] and cond_p float32 [M, k] expected")
+    _need_gpu("ids", ids, torch.int32)
+    _need_gpu("cond_p", cond_p, torch.float32)
+    m, k = ids.shape
+    if m < 2 or m >= 1 << 24:
+        raise ValueError(f"2 <= M < 2^24 expected, got M = {m}")
+    dev = ids.device
+    with _on(dev):
+        rows = torch.arange(m, device=dev, dtype=torch.int64).view(-1, 1).expand(m, k).reshape(-1)
+        cols = ids.reshape(-1).to(torch.int64)
+        if int(cols.min()) < 0 or int(cols.max()) >= m:
+            raise ValueError(f"a neighbour id is outside [0, {m})")
+        keys = torch.cat([rows * m + cols, cols * m + rows])
+        vals = torch.cat([cond_p.reshape(-1), cond_p.reshape(-1)]).to(torch.float64)
+        keys, order = torch.sort(keys, stable=True)
+        uniq, inverse = torch.unique_consecutive(keys, return_inverse=True)
+        merged = torch.zeros(uniq.numel(), dtype=torch.float64, device=dev).index_add_(0, inverse, vals[order])
+        total = merged.sum().clamp_min(torch.finfo(torch.float64).eps)
+        val = _empty(uniq.numel(), dtype=torch.float32, device=dev).copy_(merged / total)
+        col = _empty(uniq.numel(), dtype=torch.int32, device=dev).copy_(uniq % m)
+        counts = torch.bincount(torch.div(uniq, m, rounding_mode="floor"), minlength=m)
+        rowptr = _empty(m + 1, dtype=torch.int32, device=dev).zero_()
+        rowptr[1:] = torch.cumsum(counts, 0)
+    return rowptr, col, val
+
+
+def _tsne_csr(m: int, rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, dev) -> int:
+    for name, t, dtype in (("rowptr", rowptr, torch.int32), ("col", col, torch.int32), ("val", val, torch.float32)):
+        _need_gpu(name, t, dtype)
+        if t.dim() != 1 or t.device != dev:
+            raise ValueError(f"{name} must be a vector on {dev}")
+    if rowptr.numel() != m + 1 or col.numel() != val.numel():
+        raise ValueError(f"rowptr [{m + 1}], col [nnz], val [nnz] expected")
+    if col.numel() >= 1 << 31:
+        raise ValueError("nnz must be below 2^31")
+    return col.numel()
+
+
+def tsne_workspace(m: int, slices: int, device) -> torch.Tensor:
+    nbytes = int(_lib.load().rgcn_tsne_workspace_bytes(int(m), int(slices)))
+    return _empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def tsne_gradient(y: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, exaggeration: float = 1.0,
+                  slices: int = 0, compute_error: bool = True, grad: Optional[torch.Tensor] = None,
+                  z: Optional[torch.Tensor] = None, kl: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
+    """One gradient of t-SNE's objective at the layout ``y`` (float32 ``[M, 2]``) against the symmetric CSR ``P``
+    (``tsne_joint``'s): ``(grad float32 [M, 2], z float64 [1], kl float64 [1])`` with ``q_ij = 1 / (1 + |y_i - y_j|^2)`` from
+    the differences, ``Z`` the sum over all ordered pairs, ``grad_i = 4 (exaggeration sum_j p_ij q_ij (y_i - y_j) - sum_j
+    q_ij^2 (y_i - y_j) / Z)`` - EXACT repulsion, O(M^2) - and ``kl`` the Kullback-Leibler divergence of ``exaggeration * P``
+    from ``Q`` (written only with ``compute_error``; a ``kl`` the caller passes in keeps its content otherwise).
+    ``slices``: workgroups per 256-row tile (0: chosen from M); the same bits on every call for a given value."""
+    _rows_2d("y", y)
+    if y.size(1) != 2:
+        raise ValueError(f"n_components must be 2: y must be [M, 2], got [M, {y.size(1)}]")
+    slices, exaggeration = int(slices), float(exaggeration)
+    if slices < 0:
+        raise ValueError("slices must be >= 0 (0: chosen from the number of rows)")
+    if not 0.0 < exaggeration < float("inf"):
+        raise ValueError(f"exaggeration must be positive and finite, got {exaggeration}")
+    _need_gpu("y", y, torch.float32)
+    m, dev = y.size(0), y.device
+    nnz = _tsne_csr(m, rowptr, col, val, dev)
+    for name, t, shape, dtype in (("grad", grad, (m, 2), torch.float32), ("z", z, (1,), torch.float64), ("kl", kl, (1,), torch.float64)):
+        if t is not None:
+            _need_gpu(name, t, dtype)
+            if t.shape != shape or t.device != dev:
+                raise ValueError(f"{name} must be {dtype} {list(shape)} on {dev}")
+    with _on(dev):
+        grad = _empty((m, 2), dtype=torch.float32, device=dev) if grad is None else grad
+        z = _empty(1, dtype=torch.float64, device=dev) if z is None else z
+        kl = _empty(1, dtype=torch.float64, device=dev).zero_() if kl is None else kl
+        lib = _lib.load()
+        need = int(lib.rgcn_tsne_workspace_bytes(m, slices))
+        ws = _empty(need, dtype=torch.uint8, device=dev) if ws is None else ws
+        rc = lib.rgcn_tsne_gradient(_ptr(y), m, _ptr(rowptr), _ptr(col), _ptr(val), nnz, exaggeration, slices,
+                                    int(bool(compute_error)), _ptr(grad), _ptr(z), _ptr(kl), _ptr(ws), ws.numel(), _stream())
+    _lib.check(rc, "rgcn_tsne_gradient")
+    return grad, z, kl
+
+
+def tsne_update(grad: torch.Tensor, y: torch.Tensor, update: torch.Tensor, gains: torch.Tensor, momentum: float,
+                learning_rate: float, min_gain: float = 0.01, grad_norm2: Optional[torch.Tensor] = None,
+                ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One step of scikit-learn's ``_gradient_descent`` (``rgcn_tsne_update``), IN PLACE on ``y``, ``update`` and
+    ``gains`` (float32 ``[M, 2]``): gains ``+ 0.2`` where ``update * grad < 0`` and ``* 0.8`` elsewhere, at least
+    ``min_gain``; ``update = momentum * update - learning_rate * grad * gains``; ``y += update``.  -> ``grad_norm2``
+    float64 ``[1]``, the squared norm of ``grad * gains``."""
+    _rows_2d("y", y)
+    if y.size(1) != 2:
+        raise ValueError(f"n_components must be 2: y must be [M, 2], got [M, {y.size(1)}]")
+    m, dev = y.size(0), y.device
+    for name, t in (("grad", grad), ("y", y), ("update", update), ("gains", gains)):
+        _need_gpu(name, t, torch.float32)
+        if t.shape != (m, 2) or t.device != dev:
+            raise ValueError(f"{name} must be float32 [{m}, 2] on {dev}")
+    momentum, learning_rate, min_gain = float(momentum), float(learning_rate), float(min_gain)
+    if momentum != momentum or learning_rate != learning_rate or min_gain != min_gain:
+        raise ValueError("momentum, learning_rate and min_gain must not be NaN")
+    with _on(dev):
+        if grad_norm2 is None:
+            grad_norm2 = _empty(1, dtype=torch.float64, device=dev)
+        else:
+            _need_gpu("grad_norm2", grad_norm2, torch.float64)
+        ws = tsne_workspace(m, 1, dev) if ws is None else ws
+        rc = _lib.load().rgcn_tsne_update(_ptr(grad), m, momentum, learning_rate, min_gain, _ptr(y), _ptr(update),
+                                          _ptr(gains), _ptr(grad_norm2), _ptr(ws), ws.numel(), _stream())
+    _lib.check(rc, "rgcn_tsne_update")
+    return grad_norm2
+
+
+def tsne_pca_init(x: torch.Tensor) -> torch.Tensor:
+    """scikit-learn's ``init="pca"``: the rows centred, the two leading principal axes from the float64 covariance
+    (``eigh``), each flipped so that its largest-magnitude loading is positive, the projection cast to float32 and scaled
+    to ``std(first column) = 1e-4``"""
+    xc = x.to(torch.float64)
+    xc = xc - xc.mean(dim=0, keepdim=True)
+    cov = xc.t() @ xc / max(x.size(0) - 1, 1)
+    _, vec = torch.linalg.eigh(cov)
+    comp = vec[:, -2:].flip(1).t().contiguous()                               # [2, d], leading axis first
+    big = comp.abs().argmax(dim=1)
+    comp = comp * torch.sign(comp[torch.arange(2, device=comp.device), big]).view(2, 1)
+    y = (xc @ comp.t()).to(torch.float32)
+    return (y / y[:, 0].std(unbiased=False) * 1e-4).contiguous()
+
+
+def tsne(x: torch.Tensor, *, n_components: int = 2, perplexity: float = 30.0, max_iter: int = 1000,
+         early_exaggeration: float = 12.0, learning_rate="auto", init="pca", seed: int = 42,
+         n_iter_without_progress: int = 300, min_grad_norm: float = 1e-7, slices: int = 0,
+         timings: Optional[dict] = None) -> TSNEResult:
+    """t-SNE of the rows of ``x`` (float32 ``[M, d]``, ``d % 32 == 0``) to the plane, on the device - the reference's
+    ``TSNE(n_components=2, random_state=42, perplexity=min(30, n - 1), max_iter=1000)`` along scikit-learn's driver:
+    ``k = min(M - 1, int(3 perplexity + 1))`` neighbours (``knn``), conditional then joint probabilities
+    (``tsne_affinities``, ``tsne_joint``), ``learning_rate="auto"`` = ``max(M / early_exaggeration / 4, 50)``, 250
+    iterations with early exaggeration and momentum 0.5, the rest without and with momentum 0.8; every
+    ``TSNE_CHECK_EVERY`` iterations (and on the last) the error is computed and read back - the only host read-back -
+    and the run stops after ``n_iter_without_progress`` iterations without a new best error or at a gradient norm
+    ``<= min_grad_norm``.  ``init``: ``"pca"`` (``tsne_pca_init``), ``"random"`` (``1e-4 *`` a normal draw from a CPU
+    ``torch.Generator(seed)``) or an ``[M, 2]`` tensor.  ``timings``: a dict that receives the seconds of the stages
+    (``neighbours``, ``affinities``, ``init``, ``iterations``), each closed by a device synchronisation.
+
+    What differs from scikit-learn's default: the repulsion is EXACT (its ``angle = 0``; the default is Barnes-Hut at
+    0.5, whose final KL is a little higher) and costs O(M^2) per iteration; the layout, gains and update are float32;
+    ``n_iter`` counts the iterations performed (scikit-learn reports the last index); the random start is torch's
+    draw, not numpy's.  The same inputs give the same bits on every call.  Bad shapes and ranges raise ``ValueError`` by
+    name; a CPU tensor raises the package's ``RuntimeError`` ("no CPU fallback"), as every wrapper here does."""
+    if int(n_components) != 2:
+        raise ValueError(f"n_components must be 2 (the kernels are written for the plane), got {n_components}")
+    _rows_2d("x", x)
+    m, d = x.shape
+    if d == 0 or d % 32:
+        raise ValueError(f"the row width d must be a positive multiple of 32 (the matrix-core k-tile), got d = {d}")
+    perplexity, max_iter, slices = float(perplexity), int(max_iter), int(slices)
+    k = min(m - 1, int(3.0 * perplexity + 1))
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"k = min(M - 1, int(3 * perplexity + 1)) must be in [1, KNN_MAX_K = {KNN_MAX_K}], got {k}")
+    if not 0.0 < perplexity < k:
+        raise ValueError(f"perplexity must be in (0, k = {k}) (k = min(M - 1, int(3 * perplexity + 1))), got {perplexity}")
+    if max_iter < 1:
+        raise ValueError(f"max_iter must be >= 1, got {max_iter}")
+    if not float(early_exaggeration) >= 1.0:
+        raise ValueError(f"early_exaggeration must be >= 1, got {early_exaggeration}")
+    if slices < 0:
+        raise ValueError("slices must be >= 0 (0: chosen from the number of rows)")
+    if learning_rate == "auto":
+        lr = max(m / float(early_exaggeration) / 4.0, 50.0)
+    else:
+        lr = float(learning_rate)
+        if not lr > 0.0:
+            raise ValueError(f"learning_rate must be 'auto' or positive, got {learning_rate}")
+    if isinstance(init, torch.Tensor):
+        if init.shape != (m, 2):
+            raise ValueError(f"init must be 'pca', 'random' or an [M, 2] = [{m}, 2] tensor")
+    elif init not in ("pca", "random"):
+        raise ValueError(f"init must be 'pca', 'random' or an [M, 2] tensor, got {init!r}")
+    _need_gpu("x", x, torch.float32)
+    dev = x.device
+    clock = [time.perf_counter()]
+
+    def lap(stage):
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            clock.append(time.perf_counter())
+            timings[stage] = clock[-1] - clock[-2]
+
+    with _on(dev):
+        ids, sqdist = knn(x, k)
+        lap("neighbours")
+        cond_p, _ = tsne_affinities(sqdist, perplexity)
+        rowptr, col, val = tsne_joint(ids, cond_p)
+        lap("affinities")
+        y = _empty((m, 2), dtype=torch.float32, device=dev)
+        if isinstance(init, torch.Tensor):
+            y.copy_(init)
+        elif init == "pca":
+            y.copy_(tsne_pca_init(x))
+        else:
+            gen = torch.Generator().manual_seed(int(seed))
+            y.copy_(torch.randn(m, 2, generator=gen, dtype=torch.float32) * 1e-4)
+        lap("init")
+        update = _empty((m, 2), dtype=torch.float32, device=dev).zero_()
+        gains = _empty((m, 2), dtype=torch.float32, device=dev).fill_(1.0)
+        grad = _empty((m, 2), dtype=torch.float32, device=dev)
+        z = _empty(1, dtype=torch.float64, device=dev)
+        stats = _empty(2, dtype=torch.float64, device=dev).zero_()             # kl, grad_norm2: read back together
+        ws = tsne_workspace(m, slices, dev)
+        explore = min(TSNE_EXPLORATION_ITERS, max_iter)
+        stages = [(explore, float(early_exaggeration), 0.5, TSNE_EXPLORATION_ITERS),
+                  (max_iter, 1.0, 0.8, int(n_iter_without_progress))]
+        error, norm2, it = float("nan"), float("inf"), 0
+        for last, exaggeration, momentum, patience in stages:
+            first = it                                                        # stage one may have stopped early
+            best_error, best_iter = float("inf"), first
+            for i in range(first, last):
+                check = (i + 1) % TSNE_CHECK_EVERY == 0
+                want_error = check or i == last - 1
+                tsne_gradient(y, rowptr, col, val, exaggeration, slices, want_error, grad, z, stats[0:1], ws)
+                tsne_update(grad, y, update, gains, momentum, lr, 0.01, stats[1:2], ws)
+                it = i + 1
+                if want_error:
+                    error, norm2 = stats.cpu().tolist()
+                if check:
+                    if error < best_error:
+                        best_error, best_iter = error, i
+                    elif i - best_iter > patience:
+                        break
+                    if norm2 ** 0.5 <= float(min_grad_norm):
+                        break
+        lap("iterations")
+    return TSNEResult(y, float(error), it)
 
 
 def distmult_score_all_tails(head: torch.Tensor, rel: torch.Tensor, rel_idx: Optional[torch.Tensor],

@@ -1,0 +1,413 @@
+"""CPU tier of the t-SNE projection (``csrc/tsne.hip``, ``include/rgcn_tsne.h``): the C surface and every argument check
+that runs before a launch, the Python wrappers' checks by name, the float64 restatement (``tsne_reference.py``) the GPU
+tier holds the device to against scikit-learn's private helpers, the CLI's parser and JSON shape on a stubbed evaluator,
+``reduce_dimensions``' sampling, and the recorded whole-run fixture (``golden/tsne_blobs300.json``)."""
+import argparse
+import ctypes
+import functools
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import tsne_reference as R
+from conftest import ROOT
+from primekg_rgcn_linkprediction_amd import _lib, consumers, evaluate, ops
+from primekg_rgcn_linkprediction_amd import project as P
+
+NAMES = ["rgcn_knn_refine", "rgcn_tsne_affinities", "rgcn_tsne_gradient", "rgcn_tsne_update", "rgcn_tsne_workspace_bytes"]
+GOLDEN = os.path.join(ROOT, "tests", "golden", "tsne_blobs300.json")
+
+
+# ---------------------------------------------------------------------------------- C surface
+def _declared(header):
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+    found = re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", text)
+    return {name: [" ".join(p.split()) for p in params.split(",")] for name, params in found}
+
+
+def _kind_in_header(param):
+    if "*" in param:
+        return "pointer"
+    return next(k for k in ("float", "double", "size_t", "int64_t", "int") if re.search(rf"\b{k}\b", param))
+
+
+def _kind_in_ctypes(ty):
+    kinds = {ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_size_t: "size_t", ctypes.c_int64: "int64_t",
+             ctypes.c_int: "int"}
+    if ty in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ty, ctypes._Pointer):
+        return "pointer"
+    return kinds[ty]
+
+
+def test_tsne_header_table_and_library_agree():
+    declared = _declared("rgcn_tsne.h")
+    assert sorted(declared) == sorted(_lib.TSNE_PROTOTYPES) == NAMES
+    lib = _lib.load()
+    others = (_lib.PROTOTYPES, _lib.SAMPLING_PROTOTYPES, _lib.PATHS_PROTOTYPES, _lib.CLUSTER_PROTOTYPES, _lib.SEQ_FUNCTIONS)
+    for name, params in declared.items():
+        restype, argtypes = _lib.TSNE_PROTOTYPES[name]
+        assert restype is (ctypes.c_size_t if name.endswith("_bytes") else ctypes.c_int) and len(argtypes) == len(params), name
+        for i, (param, ty) in enumerate(zip(params, argtypes)):
+            assert _kind_in_ctypes(ty) == _kind_in_header(param), f"{name}: parameter {i} ({param})"
+        assert hasattr(lib, name) and getattr(lib, name).argtypes == argtypes
+        assert not any(name in table for table in others)
+    main_header = open(os.path.join(ROOT, "include", "rgcn_hip.h")).read()
+    assert "rgcn_tsne" not in main_header and "rgcn_knn" not in main_header
+    assert f"#define RGCN_ABI_VERSION {_lib.ABI_VERSION}\n" in main_header and lib.rgcn_abi_version() == _lib.ABI_VERSION >= 33
+    for other in ("rgcn_sampling.h", "rgcn_paths.h", "rgcn_cluster.h"):
+        assert not set(declared) & set(_declared(other))
+    text = open(os.path.join(ROOT, "include", "rgcn_tsne.h")).read()
+    assert '#include "rgcn_hip.h"' in text
+    assert f"#define RGCN_KNN_MAX_K {ops.KNN_MAX_K}\n" in text and ops.KNN_MAX_K + 1 == ops.TOPK_MAX_K
+    assert "angle = 0" in text and "O(M^2)" in text               # what differs from scikit-learn's default, and the cost
+
+
+def test_tsne_header_is_plain_c(tmp_path):
+    import shutil
+    import subprocess
+    if shutil.which("gcc") is None:
+        pytest.skip("no gcc")
+    src = tmp_path / "c.c"
+    src.write_text('#include "include/rgcn_tsne.h"\nint main(void) { return RGCN_KNN_MAX_K == 127 ? RGCN_OK : 1; }\n')
+    for cc, std, lang in (("gcc", "-std=c99", "c"), ("g++", "-std=c++17", "c++")):
+        subprocess.run([cc, std, "-Wall", "-Wextra", "-pedantic", "-fsyntax-only", "-x", lang, "-I", ROOT, str(src)], check=True)
+
+
+def test_tsne_entry_points_reject_bad_arguments_without_a_gpu():
+    lib = _lib.load()
+    A, U = _lib.RGCN_ERR_ARG, _lib.RGCN_ERR_UNSUPPORTED
+    big = 1 << 24
+
+    # rgcn_knn_refine(x, M, d, cand, k, ids, sqdist, stream)
+    def refine(m=700, d=128, k=91, x=8, cand=8, ids=8, sqdist=8):
+        return lib.rgcn_knn_refine(x, m, d, cand, k, ids, sqdist, None)
+
+    assert refine(m=1) == A and refine(m=0) == A and refine(d=0) == A and refine(d=-4) == A and refine(k=0) == A
+    assert refine(m=91) == A and refine(m=3, k=3) == A                          # k + 1 <= M
+    assert refine(d=6) == U and refine(k=ops.KNN_MAX_K + 1) == U and refine(m=big) == U
+    for hole in ("x", "cand", "ids", "sqdist"):
+        assert refine(**{hole: None}) == A, hole
+
+    # rgcn_tsne_affinities(sqdist, M, k, perplexity, cond_p, beta, stream)
+    def aff(m=700, k=91, perp=30.0, sqdist=8, cond_p=8, beta=8):
+        return lib.rgcn_tsne_affinities(sqdist, m, k, perp, cond_p, beta, None)
+
+    assert aff(m=0) == A and aff(k=1) == A and aff(perp=0.0) == A and aff(perp=-1.0) == A and aff(perp=91.0) == A
+    assert aff(perp=float("nan")) == A and aff(k=2, perp=2.0) == A
+    assert aff(k=ops.KNN_MAX_K + 1) == U and aff(m=big) == U
+    for hole in ("sqdist", "cond_p", "beta"):
+        assert aff(**{hole: None}) == A, hole
+
+    size = lib.rgcn_tsne_workspace_bytes
+    need = size(700, 0)
+    assert need > 0 and size(700, 1) < size(700, 2) < size(700, 3) == size(700, 7) == size(700, 1000)   # three column tiles
+    assert size(700, 0) == size(700, 3) and size(70000, 0) > 0 and size(2, 0) > 0
+    assert size(30926, 0) == size(30926, 9) < size(30926, 64) == size(30926, 100)     # about four workgroups per CU; the cap
+    for bad in ((1, 0), (0, 0), (big, 0), (700, -1)):
+        assert size(*bad) == 0, bad
+
+    # rgcn_tsne_gradient(y, M, rowptr, col, val, nnz, exaggeration, slices, compute_error, grad, z, kl, ws, ws_bytes, stream)
+    arrays = ("y", "rowptr", "col", "val", "grad", "z", "kl")
+
+    def grad(m=700, nnz=5000, ex=1.0, slices=0, err=1, ws=8, ws_bytes=need, **holes):
+        p = {name: 8 for name in arrays}
+        p.update(holes)
+        return lib.rgcn_tsne_gradient(p["y"], m, p["rowptr"], p["col"], p["val"], nnz, ex, slices, err, p["grad"], p["z"], p["kl"],
+                                      ws, ws_bytes, None)
+
+    assert grad(m=1) == A and grad(nnz=-1) == A and grad(slices=-1) == A
+    assert grad(ex=0.0) == A and grad(ex=-1.0) == A and grad(ex=float("nan")) == A and grad(ex=float("inf")) == A
+    assert grad(m=big) == U and grad(nnz=1 << 31) == U
+    for name in arrays:
+        assert grad(**{name: None}) == A, name
+    assert grad(ws=None) == A and grad(ws_bytes=need - 1) == A and grad(ws_bytes=0) == A
+    assert grad(slices=2, ws_bytes=size(700, 2) - 1) == A and grad(slices=1, ws_bytes=size(700, 1) - 1) == A
+
+    # rgcn_tsne_update(grad, M, momentum, learning_rate, min_gain, y, update, gains, grad_norm2, ws, ws_bytes, stream)
+    uarrays = ("grad", "y", "update", "gains", "norm")
+
+    def upd(m=700, momentum=0.5, lr=50.0, min_gain=0.01, ws=8, ws_bytes=size(700, 1), **holes):
+        p = {name: 8 for name in uarrays}
+        p.update(holes)
+        return lib.rgcn_tsne_update(p["grad"], m, momentum, lr, min_gain, p["y"], p["update"], p["gains"], p["norm"], ws, ws_bytes, None)
+
+    assert upd(m=1) == A and upd(m=big) == U
+    for kw in ({"momentum": float("nan")}, {"lr": float("nan")}, {"min_gain": float("nan")}):
+        assert upd(**kw) == A, kw
+    for name in uarrays:
+        assert upd(**{name: None}) == A, name
+    assert upd(ws=None) == A and upd(ws_bytes=0) == A and upd(ws_bytes=8) == A
+
+
+# ---------------------------------------------------------------------------------- the wrappers
+def test_python_wrappers_raise_by_name_and_have_no_cpu_path():
+    x = torch.zeros(40, 32)
+    for bad_x, what in ((torch.zeros(1, 32), "M >= 2"), (torch.zeros(40, 48), "multiple of 32"), (torch.zeros(40, 0), "multiple of 32"),
+                        (torch.zeros(40), r"\[M, d\]")):
+        with pytest.raises(ValueError, match=what):
+            ops.knn(bad_x, 1)
+        with pytest.raises(ValueError, match=what):
+            ops.tsne(bad_x, perplexity=5.0)
+    for k in (0, -1, 40, ops.KNN_MAX_K + 1):
+        with pytest.raises(ValueError, match="KNN_MAX_K"):
+            ops.knn(x, k)
+    with pytest.raises(ValueError, match="KNN_MAX_K"):
+        ops.tsne(torch.zeros(700, 32), perplexity=50.0)            # k = 151
+    with pytest.raises(ValueError, match="perplexity"):
+        ops.tsne(x, perplexity=39.0)                               # k = M - 1 = 39
+    with pytest.raises(ValueError, match="perplexity"):
+        ops.tsne(x, perplexity=0.0)
+    with pytest.raises(ValueError, match="n_components"):
+        ops.tsne(x, n_components=3)
+    for kw, what in (({"max_iter": 0}, "max_iter"), ({"slices": -1}, "slices"), ({"init": "spectral"}, "init"),
+                     ({"init": torch.zeros(40, 3)}, "init"), ({"learning_rate": -1.0}, "learning_rate"),
+                     ({"early_exaggeration": 0.5}, "early_exaggeration")):
+        with pytest.raises(ValueError, match=what):
+            ops.tsne(x, perplexity=5.0, **kw)
+    with pytest.raises(TypeError):
+        ops.knn([[0.0] * 32] * 4, 2)
+    d2 = torch.zeros(40, 16)
+    for perp in (0.0, 16.0, 17.0, float("nan")):
+        with pytest.raises(ValueError, match="perplexity"):
+            ops.tsne_affinities(d2, perp)
+    with pytest.raises(ValueError, match="KNN_MAX_K"):
+        ops.tsne_affinities(torch.zeros(40, 1), 0.5)
+    with pytest.raises(ValueError, match="KNN_MAX_K"):
+        ops.tsne_affinities(torch.zeros(40, 128), 30.0)
+    with pytest.raises(ValueError, match="int32"):
+        ops.tsne_joint(torch.zeros(40, 16, dtype=torch.int64), d2)
+    y = torch.zeros(40, 2)
+    csr = (torch.zeros(41, dtype=torch.int32), torch.zeros(0, dtype=torch.int32), torch.zeros(0))
+    with pytest.raises(ValueError, match="n_components"):
+        ops.tsne_gradient(torch.zeros(40, 3), *csr)
+    with pytest.raises(ValueError, match="slices"):
+        ops.tsne_gradient(y, *csr, slices=-1)
+    with pytest.raises(ValueError, match="exaggeration"):
+        ops.tsne_gradient(y, *csr, exaggeration=0.0)
+    with pytest.raises(ValueError, match="n_components"):
+        ops.tsne_update(torch.zeros(40, 3), torch.zeros(40, 3), torch.zeros(40, 3), torch.zeros(40, 3), 0.5, 50.0)
+    # CPU tensors: every range check came first; then there is no CPU path
+    for call in (lambda: ops.knn(x, 3), lambda: ops.tsne(x, perplexity=5.0), lambda: ops.tsne_affinities(d2, 5.0),
+                 lambda: ops.tsne_joint(torch.zeros(40, 16, dtype=torch.int32), d2), lambda: ops.tsne_gradient(y, *csr),
+                 lambda: ops.tsne_update(y, y.clone(), y.clone(), y.clone(), 0.5, 50.0),
+                 lambda: consumers.reduce_dimensions(x, perplexity=5.0)):
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            call()
+    with pytest.raises(NotImplementedError, match="umap"):
+        consumers.reduce_dimensions(x, method="umap")
+    with pytest.raises(ValueError, match="Unknown method"):
+        consumers.reduce_dimensions(x, method="pca")
+    assert "reduce_dimensions" in dir(evaluate.ModelEvaluator)
+    assert ops.TSNEResult._fields == ("y", "kl_divergence", "n_iter")
+    assert "O(M^2)" in ops.tsne.__doc__ and "angle = 0" in ops.tsne.__doc__
+
+
+def test_reduce_dimensions_draws_the_references_sample():
+    for n, size, seed in ((1000, 200, 42), (1000, 999, 7), (50, 10, 0)):
+        np.random.seed(seed)
+        want = np.random.choice(n, size=size, replace=False)
+        state = np.random.get_state()[1].copy()
+        got = consumers.sample_indices(n, size, seed)
+        assert np.array_equal(got, want) and len(set(got.tolist())) == size
+        assert np.array_equal(np.random.get_state()[1], state)                 # the global generator is left alone
+    for size in (None, 0, 1000, 2000):
+        assert np.array_equal(consumers.sample_indices(1000, size, 42), np.arange(1000))
+
+
+# ---------------------------------------------------------------------------------- the restatement against scikit-learn
+@functools.lru_cache(maxsize=None)
+def _pipeline(m, seed):
+    """rows, perplexity, the restatement's neighbours and joint P, and scikit-learn's P on the same rows"""
+    from sklearn.manifold import _t_sne
+    from sklearn.neighbors import NearestNeighbors
+    x = R.blobs(m, 32, seed=seed)
+    perplexity, k = 30.0, 91
+    ids, d2 = R.knn(x, k)
+    cond_p, _, margin, steps = R.binary_search(d2.astype(np.float32), perplexity)
+    p = R.joint(ids, cond_p)
+    graph = NearestNeighbors(n_neighbors=k).fit(x.astype(np.float64)).kneighbors_graph(mode="distance")
+    graph.data **= 2
+    theirs = _t_sne._joint_probabilities_nn(graph, perplexity, 0)
+    return x, ids, d2, p, theirs, margin, steps
+
+
+@pytest.mark.parametrize("m,seed", [(600, 5), (300, 11)])
+def test_restated_affinities_are_scikit_learns(m, seed):
+    """P against ``_joint_probabilities_nn``: both search and sum in double, so the gate is double rounding - 1e-14 of the
+    largest entry covers the sums of <= 2 k M terms (measured: 4e-16)"""
+    pytest.importorskip("sklearn")
+    x, ids, d2, (rowptr, col, val), theirs, margin, steps = _pipeline(m, seed)
+    mine = R.dense(rowptr, col, val, m)
+    dense = np.asarray(theirs.todense())
+    err = np.abs(mine - dense).max() / dense.max()
+    print(f"P: {err:.2e} of the largest entry; closest stop decision {margin:.2e}; steps <= {steps.max()}")
+    assert err <= 1e-14 and np.array_equal(mine != 0, dense != 0)
+    assert margin > 1e-9                                           # no decision of the search was near its threshold
+    assert np.array_equal(mine, mine.T) and abs(val.sum() - 1.0) <= 1e-12
+    assert all(np.all(np.diff(col[rowptr[i]:rowptr[i + 1]]) > 0) for i in range(m))
+    # the neighbours themselves: ascending (distance, id), never the row itself
+    assert (np.diff(d2, axis=1) >= 0).all() and not (ids == np.arange(m)[:, None]).any()
+
+
+@pytest.mark.parametrize("scale", [1e-4, 1.0, 10.0])
+def test_restated_gradient_is_scikit_learns_exact_one(scale):
+    """gradient, Z (through KL) and KL against ``_kl_divergence_bh(angle=0.0)``, which is fp32 inside.  Gradient: the gate
+    is 4 x what fp32 costs the restatement itself on these inputs (measured: about 1e-6 of the largest entry), at least
+    1e-6.  KL: the helper adds its nnz terms into a single-precision sum - a random walk of nnz roundings of 2^-24 of
+    the running total each, sqrt(nnz) 2^-24 = 1e-5 relative here - so the gate is 4 x that (measured: 2e-6 .. 2.5e-5
+    relative); the restatement's own fp32 variant sums in double and is held to a tenth of it."""
+    pytest.importorskip("sklearn")
+    from scipy.sparse import csr_matrix
+    from sklearn.manifold import _t_sne
+    m = 300
+    _, _, _, (rowptr, col, val), _, _, _ = _pipeline(m, 11)
+    y = (np.random.default_rng(int(scale * 1e4) % 1000).normal(size=(m, 2)) * scale).astype(np.float32)
+    sparse = csr_matrix((val.astype(np.float32), col, rowptr), shape=(m, m))
+    for ex in (1.0, 12.0):
+        sp = sparse * np.float32(ex)
+        kl, grad = _t_sne._kl_divergence_bh(y.ravel(), sp, 1.0, m, 2, angle=0.0, compute_error=True)
+        g64, z64, kl64 = R.gradient(y, rowptr, col, val, ex)
+        g32, z32, kl32 = R.gradient(y, rowptr, col, val, ex, np.float32)
+        top = np.abs(g64).max()
+        cost = np.abs(g32.astype(np.float64) - g64).max() / top
+        err = np.abs(grad.reshape(m, 2) - g64).max() / top
+        print(f"scale {scale:g}, exaggeration {ex:g}: scikit-learn {err:.2e}, fp32 restatement {cost:.2e} of the largest entry; "
+              f"KL {kl:.6f} / {kl64:.6f}; Z fp32 {abs(z32 - z64) / z64:.2e}")
+        assert err <= max(4 * cost, 1e-6)
+        walk = len(val) ** 0.5 * 2.0 ** -24 * abs(kl64)
+        assert abs(kl - kl64) <= 4 * walk and abs(kl32 - kl64) <= 0.4 * walk
+        assert R.gradient(y, rowptr, col, val, ex, compute_error=False)[2] is None
+
+
+def test_restated_update_is_scikit_learns_gradient_descent():
+    """two steps of ``_gradient_descent`` with a recorded objective: the first from zero updates (every gain shrinks),
+    the second with both signs of ``update * grad``"""
+    pytest.importorskip("sklearn")
+    from sklearn.manifold import _t_sne
+    rng = np.random.default_rng(3)
+    m = 50
+    y0 = rng.normal(size=(m, 2))
+    grads = [rng.normal(size=(m, 2)), rng.normal(size=(m, 2))]
+    calls = []
+
+    def objective(p, compute_error=True):
+        calls.append(p.copy())
+        return 0.5, grads[len(calls) - 1].ravel().copy()
+
+    p, _, it = _t_sne._gradient_descent(objective, y0.ravel().copy(), 0, 2, n_iter_check=50, momentum=0.8, learning_rate=50.0,
+                                        min_gain=0.01, kwargs={})
+    y, upd, gains = y0, np.zeros_like(y0), np.ones_like(y0)
+    for step in range(2):
+        assert np.array_equal(calls[step].reshape(m, 2), y)
+        y, upd, gains, norm2 = R.update(grads[step], y, upd, gains, 0.8, 50.0)
+    assert it == 1 and np.array_equal(p.reshape(m, 2), y)
+    assert set(np.unique(gains).round(6)) == {0.64, 0.8 + 0.2}     # 0.8 * 0.8 and 0.8 + 0.2: both branches ran
+    assert norm2 == pytest.approx(((grads[1] * gains) ** 2).sum(), rel=1e-12)
+    # a product of exactly 0 is "not inc", a gain never falls below min_gain
+    _, _, g, _ = R.update(np.array([[0.0, 1.0]]), np.zeros((1, 2)), np.array([[0.0, -1.0]]), np.array([[0.005, 1.0]]), 0.5, 1.0)
+    assert np.array_equal(g, [[0.01, 1.2]])
+
+
+def test_restated_pca_init_and_trustworthiness_are_scikit_learns():
+    pytest.importorskip("sklearn")
+    from sklearn.decomposition import PCA
+    from sklearn.manifold import trustworthiness
+    x = R.blobs(300, 32, seed=11)
+    theirs = PCA(n_components=2, svd_solver="full").fit_transform(x.astype(np.float64)).astype(np.float32)
+    theirs = theirs / np.std(theirs[:, 0]) * 1e-4
+    mine = R.pca_init(x)
+    # float64 projections that agree to ~1e-15 can still round to neighbouring float32 values: two float32 ulps of the largest
+    assert mine.dtype == np.float32 and np.abs(mine - theirs).max() <= 2 * np.spacing(np.abs(theirs).max())
+    assert np.std(mine[:, 0]) == pytest.approx(1e-4, rel=1e-5)
+    on_torch = ops.tsne_pca_init(torch.from_numpy(x)).numpy()
+    assert np.abs(on_torch - mine).max() <= 2 * np.spacing(np.abs(mine).max())
+    rng = np.random.default_rng(0)
+    for y, n in ((rng.normal(size=(300, 2)), 10), (x[:, :2].astype(np.float64), 5), (x[:, :2].astype(np.float64), 10)):
+        assert R.trustworthiness(x, y, n) == pytest.approx(trustworthiness(x.astype(np.float64), y, n_neighbors=n), abs=1e-12)
+
+
+# ---------------------------------------------------------------------------------- the recorded fixture
+def test_the_float64_restatement_reproduces_its_recorded_run():
+    """``make_tsne_golden.py``'s setting, re-run: the recorded pair itself, to 1e-9 relative.  The run is chaotic under
+    rounding but has nothing to round differently: from the float32 start on it is elementwise ``+ - * /`` and numpy's own
+    pairwise sums (no BLAS, no ``exp``); the library calls before it - the covariance product and ``eigh`` of the PCA start,
+    ``exp`` in the perplexity search - end in a cast to float32 that absorbs their last bits (the start and the
+    conditional probabilities are float32 arrays); ``log`` only enters the reported KL, to 1e-16.  A wrong stage switch,
+    momentum or patience in ``run`` moves KL by percents.  The four-run spread is the GPU tier's gate, not this one's."""
+    golden = json.load(open(GOLDEN))
+    s = golden["setting"]
+    x = R.blobs(s["m"], s["d"], seed=s["seed"])
+    p = R.affinities(x, s["perplexity"])
+    y, kl, n_iter = R.run(p, R.pca_init(x), s["max_iter"])
+    trust = R.trustworthiness(x, y, s["trust_neighbors"])
+    kls = [r["kl"] for r in golden["runs"].values()]
+    trusts = [r["trustworthiness"] for r in golden["runs"].values()]
+    print(f"float64 restatement: KL {kl:.6f} (recorded {golden['runs']['restatement_float64']['kl']:.6f}), "
+          f"trustworthiness {trust:.6f} (recorded {golden['runs']['restatement_float64']['trustworthiness']:.6f})")
+    assert n_iter == s["max_iter"]
+    assert kl == pytest.approx(golden["runs"]["restatement_float64"]["kl"], rel=1e-9, abs=0)
+    assert trust == pytest.approx(golden["runs"]["restatement_float64"]["trustworthiness"], rel=1e-9, abs=0)
+    assert set(golden["runs"]) == {"restatement_float64", "restatement_float32", "sklearn_angle_0", "sklearn_angle_0.5"}
+    assert golden["random_layout"]["kl"] > max(kls) + 10 * (max(kls) - min(kls))
+    assert golden["random_layout"]["trustworthiness"] < min(trusts) - 10 * (max(trusts) - min(trusts))
+    assert os.path.getsize(GOLDEN) < 2048
+
+
+# ---------------------------------------------------------------------------------- project.py
+class _StubEvaluator:
+    """``reduce_dimensions`` from fixed coordinates, on the CPU"""
+    num_nodes = 120
+
+    def __init__(self):
+        self.calls = []
+
+    def reduce_dimensions(self, method="tsne", sample_size=None, random_state=42, return_result=False, **kw):
+        self.calls.append((method, sample_size, random_state, dict(kw)))
+        idx = consumers.sample_indices(self.num_nodes, sample_size, random_state)
+        xy = torch.stack([torch.as_tensor(idx, dtype=torch.float32), -torch.as_tensor(idx, dtype=torch.float32)], 1)
+        kw["timings"].update(neighbours=0.25, affinities=0.125, init=0.0625, iterations=1.5)
+        return xy, idx, ops.TSNEResult(xy, 0.75, kw["max_iter"])
+
+
+def test_project_cli_flags_and_files_on_a_stubbed_evaluator(tmp_path):
+    base = ["--model_path", "m.pt"]
+    args = P.parse_args(base)
+    assert (args.sample_size, args.perplexity, args.max_iter, args.seed, args.init) == (None, 30.0, 1000, 42, "pca")
+    assert args.data_dir == "data/processed" and args.output_dir == "results/embeddings" and args.node_types is None
+    args = P.parse_args(base + ["--sample_size", "40", "--perplexity", "12.5", "--max_iter", "300", "--seed", "7", "--init", "random",
+                                "--node_types", "types.npz"])
+    assert (args.sample_size, args.perplexity, args.max_iter, args.seed, args.init) == (40, 12.5, 300, 7, "random")
+    for bad in (["--sample_size", "1"], ["--perplexity", "0"], ["--max_iter", "0"], ["--init", "spectral"], ["--max_iter", "x"]):
+        with pytest.raises(SystemExit):
+            P.parse_args(base + bad)
+    with pytest.raises(SystemExit):
+        P.parse_args([])                                           # --model_path is required
+    ev = _StubEvaluator()
+    node_class = torch.arange(120, dtype=torch.int32) % 5
+    arrays, summary = P.project(ev, args, node_class)
+    method, size, seed, kw = ev.calls[0]
+    assert (method, size, seed) == ("tsne", 40, 7) and kw["perplexity"] == 12.5 and kw["max_iter"] == 300 and kw["init"] == "random"
+    want = consumers.sample_indices(120, 40, 7)
+    assert np.array_equal(arrays["indices"], want) and arrays["indices"].dtype == np.int64
+    assert arrays["xy"].shape == (40, 2) and arrays["xy"].dtype == np.float32 and np.array_equal(arrays["xy"][:, 0], want)
+    assert np.array_equal(arrays["node_class"], node_class.numpy()[want]) and arrays["node_class"].dtype == np.int32
+    assert set(summary) == {"protocol", "kl_divergence", "n_iter", "num_points", "seconds"}
+    assert summary["kl_divergence"] == 0.75 and summary["n_iter"] == 300 and summary["num_points"] == 40
+    assert set(summary["seconds"]) == {"neighbours", "affinities", "init", "iterations", "total"} and summary["seconds"]["iterations"] == 1.5
+    assert {"method", "n_components", "perplexity", "max_iter", "seed", "init", "sample_size", "repulsion"} <= set(summary["protocol"])
+    assert summary["protocol"]["n_components"] == 2 and "exact" in summary["protocol"]["repulsion"]
+    # perplexity is capped at n - 1, as the reference does
+    small = P.parse_args(base + ["--sample_size", "20"])
+    _, capped = P.project(ev, small, None)
+    assert capped["protocol"]["perplexity"] == 19.0 and ev.calls[-1][3]["perplexity"] == 19.0
+    points, path = P.save(arrays, summary, tmp_path / "out")
+    assert points.name == "embedding_2d.npz" and path.name == "projection_summary.json" and json.loads(path.read_text()) == summary
+    with np.load(points) as z:
+        assert sorted(z.files) == ["indices", "node_class", "xy"] and np.array_equal(z["xy"], arrays["xy"])
+    plain, _ = P.project(ev, args, None)
+    assert sorted(plain) == ["indices", "xy"]
+    assert isinstance(P.parse_args(base), argparse.Namespace)
