@@ -19,6 +19,40 @@
  *    Nothing aborts the process.
  *  - feature dims must be multiples of 4 floats (16-byte rows); fp32 throughout
  *    ("within 1e-5 fp32 of PyG RGCNConv", BASELINE.json north_star).
+ *
+ * Non-finite values (the training path: gathers, transforms, fused layers, basis composition, the
+ * DistMult / BCE head, clip + Adam; the analysis kernels state their own rules).  NaN and +-inf are
+ * data: they index nothing and no entry point rejects them.  Against a float64 restatement of the same
+ * operation (tests/nonfinite_reference.py, enforced by tests/test_nonfinite.py):
+ *   1. an entry of an output or gradient that is non-finite under SPARSE semantics - an empty
+ *      (row, relation) segment contributes nothing, even against a NaN weight - is non-finite here;
+ *   2. an entry that is finite under DENSE IEEE semantics (0 * NaN = NaN, what PyG's dense
+ *      `h @ weight[r]` computes) is finite here when no operand tensor holds an infinity, and keeps
+ *      the accuracy the kernel has on finite data;
+ *   3. between the two sets - an empty segment against a non-finite weight, or in a parameter gradient
+ *      against a non-finite cotangent row, where a relation-occupancy mask may or may not skip the
+ *      0 * w product - an entry may come out either way;
+ *   4. the fp32 kernels are IEEE: called without a relation-occupancy mask (no empty segments) their
+ *      non-finite set is the dense set exactly, infinities included; with a mask, rules 1-3;
+ *   5. split / half arithmetic does not tell NaN and +-inf apart (the lo part of an infinity is
+ *      inf - inf); an infinite entry in an operand tensor sets that tensor's scale to 1, after which
+ *      finite entries may be over-poisoned or lose accuracy: only rule 1 holds then;
+ *   6. the fused ReLU keeps NaN: relu(NaN) = NaN, relu(+inf) = +inf, relu(-inf) = 0, and every
+ *      non-NaN input has the bits of fmaxf(v, 0.f) (-0 included);
+ *   7. the ReLU and dropout masks of the backward epilogues are selects: a position whose mask entry
+ *      is not > 0 (a NaN activation included) is exactly 0 whatever the cotangent holds, so a NaN
+ *      activation passes no gradient (torch multiplies by the mask and would pass the NaN on);
+ *   8. a published maximum (amax_out, the maxima rgcn_adam_clip_step leaves) is never NaN and never
+ *      below the largest finite |entry| of its tensor; NaN entries do not count, an infinite one does.
+ *      The operand maxima behind the split scales ignore NaN for the same reason;
+ *   9. rgcn_adam_clip_step has the finite / non-finite pattern of clip_grad_norm_ + torch.optim.Adam /
+ *      AdamW in params, exp_avg and exp_avg_sq (a NaN total norm is a NaN clip coefficient and poisons
+ *      every parameter, as in torch); total_norm is non-finite exactly when torch's is; max_norm <= 0
+ *      clips nothing, so only the entries of non-finite gradients go bad;
+ *  10. distmult_fwd, distmult_bce_fwd, distmult_bce_bwd, distmult_bce_reduce, distmult_bwd and
+ *      rgcn_segment_sum are plain fp32 arithmetic: their non-finite sets are float64's entry by entry,
+ *      rows no sample touches stay exact zeros, and the mean loss is non-finite exactly when a score
+ *      of the batch is.
  */
 #ifndef RGCN_HIP_H
 #define RGCN_HIP_H

@@ -91,7 +91,8 @@ __global__ __launch_bounds__(kThreads) void k_adam_update(const AdamList L, cons
     float s = 0.f;
     for (int i = threadIdx.x; i < num_partials; i += kThreads) s += partial[i];
     const float total = sqrtf(block_sum(s, red));
-    coef = fminf(max_norm / (total + 1e-6f), 1.f);
+    const float c = max_norm / (total + 1e-6f);
+    coef = c > 1.f ? 1.f : c;                    // torch.clamp(max=1): a NaN norm stays a NaN coefficient (fminf drops it)
     if (out_norm && blockIdx.x == 0 && threadIdx.x == 0) out_norm[0] = total;
   }
   const int t = tensor_of_block(L, blockIdx.x);

@@ -78,6 +78,13 @@ static_assert(RGCN_AMAX_HEADS * RGCN_AMAX_HEAD_STRIDE == RGCN_AMAX_FLOATS && RGC
               "amax buffer layout");
 
 #if defined(__HIPCC__)
+// The ReLU of every fused epilogue.  fmaxf returns its non-NaN operand, so fmaxf(NaN, 0) is 0 and a diverged
+// pre-activation would leave the layer looking healthy; torch.relu(NaN) is NaN.  The select puts the NaN back and
+// leaves every other input with the bits fmaxf(v, 0.f) gives it (-0 included; +inf stays +inf, -inf becomes 0).
+__device__ inline float rgcn_relu(float v) {
+  const float r = fmaxf(v, 0.f);
+  return v != v ? v : r;
+}
 extern "C" __device__ unsigned __ockl_wfred_max_u32(unsigned);
 // Called by lanes 0 .. k of a wave, for any k (a last wave that is not full) - NOT by a subset with holes: the DPP
 // reduction behind __ockl_wfred_max_u32 gathers a row of 16 lanes in the row's lane 0 and hands rows 1 and 3 on
@@ -88,8 +95,10 @@ extern "C" __device__ unsigned __ockl_wfred_max_u32(unsigned);
 __device__ inline unsigned rgcn_amax_peek(const unsigned* __restrict__ amax) {
   return amax ? amax[(blockIdx.x & (RGCN_AMAX_SLOTS - 1)) * RGCN_AMAX_STRIDE] : 0u;
 }
+// A lane whose values were all NaN arrives with a NaN maximum (fmaxf(NaN, NaN)); its bit pattern would win the integer
+// max and poison the buffer, so it reports 0 like a lane with nothing to report: a published maximum is never NaN.
 __device__ inline void rgcn_amax_publish(unsigned* __restrict__ amax, float lane_max, unsigned seen = 0u) {
-  const unsigned m = __ockl_wfred_max_u32(__float_as_uint(lane_max));
+  const unsigned m = __ockl_wfred_max_u32(__float_as_uint(fmaxf(lane_max, 0.f)));
   if (m <= seen) return;
   unsigned* slot = amax + (blockIdx.x & (RGCN_AMAX_SLOTS - 1)) * RGCN_AMAX_STRIDE;
   const unsigned long long act = __ballot(1);

@@ -312,7 +312,7 @@ __global__ __launch_bounds__(kThreads) void k_layer_fused(
       for (int r = 0; r < 16; ++r) {
         const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
         float v = acc[b][r] * ia * ib + bv;
-        if (EPI == 1) v = fmaxf(v, 0.f);
+        if (EPI == 1) v = rgcn_relu(v);
         if (EPI == 2) v = mk[b][r] > 0.f ? v : 0.f;
         if (m < N) {
           cmax = fmaxf(cmax, fabsf(v));

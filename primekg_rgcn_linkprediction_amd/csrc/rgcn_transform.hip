@@ -196,7 +196,7 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt(const float* __restrict__ 
         const int m = m0 + (wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
         if (m < M) {
           float v = acc[a][b][r] + bv;
-          if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
+          if (EPI == EPI_RELU) v = rgcn_relu(v);
           if (EPI == EPI_MASK) v = mask[(size_t)m * N + n] > 0.f ? v : 0.f;
           C[(size_t)m * N + n] = v;
         }
@@ -357,7 +357,7 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt_dma(const float* __restric
       for (int r = 0; r < 16; ++r) {
         const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
         float v = acc[b][r] + bv[b];
-        if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
+        if (EPI == EPI_RELU) v = rgcn_relu(v);
         if (EPI == EPI_MASK) v = mk[b][r] > 0.f ? v : 0.f;
         C[(size_t)m * N + n] = v;
       }
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt_dma(const float* __restric
       const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
       if (m < M) {
         float v = acc[b][r] + bv;
-        if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
+        if (EPI == EPI_RELU) v = rgcn_relu(v);
         if (EPI == EPI_MASK) v = mask[(size_t)m * N + n] > 0.f ? v : 0.f;
         C[(size_t)m * N + n] = v;
       }

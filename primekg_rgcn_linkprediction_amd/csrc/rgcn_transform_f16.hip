@@ -184,7 +184,7 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt_f16(const float* __restric
       for (int r = 0; r < 16; ++r) {
         const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
         float v = acc[b][r] + bv[b];
-        if (RELU) v = fmaxf(v, 0.f);
+        if (RELU) v = rgcn_relu(v);
         C[(size_t)m * N + n] = v;
       }
     }
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(kThreads) void k_gemm_nt_f16(const float* __restric
       const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
       if (m < M) {
         float v = acc[b][r] + bv;
-        if (RELU) v = fmaxf(v, 0.f);
+        if (RELU) v = rgcn_relu(v);
         C[(size_t)m * N + n] = v;
       }
     }

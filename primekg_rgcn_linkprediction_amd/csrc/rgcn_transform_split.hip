@@ -658,7 +658,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
       const float4 a = *reinterpret_cast<const float4*>(tr + (q * RPR + trow) * W + tc4);
       float4 v;
       v.x = a.x * ia * ib + bv4.x; v.y = a.y * ia * ib + bv4.y; v.z = a.z * ia * ib + bv4.z; v.w = a.w * ia * ib + bv4.w;
-      if (EPI == EPI_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+      if (EPI == EPI_RELU) { v.x = rgcn_relu(v.x); v.y = rgcn_relu(v.y); v.z = rgcn_relu(v.z); v.w = rgcn_relu(v.w); }
       if (EPI == EPI_MASK) {
         v.x = mk4[q].x > 0.f ? v.x : 0.f; v.y = mk4[q].y > 0.f ? v.y : 0.f;
         v.z = mk4[q].z > 0.f ? v.z : 0.f; v.w = mk4[q].w > 0.f ? v.w : 0.f;
@@ -677,7 +677,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
         const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
         if (m < M) {
           float v = acc[b][r] * ia * ib + bv;
-          if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
+          if (EPI == EPI_RELU) v = rgcn_relu(v);
           if (EPI == EPI_MASK) v = mask[(size_t)m * N + n] > 0.f ? v : 0.f;
           cmax = fmaxf(cmax, fabsf(v));
           C[(size_t)m * N + n] = v;
