@@ -1,9 +1,9 @@
 // K-means (Lloyd) and silhouette samples of embedding rows (include/rgcn_cluster.h; the reference's
 // visualize_embeddings.cluster_analysis: KMeans(n_init = 10) + silhouette_score per node type).
 //
-// Both matrix products go through the k-tile of k_gemm_nt_dma<2, B_BLK>, shared (rgcn_mma_f32_dma.h), and are walked
-// the way k_topk_select walks its entity range: a workgroup owns 64 rows and takes the (column tile, k-tile) pairs as
-// ONE stream through the three-buffer ring (walk_tiles below).  What differs is what happens to the 64 x 128
+// Both matrix products go through the k-tile of k_gemm_nt_dma<2, B_BLK> and the walk of k_topk_select over its entity
+// range, both shared (rgcn_mma_f32_dma.h): a workgroup owns 64 rows and takes the (column tile, k-tile) pairs as ONE
+// stream through the three-buffer ring (mma_f32_dma::walk_tiles).  What differs is what happens to the 64 x 128
 // accumulators after the last k-tile of a column tile:
 //   assignment  X . C^T   the centroids of all R restarts are the columns, every restart padded to a multiple of 32,
 //                         so a 32-column accumulator block belongs to one restart: key = |c|^2 - 2 acc, arg-min over
@@ -26,101 +26,18 @@
 
 namespace {
 
-using namespace mma_f32_dma;    // kThreads (256: 4 waves, 2 (m) x 2 (n)), BK, BM, NBUF, glds16, the vector types
+using namespace mma_f32_dma;    // kThreads (256: 4 waves, 2 (m) x 2 (n)), BK, BM, NBUF, walk_tiles, acc_row, the vector types
 
 typedef KTile<2, B_BLK> Tile;   // 64 x 128 outputs per workgroup
-constexpr int BN = Tile::BN, A_FLOATS = Tile::A_FLOATS, BUF_FLOATS = Tile::BUF_FLOATS;
-constexpr int A_PW = Tile::A_PW, B_PW = Tile::B_PW, P = Tile::P;
-constexpr int STAGE_BYTES = NBUF * BUF_FLOATS * 4;               // 73,728: the ring is the kernels' only LDS object
+constexpr int BN = Tile::BN;
+constexpr int STAGE_BYTES = NBUF * Tile::BUF_FLOATS * 4;         // 73,728: the ring is the kernels' only LDS object
 constexpr int kMaxK = RGCN_CLUSTER_MAX_K;
 constexpr int kMaxSlices = 256;
-constexpr int kCUs = 256;       // MI355X
 constexpr int kNanBias = 1 << 20;   // id offset of a NaN key: behind every real id, in front of the pad columns
 constexpr int kPadId = 0x7fffffff;
 constexpr int kUpdCols = 128;   // columns (= threads) of an update workgroup
 constexpr int kUpdRows = 256;   // rows whose labels an update workgroup stages at a time
 constexpr int kInertiaRows = 256;
-
-// the row inside the wave's 32 that accumulator register r of lane half lh holds (v_mfma_f32_32x32x2_f32)
-__device__ __forceinline__ int acc_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
-
-// The shared walk: rows [m0, m0 + 64) of A against the column tiles [ct_begin, ct_end) of B (row n of the product's
-// columns is row brow(n) of B), k-tiles of 32 over d.  pre(ct) runs at the first k-tile of a column tile (loads that
-// the epilogue needs go out there, a column tile ahead of their use), epi(ct, acc) after its last.
-template <class BRow, class Pre, class Epi>
-__device__ __forceinline__ void walk_tiles(float* lds, const float* __restrict__ A, const float* __restrict__ B, int M,
-                                           int d, int m0, int ct_begin, int ct_end, int wave, int lane, Tile& tile,
-                                           BRow brow, Pre pre, Epi epi) {
-  floatx16 acc[2];
-#pragma unroll
-  for (int b = 0; b < 2; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-
-  // per-lane source offsets of the LDS-DMAs
-  size_t a_off[A_PW];
-#pragma unroll
-  for (int j = 0; j < A_PW; ++j) {
-    const int row = dma_row(wave * A_PW + j, lane);
-    const int m = min(m0 + row, M - 1);                        // rows past M read a valid row; never written
-    a_off[j] = (size_t)m * d + dma_col(row, lane);
-  }
-  int b_row[B_PW], b_chunk[B_PW];
-  size_t b_off[B_PW];
-#pragma unroll
-  for (int j = 0; j < B_PW; ++j) {
-    b_row[j] = dma_row(wave * B_PW + j, lane);
-    b_chunk[j] = dma_col(b_row[j], lane);
-    b_off[j] = 0;
-  }
-  int st_ct = ct_begin, st_kt = 0;                             // next k-tile to stage
-  auto stage_next = [&](int buf) {
-    if (st_kt == 0) {
-#pragma unroll
-      for (int j = 0; j < B_PW; ++j) b_off[j] = (size_t)brow(st_ct * BN + b_row[j]) * d + b_chunk[j];
-    }
-    float* sA = lds + buf * BUF_FLOATS;
-    float* sB = sA + A_FLOATS;
-#pragma unroll
-    for (int j = 0; j < A_PW; ++j) glds16(A + a_off[j] + st_kt, sA + (wave * A_PW + j) * 8 * BK);
-#pragma unroll
-    for (int j = 0; j < B_PW; ++j) glds16(B + b_off[j] + st_kt, sB + (wave * B_PW + j) * 8 * BK);
-    st_kt += BK;
-    if (st_kt >= d) { st_kt = 0; ++st_ct; }
-  };
-
-  const int KT = d / BK;
-  const int total = (ct_end - ct_begin) * KT;                  // k-tiles of the whole walk (>= 1: the host sizes the grid)
-  stage_next(0);
-  if (total > 1) stage_next(1);
-
-  int cur_ct = ct_begin, cur_kt = 0;                           // k-tile being multiplied
-  int buf = 0, buf2 = 2;                                       // ring slots of k-tile t and t + 2
-  for (int t = 0; t < total; ++t) {
-    // k-tile t landed for this wave (all but the newest P memory operations are done - the DMAs of k-tile t + 1, or
-    // younger ones), then for all waves; the barrier also says every wave is done reading the buffer staged next
-    if (t + 1 < total) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    const unsigned buf_bytes = Tile::buf_bytes(buf);
-    tile.read_first(buf_bytes);
-    if (cur_kt == 0) pre(cur_ct);
-    if (t + 2 < total) stage_next(buf2);
-    tile.finish(acc, buf_bytes);
-    buf = buf == NBUF - 1 ? 0 : buf + 1;
-    buf2 = buf2 == NBUF - 1 ? 0 : buf2 + 1;
-    cur_kt += BK;
-    if (cur_kt == d) {
-      epi(cur_ct, acc);
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-      cur_kt = 0;
-      ++cur_ct;
-    }
-  }
-}
 
 // |row|^2 of `rows` rows, one thread per row: an fmaf chain in the order in which the tile above takes the k of a
 // product (per 8 floats: 0, 4, 1, 5, 2, 6, 3, 7), so that |x_i|^2 and <x_i, x_j> of two equal rows agree as closely as
@@ -471,8 +388,6 @@ __global__ __launch_bounds__(256) void k_mean_double(const float* __restrict__ v
 }
 
 // ------------------------------------------------------------------------------------------ host side
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 inline int kmeans_shape_error(int64_t M, int64_t d, int64_t R, int64_t k) {
   if (M < 2 || d <= 0 || R < 1 || k < 2) return RGCN_ERR_ARG;
   if (d % BK || d > (1 << 20) || k > kMaxK || R > RGCN_CLUSTER_MAX_RESTARTS || M >= (1 << 30)) return RGCN_ERR_UNSUPPORTED;
@@ -504,18 +419,6 @@ inline KmeansPlan plan_kmeans(int64_t M, int64_t d, int64_t R, int64_t k) {
   return p;
 }
 
-// the ring is more than the 64 KB a launch may ask for by default: raised once per device and kernel
-template <class K>
-inline int raise_lds(K kernel, bool (&raised)[64]) {
-  int dev = 0;
-  RGCN_HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !raised[dev]) {
-    RGCN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, STAGE_BYTES));
-    if (dev >= 0 && dev < 64) raised[dev] = true;
-  }
-  return RGCN_OK;
-}
-
 struct SilPlan {
   int num_tiles, tiles_per_slice, slices;
   size_t o_xnorm, o_cnorm, o_s, s_bytes, bytes;
@@ -528,10 +431,9 @@ inline SilPlan plan_silhouette(int64_t M, int64_t Mp, int64_t k, int64_t slices)
   SilPlan p;
   p.num_tiles = (int)(Mp / BN);
   const int64_t row_tiles = ceil_div64(M, BM);
-  int64_t want = slices > 0 ? slices : ceil_div64(4 * kCUs, row_tiles);
-  want = std::max<int64_t>(1, std::min<int64_t>(want, std::min<int64_t>(p.num_tiles, kMaxSlices)));
-  p.tiles_per_slice = (int)ceil_div64(p.num_tiles, want);
-  p.slices = (int)ceil_div64(p.num_tiles, p.tiles_per_slice);   // no empty slice
+  const rgcn_slicing cut = rgcn_slice_tiles(p.num_tiles, slices > 0 ? slices : ceil_div64(4 * kCUs, row_tiles), kMaxSlices);
+  p.tiles_per_slice = cut.tiles_per_slice;
+  p.slices = cut.slices;
   size_t at = 0;
   p.o_xnorm = at; at += align256((size_t)M * 4);
   p.o_cnorm = at; at += align256((size_t)Mp * 4);
@@ -565,7 +467,7 @@ int rgcn_kmeans_assign(const float* x, int64_t M, int64_t d, const float* centro
   if (!ws || ws_bytes < p.bytes) return RGCN_ERR_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   static bool raised[64] = {};
-  const int rc = raise_lds(k_assign, raised);
+  const int rc = raise_lds(k_assign, STAGE_BYTES, raised);
   if (rc) return rc;
   char* w = (char*)ws;
   float* cnorm = (float*)(w + p.o_cnorm);
@@ -640,7 +542,7 @@ int rgcn_silhouette_samples(const float* x, const float* xs, const int32_t* col_
   if (!ws || ws_bytes < p.bytes) return RGCN_ERR_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   static bool raised[64] = {};
-  const int rc = raise_lds(k_silhouette, raised);
+  const int rc = raise_lds(k_silhouette, STAGE_BYTES, raised);
   if (rc) return rc;
   char* w = (char*)ws;
   float* xnorm = (float*)(w + p.o_xnorm);

@@ -7,6 +7,12 @@
 //                                   (k_gemm_nt_dma<2, B_BLK>) and the one k_topk_select keeps are the same bits
 //   counted     = n < N, n != target[m], score > true_score[m], allowed (allow[query_class[m]]), not excluded
 //                 (exclude[m]); the masks are bit rows, bit (n & 31) of word (n >> 5) - see rank_filter.hip
+//
+// A workgroup has ONE column tile, so the k loop below is the one-column-tile case of mma_f32_dma::walk_tiles
+// (rgcn_mma_f32_dma.h) written out: same wait, barrier, read_first, stage t + 2, finish - and a change to the wait
+// discipline there has to be made here too.  On the walk itself the kernel was measured 28 % slower (the raw launch
+// at B = 15,372, N = 30,926, d = 128: 1.645 -> 2.109 ms, profiles/tile_walk_shared.txt): there the epilogue sits
+// inside the loop, and the kernel came out at 186 VGPRs and 2,669 instructions against 150 and 2,399 here.
 #include "rgcn_common.h"
 #include "rgcn_mma_f32_dma.h"
 
@@ -94,7 +100,7 @@ __global__ __launch_bounds__(kThreads) void k_rank_count(const float* __restrict
   unsigned aoff[16];                     // first word of the row's allow row, kNoRow: nothing is allowed
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+    const int m = m0 + wm * 32 + acc_row(r, lh);
     const bool ok = m < M;
     ts[r] = ok ? true_score[m] : 0.f;
     const int64_t t64 = ok ? target[m] : -1;
@@ -113,14 +119,14 @@ __global__ __launch_bounds__(kThreads) void k_rank_count(const float* __restrict
     unsigned aw[16], ew[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+      const int m = m0 + wm * 32 + acc_row(r, lh);
       // only the lane that counts (li == 0 of each half) needs the words
       aw[r] = allow ? ((li == 0 && wok && aoff[r] != kNoRow) ? allow[aoff[r] + (unsigned)w] : 0u) : 0xffffffffu;
       ew[r] = (li == 0 && exclude && wok && m < M) ? exclude[(size_t)m * words + w] : 0u;
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+      const int m = m0 + wm * 32 + acc_row(r, lh);
       const unsigned long long hits = __ballot(m < M && n < N && n != tl[r] && acc[b][r] > ts[r]);
       if (li == 0 && m < M) {
         const unsigned mine = lh ? (unsigned)(hits >> 32) : (unsigned)hits;

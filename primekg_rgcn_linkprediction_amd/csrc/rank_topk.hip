@@ -11,7 +11,8 @@
 //
 // Select pass, grid (ceil(B / 64), S): a workgroup owns 64 query rows and walks the 128-column tiles of slice s of
 // the entity range, ids ascending.  The (column tile, k-tile) pairs form ONE stream through the three-buffer ring,
-// so the DMA pipeline never drains between column tiles.  After the last k-tile of a column tile the accumulators
+// so the DMA pipeline never drains between column tiles: the walk is mma_f32_dma::walk_tiles (rgcn_mma_f32_dma.h), the
+// mask-word loads its `pre`, the selection its `epi`.  After the last k-tile of a column tile the accumulators
 // are tested against the row's current k-th best score (one ballot per accumulator register, filtered by one mask
 // word per row and 32-column group exactly as k_rank_count does) and the survivors - about k ln(N / k) per row
 // over the whole walk - are inserted by the whole wave into the row's sorted list in LDS.
@@ -21,22 +22,18 @@
 // Merge pass, one workgroup per row: a k-round S-way merge of the row's slice lists by the total order.
 #include <math.h>
 
-#include <algorithm>
-
 #include "rgcn_common.h"
 #include "rgcn_mma_f32_dma.h"
 
 namespace {
 
-using namespace mma_f32_dma;    // kThreads (256: 4 waves, 2 (m) x 2 (n)), BK, BM, NBUF, glds16, the vector types
+using namespace mma_f32_dma;    // kThreads (256: 4 waves, 2 (m) x 2 (n)), BK, BM, NBUF, walk_tiles, acc_row, the vector types
 
 typedef KTile<2, B_BLK> Tile;   // 64 x 128 outputs per workgroup, B = embedding rows
-constexpr int BN = Tile::BN, A_FLOATS = Tile::A_FLOATS, BUF_FLOATS = Tile::BUF_FLOATS;
-constexpr int A_PW = Tile::A_PW, B_PW = Tile::B_PW, P = Tile::P;
+constexpr int BN = Tile::BN, BUF_FLOATS = Tile::BUF_FLOATS;
 constexpr int STAGE_BYTES = NBUF * BUF_FLOATS * 4;               // 73,728
 constexpr int kMaxK = 128;      // list length the select pass is built for (two entries per lane of the inserting wave)
 constexpr int kMaxSlices = 256; // one list per thread of the merge workgroup
-constexpr int kCUs = 256;       // MI355X
 
 // dynamic LDS of the select pass: [ring 73,728 B][thr f32 x 64][cnt i32 x 64][scores f32 x 64 k][ids i32 x 64 k]
 __host__ __device__ inline size_t select_lds_bytes(int k) { return (size_t)STAGE_BYTES + 2 * BM * 4 + (size_t)BM * k * 8; }
@@ -105,39 +102,7 @@ __global__ __launch_bounds__(kThreads) void k_topk_select(const float* __restric
     s_thr[tid] = __builtin_nanf("");
     s_cnt[tid] = 0;
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // landed before the first barrier of the k loop, which every epilogue follows
-
-  floatx16 acc[2];
-#pragma unroll
-  for (int b = 0; b < 2; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-
-  // per-lane source offsets of the LDS-DMAs
-  size_t a_off[A_PW];
-#pragma unroll
-  for (int j = 0; j < A_PW; ++j) {
-    const int row = dma_row(wave * A_PW + j, lane);
-    const int m = min(m0 + row, M - 1);                        // rows past M read a valid row; never selected
-    a_off[j] = (size_t)m * d + dma_col(row, lane);
-  }
-  int b_row[B_PW], b_chunk[B_PW];
-#pragma unroll
-  for (int j = 0; j < B_PW; ++j) {
-    b_row[j] = dma_row(wave * B_PW + j, lane);
-    b_chunk[j] = dma_col(b_row[j], lane);
-  }
-  auto stage = [&](int ct, int kt, int buf) {
-    float* sA = lds + buf * BUF_FLOATS;
-    float* sB = sA + A_FLOATS;
-#pragma unroll
-    for (int j = 0; j < A_PW; ++j) glds16(q + a_off[j] + kt, sA + (wave * A_PW + j) * 8 * BK);
-#pragma unroll
-    for (int j = 0; j < B_PW; ++j) {
-      const int n = min(ct * BN + b_row[j], N - 1);            // columns past N read a valid row; never selected
-      glds16(emb + (size_t)n * d + b_chunk[j] + kt, sB + (wave * B_PW + j) * 8 * BK);
-    }
-  };
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // landed before the first barrier of the walk, which every epilogue follows
 
   // this lane's mask row: lanes 0-31 carry the first 32-column group of the wave, lanes 32-63 the second.  The words
   // are loaded at the first k-tile of a column tile from addresses that are always valid and looked at only in the
@@ -158,11 +123,11 @@ __global__ __launch_bounds__(kThreads) void k_topk_select(const float* __restric
   // every lane tests its 32 scores against the rows' thresholds and keeps the outcomes as 32 bits.  Once the lists
   // are full almost every wave leaves here.  Otherwise the slow part walks the accumulator registers that have a hit
   // in a rolled loop (one copy of the insertion code): ballot, mask words, one insertion per surviving bit.
-  auto select = [&](int ct, unsigned okw) {
+  auto select = [&](int ct, floatx16 (&acc)[2], unsigned okw) {
     float thr[16];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(&s_thr[wm * 32 + 8 * g + 4 * lh]);
+      const f32x4 v = *reinterpret_cast<const f32x4*>(&s_thr[wm * 32 + acc_row(4 * g, lh)]);   // registers 4 g .. 4 g + 3
       thr[4 * g + 0] = v.x; thr[4 * g + 1] = v.y; thr[4 * g + 2] = v.z; thr[4 * g + 3] = v.w;
     }
     unsigned mybits = 0;                                       // bit b * 16 + r: acc[b][r] of this lane is a hit
@@ -171,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void k_topk_select(const float* __restric
       const bool nok = ct * BN + (wn * 2 + b) * 32 + li < N;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int m = m0 + wm * 32 + acc_row(r, lh);
         const float v = acc[b][r];
         const bool hit = nok & (m < M) & (v >= min_score) & !(v <= thr[r]);   // no short circuit: straight-line code
         mybits |= (unsigned)hit << (b * 16 + r);
@@ -185,7 +150,7 @@ __global__ __launch_bounds__(kThreads) void k_topk_select(const float* __restric
     while (anybits) {                                          // wave-uniform; registers in (b, r) order: ids ascend per row
       const int pb = __builtin_ctz(anybits);
       anybits &= anybits - 1;
-      const int b = pb >> 4, r = pb & 15, rl = (r & 3) + 8 * (r >> 2);
+      const int b = pb >> 4, r = pb & 15;
       const int nb = ct * BN + (wn * 2 + b) * 32;
       float v = 0.f;
       switch (pb) {
@@ -199,7 +164,7 @@ __global__ __launch_bounds__(kThreads) void k_topk_select(const float* __restric
       }
       const unsigned long long hits = __ballot((mybits >> pb) & 1u);
       for (int h = 0; h < 2; ++h) {
-        const int rowl = rl + 4 * h;                           // the row of this half inside the wave's 32
+        const int rowl = acc_row(r, h);                        // the row of this half inside the wave's 32
         const unsigned word = (unsigned)__builtin_amdgcn_readlane((int)okw, b * 32 + rowl);
         unsigned mine = (h ? (unsigned)(hits >> 32) : (unsigned)hits) & word;
         while (mine) {                                         // bits (= ids) ascending
@@ -213,59 +178,28 @@ __global__ __launch_bounds__(kThreads) void k_topk_select(const float* __restric
     }
   };
 
-  const int KT = d / BK;
-  const int total = (ct_end - ct_begin) * KT;                  // k-tiles of the whole walk (>= 1: the host sizes the grid)
-  int st_ct = ct_begin, st_kt = 0;                             // next k-tile to stage
-  auto stage_next = [&](int buf) {
-    stage(st_ct, st_kt, buf);
-    st_kt += BK;
-    if (st_kt >= d) { st_kt = 0; ++st_ct; }
-  };
-  stage_next(0);
-  if (total > 1) stage_next(1);
-
-  int cur_ct = ct_begin, cur_kt = 0;                           // k-tile being multiplied
-  int buf = 0, buf2 = 2;                                       // ring slots of k-tile t and t + 2
   unsigned aw_raw = 0xffffffffu, ew_raw = 0u;
-  for (int t = 0; t < total; ++t) {
-    // k-tile t landed for this wave (all but the newest P DMAs are done), then for all waves; the barrier also says
-    // every wave is done reading the buffer the next stage overwrites
-    if (t + 1 < total) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    const unsigned buf_bytes = Tile::buf_bytes(buf);
-    tile.read_first(buf_bytes);
-    if (cur_kt == 0) {
-      // the column tile's mask words, one (row, 32-column group) per lane, a column tile ahead of their use
-      const int w = min((cur_ct * BN + (wn * 2 + lh) * 32) >> 5, words - 1);
-      if (allow) aw_raw = arow_p[w];
-      if (excl) ew_raw = erow_p[w];
+  auto pre = [&](int ct) {
+    // the column tile's mask words, one (row, 32-column group) per lane, a column tile ahead of their use
+    const int w = min((ct * BN + (wn * 2 + lh) * 32) >> 5, words - 1);
+    if (allow) aw_raw = arow_p[w];
+    if (excl) ew_raw = erow_p[w];
+  };
+  auto epi = [&](int ct, floatx16 (&acc)[2]) {
+    // wave column 0 selects, then wave column 1: one stream of ascending ids per row.  Every wave passes exactly
+    // one barrier here; the list writes of the first are complete (lgkmcnt(0)) before it, and those of the second
+    // before the barrier that opens the next k-tile.
+    if (wn == 1) {
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
     }
-    if (t + 2 < total) stage_next(buf2);
-    tile.finish(acc, buf_bytes);
-    buf = buf == NBUF - 1 ? 0 : buf + 1;
-    buf2 = buf2 == NBUF - 1 ? 0 : buf2 + 1;
-    cur_kt += BK;
-    if (cur_kt == d) {
-      // wave column 0 selects, then wave column 1: one stream of ascending ids per row.  Every wave passes exactly
-      // one barrier here; the list writes of the first are complete (lgkmcnt(0)) before it, and those of the second
-      // before the barrier that opens the next k-tile.
-      if (wn == 1) {
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      }
-      // (a 32-column group wholly past N has no word of its own: its lanes fail the n < N test)
-      select(cur_ct, (allowed_row ? aw_raw : 0u) & ~ew_raw);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (wn == 0) __builtin_amdgcn_s_barrier();
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-      cur_kt = 0;
-      ++cur_ct;
-    }
-  }
+    // (a 32-column group wholly past N has no word of its own: its lanes fail the n < N test)
+    select(ct, acc, (allowed_row ? aw_raw : 0u) & ~ew_raw);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (wn == 0) __builtin_amdgcn_s_barrier();
+  };
+  // rows past M and columns past N read a valid row; never selected
+  walk_tiles(lds, q, emb, M, d, m0, ct_begin, ct_end, wave, lane, tile, [&](int n) { return min(n, N - 1); }, pre, epi);
   __syncthreads();
 
   // the lists of this slice -> workspace [B][S][k]; slots past a list's length carry id -1
@@ -356,10 +290,10 @@ inline TopkPlan plan_topk(int64_t batch, int64_t num_entities, int64_t slices) {
   TopkPlan p;
   p.num_tiles = (int)ceil_div64(num_entities, BN);
   const int64_t row_tiles = ceil_div64(batch, BM);
-  int64_t want = slices > 0 ? slices : (row_tiles >= kCUs / 2 ? 1 : ceil_div64(kCUs, row_tiles));
-  want = std::max<int64_t>(1, std::min<int64_t>(want, std::min<int64_t>(p.num_tiles, kMaxSlices)));
-  p.tiles_per_slice = (int)ceil_div64(p.num_tiles, want);
-  p.slices = (int)ceil_div64(p.num_tiles, p.tiles_per_slice);   // no empty slice
+  const int64_t want = slices > 0 ? slices : (row_tiles >= kCUs / 2 ? 1 : ceil_div64(kCUs, row_tiles));
+  const rgcn_slicing cut = rgcn_slice_tiles(p.num_tiles, want, kMaxSlices);
+  p.tiles_per_slice = cut.tiles_per_slice;
+  p.slices = cut.slices;
   return p;
 }
 
@@ -390,15 +324,9 @@ int distmult_topk_masked(const float* q, const float* emb, const uint32_t* allow
   hipStream_t stream = (hipStream_t)stream_;
   const TopkPlan p = plan_topk(batch, num_entities, slices);
   const size_t lds_bytes = select_lds_bytes((int)k);
-  // more than the 64 KB a launch may ask for by default: raised once per device (not a stream operation)
   static bool raised[64] = {};
-  int dev = 0;
-  RGCN_HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !raised[dev]) {
-    RGCN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_topk_select), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)select_lds_bytes(kMaxK)));
-    if (dev >= 0 && dev < 64) raised[dev] = true;
-  }
+  const int rc = raise_lds(k_topk_select, (int)select_lds_bytes(kMaxK), raised);
+  if (rc) return rc;
   float* ws_score = (float*)workspace;
   int* ws_id = (int*)(ws_score + (size_t)batch * p.slices * k);
   dim3 grid((unsigned)ceil_div64(batch, BM), (unsigned)p.slices);

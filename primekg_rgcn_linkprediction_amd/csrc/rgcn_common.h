@@ -11,6 +11,41 @@
     if (err__ != hipSuccess) return RGCN_ERR_HIP; \
   } while (0)
 
+// ---------------------------------------------------------------------------------------------
+// Host scaffolding of the launches, one copy each.
+// ---------------------------------------------------------------------------------------------
+constexpr int kCUs = 256;       // MI355X
+
+// workspace sections start on 256-byte boundaries
+static inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// The slice rule of the kernels that walk a range of column tiles (top-k select, silhouette, t-SNE repulsion): `tiles`
+// tiles cut into at most min(want, cap) slices of equal length, the last one shorter, none empty.  `want` is what the
+// caller was asked for or, for "choose yourself", its own default - the defaults differ on measured grounds.
+struct rgcn_slicing {
+  int tiles_per_slice, slices;
+};
+static inline rgcn_slicing rgcn_slice_tiles(int64_t tiles, int64_t want, int64_t cap) {
+  const int64_t most = tiles < cap ? tiles : cap;
+  want = want < most ? want : most;
+  want = want > 1 ? want : 1;
+  const int64_t per = (tiles + want - 1) / want;
+  return {(int)per, (int)((tiles + per - 1) / per)};
+}
+
+// A launch may ask for 64 KB of dynamic LDS by default and the three-buffer ring of the fp32 k-tile is more: the limit
+// of `kernel` is raised to `bytes` once per device (`raised`: the caller's static flags; not a stream operation).
+template <class K>
+static inline int raise_lds(K kernel, int bytes, bool (&raised)[64]) {
+  int dev = 0;
+  RGCN_HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64 || !raised[dev]) {
+    RGCN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    if (dev >= 0 && dev < 64) raised[dev] = true;
+  }
+  return RGCN_OK;
+}
+
 // The work plan's constants and item record live in rgcn_plan.h (plain host code, shared with the host check).
 // Edges of an item whose ids travel with the item (= rows a lane group keeps in flight).
 constexpr int RGCN_HEAD = 8;

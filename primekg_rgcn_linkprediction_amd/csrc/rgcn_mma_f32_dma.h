@@ -1,13 +1,18 @@
-// The fp32 LDS-DMA k-tile: ONE definition of what k_gemm_nt_dma (rgcn_transform.hip), k_rank_count (rank_count.hip)
-// and k_topk_select (rank_topk.hip) do with a staged 64 x (64 TN) x 32 tile - so that an output element is the same
-// k-ordered v_mfma_f32_32x32x2_f32 chain, hence the same bits, in all three.
+// The fp32 LDS-DMA k-tile and the streamed walk around it: ONE definition of what k_gemm_nt_dma (rgcn_transform.hip),
+// k_rank_count (rank_count.hip), k_topk_select (rank_topk.hip) and k_assign / k_silhouette (cluster.hip) do with a staged
+// 64 x (64 TN) x 32 tile - so that an output element is the same k-ordered v_mfma_f32_32x32x2_f32 chain, hence the same
+// bits, in all of them - and the loop that streams (column tile, k-tile) pairs through the ring, for those that share it.
 //
 // Shape: 256 threads as 2 (m) x 2 (n) waves, a wave owns 32 rows x 32 TN columns; k-tile of 32 floats; a ring of
 // three LDS buffers [A 64 x 32 | B] filled by `global_load_lds_dwordx4`.  An LDS-DMA wave instruction writes
 // 64 x 16 B linearly, so the 128-byte-row tiles (A, and B in B_BLK form) are stored unpadded and bank conflicts are
 // removed by XOR-swizzling the 16-byte chunk index with (row >> 1) & 7 - applied to the per-lane SOURCE address on the
 // way in (dma_row / dma_col) and to the ds_read_b128 address on the way out (KTile).
-// Staging policy - which k-tile goes where, when, from which operand - stays with each kernel; the loop they share:
+// Staging policy - which k-tile goes where, when, from which operand - is walk_tiles below for the kernels with one A
+// operand and a range of B_BLK column tiles: k_topk_select, k_assign, k_silhouette.  Two kernels keep a loop of their
+// own: k_gemm_nt_dma (two A operands, relation blocks, skipped k-tiles) and k_rank_count (a single column tile per
+// workgroup: its loop is the walk's special case, and on the walk it measured 28 % slower - see rank_count.hip).  Both
+// have the same shape:
 //     wait vmcnt, s_barrier;  tile.read_first(buf_bytes);  <issue the DMAs of k-tile t + 2>;  tile.finish(acc, buf_bytes);
 // The ring must be the kernel's first LDS object (LDS address 0): the fragment reads address it absolutely.
 #pragma once
@@ -42,6 +47,7 @@ __device__ inline int dma_col(int row, int lane) { return swizzled_chunk(lane & 
 
 template <int TN, int BMODE>
 struct KTile {
+  static constexpr int NACC = TN;               // accumulators (32 x 32 blocks) of a wave
   static constexpr int BN = 64 * TN;
   static constexpr int A_FLOATS = BM * BK, B_FLOATS = BN * BK, BUF_FLOATS = A_FLOATS + B_FLOATS;
   static constexpr int A_PW = BM / 32;          // A wave-instructions per wave and k-tile (8 rows each)
@@ -121,6 +127,99 @@ struct KTile {
     }
   }
 };
+
+// the row inside the wave's 32 that accumulator register r of lane half lh holds (v_mfma_f32_32x32x2_f32)
+__device__ __forceinline__ int acc_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
+
+// The streamed walk: rows [m0, m0 + 64) of A (clamped to M - 1) against the column tiles [ct_begin, ct_end) of B (row n
+// of the product's columns is row brow(n) of B), k-tiles of 32 over d.  The (column tile, k-tile) pairs are ONE stream
+// through the ring (`lds`), so the DMA pipeline never drains between column tiles.  pre(ct) runs at the first k-tile of
+// a column tile (loads that the epilogue needs go out there, a column tile ahead of their use), epi(ct, acc) after its
+// last; the accumulators are zero again behind it.  Tile is a B_BLK KTile.
+// One iteration is: wait, barrier, read_first, pre, stage k-tile t + 2, finish (, epi).  The wait is counted, not
+// addressed - vmcnt(P): all but the newest P vector-memory operations of this wave are done - and this order is what
+// makes the count right.  The loads of pre are issued before the P DMAs of the same iteration, so they sit between two
+// groups of P DMAs: at the wait for k-tile t the newest P operations are the DMAs of k-tile t + 1, everything older -
+// k-tile t and the loads of pre - has landed, and the loads cost the wait nothing.  What epi issues comes after a
+// group of DMAs and only pushes that group further from the newest P: the wait is then stronger than needed, never
+// weaker.  (A load issued after the staging would likewise make the next wait hold back DMAs it is meant to leave in
+// flight, and a load whose value is used before the epilogue would drain the ring.)
+template <class Tile, class BRow, class Pre, class Epi>
+__device__ __forceinline__ void walk_tiles(float* lds, const float* __restrict__ A, const float* __restrict__ B, int M,
+                                           int d, int m0, int ct_begin, int ct_end, int wave, int lane, Tile& tile,
+                                           BRow brow, Pre pre, Epi epi) {
+  constexpr int TN = Tile::NACC, BN = Tile::BN, A_FLOATS = Tile::A_FLOATS, BUF_FLOATS = Tile::BUF_FLOATS;
+  constexpr int A_PW = Tile::A_PW, B_PW = Tile::B_PW, P = Tile::P;
+  floatx16 acc[TN];
+#pragma unroll
+  for (int b = 0; b < TN; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+
+  // per-lane source offsets of the LDS-DMAs
+  size_t a_off[A_PW];
+#pragma unroll
+  for (int j = 0; j < A_PW; ++j) {
+    const int row = dma_row(wave * A_PW + j, lane);
+    const int m = min(m0 + row, M - 1);                        // rows past M read a valid row; never written
+    a_off[j] = (size_t)m * d + dma_col(row, lane);
+  }
+  int b_row[B_PW], b_chunk[B_PW];
+  size_t b_off[B_PW];
+#pragma unroll
+  for (int j = 0; j < B_PW; ++j) {
+    b_row[j] = dma_row(wave * B_PW + j, lane);
+    b_chunk[j] = dma_col(b_row[j], lane);
+    b_off[j] = 0;
+  }
+  int st_ct = ct_begin, st_kt = 0;                             // next k-tile to stage
+  auto stage_next = [&](int buf) {
+    if (st_kt == 0) {
+#pragma unroll
+      for (int j = 0; j < B_PW; ++j) b_off[j] = (size_t)brow(st_ct * BN + b_row[j]) * d + b_chunk[j];
+    }
+    float* sA = lds + buf * BUF_FLOATS;
+    float* sB = sA + A_FLOATS;
+#pragma unroll
+    for (int j = 0; j < A_PW; ++j) glds16(A + a_off[j] + st_kt, sA + (wave * A_PW + j) * 8 * BK);
+#pragma unroll
+    for (int j = 0; j < B_PW; ++j) glds16(B + b_off[j] + st_kt, sB + (wave * B_PW + j) * 8 * BK);
+    st_kt += BK;
+    if (st_kt >= d) { st_kt = 0; ++st_ct; }
+  };
+
+  const int KT = d / BK;
+  const int total = (ct_end - ct_begin) * KT;                  // k-tiles of the whole walk (>= 1: the host sizes the grid)
+  stage_next(0);
+  if (total > 1) stage_next(1);
+
+  int cur_ct = ct_begin, cur_kt = 0;                           // k-tile being multiplied
+  int buf = 0, buf2 = 2;                                       // ring slots of k-tile t and t + 2
+  for (int t = 0; t < total; ++t) {
+    // k-tile t landed for this wave (see above; the last k-tile has nothing younger behind it), then for all waves; the
+    // barrier also says every wave is done reading the buffer staged next
+    if (t + 1 < total) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    const unsigned buf_bytes = Tile::buf_bytes(buf);
+    tile.read_first(buf_bytes);
+    if (cur_kt == 0) pre(cur_ct);
+    if (t + 2 < total) stage_next(buf2);
+    tile.finish(acc, buf_bytes);
+    buf = buf == NBUF - 1 ? 0 : buf + 1;
+    buf2 = buf2 == NBUF - 1 ? 0 : buf2 + 1;
+    cur_kt += BK;
+    if (cur_kt == d) {
+      epi(cur_ct, acc);
+#pragma unroll
+      for (int b = 0; b < TN; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+      cur_kt = 0;
+      ++cur_ct;
+    }
+  }
+}
 
 }  // namespace mma_f32_dma
 #endif

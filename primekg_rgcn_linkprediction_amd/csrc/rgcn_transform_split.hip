@@ -1016,8 +1016,6 @@ __global__ __launch_bounds__(2 * kThreads) void k_gemm_tn_coop(const float* __re
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // The split weights of one layer (rgcn_weights_split_pack):
 //   [ Bh_f ][ Bl_f ][ Bh_b ][ Bl_b ]  four fp16 images of (R+1)*d_in*d_out elements each (256-aligned), k contiguous
 //   [ Fh_f ][ Fl_f ][ Fh_b ][ Fl_b ]  the same four in MFMA B-fragment order (the fused layer kernels)

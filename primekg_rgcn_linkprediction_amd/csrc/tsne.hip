@@ -19,8 +19,6 @@
 #include <float.h>
 #include <math.h>
 
-#include <algorithm>
-
 #include "../../include/rgcn_tsne.h"
 #include "rgcn_common.h"
 
@@ -31,7 +29,6 @@ constexpr int kSlots = 128;          // candidates of a row: k + 1 <= 128, two p
 constexpr int kTile = 256;           // rows of a repulsion workgroup = the unit in which slices divide the columns
 constexpr int kChunk = 1024;         // columns staged in LDS at a time (8 KB)
 constexpr int kMaxSlices = 64;
-constexpr int kCUs = 256;            // MI355X
 constexpr int64_t kMaxM = (int64_t)1 << 24;
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -328,8 +325,6 @@ __global__ __launch_bounds__(256) void k_tsne_update(const float* __restrict__ g
 }
 
 // ------------------------------------------------------------------------------------------ host side
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct TsnePlan {
   int tiles, tiles_per_slice, slices, upd_blocks;
   size_t o_npart, o_klrow, o_ztile, o_zpart, o_rpart, upd_bytes, bytes;
@@ -340,10 +335,9 @@ inline bool tsne_shape_ok(int64_t M, int64_t slices) { return M >= 2 && M < kMax
 inline TsnePlan plan_tsne(int64_t M, int64_t slices) {
   TsnePlan p;
   p.tiles = (int)ceil_div64(M, kTile);
-  int64_t want = slices > 0 ? slices : ceil_div64(4 * kCUs, p.tiles);
-  want = std::max<int64_t>(1, std::min<int64_t>(want, std::min<int64_t>(p.tiles, kMaxSlices)));
-  p.tiles_per_slice = (int)ceil_div64(p.tiles, want);
-  p.slices = (int)ceil_div64(p.tiles, p.tiles_per_slice);      // no empty slice
+  const rgcn_slicing cut = rgcn_slice_tiles(p.tiles, slices > 0 ? slices : ceil_div64(4 * kCUs, p.tiles), kMaxSlices);
+  p.tiles_per_slice = cut.tiles_per_slice;
+  p.slices = cut.slices;
   p.upd_blocks = (int)ceil_div64(2 * M, 256);
   size_t at = 0;
   p.o_npart = at; at += align256((size_t)p.upd_blocks * 8);

@@ -110,7 +110,8 @@ def test_masked_ranks_equal_the_host_restatement_exactly(case6, side):
 
 
 @pytest.mark.parametrize("batch,entities,d", [(1, 100, 32), (63, 127, 128), (65, 129, 32), (64, 128, 128), (65, 30926, 128),
-                                              (130, 100, 128), (1, 129, 128), (63, 100, 32), (65, 127, 128)])
+                                              (130, 100, 128), (1, 129, 128), (63, 100, 32), (65, 127, 128),
+                                              (65, 129, 64), (65, 129, 96)])
 def test_masked_ranks_ragged_shapes(batch, entities, d):
     dev = need_gpu()
     g = torch.Generator().manual_seed(batch * 1000 + entities + d)

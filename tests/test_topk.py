@@ -25,7 +25,7 @@ def _same(got, want):
 
 @pytest.mark.parametrize("batch,entities,d", RAGGED)
 def test_topk_ragged_shapes_all_masks_k_and_slices(batch, entities, d):
-    """The nine ragged shapes of the masked ranking test with its generator and masks, all four mask combinations,
+    """The eleven ragged shapes of the masked ranking test with its generator and masks, all four mask combinations,
     k in {1, 10, 64, 128} (k > N at N = 100), slices in {0, 1, 2, 7}: equal to the restatement, to each other across
     slice counts, and on a second call."""
     dev = need_gpu()

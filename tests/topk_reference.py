@@ -77,7 +77,7 @@ def host_known(edge_index, edge_type, anchors, rels, side, n):
 
 
 RAGGED = [(1, 100, 32), (63, 127, 128), (65, 129, 32), (64, 128, 128), (65, 30926, 128), (130, 100, 128), (1, 129, 128),
-          (63, 100, 32), (65, 127, 128)]
+          (63, 100, 32), (65, 127, 128), (65, 129, 64), (65, 129, 96)]
 
 
 def ragged_case(batch, entities, d):
