@@ -46,6 +46,15 @@ static inline int raise_lds(K kernel, int bytes, bool (&raised)[64]) {
   return RGCN_OK;
 }
 
+// The parameter gradients of a layer over an empty graph (N == 0): all zero, nothing to launch.
+static inline int rgcn_zero_param_grads(float* grad_weight, float* grad_root, float* grad_bias, int64_t R, int64_t d_in,
+                                        int64_t d_out, hipStream_t stream) {
+  RGCN_HIP_TRY(hipMemsetAsync(grad_weight, 0, (size_t)(R * d_in) * d_out * sizeof(float), stream));
+  if (grad_root) RGCN_HIP_TRY(hipMemsetAsync(grad_root, 0, (size_t)d_in * d_out * sizeof(float), stream));
+  if (grad_bias) RGCN_HIP_TRY(hipMemsetAsync(grad_bias, 0, (size_t)d_out * sizeof(float), stream));
+  return RGCN_OK;
+}
+
 // The work plan's constants and item record live in rgcn_plan.h (plain host code, shared with the host check).
 // Edges of an item whose ids travel with the item (= rows a lane group keeps in flight).
 constexpr int RGCN_HEAD = 8;

@@ -20,6 +20,7 @@
 #include "rgcn_common.h"
 #include "rgcn_mma_f32_dma.h"
 #include "rgcn_slab_reduce.h"
+#include "rgcn_transform_host.h"
 
 namespace {
 
@@ -721,32 +722,13 @@ __global__ __launch_bounds__(kThreads * WG) void k_gemm_tn_dma(const float* __re
   if (do_bias && n0 + tid < N) bias_part[(size_t)split * N + n0 + tid] = bsum;
 }
 
-struct SplitPlan { int kc_tiles, n_tiles, splits, rows_per_split; };
-
 constexpr int TN_TKC = 64;          // kc columns per workgroup of k_gemm_tn_slab<1>
 
-// Workgroups per launch.  Slab bytes (and the reduce that follows) scale with the count, so a
-// graph of C2's size gets one workgroup per CU (measured best); once every workgroup still has
-// >= 2,048 rows to stream, two per CU are worth their slabs: the second wave per SIMD covers
-// the per-tile barrier (C4 on one GPU: 2.5 -> 2.0 ms per launch).
-int tn_target_blocks(int64_t M, int tiles) {
-  return M / std::max(1, 512 / tiles) >= 2048 ? 512 : 256;
+// the row splits of a parameter-gradient launch (rgcn_transform_host.h): one or two workgroups per CU
+rgcn_tn_split plan_tn(int64_t M, int64_t Kc, int64_t N) {
+  const int tiles = (int)(ceil_div64(Kc, TN_TKC) * ceil_div64(N, 128));
+  return rgcn_tn_plan(M, Kc, N, TN_TKC, rgcn_tn_target_blocks(M, tiles));
 }
-
-SplitPlan plan_splits(int64_t M, int64_t Kc, int64_t N) {
-  SplitPlan p;
-  p.kc_tiles = (int)ceil_div64(Kc, TN_TKC);
-  p.n_tiles = (int)ceil_div64(N, 128);
-  const int tiles = p.kc_tiles * p.n_tiles;
-  int64_t s = std::max<int64_t>(1, tn_target_blocks(M, tiles) / tiles);
-  s = std::min<int64_t>(s, std::max<int64_t>(1, ceil_div64(M, 128)));
-  int64_t rps = ceil_div64(ceil_div64(M, s), 32) * 32;
-  if (rps < 32) rps = 32;
-  p.rows_per_split = (int)rps;
-  p.splits = (int)std::max<int64_t>(1, ceil_div64(M, rps));
-  return p;
-}
-
 
 template <int BMODE, int EPI>
 void launch_nt(const float* A1, int K1, const float* A2, int K2, const float* W, const float* Rt, int dk,
@@ -773,10 +755,6 @@ void launch_nt(const float* A1, int K1, const float* A2, int K2, const float* W,
     dim3 grid((unsigned)ceil_div64(M, 64), (unsigned)ceil_div64(N, 128));
     k_gemm_nt<1, 2, BMODE, EPI><<<grid, kThreads, 0, stream>>>(A1, K1, A2, K2, W, Rt, dk, bias, mask, C, M, N);
   }
-}
-
-bool bad_dims(int64_t n, int64_t r, int64_t di, int64_t dout) {
-  return n < 0 || r <= 0 || di <= 0 || dout <= 0 || (di & 3) || (dout & 3);
 }
 
 // hr[b, :] = head[b, :] * rel[rel_idx ? rel_idx[b] : b, :] (LinkPredictor.score_all_tails rgcn.py:215-243: the A operand of
@@ -810,10 +788,10 @@ extern "C" {
 int rgcn_transform_fwd(const float* agg, const float* x, const float* weight, const float* root,
                        const float* bias, int relu, const uint32_t* tile_mask, int64_t N, int64_t R,
                        int64_t d_in, int64_t d_out, float* out, void* stream_) {
-  if (bad_dims(N, R, d_in, d_out) || !out) return RGCN_ERR_ARG;
+  if (rgcn_layer_bad_dims(N, R, d_in, d_out) || !out) return RGCN_ERR_ARG;
   if (N == 0) return RGCN_OK;
   if (!agg || !x || !weight) return RGCN_ERR_ARG;
-  if (N > INT32_MAX / 2 || (R + 1) * d_in > (1 << 24) || d_out > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
+  if (rgcn_gemm_out_of_range(N, (R + 1) * d_in, d_out)) return RGCN_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
   const int K1 = (int)(R * d_in), K2 = root ? (int)d_in : 0;
   if (relu)
@@ -829,10 +807,10 @@ int rgcn_transform_fwd(const float* agg, const float* x, const float* weight, co
 int rgcn_transform_bwd_input(const float* gagg, const float* g, const float* weight, const float* root,
                              const float* relu_mask, const uint32_t* tile_mask, int64_t N, int64_t R,
                              int64_t d_in, int64_t d_out, float* grad_x, void* stream_) {
-  if (bad_dims(N, R, d_in, d_out) || !grad_x) return RGCN_ERR_ARG;
+  if (rgcn_layer_bad_dims(N, R, d_in, d_out) || !grad_x) return RGCN_ERR_ARG;
   if (N == 0) return RGCN_OK;
   if (!gagg || !g || !weight) return RGCN_ERR_ARG;
-  if (N > INT32_MAX / 2 || (R + 1) * d_out > (1 << 24) || d_in > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
+  if (rgcn_gemm_out_of_range(N, (R + 1) * d_out, d_in)) return RGCN_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
   const int K1 = (int)(R * d_out), K2 = root ? (int)d_out : 0;
   if (relu_mask)
@@ -869,34 +847,25 @@ int distmult_score_all_tails(const float* head, const float* rel, const int64_t*
 size_t rgcn_transform_bwd_params_workspace_bytes(int64_t N, int64_t R, int64_t d_in, int64_t d_out) {
   if (N < 0 || R <= 0 || d_in <= 0 || d_out <= 0) return 0;
   const int64_t Kc = (R + 1) * d_in;
-  const SplitPlan p = plan_splits(N, Kc, d_out);
-  return ((size_t)p.splits * Kc * d_out + (size_t)p.splits * d_out) * sizeof(float);
+  return rgcn_slab_layout_of(plan_tn(N, Kc, d_out), Kc, d_out).bytes();
 }
 
 int rgcn_transform_bwd_params_begin(const float* agg, const float* x, const float* g, const uint32_t* tile_mask,
                                     int64_t N, int64_t R, int64_t d_in, int64_t d_out, float* grad_weight,
                                     float* grad_root, float* grad_bias, void* workspace, size_t workspace_bytes,
                                     void* stream_, rgcn_slab_job* job) {
-  if (!job) return RGCN_ERR_ARG;
-  *job = rgcn_slab_job{};
-  if (bad_dims(N, R, d_in, d_out) || !grad_weight) return RGCN_ERR_ARG;
-  if (N > 0 && (!agg || !x || !g)) return RGCN_ERR_ARG;
-  if (N > INT32_MAX / 2 || (R + 1) * d_in > (1 << 24) || d_out > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
-  if (!workspace || workspace_bytes < rgcn_transform_bwd_params_workspace_bytes(N, R, d_in, d_out))
-    return RGCN_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  const int K1 = (int)(R * d_in), K2 = grad_root ? (int)d_in : 0, Kc = K1 + K2;
+  const int rc = rgcn_params_begin_check(job, agg, x, g, N, R, d_in, d_out, grad_weight, 0);
+  if (rc != RGCN_OK) return rc;
   // the slab layout is sized for (R+1)*d_in rows; with grad_root == NULL only K1 are used
-  SplitPlan p = plan_splits(N, (R + 1) * d_in, d_out);
+  rgcn_tn_split p = plan_tn(N, (R + 1) * d_in, d_out);
+  const rgcn_slab_layout lay = rgcn_slab_layout_of(p, (R + 1) * d_in, d_out);
+  if (!workspace || workspace_bytes < lay.bytes()) return RGCN_ERR_WORKSPACE;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (N == 0) return rgcn_zero_param_grads(grad_weight, grad_root, grad_bias, R, d_in, d_out, stream);
+  const int K1 = (int)(R * d_in), K2 = grad_root ? (int)d_in : 0, Kc = K1 + K2;
   p.kc_tiles = (int)ceil_div64(Kc, TN_TKC);
   float* slab = (float*)workspace;
-  float* bias_part = slab + (size_t)p.splits * (R + 1) * d_in * d_out;
-  if (N == 0) {   // empty graph: all parameter grads are zero
-    RGCN_HIP_TRY(hipMemsetAsync(grad_weight, 0, (size_t)K1 * d_out * sizeof(float), stream));
-    if (grad_root) RGCN_HIP_TRY(hipMemsetAsync(grad_root, 0, (size_t)d_in * d_out * sizeof(float), stream));
-    if (grad_bias) RGCN_HIP_TRY(hipMemsetAsync(grad_bias, 0, (size_t)d_out * sizeof(float), stream));
-    return RGCN_OK;
-  }
+  float* bias_part = slab + lay.slab_floats;
   dim3 grid((unsigned)(p.kc_tiles * p.n_tiles), (unsigned)p.splits);
   if (K1 % 64 == 0 && K2 % 64 == 0)
   {
@@ -914,15 +883,7 @@ int rgcn_transform_bwd_params_begin(const float* agg, const float* x, const floa
     k_gemm_tn_slab<1><<<grid, kThreads, 0, stream>>>(agg, K1, x, K2, g, (int)N, (int)d_out, p.n_tiles,
                                                      p.rows_per_split, slab, grad_bias ? bias_part : nullptr);
   RGCN_HIP_TRY(hipGetLastError());
-  job->slab = slab;
-  job->bias_part = bias_part;
-  job->splits = p.splits;
-  job->K1 = K1;
-  job->Kc = Kc;
-  job->N = (int32_t)d_out;
-  job->grad_weight = grad_weight;
-  job->grad_root = grad_root;
-  job->grad_bias = grad_bias;
+  rgcn_slab_job_fill(job, workspace, lay, p.splits, K1, Kc, d_out, grad_weight, grad_root, grad_bias);
   return RGCN_OK;
 }
 

@@ -17,6 +17,7 @@
 #include <hip/hip_fp16.h>
 
 #include "rgcn_common.h"
+#include "rgcn_transform_host.h"
 
 namespace {
 
@@ -220,11 +221,11 @@ int rgcn_transform_fwd_f16(const float* agg, const float* x, const float* weight
                            const float* bias, int relu, const uint32_t* tile_mask, int64_t N, int64_t R,
                            int64_t d_in, int64_t d_out, float* out, void* workspace, size_t workspace_bytes,
                            void* stream_) {
-  if (N < 0 || R <= 0 || d_in <= 0 || d_out <= 0 || (d_in & 3) || (d_out & 3) || !out) return RGCN_ERR_ARG;
+  if (rgcn_layer_bad_dims(N, R, d_in, d_out) || !out) return RGCN_ERR_ARG;
   if (N == 0) return RGCN_OK;
   if (!agg || !x || !weight) return RGCN_ERR_ARG;
   if (d_in % BK) return RGCN_ERR_UNSUPPORTED;                     // a k-tile must not straddle two relations
-  if (N > INT32_MAX / 2 || (R + 1) * d_in > (1 << 24) || d_out > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
+  if (rgcn_gemm_out_of_range(N, (R + 1) * d_in, d_out)) return RGCN_ERR_UNSUPPORTED;
   if (!workspace || workspace_bytes < rgcn_transform_fwd_f16_workspace_bytes(R, d_in, d_out)) return RGCN_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   const int K1 = (int)(R * d_in), K2 = root ? (int)d_in : 0, n = (int)d_out;

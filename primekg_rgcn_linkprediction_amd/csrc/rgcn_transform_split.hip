@@ -31,8 +31,12 @@
 // k-tile, counted vmcnt, relation-occupancy skipping of all-zero k-tiles.  The A operand stays fp32
 // in memory and in LDS; a lane splits the 8 consecutive k it owns in registers.  The (small) B
 // operand is split once per call by k_pack_split into two k-contiguous fp16 images Bh / Bl [n][K].
+// Host side: an NT entry point validates, nt_prepare()s (workspace, pack-if-missing, views, hub tails) and describes its
+// launch as one `struct nt_call` for launch_nt_split; the argument rules, the row-split plan and the slab layout of the
+// parameter gradients are plain host code in rgcn_transform_host.h, shared with the fp32 and fp16 files.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include <hip/hip_fp16.h>
 
@@ -40,6 +44,7 @@
 #include "rgcn_slab_reduce.h"
 #include "rgcn_hub_finish.h"
 #include "rgcn_split.h"
+#include "rgcn_transform_host.h"
 
 // tools/gemm_stamps.hip includes this file with RGCN_STAMPS defined: thread 0 of every workgroup then leaves the 100 MHz
 // wall clock at four points of the kernel (entry, main loop reached, main loop left, end) - where a launch's time goes.
@@ -1081,55 +1086,75 @@ size_t nt_workspace_bytes(int64_t R, int64_t d_in, int64_t d_out) {
   return packed_bytes(R, d_in, d_out) + 2 * kMaxSlots * sizeof(float);
 }
 
-int launch_nt_split(const float* A1, int K1, const float* A2, int K2, const __half* Bh, const __half* Bl,
-                    const float* b_inv, const float* bias, const float* mask, int epi, float* C, int M, int N,
-                    const uint32_t* tile_mask, int kseg, const float* a1_amax, float a1_mul, const float* a2_amax,
-                    float* c_amax, float* scan_slots, bool half, hipStream_t stream, const hub_fin* hubs = nullptr,
-                    float out_scale = 1.f, const nt_chain* chained = nullptr) {
-  const nt_chain chain = chained ? *chained : nt_chain{};
-  if (chained && (half || N != 128 || bias || epi == EPI_RELU || !chain.Ch || !chain.Cl || !chain.c_inv_scale || !chain.T ||
-                  chain.N2 <= 0 || (chain.N2 & 3)))
+// One NT launch as a record: C[M, N] = [A1 | A2][M, K1 + K2] * B (+ bias) (epilogue).  An entry point names what its call
+// has; what it leaves alone is "none".
+struct nt_call {
+  const float *A1 = nullptr, *A2 = nullptr;
+  int K1 = 0, K2 = 0;
+  const __half *Bh = nullptr, *Bl = nullptr;   // the image of the split weights this product multiplies by, [N][K1 + K2]
+  const float* b_inv = nullptr;                // its inverse scale
+  const float *bias = nullptr, *mask = nullptr;   // mask (EPI_MASK): the ReLU output whose backward rides in the epilogue
+  int epi = EPI_NONE;
+  float* C = nullptr;
+  int M = 0, N = 0;
+  const uint32_t* tile_mask = nullptr;         // relation occupancy of A1's row tiles, `kseg` columns per relation
+  int kseg = 0;
+  const float *a1_amax = nullptr, *a2_amax = nullptr;   // amax buffers of the A operands; NULL: scanned into scan_slots
+  float a1_mul = 1.f, out_scale = 1.f;
+  float* c_amax = nullptr;                     // amax buffer that receives max |C|
+  float* scan_slots = nullptr;                 // 2 * kMaxSlots floats
+  bool half = false;                           // one pass on the hi parts
+  hub_fin fin{};                               // hub tails of A1 left to this launch
+  bool chained = false;                        // `chain` rides behind the product
+  nt_chain chain{};
+  hipStream_t stream = nullptr;
+  amax_ref r1{}, r2{};                         // (launch_nt_split's: the maxima as the kernel receives them)
+};
+
+// two wave columns (WM x WN = 2 x 2): see the notes in launch_nt_split
+template <int TN, int EPI, bool LO, bool CHAIN>
+void nt_launch(const nt_call& c) {
+  const dim3 grid((unsigned)ceil_div64(c.M, 64), CHAIN ? 1u : (unsigned)ceil_div64(c.N, 64 * TN));
+  k_gemm_nt_split<2, 2, TN, EPI, LO, CHAIN><<<grid, 256, 0, c.stream>>>(
+      c.A1, c.K1, c.A2, c.K2, c.Bh, c.Bl, c.b_inv, c.r1, c.a1_mul, c.r2, c.bias, c.mask, c.C, c.M, c.N, c.tile_mask, c.kseg,
+      reinterpret_cast<unsigned*>(c.c_amax), c.fin, c.out_scale, CHAIN ? c.chain : nt_chain{});
+}
+
+int launch_nt_split(nt_call c) {
+  const nt_chain& chain = c.chain;
+  if (c.chained && (c.half || c.N != 128 || c.bias || c.epi == EPI_RELU || !chain.Ch || !chain.Cl || !chain.c_inv_scale ||
+                    !chain.T || chain.N2 <= 0 || (chain.N2 & 3)))
     return RGCN_ERR_UNSUPPORTED;
-  const hub_fin fin = hubs ? *hubs : hub_fin{};
+  const hub_fin& fin = c.fin;
   if (fin.ptr && fin.d != 64 && fin.d != 128 && fin.d != 256) return RGCN_ERR_UNSUPPORTED;
-  if (fin.ptr && (!a1_amax || fin.d != kseg)) return RGCN_ERR_ARG;   // an unfinished A1 cannot be scanned for its maximum
-  const int K = K1 + K2;
-  if (K1 % BK || K2 % BK || K <= 0) return RGCN_ERR_UNSUPPORTED;
+  if (fin.ptr && (!c.a1_amax || fin.d != c.kseg)) return RGCN_ERR_ARG;   // an unfinished A1 cannot be scanned for its maximum
+  const int K1 = c.K1, K2 = c.K2;
+  if (K1 % BK || K2 % BK || K1 + K2 <= 0) return RGCN_ERR_UNSUPPORTED;
   // maxima of the A operands: from their producers, or scanned here (one launch over what is missing)
-  const bool scan1 = K1 && !a1_amax, scan2 = K2 && !a2_amax;
+  const bool scan1 = K1 && !c.a1_amax, scan2 = K2 && !c.a2_amax;
   if (scan1 || scan2) {
     absmax_job J{};
-    if (scan1) { J.p[0] = A1; J.n[0] = (int64_t)M * K1; }
-    if (scan2) { J.p[1] = A2; J.n[1] = (int64_t)M * K2; }
-    k_absmax<<<kMaxSlots, kThreads, 0, stream>>>(J, scan_slots);
+    if (scan1) { J.p[0] = c.A1; J.n[0] = (int64_t)c.M * K1; }
+    if (scan2) { J.p[1] = c.A2; J.n[1] = (int64_t)c.M * K2; }
+    k_absmax<<<kMaxSlots, kThreads, 0, c.stream>>>(J, c.scan_slots);
   }
-  amax_ref r1 = !K1 ? amax_ref{nullptr, 0} : (scan1 ? amax_ref{scan_slots, kMaxSlots} : amax_ref{a1_amax, 0});
-  amax_ref r2 = !K2 ? amax_ref{nullptr, 0} : (scan2 ? amax_ref{scan_slots + kMaxSlots, kMaxSlots} : amax_ref{a2_amax, 0});
-  if (scan1 || !(a1_mul > 0.f)) a1_mul = 1.f;                  // a scanned maximum is exact
-  if (!r1.slots) { r1 = r2; r2 = amax_ref{nullptr, 0}; a1_mul = 1.f; }   // the kernels read r1 unconditionally
-  if (kseg <= 0 || kseg % BK != 0) tile_mask = nullptr;
-  unsigned* amax_out = reinterpret_cast<unsigned*>(c_amax);
-  if (chained) {                                 // the second product rides behind the first one (64 x 128 tiles, whole rows)
-    dim3 grid((unsigned)ceil_div64(M, 64), 1);
-    if (epi == EPI_MASK)
-      k_gemm_nt_split<2, 2, 2, EPI_MASK, true, true><<<grid, 256, 0, stream>>>(A1, K1, A2, K2, Bh, Bl, b_inv, r1, a1_mul, r2, bias, mask, C,
-                                                                             M, N, tile_mask, kseg, amax_out, fin, out_scale, chain);
-    else
-      k_gemm_nt_split<2, 2, 2, EPI_NONE, true, true><<<grid, 256, 0, stream>>>(A1, K1, A2, K2, Bh, Bl, b_inv, r1, a1_mul, r2, bias, mask, C,
-                                                                             M, N, tile_mask, kseg, amax_out, fin, out_scale, chain);
-    RGCN_HIP_TRY(hipGetLastError());
-    return RGCN_OK;
-  }
-#define RGCN_NT_LAUNCH(WM_, WN_, TN_, EPI_, LO_)                                                                     \
-  k_gemm_nt_split<WM_, WN_, TN_, EPI_, LO_><<<grid, 64 * WM_ * WN_, 0, stream>>>(                                     \
-      A1, K1, A2, K2, Bh, Bl, b_inv, r1, a1_mul, r2, bias, mask, C, M, N, tile_mask, kseg, amax_out, fin, out_scale,  \
-      nt_chain{})
-#define RGCN_NT_SPLIT_W(WM_, WN_, TN_, EPI_)             \
-  do {                                                   \
-    if (half) RGCN_NT_LAUNCH(WM_, WN_, TN_, EPI_, false); \
-    else RGCN_NT_LAUNCH(WM_, WN_, TN_, EPI_, true);       \
-  } while (0)
-#define RGCN_NT_SPLIT(WM_, TN_, EPI_) RGCN_NT_SPLIT_W(WM_, 2, TN_, EPI_)   /* two wave columns: see the note below */
+  c.r1 = !K1 ? amax_ref{nullptr, 0} : (scan1 ? amax_ref{c.scan_slots, kMaxSlots} : amax_ref{c.a1_amax, 0});
+  c.r2 = !K2 ? amax_ref{nullptr, 0} : (scan2 ? amax_ref{c.scan_slots + kMaxSlots, kMaxSlots} : amax_ref{c.a2_amax, 0});
+  if (scan1 || !(c.a1_mul > 0.f)) c.a1_mul = 1.f;              // a scanned maximum is exact
+  if (!c.r1.slots) { c.r1 = c.r2; c.r2 = amax_ref{nullptr, 0}; c.a1_mul = 1.f; }   // the kernels read r1 unconditionally
+  if (c.kseg <= 0 || c.kseg % BK != 0) c.tile_mask = nullptr;
+  // the RELU / MASK / NONE switch, once: `launch` is a generic lambda, instantiated per epilogue
+  auto with_epi = [&](auto launch) {
+    if (c.epi == EPI_RELU) launch(std::integral_constant<int, EPI_RELU>{});
+    else if (c.epi == EPI_MASK) launch(std::integral_constant<int, EPI_MASK>{});
+    else launch(std::integral_constant<int, EPI_NONE>{});
+  };
+  auto plain = [&](auto tn) {
+    with_epi([&](auto epi) {
+      if (c.half) nt_launch<decltype(tn)::value, decltype(epi)::value, false, false>(c);
+      else nt_launch<decltype(tn)::value, decltype(epi)::value, true, false>(c);
+    });
+  };
   // (Round 3 also built WM x WN = 4 x 1 with TN = 4 - four waves of 32 rows x 128 columns, a 128 x 128 tile, one
   // workgroup per CU: A read and split once per row, 112 KB of LDS traffic per k-tile round instead of 144 - and
   // measured it 16 % SLOWER per k-tile (1.08 against 0.94 us, step 0.312 against 0.285 ms): at one wave per SIMD nothing
@@ -1138,20 +1163,12 @@ int launch_nt_split(const float* A1, int K1, const float* A2, int K2, const __ha
   // apart, one multiplying while the other reads, splits and stages; commit "NT: ping-pong k loop" - bit-identical and
   // SLOWER, 1.26 us per k-tile against 0.99 in lockstep and 0.94 for two 64-row workgroups: the read / split / stage
   // phase of four waves alone takes ~0.6 us, longer than the 0.25 us of MFMAs it was meant to hide behind.)
-  if (N <= 64) {
-    dim3 grid((unsigned)ceil_div64(M, 64), (unsigned)ceil_div64(N, 64));
-    if (epi == EPI_RELU) RGCN_NT_SPLIT(2, 1, EPI_RELU);
-    else if (epi == EPI_MASK) RGCN_NT_SPLIT(2, 1, EPI_MASK);
-    else RGCN_NT_SPLIT(2, 1, EPI_NONE);
-  } else {                       // (a 128-row tile, WM = 4, was measured no faster at C2: 15.8 against 15.2 us of main loop)
-    dim3 grid((unsigned)ceil_div64(M, 64), (unsigned)ceil_div64(N, 128));
-    if (epi == EPI_RELU) RGCN_NT_SPLIT(2, 2, EPI_RELU);
-    else if (epi == EPI_MASK) RGCN_NT_SPLIT(2, 2, EPI_MASK);
-    else RGCN_NT_SPLIT(2, 2, EPI_NONE);
-  }
-#undef RGCN_NT_LAUNCH
-#undef RGCN_NT_SPLIT
-#undef RGCN_NT_SPLIT_W
+  if (c.chained)                 // the second product rides behind the first one (64 x 128 tiles, whole rows; no RELU: above)
+    with_epi([&](auto epi) {
+      if constexpr (decltype(epi)::value != EPI_RELU) nt_launch<2, decltype(epi)::value, true, true>(c);
+    });
+  else if (c.N <= 64) plain(std::integral_constant<int, 1>{});
+  else plain(std::integral_constant<int, 2>{});   // (a 128-row tile, WM = 4, was measured no faster at C2: 15.8 against 15.2 us of main loop)
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
@@ -1173,33 +1190,35 @@ int make_hub_fin(const rgcn_graph* g, int transposed, float* partial, int64_t N,
   return 1;
 }
 
-bool bad_dims(int64_t n, int64_t r, int64_t di, int64_t dout) {
-  return n < 0 || r <= 0 || di <= 0 || dout <= 0 || (di & 3) || (dout & 3);
+// What the layer entry points do between their argument checks and the launch, once: the workspace of the call, the
+// split weights (packed here when nobody split them for this step yet), where missing maxima are scanned to, the extents
+// of the A operands - `dk` columns per relation and for the root part - and the hub tails the gather left.  The caller
+// picks its B images from `*w`.
+int nt_prepare(nt_call* c, PackedWeights* w, const float* weight, const float* root, const void* packed, int64_t N,
+               int64_t R, int64_t d_in, int64_t d_out, int64_t dk, void* workspace, size_t workspace_bytes,
+               const rgcn_graph* hub_graph, int hub_transposed, float* hub_partial, void* stream) {
+  if (!workspace || workspace_bytes < nt_workspace_bytes(R, d_in, d_out)) return RGCN_ERR_WORKSPACE;
+  c->stream = (hipStream_t)stream;
+  if (!packed) {
+    const int rc = pack_weights(weight, root, R, d_in, d_out, workspace, c->stream);
+    if (rc != RGCN_OK) return rc;
+    packed = workspace;
+  }
+  *w = packed_view(const_cast<void*>(packed), R, d_in, d_out);
+  c->scan_slots = (float*)((char*)workspace + packed_bytes(R, d_in, d_out));
+  c->K1 = (int)(R * dk);
+  c->K2 = root ? (int)dk : 0;
+  c->kseg = (int)dk;
+  c->M = (int)N;
+  const int hrc = make_hub_fin(hub_graph, hub_transposed, hub_partial, N, R, dk, &c->fin);
+  return hrc < 0 ? hrc : RGCN_OK;
 }
-
-struct TnPlan { int kc_tiles, n_tiles, splits, rows_per_split; };
 
 // one workgroup per CU (the 128 KB ring leaves no room for a second): as many row splits as that gives
-TnPlan tn_plan(int64_t M, int64_t Kc, int64_t N) {
-  TnPlan p;
-  p.kc_tiles = (int)ceil_div64(Kc, TN_TKC);
-  p.n_tiles = (int)ceil_div64(N, 128);
-  const int tiles = p.kc_tiles * p.n_tiles;
-  const int target = 256;
-  int64_t s = std::max<int64_t>(1, target / tiles);
-  s = std::min<int64_t>(s, std::max<int64_t>(1, ceil_div64(M, 128)));
-  int64_t rps = ceil_div64(ceil_div64(M, s), 32) * 32;
-  if (rps < 32) rps = 32;
-  p.rows_per_split = (int)rps;
-  p.splits = (int)std::max<int64_t>(1, ceil_div64(M, rps));
-  return p;
-}
-
-size_t tn_workspace_bytes(int64_t N, int64_t R, int64_t d_in, int64_t d_out) {
-  const int64_t Kc = (R + 1) * d_in;
-  const TnPlan p = tn_plan(N, Kc, d_out);
-  return align256(((size_t)p.splits * Kc * d_out + (size_t)p.splits * d_out) * sizeof(float)) +
-         kAbsmaxSegs * kMaxSlots * sizeof(float);
+constexpr int kTnBlocks = 256;
+// its workspace: the slabs and bias partials (256-aligned), then the partial maxima of operands nobody left a maximum for
+size_t tn_workspace_bytes(const rgcn_slab_layout& lay) {
+  return align256(lay.bytes()) + kAbsmaxSegs * kMaxSlots * sizeof(float);
 }
 
 }  // namespace
@@ -1225,9 +1244,9 @@ int rgcn_prep_fill(const float* x, int64_t numel, float* x_amax, float* zero_buf
   out->zero_count = zero_count;
   int64_t most = 0;
   for (int l = 0; l < count; ++l) {
-    if (R[l] <= 0 || d_in[l] <= 0 || d_out[l] <= 0 || (d_out[l] & 3) || !weights[l]) return RGCN_ERR_ARG;
-    if ((R[l] + 1) * d_in[l] > (1 << 24) || (R[l] + 1) * d_out[l] > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
-    if (!packed[l] || packed_bytes_[l] < packed_bytes(R[l], d_in[l], d_out[l])) return RGCN_ERR_WORKSPACE;
+    const int rc = rgcn_pack_layer_check(R[l], d_in[l], d_out[l], 4, weights[l], packed[l], packed_bytes_[l],
+                                         packed_bytes(R[l], d_in[l], d_out[l]));
+    if (rc != RGCN_OK) return rc;
     out->JJ.j[l] = make_pack_job(weights[l], roots[l], R[l], d_in[l], d_out[l], packed[l], nullptr, nullptr);
     most = std::max<int64_t>(most, (R[l] + (roots[l] ? 1 : 0)) * d_in[l] * d_out[l]);
   }
@@ -1280,9 +1299,8 @@ size_t rgcn_weights_split_bytes(int64_t R, int64_t d_in, int64_t d_out) {
 
 int rgcn_weights_split_pack(const float* weight, const float* root, int64_t R, int64_t d_in, int64_t d_out,
                             void* packed, size_t packed_bytes_, void* stream_) {
-  if (R <= 0 || d_in <= 0 || d_out <= 0 || !weight) return RGCN_ERR_ARG;
-  if ((R + 1) * d_in > (1 << 24) || (R + 1) * d_out > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
-  if (!packed || packed_bytes_ < packed_bytes(R, d_in, d_out)) return RGCN_ERR_WORKSPACE;
+  const int rc = rgcn_pack_layer_check(R, d_in, d_out, 1, weight, packed, packed_bytes_, packed_bytes(R, d_in, d_out));
+  if (rc != RGCN_OK) return rc;
   return pack_weights(weight, root, R, d_in, d_out, packed, (hipStream_t)stream_);
 }
 
@@ -1296,9 +1314,9 @@ int rgcn_weights_split_pack_multi(int count, const float* const* weights, const 
   pack_jobs JJ{};
   int64_t most = 0;
   for (int l = 0; l < count; ++l) {
-    if (R[l] <= 0 || d_in[l] <= 0 || d_out[l] <= 0 || (d_out[l] & 3) || !weights[l]) return RGCN_ERR_ARG;
-    if ((R[l] + 1) * d_in[l] > (1 << 24) || (R[l] + 1) * d_out[l] > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
-    if (!packed[l] || packed_bytes_[l] < packed_bytes(R[l], d_in[l], d_out[l])) return RGCN_ERR_WORKSPACE;
+    const int rc = rgcn_pack_layer_check(R[l], d_in[l], d_out[l], 4, weights[l], packed[l], packed_bytes_[l],
+                                         packed_bytes(R[l], d_in[l], d_out[l]));
+    if (rc != RGCN_OK) return rc;
     JJ.j[l] = make_pack_job(weights[l], roots[l], R[l], d_in[l], d_out[l], packed[l], w_amax ? w_amax[l] : nullptr,
                             r_amax ? r_amax[l] : nullptr);
     most = std::max<int64_t>(most, (R[l] + (roots[l] ? 1 : 0)) * d_in[l] * d_out[l]);
@@ -1320,27 +1338,23 @@ int rgcn_transform_fwd_split(const float* agg, const float* x, const float* weig
                              const float* x_amax, int half, float* out, float* out_amax, void* workspace,
                              size_t workspace_bytes, void* stream_, const rgcn_graph* hub_graph, int hub_transposed,
                              float* hub_partial) {
-  if (bad_dims(N, R, d_in, d_out) || !out) return RGCN_ERR_ARG;
+  if (rgcn_layer_bad_dims(N, R, d_in, d_out) || !out) return RGCN_ERR_ARG;
   if (N == 0) return RGCN_OK;
   if (!agg || !x || !weight) return RGCN_ERR_ARG;
   if (d_in % BK) return RGCN_ERR_UNSUPPORTED;
-  if (N > INT32_MAX / 2 || (R + 1) * d_in > (1 << 24) || d_out > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
-  if (!workspace || workspace_bytes < nt_workspace_bytes(R, d_in, d_out)) return RGCN_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!packed) {                                            // nobody split the weights for this step yet
-    const int rc = pack_weights(weight, root, R, d_in, d_out, workspace, stream);
-    if (rc != RGCN_OK) return rc;
-    packed = workspace;
-  }
-  const PackedWeights v = packed_view(const_cast<void*>(packed), R, d_in, d_out);
-  float* scan = (float*)((char*)workspace + packed_bytes(R, d_in, d_out));
-  const int K1 = (int)(R * d_in), K2 = root ? (int)d_in : 0;
-  hub_fin fin;
-  const int hrc = make_hub_fin(hub_graph, hub_transposed, hub_partial, N, R, d_in, &fin);
-  if (hrc < 0) return hrc;
-  return launch_nt_split(agg, K1, x, K2, v.Bh_f, v.Bl_f, v.inv_scale, bias, nullptr, relu ? EPI_RELU : EPI_NONE, out,
-                         (int)N, (int)d_out, tile_mask, (int)d_in, agg_amax, agg_amax_mul, x_amax, out_amax, scan, half != 0,
-                         stream, hrc ? &fin : nullptr);
+  if (rgcn_gemm_out_of_range(N, (R + 1) * d_in, d_out)) return RGCN_ERR_UNSUPPORTED;
+  nt_call c;
+  PackedWeights v;
+  const int rc = nt_prepare(&c, &v, weight, root, packed, N, R, d_in, d_out, d_in, workspace, workspace_bytes, hub_graph,
+                            hub_transposed, hub_partial, stream_);
+  if (rc != RGCN_OK) return rc;
+  c.A1 = agg; c.a1_amax = agg_amax; c.a1_mul = agg_amax_mul; c.tile_mask = tile_mask;
+  c.A2 = x; c.a2_amax = x_amax;
+  c.Bh = v.Bh_f; c.Bl = v.Bl_f; c.b_inv = v.inv_scale;
+  c.bias = bias; c.epi = relu ? EPI_RELU : EPI_NONE;
+  c.C = out; c.N = (int)d_out; c.c_amax = out_amax;
+  c.half = half != 0;
+  return launch_nt_split(c);
 }
 
 int rgcn_transform_bwd_input_split(const float* gagg, const float* g, const float* weight, const float* root,
@@ -1350,27 +1364,23 @@ int rgcn_transform_bwd_input_split(const float* gagg, const float* g, const floa
                                    float* grad_x_amax, void* workspace, size_t workspace_bytes, void* stream_,
                                    const rgcn_graph* hub_graph, int hub_transposed, float* hub_partial,
                                    float out_scale) {
-  if (bad_dims(N, R, d_in, d_out) || !grad_x || !(out_scale > 0.f)) return RGCN_ERR_ARG;
+  if (rgcn_layer_bad_dims(N, R, d_in, d_out) || !grad_x || !(out_scale > 0.f)) return RGCN_ERR_ARG;
   if (N == 0) return RGCN_OK;
   if (!gagg || !g || !weight) return RGCN_ERR_ARG;
   if (d_out % BK) return RGCN_ERR_UNSUPPORTED;
-  if (N > INT32_MAX / 2 || (R + 1) * d_out > (1 << 24) || d_in > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
-  if (!workspace || workspace_bytes < nt_workspace_bytes(R, d_in, d_out)) return RGCN_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!packed) {
-    const int rc = pack_weights(weight, root, R, d_in, d_out, workspace, stream);
-    if (rc != RGCN_OK) return rc;
-    packed = workspace;
-  }
-  const PackedWeights v = packed_view(const_cast<void*>(packed), R, d_in, d_out);
-  float* scan = (float*)((char*)workspace + packed_bytes(R, d_in, d_out));
-  const int K1 = (int)(R * d_out), K2 = root ? (int)d_out : 0;
-  hub_fin fin;
-  const int hrc = make_hub_fin(hub_graph, hub_transposed, hub_partial, N, R, d_out, &fin);
-  if (hrc < 0) return hrc;
-  return launch_nt_split(gagg, K1, g, K2, v.Bh_b, v.Bl_b, v.inv_scale, nullptr, relu_mask,
-                         relu_mask ? EPI_MASK : EPI_NONE, grad_x, (int)N, (int)d_in, tile_mask, (int)d_out, gagg_amax,
-                         gagg_amax_mul, g_amax, grad_x_amax, scan, half != 0, stream, hrc ? &fin : nullptr, out_scale);
+  if (rgcn_gemm_out_of_range(N, (R + 1) * d_out, d_in)) return RGCN_ERR_UNSUPPORTED;
+  nt_call c;
+  PackedWeights v;
+  const int rc = nt_prepare(&c, &v, weight, root, packed, N, R, d_in, d_out, d_out, workspace, workspace_bytes, hub_graph,
+                            hub_transposed, hub_partial, stream_);
+  if (rc != RGCN_OK) return rc;
+  c.A1 = gagg; c.a1_amax = gagg_amax; c.a1_mul = gagg_amax_mul; c.tile_mask = tile_mask;
+  c.A2 = g; c.a2_amax = g_amax;
+  c.Bh = v.Bh_b; c.Bl = v.Bl_b; c.b_inv = v.inv_scale;
+  c.mask = relu_mask; c.epi = relu_mask ? EPI_MASK : EPI_NONE;
+  c.C = grad_x; c.N = (int)d_in; c.c_amax = grad_x_amax; c.out_scale = out_scale;
+  c.half = half != 0;
+  return launch_nt_split(c);
 }
 
 int rgcn_transform_bwd_input_chain_supported(int64_t R, int64_t d_in, int64_t d_out, int64_t R1, int64_t d_in1) {
@@ -1387,45 +1397,53 @@ int rgcn_transform_bwd_input_chain_split(const float* gagg, const float* g, cons
                                          const rgcn_graph* hub_graph, int hub_transposed, float* hub_partial,
                                          float out_scale, const void* packed1, int has_root1, int64_t R1, int64_t d_in1,
                                          float* t_out) {
-  if (bad_dims(N, R, d_in, d_out) || !grad_x || !t_out || !packed || !packed1 || !(out_scale > 0.f)) return RGCN_ERR_ARG;
+  if (rgcn_layer_bad_dims(N, R, d_in, d_out) || !grad_x || !t_out || !packed || !packed1 || !(out_scale > 0.f))
+    return RGCN_ERR_ARG;
   if (!rgcn_transform_bwd_input_chain_supported(R, d_in, d_out, R1, d_in1)) return RGCN_ERR_UNSUPPORTED;
   if (N == 0) return RGCN_OK;
   if (!gagg || !g || !weight || !gagg_amax || !g_amax) return RGCN_ERR_ARG;
-  if (N > INT32_MAX / 2 || (R + 1) * d_out > (1 << 24) || (R1 + 1) * d_in1 > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
-  if (!workspace || workspace_bytes < nt_workspace_bytes(R, d_in, d_out)) return RGCN_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  const PackedWeights v = packed_view(const_cast<void*>(packed), R, d_in, d_out);
+  if (rgcn_gemm_out_of_range(N, (R + 1) * d_out, (R1 + 1) * d_in1)) return RGCN_ERR_UNSUPPORTED;
+  nt_call c;
+  PackedWeights v;
+  const int rc = nt_prepare(&c, &v, weight, root, packed, N, R, d_in, d_out, d_out, workspace, workspace_bytes, hub_graph,
+                            hub_transposed, hub_partial, stream_);
+  if (rc != RGCN_OK) return rc;
   const PackedWeights v1 = packed_view(const_cast<void*>(packed1), R1, d_in1, d_in);     // conv1: d_out1 = d_in of conv2
-  float* scan = (float*)((char*)workspace + packed_bytes(R, d_in, d_out));
-  const int K1 = (int)(R * d_out), K2 = root ? (int)d_out : 0;
-  hub_fin fin;
-  const int hrc = make_hub_fin(hub_graph, hub_transposed, hub_partial, N, R, d_out, &fin);
-  if (hrc < 0) return hrc;
-  nt_chain chain{v1.Bh_n, v1.Bl_n, v1.inv_scale, t_out, (int)((R1 + (has_root1 ? 1 : 0)) * d_in1)};
-  return launch_nt_split(gagg, K1, g, K2, v.Bh_b, v.Bl_b, v.inv_scale, nullptr, relu_mask, relu_mask ? EPI_MASK : EPI_NONE,
-                         grad_x, (int)N, (int)d_in, tile_mask, (int)d_out, gagg_amax, gagg_amax_mul, g_amax, grad_x_amax, scan,
-                         false, stream, hrc ? &fin : nullptr, out_scale, &chain);
+  c.A1 = gagg; c.a1_amax = gagg_amax; c.a1_mul = gagg_amax_mul; c.tile_mask = tile_mask;
+  c.A2 = g; c.a2_amax = g_amax;
+  c.Bh = v.Bh_b; c.Bl = v.Bl_b; c.b_inv = v.inv_scale;
+  c.mask = relu_mask; c.epi = relu_mask ? EPI_MASK : EPI_NONE;
+  c.C = grad_x; c.N = (int)d_in; c.c_amax = grad_x_amax; c.out_scale = out_scale;
+  c.chained = true;
+  c.chain = nt_chain{v1.Bh_n, v1.Bl_n, v1.inv_scale, t_out, (int)((R1 + (has_root1 ? 1 : 0)) * d_in1)};
+  return launch_nt_split(c);
 }
 
 int rgcn_transform_first_split(const float* g, const void* packed, int has_root, int64_t N, int64_t R, int64_t d_in,
                                int64_t d_out, const float* g_amax, int half, float* t_out, void* workspace,
                                size_t workspace_bytes, void* stream_) {
-  if (bad_dims(N, R, d_in, d_out) || !t_out || !packed) return RGCN_ERR_ARG;
+  if (rgcn_layer_bad_dims(N, R, d_in, d_out) || !t_out || !packed) return RGCN_ERR_ARG;
   if (N == 0) return RGCN_OK;
   if (!g) return RGCN_ERR_ARG;
   if (d_out % BK) return RGCN_ERR_UNSUPPORTED;
   const int64_t cols = (R + (has_root ? 1 : 0)) * d_in;
-  if (N > INT32_MAX / 2 || cols > (1 << 24) || d_out > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
+  if (rgcn_gemm_out_of_range(N, d_out, cols)) return RGCN_ERR_UNSUPPORTED;
   if (!workspace || workspace_bytes < 2 * kMaxSlots * sizeof(float)) return RGCN_ERR_WORKSPACE;
   const PackedWeights v = packed_view(const_cast<void*>(packed), R, d_in, d_out);
-  return launch_nt_split(g, (int)d_out, nullptr, 0, v.Bh_n, v.Bl_n, v.inv_scale, nullptr, nullptr, EPI_NONE, t_out, (int)N,
-                         (int)cols, nullptr, 0, g_amax, 1.f, nullptr, nullptr, (float*)workspace, half != 0,
-                         (hipStream_t)stream_);
+  nt_call c;                                                   // one operand, no occupancy mask, nothing deferred
+  c.A1 = g; c.K1 = (int)d_out; c.a1_amax = g_amax;
+  c.Bh = v.Bh_n; c.Bl = v.Bl_n; c.b_inv = v.inv_scale;
+  c.C = t_out; c.M = (int)N; c.N = (int)cols;
+  c.scan_slots = (float*)workspace;
+  c.half = half != 0;
+  c.stream = (hipStream_t)stream_;
+  return launch_nt_split(c);
 }
 
 size_t rgcn_transform_bwd_params_split_workspace_bytes(int64_t N, int64_t R, int64_t d_in, int64_t d_out) {
   if (N < 0 || R <= 0 || d_in <= 0 || d_out <= 0) return 0;
-  return tn_workspace_bytes(N, R, d_in, d_out);
+  const int64_t Kc = (R + 1) * d_in;
+  return tn_workspace_bytes(rgcn_slab_layout_of(rgcn_tn_plan(N, Kc, d_out, TN_TKC, kTnBlocks), Kc, d_out));
 }
 
 int rgcn_transform_bwd_params_split_begin(const float* agg, const float* x, const float* g,
@@ -1435,27 +1453,20 @@ int rgcn_transform_bwd_params_split_begin(const float* agg, const float* x, cons
                                           float* grad_root,
                                           float* grad_bias, void* workspace, size_t workspace_bytes, void* stream_,
                                           rgcn_slab_job* job) {
-  if (!job) return RGCN_ERR_ARG;
-  *job = rgcn_slab_job{};
-  if (bad_dims(N, R, d_in, d_out) || !grad_weight) return RGCN_ERR_ARG;
-  if (N > 0 && (!agg || !x || !g)) return RGCN_ERR_ARG;
-  if (d_in % 64) return RGCN_ERR_UNSUPPORTED;                  // a 64-column kc tile lies in one operand / relation
-  if (N > INT32_MAX / 2 || (R + 1) * d_in > (1 << 24) || d_out > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
-  if (!workspace || workspace_bytes < tn_workspace_bytes(N, R, d_in, d_out)) return RGCN_ERR_WORKSPACE;
+  // (64: a 64-column half of a kc tile lies in one operand / relation)
+  const int rc = rgcn_params_begin_check(job, agg, x, g, N, R, d_in, d_out, grad_weight, 64);
+  if (rc != RGCN_OK) return rc;
+  // the slab layout is sized for (R+1)*d_in rows; with grad_root == NULL only K1 are used
+  rgcn_tn_split p = rgcn_tn_plan(N, (R + 1) * d_in, d_out, TN_TKC, kTnBlocks);
+  const rgcn_slab_layout lay = rgcn_slab_layout_of(p, (R + 1) * d_in, d_out);
+  if (!workspace || workspace_bytes < tn_workspace_bytes(lay)) return RGCN_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
+  if (N == 0) return rgcn_zero_param_grads(grad_weight, grad_root, grad_bias, R, d_in, d_out, stream);
   const int K1 = (int)(R * d_in), K2 = grad_root ? (int)d_in : 0, Kc = K1 + K2;
-  TnPlan p = tn_plan(N, (R + 1) * d_in, d_out);
   p.kc_tiles = (int)ceil_div64(Kc, TN_TKC);
   float* slab = (float*)workspace;
-  float* bias_part = slab + (size_t)p.splits * (R + 1) * d_in * d_out;
-  float* slots = (float*)((char*)workspace +
-                          align256(((size_t)p.splits * (R + 1) * d_in * d_out + (size_t)p.splits * d_out) * sizeof(float)));
-  if (N == 0) {
-    RGCN_HIP_TRY(hipMemsetAsync(grad_weight, 0, (size_t)K1 * d_out * sizeof(float), stream));
-    if (grad_root) RGCN_HIP_TRY(hipMemsetAsync(grad_root, 0, (size_t)d_in * d_out * sizeof(float), stream));
-    if (grad_bias) RGCN_HIP_TRY(hipMemsetAsync(grad_bias, 0, (size_t)d_out * sizeof(float), stream));
-    return RGCN_OK;
-  }
+  float* bias_part = slab + lay.slab_floats;
+  float* slots = (float*)((char*)workspace + align256(lay.bytes()));
   absmax_job J{};
   const bool scan1 = !agg_amax, scan2 = K2 && !x_amax, scang = !g_amax;
   if (scan1) { J.p[0] = agg; J.n[0] = N * (int64_t)K1; }
@@ -1476,15 +1487,7 @@ int rgcn_transform_bwd_params_split_begin(const float* agg, const float* x, cons
   else RGCN_TN_LAUNCH(k_gemm_tn_coop, true);
 #undef RGCN_TN_LAUNCH
   RGCN_HIP_TRY(hipGetLastError());
-  job->slab = slab;
-  job->bias_part = bias_part;
-  job->splits = p.splits;
-  job->K1 = K1;
-  job->Kc = Kc;
-  job->N = (int32_t)d_out;
-  job->grad_weight = grad_weight;
-  job->grad_root = grad_root;
-  job->grad_bias = grad_bias;
+  rgcn_slab_job_fill(job, workspace, lay, p.splits, K1, Kc, d_out, grad_weight, grad_root, grad_bias);
   return RGCN_OK;
 }
 

@@ -109,6 +109,16 @@ def _use_split(precision: Optional[str], k_dim: int, multiple: int) -> int:
     return 2 if mode == "half" else 1
 
 
+def _split_label(split: int) -> str:
+    """what a ``_use_split`` mode (1 or 2) is called in the GEMM brackets"""
+    return "split" if split == 1 else "half"
+
+
+def _pair(amax, k: int):
+    """the ``amax=`` argument of a transform as ``k`` buffers: the caller's tuple, or nothing known"""
+    return amax if amax is not None else (None,) * k
+
+
 # An "amax buffer" (include/rgcn_hip.h, RGCN_AMAX_FLOATS): AMAX_FLOATS floats; its VALUE, max |tensor|, is the
 # maximum over its 256 heads (every 8th entry; the rest is never touched).  Producing kernels publish wave maxima
 # into 64 of the heads with an atomic max on the bit pattern (spread so the atomics of a launch do not queue on
@@ -1061,6 +1071,24 @@ def _check_layer(agg, x, weight, root, bias):
     return n, r, d_in, d_out
 
 
+def _check_bwd_input(gagg, g, weight, root, relu_mask):
+    """operands of an input gradient (with or without the chained product) -> ``(n, r, d_in, d_out)``"""
+    _need_gpu("g", g, torch.float32)
+    _need_gpu("gagg", gagg, torch.float32)
+    _need_gpu("weight", weight, torch.float32)
+    r, d_in, d_out = weight.shape
+    n = g.size(0)
+    if tuple(g.shape) != (n, d_out) or tuple(gagg.shape) != (n, r * d_out):
+        raise ValueError("g must be [N, d_out] and gagg [N, R*d_out]")
+    if root is not None:
+        _need_gpu("root", root, torch.float32)
+    if relu_mask is not None:
+        _need_gpu("relu_mask", relu_mask, torch.float32)
+        if tuple(relu_mask.shape) != (n, d_in):
+            raise ValueError(f"relu_mask must be [{n}, {d_in}]")
+    return n, r, d_in, d_out
+
+
 def _mask_for(graph: Optional[BucketedGraph], transposed: bool, n: int, r: int) -> Optional[int]:
     """relation-occupancy mask of the structure the aggregate came from (None = dense)"""
     if graph is None:
@@ -1097,48 +1125,46 @@ def transform_fwd(agg, x, weight, root=None, bias=None, relu: bool = False,
         _need_gpu("out", out, torch.float32)
         if tuple(out.shape) != (n, d_out) or out.device != x.device:
             raise ValueError(f"out must be [{n}, {d_out}] on x's device")
-    given_out = out
     split = 0 if half else _use_split(precision, d_in, 32)
-    if split and n > 0:
-        a1, a2 = amax if amax is not None else (None, None)
+    if not n:
+        split = 0                                          # nothing to multiply: the fp32 entry point returns at once
+    if split:
+        a1, a2 = _pair(amax, 2)
         _check_amax("agg_amax", a1, x.device)
         _check_amax("x_amax", a2, x.device)
         if packed is not None and not packed.matches(weight, root):
             raise ValueError("packed does not belong to these weights")
-        with _on(x.device):
-            out = given_out if given_out is not None else _empty(n, d_out, dtype=torch.float32, device=x.device)
+    elif hubs is not None:
+        raise ValueError("deferred hub tails need the split-precision transform (finish them with aggregate instead)")
+    k = (r + (root is not None)) * d_in
+    with _on(x.device):
+        if out is None:
+            out = _empty(n, d_out, dtype=torch.float32, device=x.device)
+        if split:
+            name = "rgcn_transform_fwd_split"
             nbytes = _query("rgcn_transform_split_workspace_bytes", r, d_in, d_out)
             ws = _workspace(nbytes, x.device)
-            with _GemmBracket("fwd", n, (r + (root is not None)) * d_in, d_out, "split" if split == 1 else "half"):
+            with _GemmBracket("fwd", n, k, d_out, _split_label(split)):
                 rc = lib.rgcn_transform_fwd_split(_ptr(agg), _ptr(x), _ptr(weight), _ptr(root),
                                                   _ptr(packed.buf) if packed is not None else None, _ptr(bias),
                                                   int(relu), _mask_for(graph, False, n, r), n, r, d_in, d_out,
                                                   _ptr(a1), float(amax_mul), _ptr(a2), int(split == 2), _ptr(out),
                                                   _ptr(amax_out), _ptr(ws), nbytes, _stream(), *_hub_args(hubs, n, r))
-        _lib.check(rc, "rgcn_transform_fwd_split")
-        return out
-    if hubs is not None:
-        raise ValueError("deferred hub tails need the split-precision transform (finish them with aggregate instead)")
-    if half and d_in % 32 == 0:
-        with _on(x.device):
-            out = given_out if given_out is not None else _empty(n, d_out, dtype=torch.float32, device=x.device)
+        elif half and d_in % 32 == 0:
+            name = "rgcn_transform_fwd_f16"
             nbytes = lib.rgcn_transform_fwd_f16_workspace_bytes(r, d_in, d_out)
             ws = _workspace(nbytes, x.device)
-            with _GemmBracket("fwd", n, (r + (root is not None)) * d_in, d_out, "f16"):
+            with _GemmBracket("fwd", n, k, d_out, "f16"):
                 rc = lib.rgcn_transform_fwd_f16(_ptr(agg), _ptr(x), _ptr(weight), _ptr(root), _ptr(bias), int(relu),
                                                 _mask_for(graph, False, n, r), n, r, d_in, d_out, _ptr(out), _ptr(ws),
                                                 nbytes, _stream())
-        _lib.check(rc, "rgcn_transform_fwd_f16")
-        if amax_out is not None:
-            absmax(out, amax_out)
-        return out
-    with _on(x.device):
-        out = given_out if given_out is not None else _empty(n, d_out, dtype=torch.float32, device=x.device)
-        with _GemmBracket("fwd", n, (r + (root is not None)) * d_in, d_out, "fp32"):
-            rc = lib.rgcn_transform_fwd(_ptr(agg), _ptr(x), _ptr(weight), _ptr(root), _ptr(bias), int(relu),
-                                        _mask_for(graph, False, n, r), n, r, d_in, d_out, _ptr(out), _stream())
-    _lib.check(rc, "rgcn_transform_fwd")
-    if amax_out is not None:
+        else:
+            name = "rgcn_transform_fwd"
+            with _GemmBracket("fwd", n, k, d_out, "fp32"):
+                rc = lib.rgcn_transform_fwd(_ptr(agg), _ptr(x), _ptr(weight), _ptr(root), _ptr(bias), int(relu),
+                                            _mask_for(graph, False, n, r), n, r, d_in, d_out, _ptr(out), _stream())
+    _lib.check(rc, name)
+    if not split and amax_out is not None:                 # (the split kernel publishes max |out| itself)
         absmax(out, amax_out)
     return out
 
@@ -1153,26 +1179,14 @@ def transform_bwd_input(gagg, g, weight, root=None, relu_mask=None,
     additionally multiplied by ``relu_mask > 0``.  ``out_scale`` (the ``1 / (1 - p)`` of a dropout whose
     backward rides in this call) is applied in the split kernels' epilogue; the fp32 kernels get scaled
     weights instead."""
-    _need_gpu("g", g, torch.float32)
-    _need_gpu("gagg", gagg, torch.float32)
-    _need_gpu("weight", weight, torch.float32)
-    r, d_in, d_out = weight.shape
-    n = g.size(0)
-    if tuple(g.shape) != (n, d_out) or tuple(gagg.shape) != (n, r * d_out):
-        raise ValueError("g must be [N, d_out] and gagg [N, R*d_out]")
-    if root is not None:
-        _need_gpu("root", root, torch.float32)
-    if relu_mask is not None:
-        _need_gpu("relu_mask", relu_mask, torch.float32)
-        if tuple(relu_mask.shape) != (n, d_in):
-            raise ValueError(f"relu_mask must be [{n}, {d_in}]")
+    n, r, d_in, d_out = _check_bwd_input(gagg, g, weight, root, relu_mask)
     lib = _L()
     _check_amax("amax_out", amax_out, g.device)
     if d_in % 4 or d_out % 4:
         raise ValueError("in/out channels must be multiples of 4")
     split = _use_split(precision, d_out, 32)
     if split and n > 0:
-        a1, a2 = amax if amax is not None else (None, None)
+        a1, a2 = _pair(amax, 2)
         _check_amax("gagg_amax", a1, g.device)
         _check_amax("g_amax", a2, g.device)
         if packed is not None and not packed.matches(weight, root):
@@ -1181,7 +1195,7 @@ def transform_bwd_input(gagg, g, weight, root=None, relu_mask=None,
             gx = _empty(n, d_in, dtype=torch.float32, device=g.device)
             nbytes = _query("rgcn_transform_split_workspace_bytes", r, d_in, d_out)
             ws = _workspace(nbytes, g.device)
-            with _GemmBracket("bwd_input", n, (r + (root is not None)) * d_out, d_in, "split" if split == 1 else "half"):
+            with _GemmBracket("bwd_input", n, (r + (root is not None)) * d_out, d_in, _split_label(split)):
                 rc = lib.rgcn_transform_bwd_input_split(_ptr(gagg), _ptr(g), _ptr(weight), _ptr(root),
                                                         _ptr(packed.buf) if packed is not None else None,
                                                         _ptr(relu_mask), _mask_for(graph, True, n, r), n, r, d_in,
@@ -1222,23 +1236,11 @@ def transform_bwd_input_chain(gagg, g, weight, root, relu_mask, packed: SplitWei
     ``T = transform_first(gz, packed1)``, conv1's transform-first product (``[N, (R1 + 1) * d_in1]``), computed by the
     SAME launch: every workgroup keeps its 64-row tile of ``gz`` as fp16 hi / lo fragments and multiplies it by conv1's
     weights right away (``rgcn_transform_bwd_input_chain_split``; 47.6-49.5 -> 43.2 us at C2)."""
-    _need_gpu("g", g, torch.float32)
-    _need_gpu("gagg", gagg, torch.float32)
-    _need_gpu("weight", weight, torch.float32)
-    r, d_in, d_out = weight.shape
+    n, r, d_in, d_out = _check_bwd_input(gagg, g, weight, root, relu_mask)
     r1, d_in1, _ = packed1.shape
-    n = g.size(0)
-    if tuple(g.shape) != (n, d_out) or tuple(gagg.shape) != (n, r * d_out):
-        raise ValueError("g must be [N, d_out] and gagg [N, R*d_out]")
-    if root is not None:
-        _need_gpu("root", root, torch.float32)
-    if relu_mask is not None:
-        _need_gpu("relu_mask", relu_mask, torch.float32)
-        if tuple(relu_mask.shape) != (n, d_in):
-            raise ValueError(f"relu_mask must be [{n}, {d_in}]")
     if not packed.matches(weight, root) or packed1.shape[2] != d_in:
         raise ValueError("packed / packed1 do not belong to these layers")
-    a1, a2 = amax if amax is not None else (None, None)
+    a1, a2 = _pair(amax, 2)
     _check_amax("gagg_amax", a1, g.device)
     _check_amax("g_amax", a2, g.device)
     _check_amax("amax_out", amax_out, g.device)
@@ -1280,7 +1282,7 @@ def transform_first(g: torch.Tensor, packed: SplitWeights, amax: Optional[torch.
     with _on(g.device):
         t = _empty(n, (r + int(packed.has_root)) * d_in, dtype=torch.float32, device=g.device)
         ws = _workspace(2048, g.device)
-        with _GemmBracket("bwd_input", n, d_out, t.size(1), "split" if split == 1 else "half"):
+        with _GemmBracket("bwd_input", n, d_out, t.size(1), _split_label(split)):
             rc = lib.rgcn_transform_first_split(_ptr(g), _ptr(packed.buf), int(packed.has_root), n, r, d_in, d_out,
                                                 _ptr(amax), int(split == 2), _ptr(t), _ptr(ws), 2048, _stream())
     _lib.check(rc, "rgcn_transform_first_split")
@@ -1308,13 +1310,13 @@ def transform_bwd_params(agg, x, g, num_relations: int, want_root: bool = True, 
         gbias = _empty(d_out, dtype=torch.float32, device=x.device) if want_bias else None
         split = _use_split(precision, d_in, 64)
         if split and n > 0:
-            a1, a2, a3 = amax if amax is not None else (None, None, None)
+            a1, a2, a3 = _pair(amax, 3)
             for nm, t in (("agg_amax", a1), ("x_amax", a2), ("g_amax", a3)):
                 _check_amax(nm, t, x.device)
             nbytes = _query("rgcn_transform_bwd_params_split_workspace_bytes", n, r, d_in, d_out)
             ws = _workspace(nbytes, x.device)
             job = _lib.SlabJob()
-            with _GemmBracket("bwd_params", (r + want_root) * d_in, n, d_out, "split" if split == 1 else "half"):
+            with _GemmBracket("bwd_params", (r + want_root) * d_in, n, d_out, _split_label(split)):
                 rc = lib.rgcn_transform_bwd_params_split_begin(_ptr(agg), _ptr(x), _ptr(g),
                                                                _mask_for(graph, False, n, r), n, r, d_in, d_out,
                                                                _ptr(a1), float(amax_mul), _ptr(a2), _ptr(a3),

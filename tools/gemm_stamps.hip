@@ -84,7 +84,7 @@ int main() {
                                          nt_ws, stream, nullptr, 0, nullptr); }, name, (int)((N + 63) / 64));
     rgcn_slab_job job;
     snprintf(name, sizeof name, "TN params   [%lld x %lld]^T x [%lld x %lld]", (long long)N, (long long)(K1 + d_in), (long long)N, (long long)d_out);
-    const TnPlan p = tn_plan(N, K1 + d_in, d_out);
+    const rgcn_tn_split p = rgcn_tn_plan(N, K1 + d_in, d_out, TN_TKC, kTnBlocks);
     timed([&] { rgcn_transform_bwd_params_split_begin(agg, x, g, nullptr, N, R, d_in, d_out, aa, 1.f, ax, ag, 0, gw, groot, gbias, ws2,
                                                       tn_ws, stream, &job); }, name, p.kc_tiles * p.n_tiles * p.splits);
     hipFree(agg); hipFree(x); hipFree(g); hipFree(w); hipFree(root); hipFree(bias); hipFree(out); hipFree(gw); hipFree(groot);
