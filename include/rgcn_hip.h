@@ -21,7 +21,8 @@
  *    ("within 1e-5 fp32 of PyG RGCNConv", BASELINE.json north_star).
  *
  * Non-finite values (the training path: gathers, transforms, fused layers, basis composition, the
- * DistMult / BCE head, clip + Adam; the analysis kernels state their own rules).  NaN and +-inf are
+ * DistMult / BCE head, clip + Adam; the analysis kernels state their own rules, link ranking states its
+ * rule at distmult_rank_masked and the top-k list at distmult_topk_masked).  NaN and +-inf are
  * data: they index nothing and no entry point rejects them.  Against a float64 restatement of the same
  * operation (tests/nonfinite_reference.py, enforced by tests/test_nonfinite.py):
  *   1. an entry of an output or gradient that is non-finite under SPARSE semantics - an empty
@@ -551,9 +552,11 @@ int rgcn_adam_clip_step(int num_tensors, float* const* params, const float* cons
 /* Tail ranking for evaluation (LinkPredictor.score_all_tails rgcn.py:215-243 +
  * compute_ranking_metrics evaluate.py:260-276, without materialising the [B, N] score matrix
  * or sorting it): hr = head_emb * rel_emb rows [B, d]; scores[b, n] = <hr[b], emb[n]> on the
- * fp32 MFMA; beaten_by[b] += #{ n != tail[b] : scores[b, n] > true_score[b] } (int atomics into
+ * fp32 MFMA; beaten_by[b] += #{ n != tail[b] : NOT (scores[b, n] <= true_score[b]) } (int atomics into
  * a caller-zeroed buffer), so rank[b] = 1 + beaten_by[b].  d must be a multiple of 32.  The launch of
- * distmult_rank_masked with no mask; a tail outside [0, num_entities) leaves no candidate out. */
+ * distmult_rank_masked with no mask; a tail outside [0, num_entities) leaves no candidate out.  Non-finite values:
+ * the rule stated at distmult_rank_masked - a NaN true score gives rank num_entities (num_entities + 1 when the tail is
+ * outside the range), the worst rank there is. */
 int distmult_rank_tails(const float* hr, const float* emb, const float* true_score,
                         const int64_t* tail, int64_t batch, int64_t num_entities, int64_t d,
                         int32_t* beaten_by, void* stream);
@@ -562,13 +565,29 @@ int distmult_rank_tails(const float* hr, const float* emb, const float* true_sco
  * ranks tails, q = tail_emb * rel_emb ranks heads): the kernel of distmult_rank_tails - one k-tile definition with
  * distmult_score_all_tails on the fp32 MFMA, so a score compared here, there and the one that entry point stores are
  * the same bits - with a candidate filter, typed parameters of the kernel, in the counting epilogue:
- *   beaten_by[b] += #{ n != target[b] : scores[b, n] > true_score[b]
+ *   beaten_by[b] += #{ n != target[b] : NOT (scores[b, n] <= true_score[b])
  *                                       and bit n of allow[query_class[b]] is set   (allow != NULL)
  *                                       and bit n of exclude[b]            is clear (exclude != NULL) }
  * Bit masks over the entities: W = ceil(num_entities / 32) uint32 words per row, entity n is bit (n & 31) of word
  * (n >> 5); allow: [num_classes, W], query_class: int32[batch] (required with allow; a value outside
  * [0, num_classes) allows no candidate), exclude: [batch, W].  Both NULL: exactly distmult_rank_tails.  Integer
- * atomics into the caller-zeroed beaten_by, as there: two runs give the same counts.  d a multiple of 32. */
+ * atomics into the caller-zeroed beaten_by, as there: two runs give the same counts.  d a multiple of 32.
+ *
+ * Non-finite values (the ranking rule; tests/rank_reference.py restates it, tests/test_rank_nonfinite.py enforces it).
+ * Call a candidate n ELIGIBLE for query b when n != target[b], it is allowed and it is not excluded.  An eligible
+ * candidate counts against query b UNLESS scores[b, n] <= true_score[b]:
+ *   - on data without NaN that is scores[b, n] > true_score[b], infinities included: the counts on finite data are
+ *     what they always were, and equal scores do not count (+inf against +inf, -inf against -inf);
+ *   - a NaN candidate counts against every true score - where the reference protocol's descending argsort puts it
+ *     (evaluate.py:266-274: torch orders NaN above every number);
+ *   - a NaN true score is beaten by every eligible candidate: rank[b] = 1 + the number of eligible candidates, with no
+ *     mask and a target in range that is num_entities.  This departs from the reference on purpose: its argsort puts
+ *     a NaN true score first (or anywhere among other NaN scores), and a metric must not improve because a value is
+ *     missing.  So a query whose score row is all NaN - a NaN in q[b], or an embedding table that is all NaN - ranks
+ *     last among its eligible candidates, whatever true_score[b] holds;
+ *   - the counts still do not depend on launch order.
+ * distmult_topk_masked keeps a different rule - a NaN score is never listed - because a list shows answers and a rank
+ * counts threats: a missing score is no answer, but it may not be counted as a win either. */
 int distmult_rank_masked(const float* q, const float* emb, const float* true_score, const int64_t* target,
                          const uint32_t* allow, const int32_t* query_class, int64_t num_classes,
                          const uint32_t* exclude, int64_t batch, int64_t num_entities, int64_t d,
@@ -593,6 +612,9 @@ int rgcn_rank_allow_bits(const int32_t* class_of, int64_t num_entities, int64_t 
  *                             exclude[b] clear (exclude != NULL), scores[b, n] not NaN and >= min_score }
  *   with scores[b, n] = <q[b], emb[n]>, the bits distmult_score_all_tails stores (same operands, tile walk and
  *   accumulation on the fp32 MFMA).  There is no true target: nothing else is left out.  min_score = -INFINITY: none.
+ *   +inf and -inf are scores like any other: +inf candidates come first (by id), a candidate that scores -inf is
+ *   listed with its id behind every finite one (unless min_score strikes it); a query whose scores are all NaN has
+ *   no candidate.  (The ranking count treats NaN differently, see distmult_rank_masked.)
  *   order = score descending, equal scores by entity id ascending (a total order: the result does not depend on
  *   `slices` or on launch order, and two calls return the same bytes).
  *   top_ids int64 [batch, k], top_scores float [batch, k]: the first k candidates in that order; the slots past the

@@ -5,8 +5,12 @@
 //   score[m, n] = <q[m], emb[n]>  - the shared fp32 LDS-DMA k-tile (rgcn_mma_f32_dma.h) with one A operand and one
 //                                   B_BLK block, so a score here, the one distmult_score_all_tails stores
 //                                   (k_gemm_nt_dma<2, B_BLK>) and the one k_topk_select keeps are the same bits
-//   counted     = n < N, n != target[m], score > true_score[m], allowed (allow[query_class[m]]), not excluded
+//   counted     = n < N, n != target[m], NOT (score <= true_score[m]), allowed (allow[query_class[m]]), not excluded
 //                 (exclude[m]); the masks are bit rows, bit (n & 31) of word (n >> 5) - see rank_filter.hip
+//   non-finite  = without NaN "not <=" is ">", infinities included (equal scores do not count: +inf against +inf,
+//                 -inf against -inf), so finite data counts as it always did.  A NaN candidate counts against every
+//                 true score (where torch's descending argsort puts it); a NaN true score is beaten by every eligible
+//                 candidate: rank = 1 + #eligible, never a good rank for a missing value (include/rgcn_hip.h)
 //
 // A workgroup has ONE column tile, so the k loop below is the one-column-tile case of mma_f32_dma::walk_tiles
 // (rgcn_mma_f32_dma.h) written out: same wait, barrier, read_first, stage t + 2, finish - and a change to the wait
@@ -127,7 +131,8 @@ __global__ __launch_bounds__(kThreads) void k_rank_count(const float* __restrict
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int m = m0 + wm * 32 + acc_row(r, lh);
-      const unsigned long long hits = __ballot(m < M && n < N && n != tl[r] && acc[b][r] > ts[r]);
+      // counted UNLESS score <= true score: a NaN on either side counts (the > form would count neither)
+      const unsigned long long hits = __ballot(m < M && n < N && n != tl[r] && !(acc[b][r] <= ts[r]));
       if (li == 0 && m < M) {
         const unsigned mine = lh ? (unsigned)(hits >> 32) : (unsigned)hits;
         const int c = __popc(mine & aw[r] & ~ew[r]);

@@ -45,12 +45,20 @@ class ModelEvaluator:
         self.num_nodes = int(full_graph["num_nodes"])
         self.num_test_edges = int(self.test_edge_index.size(1))
         self._emb = None
+        self.nonfinite_rows = None       # rows of the embedding table with a NaN or an infinity; set by embeddings()
 
     @torch.no_grad()
     def embeddings(self) -> torch.Tensor:
-        """node embeddings of the full graph, encoded once and kept"""
+        """node embeddings of the full graph, encoded once and kept.  The first call counts the rows that hold a NaN or
+        an infinity (``nonfinite_rows``) and warns when there are any: every rank such a row takes part in is then a
+        statement about the missing value, not about the model (a NaN true score ranks last among its eligible
+        candidates, a NaN candidate counts against every true score - ``LinkPredictor.rank_tails``)."""
         if self._emb is None:
             self._emb = self.model.encoder(self.full_edge_index, self.full_edge_type)
+            self.nonfinite_rows = int((~torch.isfinite(self._emb)).any(dim=1).sum())
+            if self.nonfinite_rows:
+                logger.warning("%d of %d node embedding rows hold a NaN or an infinity: the ranking metrics count every "
+                               "such row against the model", self.nonfinite_rows, self._emb.size(0))
         return self._emb
 
     @torch.no_grad()

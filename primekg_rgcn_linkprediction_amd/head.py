@@ -212,7 +212,14 @@ class LinkPredictor(nn.Module):
         ``known`` (with ``head_indices``, the node ids of the heads): the filtered protocol - a candidate ``n`` with
         ``(head, relation, n)`` among the known triples does not count.  ``node_class`` (int ``[N]``): the
         type-constrained protocol - only candidates of the true tail's class count.  Both default to the raw
-        protocol above, through the same kernel as before."""
+        protocol above, through the same kernel as before.
+
+        Non-finite values: an eligible candidate (not the true tail, not known, of the asked class) counts unless its
+        score is ``<=`` the true score.  On data without NaN that is the count above, infinities included.  A NaN
+        candidate counts against every true score, as in the reference's argsort.  A NaN true score - a NaN in the true
+        tail's row, in the head's row or in the relation's - is beaten by every eligible candidate: rank ``1 +
+        #eligible``, raw that is ``N``, where the reference's argsort would put the missing value first.  A model whose
+        table is all NaN ranks every triple last, never first."""
         hr = (head_embeddings * self.relation_embeddings(relation_types)).contiguous()
         emb = all_tail_embeddings.contiguous()
         true_score = (hr * emb[tail_indices]).sum(1)
@@ -229,7 +236,9 @@ class LinkPredictor(nn.Module):
         """1-based rank of ``head_indices[b]`` among all entities for ``(?, relation, tail)``.  DistMult is symmetric
         in head and tail, so this is ``rank_tails``'s pass with ``q = tail * rel``; ``known`` filters by the
         ``(tail, relation)`` sets (``tail_indices``: the node ids of the tails), ``node_class`` restricts the
-        candidates to the true head's class."""
+        candidates to the true head's class.  Non-finite values as in ``rank_tails``: an eligible candidate counts
+        unless its score is ``<=`` the true score, so a NaN candidate counts against every query and a NaN true score
+        ranks ``1 + #eligible``."""
         tr = (tail_embeddings * self.relation_embeddings(relation_types)).contiguous()
         emb = all_head_embeddings.contiguous()
         true_score = (tr * emb[head_indices]).sum(1)

@@ -1636,9 +1636,11 @@ def distmult_bwd(gs, h, h_idx, t, t_idx, r, r_idx, batch: int, grad_h, grad_t, g
 
 def distmult_rank_tails(hr: torch.Tensor, emb: torch.Tensor, true_score: torch.Tensor,
                         tail: torch.Tensor) -> torch.Tensor:
-    """``rank[b] = 1 + #{n != tail[b] : <hr[b], emb[n]> > true_score[b]}`` (int64 [B]): the
+    """``rank[b] = 1 + #{n != tail[b] : not (<hr[b], emb[n]> <= true_score[b])}`` (int64 [B]): the
     rank of the true tail among all entities without the [B, N] score matrix
-    (``evaluate.py:260-276``)."""
+    (``evaluate.py:260-276``).  Without NaN "not <=" is ">", infinities included, and equal scores do not count.  A NaN
+    candidate counts against every true score (torch's descending argsort puts it there too); a NaN true score is beaten
+    by every candidate: rank ``N`` - a missing value never ranks well (the rule of ``distmult_rank_masked``)."""
     _need_gpu("hr", hr, torch.float32)
     _need_gpu("emb", emb, torch.float32)
     _need_gpu("true_score", true_score, torch.float32)
@@ -1859,10 +1861,16 @@ def sample_batch_constrained(edge_index: torch.Tensor, edge_type: torch.Tensor, 
 def distmult_rank_masked(q: torch.Tensor, emb: torch.Tensor, true_score: torch.Tensor, target: torch.Tensor,
                          allow: Optional[torch.Tensor] = None, query_class: Optional[torch.Tensor] = None,
                          exclude: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``rank[b] = 1 + #{n != target[b] : <q[b], emb[n]> > true_score[b], n allowed, n not excluded}`` (int64 [B]):
-    ``distmult_rank_tails`` with the candidate filters in the epilogue (``distmult_rank_masked``).  ``allow`` int32
-    ``[C, W]`` with ``query_class`` int32 ``[B]`` in ``[0, C)``; ``exclude`` int32 ``[B, W]``; both ``None``: exactly
-    ``distmult_rank_tails``."""
+    """``rank[b] = 1 + #{n eligible : not (<q[b], emb[n]> <= true_score[b])}`` (int64 [B]), ``n`` eligible when
+    ``n != target[b]``, allowed and not excluded: ``distmult_rank_tails`` with the candidate filters in the epilogue
+    (``distmult_rank_masked``).  ``allow`` int32 ``[C, W]`` with ``query_class`` int32 ``[B]`` in ``[0, C)``; ``exclude``
+    int32 ``[B, W]``; both ``None``: exactly ``distmult_rank_tails``.
+
+    Non-finite values (``include/rgcn_hip.h``): without NaN the count is ``score > true_score``, infinities included, equal
+    scores do not count - the counts on finite data are unchanged.  A NaN candidate counts against every true score (the
+    reference protocol's argsort order).  A NaN true score is beaten by every eligible candidate: ``rank = 1 +
+    #eligible`` (no mask: ``N``), on purpose unlike the reference, whose argsort would rank the missing value first.
+    ``distmult_topk_masked`` differs: it never lists a NaN score - a list shows answers, a rank counts threats."""
     _need_gpu("q", q, torch.float32)
     _need_gpu("emb", emb, torch.float32)
     _need_gpu("true_score", true_score, torch.float32)
@@ -1901,7 +1909,9 @@ def distmult_rank_filtered(q: torch.Tensor, emb: torch.Tensor, true_score: torch
                            max_mask_bytes: int = 256 << 20) -> torch.Tensor:
     """``distmult_rank_masked`` over all queries with the exclude mask of ``known`` built chunk by chunk: a mask row
     costs ``W * 4`` bytes (62 KB per query at 500k nodes), so the queries are taken in chunks whose mask stays under
-    ``max_mask_bytes``, all through one buffer."""
+    ``max_mask_bytes``, all through one buffer.  The count is ``distmult_rank_masked``'s - an eligible candidate counts
+    unless ``score <= true_score`` - so a NaN candidate counts against every query that does not know it, and a NaN true
+    score gives ``1 +`` the number of eligible (allowed, unknown, not the target) candidates."""
     b = q.size(0)
     if known is None or b == 0:
         return distmult_rank_masked(q, emb, true_score, target, allow, query_class)
@@ -2443,7 +2453,13 @@ def knn(x: torch.Tensor, k: int, slices: int = 0):
     for ``k + 1`` candidates; ``rgcn_knn_refine`` drops the row itself (or, among more than ``k`` duplicates of it, the last
     candidate), recomputes the distances from the differences (duplicates are at exactly 0) and orders the row.  Rows whose
     distances differ by less than the fp32 rounding of the selection key (relative to ``|xc|^2``) may swap places at the
-    k-th position.  ``2 <= k + 1 <= min(M, 128)``."""
+    k-th position.  ``2 <= k + 1 <= min(M, 128)``.
+
+    A row that holds a NaN or an infinity is at no finite distance from any row, and a distance that is not finite
+    orders as +inf (``rgcn_knn_refine``): such a row stands in another row's list only behind every finite-distance
+    neighbour, by id, and its own list is the first ``k`` other ids; its ``sqdist`` entries are +inf or NaN as the
+    differences give them.  The mean the rows are centred at is taken over the finite rows, so that one such row does
+    not spread to all; on finite data nothing changes."""
     _rows_2d("x", x)
     m, d = x.shape
     if d == 0 or d % 32:
@@ -2454,14 +2470,27 @@ def knn(x: torch.Tensor, k: int, slices: int = 0):
     _need_gpu("x", x, torch.float32)
     dev = x.device
     with _on(dev):
-        xc = (x - x.mean(dim=0, keepdim=True)).contiguous()
+        finite = torch.isfinite(x).all(dim=1)
+        some = ~finite.unsqueeze(1)
+        mean_finite = torch.where(some, 0.0, x).sum(dim=0, keepdim=True) / finite.sum().clamp(min=1)
+        mean = torch.where(finite.all(), x.mean(dim=0, keepdim=True), mean_finite)      # all rows finite: x.mean's bits
+        xc = (x - mean).contiguous()
         q = _empty((m, d + 32), dtype=torch.float32, device=dev).zero_()
         e = _empty((m, d + 32), dtype=torch.float32, device=dev).zero_()
         q[:, :d] = xc
         q[:, d] = 1.0
         e[:, :d] = xc
         e[:, d] = (xc * xc).sum(dim=1) * -0.5
+        # every score of a non-finite row NaN, as a query and as an entity: the selection (which never lists a NaN
+        # score) leaves it out; the slots it leaves empty are then filled by id - the non-finite rows for a finite
+        # query, ids 0 .. k for a non-finite one - and rgcn_knn_refine orders them as +inf, behind the rest
+        q.masked_fill_(some, float("nan"))
+        e.masked_fill_(some, float("nan"))
         cand, _ = distmult_topk_masked(q, e, k + 1, slices=slices)
+        slot = torch.arange(k + 1, device=dev).unsqueeze(0)
+        by_id = torch.sort(finite.to(torch.int8), stable=True).indices[:k + 1]      # the non-finite rows first, ids ascending
+        missing = (slot - (cand >= 0).sum(dim=1, keepdim=True)).clamp(min=0)
+        cand = torch.where(cand >= 0, cand, torch.where(some, slot, by_id[missing]))
         ids = _empty((m, k), dtype=torch.int32, device=dev)
         sqdist = _empty((m, k), dtype=torch.float32, device=dev)
         rc = _lib.load().rgcn_knn_refine(_ptr(xc), m, d, _ptr(cand), k, _ptr(ids), _ptr(sqdist), _stream())

@@ -156,6 +156,58 @@ def test_a_nan_centroid_never_wins_a_point():
         assert int(fit.sizes.sum()) == m and np.isfinite(fit.inertia)
 
 
+def test_a_nan_row_gets_the_lowest_id_and_an_infinite_row_the_restatements_label():
+    """M = 130 (two row tiles and a ragged third), d = 32, k = 5, R = 2.  Rows 0, 63, 64 and 129 all NaN, row 5 with one
+    NaN element: every key of such a row is NaN, the label is 0 in every restart; every other row keeps the label it has
+    without the poison, and ``num_changed`` counts exactly the poisoned rows that had another label.  Infinite rows: a
+    key is then -inf, +inf or NaN whatever the precision, so the label is the restatement's, exactly."""
+    dev = need_gpu()
+    m, d, k, restarts = 130, 32, 5, 2
+    x = R.blobs(m, d, seed=4100)
+    init = R.starts(x, k, restarts, seed=9)
+    xd, cd = _t(x, dev), _t(init, dev)
+    clean_dev, changed = ops.kmeans_assign(xd, cd)
+    clean = clean_dev.cpu().numpy()
+    assert changed.tolist() == [m] * restarts
+    bad = [0, 5, 63, 64, 129]
+    others = np.setdiff1d(np.arange(m), bad)
+    xp = x.copy()
+    xp[[0, 63, 64, 129]] = np.nan
+    xp[5, 31] = np.nan
+    labels, changed = ops.kmeans_assign(_t(xp, dev), cd)
+    got = labels.cpu().numpy()
+    assert changed.tolist() == [m] * restarts                                     # no previous labels: every row counts
+    assert (got[:, bad] == 0).all() and np.array_equal(got[:, others], clean[:, others])
+    again, changed = ops.kmeans_assign(_t(xp, dev), cd, labels_prev=clean_dev)
+    moved = [int((clean[r][bad] != 0).sum()) for r in range(restarts)]
+    print(f"NaN rows {bad}: clean labels {clean[:, bad].tolist()}, num_changed {changed.tolist()}")
+    assert sum(moved) > 0                                                          # a condition on the inputs
+    assert torch.equal(again, labels) and changed.tolist() == moved
+    with np.errstate(invalid="ignore"):
+        for r in range(restarts):
+            assert (R.assign(xp, init[r])[0][bad] == 0).all()
+    # infinities: a whole row of +inf, one +inf element, one -inf element, +inf and -inf in one row
+    xq = x.copy()
+    xq[7] = np.inf
+    xq[70, 3] = np.inf
+    xq[100, 5] = -np.inf
+    xq[129, 0], xq[129, 31] = np.inf, -np.inf
+    rows = [7, 70, 100, 129]
+    others = np.setdiff1d(np.arange(m), rows)
+    got = ops.kmeans_assign(_t(xq, dev), cd)[0].cpu().numpy()
+    assert np.array_equal(got[:, others], clean[:, others])
+    seen = set()
+    with np.errstate(invalid="ignore"):
+        for r in range(restarts):
+            key = R.keys(xq[rows], init[r])
+            assert not np.isfinite(key).any()                                      # nothing a rounding could turn
+            want = R.assign(xq, init[r])[0]
+            print(f"restart {r}: infinite rows {rows} -> {got[r][rows].tolist()}, restatement {want[rows].tolist()}")
+            assert np.array_equal(got[r][rows], want[rows])
+            seen |= set(want[rows].tolist())
+    assert len(seen) > 1                                                           # not every such row ends at id 0
+
+
 # ---------------------------------------------------------------------------------- full runs
 def _same_fit(a, b):
     return (torch.equal(a.labels, b.labels) and torch.equal(a.centers, b.centers) and a.inertia == b.inertia

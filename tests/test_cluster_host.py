@@ -235,6 +235,33 @@ def test_restatement_rules_scikit_learn_does_not_have():
     assert R.tol_abs(x, 1e-4) == pytest.approx(1e-4 * x.astype(np.float64).var(0).mean())
 
 
+def test_restated_assignment_of_non_finite_rows():
+    """the inputs of the GPU tier's non-finite assignment case: a row whose keys are all NaN gets the lowest id, an
+    infinite key is a key like any other (-inf wins, +inf loses), equal keys go to the lower id"""
+    x = R.blobs(130, 32, seed=4100)
+    init = R.starts(x, 5, 2, seed=9)
+    for c in init:
+        clean, _ = R.assign(x, c)
+        xp = x.copy()
+        xp[[0, 63, 64, 129]] = np.nan
+        xp[5, 31] = np.nan
+        with np.errstate(invalid="ignore"):
+            labels, _ = R.assign(xp, c)
+            assert np.isinf(R.keys(xp, c)[[0, 5, 63, 64, 129]]).all()
+        bad = [0, 5, 63, 64, 129]
+        others = np.setdiff1d(np.arange(130), bad)
+        assert (labels[bad] == 0).all() and np.array_equal(labels[others], clean[others])
+        xq = x.copy()
+        xq[70, 3] = np.inf                                     # key -inf where the centroid's coordinate is positive
+        xq[100, 5] = -np.inf                                   # ... where it is negative
+        xq[7] = np.inf                                         # inf - inf: every key NaN
+        with np.errstate(invalid="ignore"):
+            labels, _ = R.assign(xq, c)
+        up, down = np.nonzero(c[:, 3] > 0)[0], np.nonzero(c[:, 5] < 0)[0]
+        assert labels[70] == (up[0] if up.size else 0) and labels[100] == (down[0] if down.size else 0) and labels[7] == 0
+    assert sum(int((R.assign(x, c)[0][[0, 5, 63, 64, 129]] != 0).sum()) for c in init) > 0
+
+
 @pytest.mark.parametrize("m,d,k", [(700, 128, 10), (129, 96, 33), (65, 32, 5)])
 def test_restated_silhouette_is_scikit_learns(m, d, k):
     pytest.importorskip("sklearn")

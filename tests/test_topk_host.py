@@ -98,6 +98,50 @@ def test_host_restatement_against_a_brute_force_loop():
     assert 7 in ids[0].tolist() and bool((vals[0][ids[0] >= 0] >= s[0, 7]).all())
 
 
+def test_host_restatement_with_infinite_and_nan_scores():
+    """+inf and -inf are scores like any other, NaN is no candidate: +inf candidates first by id, a -inf candidate after
+    every finite one with its real id, padding (id -1) behind it; a ``min_score`` strikes the -inf candidates."""
+    g = torch.Generator().manual_seed(12)
+    s = torch.randn(8, 45, generator=g)
+    inf = math.inf
+    s[0, [3, 17, 40]] = inf
+    s[1, [0, 44]] = -inf
+    s[2, 5], s[2, 6], s[2, 7] = inf, -inf, math.nan
+    s[3] = math.nan                                              # a NaN row: no candidate at all
+    s[4] = -inf                                                  # every candidate scores -inf: ids ascending
+    s[5] = inf
+    s[6, ::2] = math.nan
+    s[6, 1] = -inf
+    allowed = torch.rand(8, 45, generator=g) < 0.5
+    allowed[0, 17] = False
+    allowed[0, 3] = allowed[0, 40] = allowed[1, 44] = True
+    known = torch.rand(8, 45, generator=g) < 0.3
+    known[1, 0] = known[1, 44] = False
+    for k in (1, 5, 44, 45, 60):
+        for a in (None, allowed):
+            for e in (None, known):
+                for floor in (None, 0.25, -inf, inf):
+                    got, want = restate_topk(s, k, a, e, floor), brute_topk(s, k, a, e, floor)
+                    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), (k, a is None, e is None, floor)
+                    assert not bool(((got[0][:, :-1] < 0) & (got[0][:, 1:] >= 0)).any())       # valid slots come first
+                    assert not bool(torch.isnan(got[1]).any())
+    ids, vals = restate_topk(s, 45)
+    assert ids[0, :3].tolist() == [3, 17, 40] and bool((vals[0, :3] == inf).all())
+    assert ids[1, 43:].tolist() == [0, 44] and bool((vals[1, 43:] == NINF).all()) and bool((vals[1, :43] > NINF).all())
+    assert ids[2, 0] == 5 and ids[2, 43:].tolist() == [6, -1] and 7 not in ids[2].tolist()
+    assert bool((ids[3] == -1).all()) and bool((vals[3] == NINF).all())
+    assert ids[4].tolist() == list(range(45)) and ids[5].tolist() == list(range(45))
+    assert sorted(ids[6, :21].tolist()) == list(range(3, 45, 2)) and ids[6, 21:23].tolist() == [1, -1]
+    assert int((ids[6] >= 0).sum()) == 22
+    ids, vals = restate_topk(s, 60, allowed)
+    assert ids[0, :2].tolist() == [3, 40] and 44 in ids[1].tolist() and bool((ids[:, 45:] == -1).all())
+    # a floor strikes the -inf candidates: the slot holds padding, not an id
+    ids, vals = restate_topk(s, 45, min_score=-1e30)
+    assert ids[1, 43:].tolist() == [-1, -1] and bool((ids[4] == -1).all())
+    ids, _ = restate_topk(s, 45, min_score=inf)
+    assert ids[0, :4].tolist() == [3, 17, 40, -1] and ids[5].tolist() == list(range(45)) and bool((ids[1] == -1).all())
+
+
 def test_exclude_mask_changes_most_top10_lists_of_the_ragged_shapes():
     """the condition the GPU test relies on, from the generators alone (randn scores): 1 - 0.7^10 = 0.97 expected"""
     from topk_reference import RAGGED

@@ -102,6 +102,89 @@ def test_knn_rows_are_the_float64_neighbours(name):
     assert np.array_equal(again[0].cpu().numpy(), ids) and np.array_equal(again[1].cpu().numpy(), sq)
 
 
+def _knn_gate(x):
+    """4 x the fp32 restatement's largest error over the pairs of finite rows, and the float64 distances"""
+    d64 = R.sqdist_matrix(x)
+    fin = np.isfinite(x).all(1)
+    pairs = np.ix_(fin, fin)
+    with np.errstate(invalid="ignore"):
+        err_diff = float(np.abs(R.sqdist_matrix(x, np.float32).astype(np.float64) - d64)[pairs].max())
+        err_key = float(np.abs(R.selection_key_sqdist(x, np.float32) - d64)[pairs].max())
+    return d64, 4 * max(err_diff, err_key)
+
+
+@pytest.mark.parametrize("bad", [0, 63, 64, 129])
+def test_knn_orders_a_nan_row_as_infinitely_far(bad):
+    """M = 130, d = 32, k = 8, row ``bad`` NaN: a NaN distance orders as +inf.  In every other row's list the row could
+    stand only behind all finite-distance neighbours - there are 128 of those, so it is not listed and the list is the
+    float64 list of the finite rows (the gates of ``test_knn_rows_are_the_float64_neighbours``); the NaN row's own
+    list is the first k other ids, ascending, all at a NaN distance.  Both are the restatement's lists."""
+    dev = need_gpu()
+    m, d, k = 130, 32, 8
+    x = R.blobs(m, d, seed=5130)
+    x[bad] = np.nan
+    d64, gate = _knn_gate(x)
+    ids, sq = ops.knn(_t(x, dev), k)
+    ids, sq = ids.cpu().numpy().astype(np.int64), sq.cpu().numpy()
+    want_ids, want_sq = R.knn(x, k)
+    first = [j for j in range(m) if j != bad][:k]
+    assert ids[bad].tolist() == first == want_ids[bad].tolist()
+    assert np.isnan(sq[bad]).all() and np.isnan(want_sq[bad]).all()
+    rest = np.array([i for i in range(m) if i != bad])
+    rows = rest[:, None]
+    assert not (ids[rest] == bad).any() and not (want_ids[rest] == bad).any()
+    assert (ids[rest] >= 0).all() and (ids[rest] < m).all() and not (ids[rest] == rows).any() and np.isfinite(sq[rest]).all()
+    step = np.diff(sq[rest], axis=1)
+    assert (step >= 0).all() and (np.diff(ids[rest], axis=1)[step == 0] > 0).all()          # (sqdist, id) ascending
+    worst = float(np.abs(sq[rest].astype(np.float64) - d64[rows, ids[rest]]).max())
+    others = np.where(np.isnan(d64), np.inf, d64)
+    np.fill_diagonal(others, np.inf)
+    assert worst <= gate
+    kth = np.sort(others[rest], axis=1)[:, k - 1:k]                                # the true k-th distance of every row
+    present = np.zeros((m, m), bool)
+    present[rows, ids[rest]] = True
+    assert present[rest][others[rest] < kth - gate].all() and not present[rest][others[rest] > kth + gate].any()
+    # where the first k + 1 distances of a row are further apart than the gate can bridge no order can flip: there the
+    # list is the restatement's, id by id
+    sure = np.diff(np.sort(others[rest], axis=1)[:, :k + 1], axis=1).min(1) > 2 * gate
+    print(f"NaN row {bad}: gate {gate:.3e}, device {worst:.3e}, {int((~sure).sum())} of {rest.size} rows below the margin, "
+          f"{int((ids[rest] != want_ids[rest]).any(1).sum())} differ")
+    assert (~sure).mean() <= 0.05                                # a condition on the inputs, not a tolerance
+    assert np.array_equal(ids[rest][sure], want_ids[rest][sure])
+    again = ops.knn(_t(x, dev), k)
+    assert np.array_equal(again[0].cpu().numpy(), ids) and np.array_equal(again[1].cpu().numpy(), sq, equal_nan=True)
+
+
+def test_knn_lists_non_finite_rows_last_by_id_when_the_finite_ones_run_out():
+    """M = 12, k = 10, rows 2, 7 and 9 not finite (NaN, one NaN element, one +inf element): a finite row has 8
+    finite-distance neighbours, then the two lowest of {2, 7, 9}; a non-finite row lists the first 10 other ids."""
+    dev = need_gpu()
+    m, d, k = 12, 32, 10
+    x = R.blobs(m, d, seed=5012)
+    x[2] = np.nan
+    x[7, 31] = np.nan
+    x[9, 0] = np.inf
+    d64, gate = _knn_gate(x)
+    ids, sq = ops.knn(_t(x, dev), k)
+    ids, sq = ids.cpu().numpy().astype(np.int64), sq.cpu().numpy()
+    want_ids, want_sq = R.knn(x, k)
+    others = np.where(np.isnan(d64), np.inf, d64)
+    np.fill_diagonal(others, np.inf)
+    fin = np.isfinite(x).all(1)
+    gaps = np.diff(np.sort(others[fin], axis=1)[:, :8], axis=1).min()
+    print(f"gate {gate:.3e}, least gap between neighbouring finite distances {gaps:.3e}; lists {ids.tolist()}")
+    assert gaps > 2 * gate                                       # a condition on the inputs
+    assert np.array_equal(ids, want_ids)
+    for i in range(m):
+        if fin[i]:
+            assert ids[i, 8:].tolist() == [2, 7] and fin[ids[i, :8]].all() and np.isfinite(sq[i, :8]).all()
+            assert not np.isfinite(sq[i, 8:]).any()
+            assert np.abs(sq[i, :8].astype(np.float64) - want_sq[i, :8]).max() <= gate
+        else:
+            assert ids[i].tolist() == [j for j in range(m) if j != i][:k] and not np.isfinite(sq[i]).any()
+    assert np.array_equal(np.isnan(sq), np.isnan(want_sq)) and np.array_equal(np.isinf(sq), np.isinf(want_sq))
+
+
 # ---------------------------------------------------------------------------------- affinities
 @functools.lru_cache(maxsize=None)
 def _device_knn(k):

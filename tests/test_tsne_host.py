@@ -218,6 +218,44 @@ def test_reduce_dimensions_draws_the_references_sample():
         assert np.array_equal(consumers.sample_indices(1000, size, 42), np.arange(1000))
 
 
+def test_restated_neighbours_order_a_non_finite_distance_as_plus_infinity():
+    """the inputs of the GPU tier's two non-finite neighbour cases, against a python sort by ``(distance with NaN as
+    +inf, id)`` over distances taken from the differences of the rows as they are; on finite rows the mean of the
+    finite rows is the mean (the same bits)"""
+    clean = R.blobs(130, 32, seed=5130)
+    assert np.array_equal(R.sqdist_matrix(clean), R.sqdist_matrix(clean.copy()))
+    xc = clean.astype(np.float64) - clean.astype(np.float64).mean(0)
+    assert np.array_equal(R.sqdist_matrix(clean)[3], ((xc - xc[3]) ** 2).sum(1))           # finite data: x.mean, as before
+    cases = []
+    for bad in (0, 63, 64, 129):
+        x = clean.copy()
+        x[bad] = np.nan
+        cases.append((x, 8))
+    x = R.blobs(12, 32, seed=5012)
+    x[2] = np.nan
+    x[7, 31] = np.nan
+    x[9, 0] = np.inf
+    cases.append((x, 10))
+    for x, k in cases:
+        m = x.shape[0]
+        fin = np.isfinite(x).all(1)
+        ids, sq = R.knn(x, k)
+        d2 = R.sqdist_matrix(x)
+        assert np.isfinite(d2[np.ix_(fin, fin)]).all() and not np.isfinite(d2[~fin]).any() and not np.isfinite(d2[:, ~fin]).any()
+        x64 = x.astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            for i in range(m):
+                plain = ((x64 - x64[i]) ** 2).sum(1)               # no centring at all: the same distances up to rounding
+                key = [(np.inf if not np.isfinite(plain[j]) else plain[j], j) for j in range(m) if j != i]
+                assert ids[i].tolist() == [j for _, j in sorted(key)][:k]
+                assert np.array_equal(np.isnan(sq[i]), np.isnan(plain[ids[i]]))
+        for i in np.nonzero(~fin)[0]:
+            assert ids[i].tolist() == [j for j in range(m) if j != i][:k]
+        for i in np.nonzero(fin)[0]:
+            n_fin = min(k, int(fin.sum()) - 1)
+            assert fin[ids[i, :n_fin]].all() and ids[i, n_fin:].tolist() == np.nonzero(~fin)[0][:k - n_fin].tolist()
+
+
 # ---------------------------------------------------------------------------------- the restatement against scikit-learn
 @functools.lru_cache(maxsize=None)
 def _pipeline(m, seed):

@@ -1,8 +1,9 @@
 """Host restatement of the top-k selection, shared by ``test_topk_host.py`` and ``test_topk.py`` (no GPU here).
 
 Candidates of a row: allowed, not known, not NaN, ``>= min_score``.  Order: score descending, equal scores by id
-ascending - what a stable descending sort over ids ``0 .. N-1`` gives.  Output: the first ``k`` candidates, id -1 and
-score -inf past their number (``k > N`` included)."""
+ascending - what a stable descending sort over ids ``0 .. N-1`` gives.  +inf and -inf are scores like any other: a
+candidate that scores -inf (no ``min_score``) is listed with its id after every finite one.  Output: the first ``k``
+candidates, id -1 and score -inf past their number (``k > N`` included)."""
 import numpy as np
 import torch
 
@@ -19,17 +20,22 @@ def restate_topk(scores: torch.Tensor, k: int, allowed=None, known=None, min_sco
     if min_score is not None:
         invalid |= ~(s >= min_score)
     s[invalid] = float("-inf")
-    order = torch.sort(s, dim=1, descending=True, stable=True)
+    # two stable sorts: by score descending (ids ascending among equals), then the candidates in front of the rest -
+    # a candidate that scores -inf keeps its id and stands after every finite one, the padding after it
+    by_score = torch.sort(s, dim=1, descending=True, stable=True).indices
+    front = torch.sort(invalid.gather(1, by_score).to(torch.int8), dim=1, stable=True).indices
+    order = by_score.gather(1, front)
     b, n = s.shape
     ids = torch.full((b, k), -1, dtype=torch.int64)
     vals = torch.full((b, k), float("-inf"), dtype=torch.float32)
     m = min(k, n)
-    idx, val = order.indices[:, :m].clone(), order.values[:, :m].clone()
+    idx = order[:, :m].clone()
+    val = s.gather(1, idx)
     bad = invalid.gather(1, idx)
     idx[bad] = -1
     val[bad] = float("-inf")
     ids[:, :m], vals[:, :m] = idx, val
-    # the candidates come first: an invalid slot is never followed by a valid one (no candidate scores -inf here)
+    # valid slots come first: an invalid slot is never followed by a valid one
     assert not bool(((ids[:, :-1] < 0) & (ids[:, 1:] >= 0)).any())
     return ids, vals
 

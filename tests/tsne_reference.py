@@ -15,13 +15,18 @@ TINY32 = float(np.finfo(np.float32).tiny)
 
 # ---------------------------------------------------------------------------------- neighbours
 def sqdist_matrix(x, dtype=np.float64):
-    """``[M, M]`` squared distances from the differences of the mean-centred rows, summed over the columns in ``dtype``"""
+    """``[M, M]`` squared distances from the differences of the mean-centred rows, summed over the columns in ``dtype``.
+    The mean is that of the rows without a NaN or an infinity (of all rows, on finite data): one such row does not
+    spread to the others; its own distances are +inf or NaN as the differences give them."""
     x = x.astype(dtype)
-    x = x - x.mean(0, dtype=dtype)
+    fin = np.isfinite(x).all(1)
     out = np.empty((x.shape[0], x.shape[0]), dtype)
-    for i in range(x.shape[0]):
-        diff = x - x[i]
-        out[i] = (diff * diff).sum(1, dtype=dtype)
+    with np.errstate(invalid="ignore"):
+        if fin.any():
+            x = x - x[fin].mean(0, dtype=dtype)
+        for i in range(x.shape[0]):
+            diff = x - x[i]
+            out[i] = (diff * diff).sum(1, dtype=dtype)
     return out
 
 
@@ -29,20 +34,23 @@ def selection_key_sqdist(x, dtype=np.float32):
     """what the selection pass orders by, as a squared distance: ``|xc_i|^2 - 2 (<xc_i, xc_j> - |xc_j|^2 / 2)`` with the
     bracket in ``dtype`` (the augmented-row score) and the row's own constant exact"""
     xc = x.astype(dtype)
-    xc = xc - xc.mean(0, dtype=dtype)
+    fin = np.isfinite(xc).all(1)
+    xc = xc - (xc[fin] if fin.any() else xc).mean(0, dtype=dtype)   # the mean of the finite rows, as sqdist_matrix
     sq = (xc * xc).sum(1, dtype=dtype)
     score = xc @ xc.T + (sq * dtype(-0.5))[None, :]
     return (xc.astype(np.float64) ** 2).sum(1)[:, None] - 2.0 * score.astype(np.float64)
 
 
 def knn(x, k, dtype=np.float64):
-    """``(ids [M, k], sqdist [M, k])``: the k nearest other rows, every row ordered by ``(sqdist, id)``"""
+    """``(ids [M, k], sqdist [M, k])``: the k nearest other rows, every row ordered by ``(sqdist, id)``; a NaN distance
+    orders as +inf (equal to an infinite one: the id decides) and is returned as it is"""
     d2 = sqdist_matrix(x, dtype)
+    key = np.where(np.isnan(d2), np.inf, d2)
     m = d2.shape[0]
     ids = np.empty((m, k), np.int64)
     for i in range(m):
         others = np.delete(np.arange(m), i)
-        order = others[np.lexsort((others, d2[i, others]))]
+        order = others[np.lexsort((others, key[i, others]))]
         ids[i] = order[:k]
     return ids, np.take_along_axis(d2, ids, 1)
 
