@@ -13,7 +13,7 @@ from ctypes import c_double, c_float, POINTER, c_char_p, c_int, c_int64, c_size_
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-ABI_VERSION = 33
+ABI_VERSION = 34
 LIB_NAME = "librgcn_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -190,6 +190,16 @@ TSNE_PROTOTYPES = {
     "rgcn_tsne_update": (c_int, [_P, _I64, c_float, c_float, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
+# include/rgcn_neighborhood.h, one to one: local-neighbourhood statistics of node pairs (csrc/neighborhood.hip; not part
+# of rgcn_hip.h, never forwarded by rgcn_sequence_run - an analysis call, outside any recorded Region)
+NEIGHBORHOOD_PROTOTYPES = {
+    "rgcn_neighborhood_max_nodes": (_I64, []),
+    "rgcn_pair_neighborhood": (c_int, [_P, _P, _P, _P, _I64, _I64,                 # structure
+                                       _P, _P, _I64, c_int,                        # queries, radius
+                                       _P, c_int, c_int,                           # node classes, common_cap
+                                       _P, _P, _P, _P, _P, _P, _P, _P]),           # outputs, stream
+}
+
 _lib = None
 
 
@@ -211,7 +221,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise RGCNLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

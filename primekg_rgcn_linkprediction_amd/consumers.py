@@ -31,6 +31,13 @@ and members - ``ops.kmeans`` and ``ops.silhouette_score``, the table never leave
 ``reduce_dimensions`` is ``visualize_embeddings.reduce_dimensions`` (``src/visualize_embeddings.py:176-236``): the
 optional node sample and ``TSNE(n_components=2, perplexity=min(30, n - 1), max_iter=1000)`` - ``ops.tsne``, with exact
 repulsion instead of scikit-learn's Barnes-Hut approximation.
+
+``pair_subgraph_stats`` is ``analyze_failures.analyze_subgraph`` (``src/analyze_failures.py:368-437``) and
+``medical_validation.find_common_neighbors`` (``src/medical_validation.py:356-394``): the radius-2 balls around a drug
+and a disease over successors + predecessors, their intersection and the induced subgraph on their union -
+``ops.pair_neighborhood``, one workgroup per pair.  ``failure_analysis`` is the analysis built on it
+(``analyze_failures.py:273-489``): typing every labelled pair FP / FN / Correct and comparing the groups' structure,
+over all sampled pairs instead of the ten networkx has time for.
 """
 from __future__ import annotations
 
@@ -169,6 +176,149 @@ def connecting_paths(embeddings: Tensor, graph: "ops.PathGraph", pairs, k: int =
     paths = [[{"nodes": nodes[q][j][:length[q][j] + 1], "relations": rel[q][j][:length[q][j]], "length": length[q][j],
                "score": score[q][j]} for j in range(len(length[q])) if length[q][j] > 0] for q in range(len(length))]
     return (paths, count.cpu().tolist()) if return_counts else paths
+
+
+def _class_names(class_names, num_classes: int) -> List[str]:
+    """name of every class id in ``[0, num_classes)``: from ``{name: class id}`` or a sequence indexed by class id; an
+    id without a name is called by its number"""
+    names = [str(c) for c in range(num_classes)]
+    if class_names is None:
+        return names
+    named = class_names.items() if isinstance(class_names, Mapping) else [(n, c) for c, n in enumerate(class_names) if n is not None]
+    for name, cls in named:
+        if 0 <= int(cls) < num_classes:
+            names[int(cls)] = str(name)
+    return names
+
+
+@torch.no_grad()
+def pair_subgraph_stats(graph: "ops.PathGraph", pairs, radius: int = 2, node_class: Optional[Tensor] = None,
+                        class_names=None, common_cap: int = 0) -> List[Dict]:
+    """``analyze_failures.analyze_subgraph`` (``src/analyze_failures.py:368-437``) without its path search, for every
+    ``(drug, disease)`` of ``pairs`` at once (``ops.pair_neighborhood``): a dict per pair with the reference's keys
+    ``drug_neighborhood_size``, ``disease_neighborhood_size``, ``common_neighbors`` (nodes in both radius-``radius``
+    balls), ``subgraph_nodes``, ``subgraph_edges`` (the induced subgraph on the balls' union) and ``node_type_counts``
+    (``{type name: nodes of the union}``, types without a node left out as a ``Counter`` leaves them out, ``"unknown"``
+    for a class outside ``[0, num_classes)``; empty without ``node_class``), plus ``degree`` (``{"drug", "disease"}``:
+    distinct neighbours, the node itself not counted; None at radius 0), ``distance`` (undirected hops when at most
+    ``radius``, else None) and ``common_nodes`` (the ``common_cap`` smallest ids of the intersection, what
+    ``medical_validation.find_common_neighbors`` lists).  A node without any edge is not in the reference's graph: its
+    ball is empty.  ``class_names``: ``{name: class id}`` or a sequence indexed by class id."""
+    dev = graph.device
+    p = torch.as_tensor(pairs, dtype=torch.int64).reshape(-1, 2).to(dev)
+    num_classes, classes = 0, None
+    if node_class is not None:
+        classes = torch.as_tensor(node_class).to(device=dev, dtype=torch.int32).contiguous()
+        num_classes = int(classes.max()) + 1 if classes.numel() else 0
+        if num_classes > ops.NEIGHBORHOOD_MAX_CLASSES:
+            raise ValueError(f"at most {ops.NEIGHBORHOOD_MAX_CLASSES} node classes are counted, got {num_classes}")
+        if num_classes <= 0:
+            classes = None
+    nb = ops.pair_neighborhood(graph, p[:, 0].contiguous(), p[:, 1].contiguous(), radius, classes, max(num_classes, 0), common_cap)
+    names = _class_names(class_names, max(num_classes, 0))
+    ball, distance = nb.ball.cpu().tolist(), nb.distance.cpu().tolist()
+    common, nodes, edges = nb.common.cpu().tolist(), nb.union_nodes.cpu().tolist(), nb.union_edges.cpu().tolist()
+    per_class = None if nb.class_count is None else nb.class_count.cpu().tolist()
+    listed = None if nb.common_nodes is None else nb.common_nodes.cpu().tolist()
+    stats = []
+    for q in range(p.size(0)):
+        types = {}
+        if per_class is not None:
+            types = {names[c]: k for c, k in enumerate(per_class[q]) if k > 0}
+            if nodes[q] > sum(per_class[q]):
+                types["unknown"] = types.get("unknown", 0) + nodes[q] - sum(per_class[q])
+        stats.append({
+            "drug_neighborhood_size": ball[q][0][radius], "disease_neighborhood_size": ball[q][1][radius],
+            "common_neighbors": common[q], "subgraph_nodes": nodes[q], "subgraph_edges": edges[q],
+            "node_type_counts": types,
+            "degree": None if radius < 1 else {"drug": max(ball[q][0][1] - 1, 0), "disease": max(ball[q][1][1] - 1, 0)},
+            "distance": None if distance[q] < 0 else distance[q],
+            "common_nodes": [] if listed is None else [i for i in listed[q] if i >= 0]})
+    return stats
+
+
+def classify_predictions(scores, labels) -> List[Dict]:
+    """The typing of ``analyze_failures.identify_failures_and_successes`` (``src/analyze_failures.py:298-329``) for
+    scores in [0, 1] and labels in {0, 1}, in the reference's own comparisons on Python floats: ``error = |score -
+    label|``; ``confidence_error`` = the score of a negative scored ABOVE 0.7, one minus the score of a positive scored
+    BELOW 0.3, else 0; ``type`` = FP for a negative above 0.5, FN for a positive at or below 0.5, else Correct."""
+    scores = scores.tolist() if hasattr(scores, "tolist") else list(scores)
+    labels = labels.tolist() if hasattr(labels, "tolist") else list(labels)
+    if len(scores) != len(labels):
+        raise ValueError("one label per score expected")
+    rows = []
+    for score, label in zip(scores, labels):
+        score, label = float(score), int(label)
+        if label == 0 and score > 0.7:
+            confidence_error = score
+        elif label == 1 and score < 0.3:
+            confidence_error = 1 - score
+        else:
+            confidence_error = 0
+        rows.append({"prediction": score, "ground_truth": label, "error": abs(score - label),
+                     "confidence_error": confidence_error,
+                     "type": "FP" if (label == 0 and score > 0.5) else ("FN" if (label == 1 and score <= 0.5) else "Correct")})
+    return rows
+
+
+def shortest_path_length(counts) -> Optional[int]:
+    """from ``paths_topk``'s exact counts per length: the smallest L with a path of L edges, else None"""
+    return next((length + 1 for length, c in enumerate(counts) if c > 0), None)
+
+
+_MEAN_KEYS = ("drug_neighborhood_size", "disease_neighborhood_size", "common_neighbors", "subgraph_nodes", "subgraph_edges",
+              "num_paths")
+_DIFFERENCES = (("drug_neighborhood_diff", "drug_neighborhood_size"), ("disease_neighborhood_diff", "disease_neighborhood_size"),
+                ("common_neighbors_diff", "common_neighbors"), ("path_count_diff", "num_paths"))
+
+
+def summarize_failures(rows: List[Dict], num_failures: int = 5, num_successes: int = 5) -> Dict:
+    """``rows``: one dict per pair with ``classify_predictions``' keys and the numeric keys of the stats.  -> the means
+    per type, the reference's four ``differences`` (``compare_failure_with_success``: success minus failure - here
+    between the MEANS of all Correct pairs and of all FP + FN pairs, None when a group is empty), and the reference's
+    selection: rows by confidence error descending (a stable sort: ties keep their order), the first ``num_failures``
+    FP / FN of them, and the ``num_successes`` Correct ones farthest from 0.5."""
+    def means(group):
+        return {"count": len(group), **{k: (sum(r[k] for r in group) / len(group) if group else None) for k in _MEAN_KEYS}}
+
+    by_type = {t: [r for r in rows if r["type"] == t] for t in ("FP", "FN", "Correct")}
+    failed, succeeded = means(by_type["FP"] + by_type["FN"]), means(by_type["Correct"])
+    ranked = sorted(rows, key=lambda r: r["confidence_error"], reverse=True)
+    failures = [r for r in ranked if r["type"] in ("FP", "FN")][:num_failures]
+    correct = [r for r in ranked if r["type"] == "Correct"]
+    successes = sorted(correct, key=lambda r: abs(r["prediction"] - 0.5), reverse=True)[:num_successes]
+    return {"num_pairs": len(rows), "means": {**{t: means(g) for t, g in by_type.items()}, "failure": failed, "success": succeeded},
+            "differences": {name: (succeeded[key] - failed[key] if failed["count"] and succeeded["count"] else None)
+                            for name, key in _DIFFERENCES},
+            "failures": failures, "successes": successes}
+
+
+@torch.no_grad()
+def failure_analysis(embeddings: Tensor, graph: "ops.PathGraph", pairs, labels, radius: int = 2, num_failures: int = 5,
+                     num_successes: int = 5, node_class: Optional[Tensor] = None, class_names=None, common_cap: int = 0,
+                     max_len: int = 4, edge_score: Optional[Tensor] = None) -> Dict:
+    """The reference's failure analysis (``analyze_failures.py:273-489``) over EVERY labelled pair instead of five
+    failures and five successes: every ``(drug, disease)`` of ``pairs`` is scored ``(cos + 1) / 2``
+    (``cosine_pair_scores``) and typed (``classify_predictions``), gets its ``pair_subgraph_stats`` and, from
+    ``ops.paths_topk``'s exact counts, ``path_counts`` (per length 1..4), ``num_paths`` (all simple paths of at most
+    ``max_len`` edges; the reference stops counting at 20) and ``shortest_path_length``.  -> ``summarize_failures`` of
+    those rows: per-type means, the four differences, the worst failures and best successes with their stats."""
+    dev = embeddings.device
+    p = torch.as_tensor(pairs, dtype=torch.int64).reshape(-1, 2).to(dev)
+    graph = graph.to(dev)
+    rows = classify_predictions(cosine_pair_scores(embeddings, p[:, 0], p[:, 1]).cpu(), torch.as_tensor(labels).reshape(-1))
+    if len(rows) != p.size(0):
+        raise ValueError("one label per pair expected")
+    stats = pair_subgraph_stats(graph, p, radius, node_class, class_names, common_cap)
+    if edge_score is None:
+        edge_score = ops.edge_cosine(embeddings.contiguous(), graph)
+    counts = ops.paths_topk(graph, edge_score, p[:, 0].contiguous(), p[:, 1].contiguous(), 1, max_len)[3].cpu().tolist()
+    for row, (drug, disease), stat, count in zip(rows, p.cpu().tolist(), stats, counts):
+        row.update(drug_idx=drug, disease_idx=disease, **stat, path_counts=count, num_paths=sum(count),
+                   shortest_path_length=shortest_path_length(count))
+    result = summarize_failures(rows, num_failures, num_successes)
+    result["radius"], result["max_path_length"] = radius, max_len
+    return result
 
 
 @torch.no_grad()

@@ -193,6 +193,33 @@ class ModelEvaluator:
         return consumers.connecting_paths(emb, self._path_graph, pairs, k, max_len, return_counts=True,
                                           edge_score=self._edge_cosine)
 
+    def _structure(self):
+        """the full graph's ``PathGraph``, built on first use and kept (``explain`` shares it)"""
+        from . import ops
+        if self._path_graph is None:
+            self._path_graph = ops.PathGraph(self.full_edge_index, self.full_edge_type, self.num_nodes)
+        return self._path_graph
+
+    @torch.no_grad()
+    def subgraph_stats(self, pairs, radius: int = 2, class_names=None, common_cap: int = 0):
+        """the structural context of every ``(drug, disease)`` of ``pairs`` in the full graph:
+        ``consumers.pair_subgraph_stats`` on the cached ``PathGraph`` and the evaluator's node classes"""
+        from . import consumers
+        return consumers.pair_subgraph_stats(self._structure(), pairs, radius, self.node_class, class_names, common_cap)
+
+    @torch.no_grad()
+    def failure_analysis(self, pairs, labels, radius: int = 2, num_failures: int = 5, num_successes: int = 5,
+                         class_names=None, common_cap: int = 0, max_len: int = 4):
+        """which labelled ``(drug, disease)`` pairs the embeddings get wrong, and how their neighbourhoods differ from
+        the ones they get right: ``consumers.failure_analysis`` on the cached embeddings, ``PathGraph``, edge cosines
+        and node classes"""
+        from . import consumers, ops
+        graph, emb = self._structure(), self.embeddings()
+        if self._edge_cosine is None:
+            self._edge_cosine = ops.edge_cosine(emb.contiguous(), graph)
+        return consumers.failure_analysis(emb, graph, pairs, labels, radius, num_failures, num_successes, self.node_class,
+                                          class_names, common_cap, max_len, edge_score=self._edge_cosine)
+
     @torch.no_grad()
     def cluster_analysis(self, class_names, n_clusters: int = 10, **kmeans_kw):
         """which nodes of a type the model groups together, and how well separated the groups are:

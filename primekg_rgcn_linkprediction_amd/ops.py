@@ -2151,6 +2151,83 @@ def paths_topk(graph: PathGraph, edge_score: torch.Tensor, sources: torch.Tensor
     return nodes, length, score, count
 
 
+NEIGHBORHOOD_MAX_RADIUS = 4       # RGCN_NEIGHBORHOOD_MAX_RADIUS
+NEIGHBORHOOD_MAX_CLASSES = 32     # RGCN_NEIGHBORHOOD_MAX_CLASSES
+NEIGHBORHOOD_MAX_COMMON = 1024    # RGCN_NEIGHBORHOOD_MAX_COMMON
+NEIGHBORHOOD_HUB_DEGREE = 64      # RGCN_NEIGHBORHOOD_HUB_DEGREE: adjacency rows this long are walked by a whole wave
+
+
+class PairNeighborhood(NamedTuple):
+    ball: torch.Tensor                       # int64 [Q, 2, 5]: |B_j| of the source (0) and the target (1), 0 past the radius
+    distance: torch.Tensor                   # int32 [Q]: undirected hop distance when <= radius, else -1
+    common: torch.Tensor                     # int64 [Q]: nodes in both balls
+    union_nodes: torch.Tensor                # int64 [Q]: nodes in either ball
+    union_edges: torch.Tensor                # int64 [Q]: unique directed pairs inside the union
+    class_count: Optional[torch.Tensor]      # int64 [Q, num_classes], None without node classes
+    common_nodes: Optional[torch.Tensor]     # int32 [Q, common_cap]: smallest common ids ascending, then -1; None for cap 0
+
+
+def neighborhood_max_nodes() -> int:
+    """the largest ``PathGraph.num_nodes`` ``pair_neighborhood`` takes (its bitsets live in a workgroup's LDS)"""
+    return _query("rgcn_neighborhood_max_nodes")
+
+
+def pair_neighborhood(graph: PathGraph, sources: torch.Tensor, targets: torch.Tensor, radius: int = 2,
+                      node_class: Optional[torch.Tensor] = None, num_classes: int = 0,
+                      common_cap: int = 0) -> PairNeighborhood:
+    """The radius-``radius`` balls around ``sources[q]`` and ``targets[q]`` over successors + predecessors, their
+    intersection, and the induced subgraph on their union (``rgcn_pair_neighborhood``, ``include/rgcn_neighborhood.h``:
+    the reference's ``analyze_subgraph`` for a whole batch).  A node without any edge, or an id outside
+    ``[0, num_nodes)``, has empty balls - it is not in the reference's networkx graph.  ``node_class`` int32 ``[N]``
+    with ``num_classes`` in 1..32 adds the union's nodes per class; ``common_cap`` in 1..1024 the smallest ids of the
+    intersection.  Every count is exact and does not depend on scheduling."""
+    radius, num_classes, common_cap = int(radius), int(num_classes), int(common_cap)
+    if not 0 <= radius <= NEIGHBORHOOD_MAX_RADIUS:
+        raise ValueError(f"radius must be in [0, {NEIGHBORHOOD_MAX_RADIUS}], got {radius}")
+    if not 0 <= num_classes <= NEIGHBORHOOD_MAX_CLASSES:
+        raise ValueError(f"num_classes must be in [0, {NEIGHBORHOOD_MAX_CLASSES}], got {num_classes}")
+    if not 0 <= common_cap <= NEIGHBORHOOD_MAX_COMMON:
+        raise ValueError(f"common_cap must be in [0, {NEIGHBORHOOD_MAX_COMMON}], got {common_cap}")
+    if not isinstance(graph, PathGraph):
+        raise TypeError("graph must be an ops.PathGraph")
+    _need_gpu("sources", sources, torch.int64)
+    _need_gpu("targets", targets, torch.int64)
+    dev = sources.device
+    for name, t, dtype in graph._arrays()[:4]:
+        _need_gpu(f"graph.{name}", t, dtype)
+        if t.device != dev:
+            raise ValueError(f"graph.{name} is on {t.device}, sources on {dev}")
+    if sources.dim() != 1 or sources.shape != targets.shape or targets.device != dev:
+        raise ValueError("sources [Q] and targets [Q] on the graph's device expected")
+    classes = node_class is not None and num_classes > 0
+    if classes:
+        _need_gpu("node_class", node_class, torch.int32)
+        if node_class.shape != (graph.num_nodes,) or node_class.device != dev:
+            raise ValueError(f"node_class [{graph.num_nodes}] on the graph's device expected")
+    lib = _L()
+    if graph.num_nodes > neighborhood_max_nodes():
+        raise ValueError(f"pair_neighborhood keeps its bitsets in LDS: at most {neighborhood_max_nodes()} nodes, got {graph.num_nodes}")
+    q = sources.numel()
+    with _on(dev):
+        ball = _empty((q, 2, NEIGHBORHOOD_MAX_RADIUS + 1), dtype=torch.int64, device=dev)
+        distance = _empty(q, dtype=torch.int32, device=dev)
+        common = _empty(q, dtype=torch.int64, device=dev)
+        union_nodes = _empty(q, dtype=torch.int64, device=dev)
+        union_edges = _empty(q, dtype=torch.int64, device=dev)
+        class_count = _empty((q, num_classes), dtype=torch.int64, device=dev) if classes else None
+        common_nodes = _empty((q, common_cap), dtype=torch.int32, device=dev) if common_cap > 0 else None
+        result = PairNeighborhood(ball, distance, common, union_nodes, union_edges, class_count, common_nodes)
+        if q == 0:
+            return result
+        rc = lib.rgcn_pair_neighborhood(_ptr(graph.out_ptr), _ptr(graph.out_dst), _ptr(graph.in_ptr), _ptr(graph.in_src),
+                                        graph.num_nodes, graph.nnz, _ptr(sources), _ptr(targets), q, radius,
+                                        _ptr(node_class) if classes else None, num_classes, common_cap, _ptr(ball),
+                                        _ptr(distance), _ptr(common), _ptr(union_nodes), _ptr(union_edges),
+                                        _ptr(class_count), _ptr(common_nodes), _stream())
+    _lib.check(rc, "rgcn_pair_neighborhood")
+    return result
+
+
 CLUSTER_MAX_K = 64            # RGCN_CLUSTER_MAX_K: two 32-column blocks per restart, 32 KB of sums per update workgroup
 CLUSTER_MAX_RESTARTS = 1024   # RGCN_CLUSTER_MAX_RESTARTS
 
