@@ -65,7 +65,7 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 34
+#define RGCN_ABI_VERSION 35
 
 enum {
   RGCN_OK = 0,

@@ -8,7 +8,7 @@ behind a C ABI (``include/rgcn_hip.h`` -> ``librgcn_hip.so``).  See DESIGN.md.
 from .conv import RGCNConv, rgcn_conv, rgcn_encoder2, rgcn_encoder2_step
 from .head import LinkPredictor, distmult
 from .model import DrugDiseaseModel, DrugDiseaseRGCN
-from . import consumers, ops, synth
+from . import baselines, consumers, ops, synth
 
 __all__ = ["RGCNConv", "rgcn_conv", "rgcn_encoder2", "rgcn_encoder2_step", "LinkPredictor", "distmult", "DrugDiseaseModel",
-           "DrugDiseaseRGCN", "consumers", "ops", "synth"]
+           "DrugDiseaseRGCN", "baselines", "consumers", "ops", "synth"]

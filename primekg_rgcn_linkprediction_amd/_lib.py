@@ -13,7 +13,7 @@ from ctypes import c_double, c_float, POINTER, c_char_p, c_int, c_int64, c_size_
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-ABI_VERSION = 34
+ABI_VERSION = 35
 LIB_NAME = "librgcn_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -200,6 +200,15 @@ NEIGHBORHOOD_PROTOTYPES = {
                                        _P, _P, _P, _P, _P, _P, _P, _P]),           # outputs, stream
 }
 
+# include/rgcn_transe.h, one to one: one batch-synchronous TransE training step (csrc/transe.hip; not part of
+# rgcn_hip.h, never forwarded by rgcn_sequence_run - the baseline trains outside any recorded Region)
+TRANSE_PROTOTYPES = {
+    "rgcn_transe_step_workspace_bytes": (c_size_t, [_I64, _I64, _I64]),
+    "rgcn_transe_step": (c_int, [_P, _I64, _P, _I64, _I64,                         # tables
+                                 _P, _P, _P, _I64, c_float, c_float,               # batch, lr, margin
+                                 _P, _P, _P, _P, c_size_t, _P]),                   # loss outputs, workspace, stream
+}
+
 _lib = None
 
 
@@ -221,7 +230,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise RGCNLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -232,6 +232,22 @@ class ModelEvaluator:
         return consumers.cluster_analysis(self.embeddings(), self.node_class, class_names, n_clusters, **kmeans_kw)
 
     @torch.no_grad()
+    def compare_methods(self, train_data: Dict, methods: Sequence[str] = ("random", "degree", "transe", "rgcn"),
+                        k_values: Sequence[int] = (1, 5, 10, 20, 50), filtered: bool = False, type_constrained: bool = False,
+                        both_sides: bool = False, transe_epochs: int = 50, seed: int = 0, drug_class: Optional[int] = None,
+                        disease_class: Optional[int] = None, **transe_kwargs) -> Dict:
+        """this model next to the Random, Node Degree and TransE baselines (``baselines.py``, fitted on ``train_data``),
+        every method under one ranking protocol on the test triples and one set of labelled per-triple scores:
+        ``compare.compare_methods`` on the evaluator's test set, full graph and node classes"""
+        from . import compare
+        test = {"edge_index": self.test_edge_index, "edge_type": self.test_edge_type}
+        full = {"edge_index": self.full_edge_index, "edge_type": self.full_edge_type, "num_nodes": self.num_nodes,
+                "num_relations": self.model.decoder.num_relations}
+        return compare.compare_methods(train_data, test, full, self.device, self.model, self.node_class, methods, k_values,
+                                       filtered, type_constrained, both_sides, transe_epochs, seed, drug_class,
+                                       disease_class, transe_kwargs or None)
+
+    @torch.no_grad()
     def reduce_dimensions(self, method: str = "tsne", sample_size: Optional[int] = None, random_state: int = 42, **tsne_kw):
         """the 2-D t-SNE projection of (a sample of) the cached embeddings, on the device:
         ``consumers.reduce_dimensions`` -> ``(xy float32 [n, 2], sample_indices [n])`` (and the ``ops.TSNEResult`` with

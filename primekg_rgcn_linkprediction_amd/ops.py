@@ -2228,6 +2228,85 @@ def pair_neighborhood(graph: PathGraph, sources: torch.Tensor, targets: torch.Te
     return result
 
 
+def transe_step(emb: torch.Tensor, rel: torch.Tensor, heads: torch.Tensor, tails: torch.Tensor, rels: torch.Tensor,
+                batch: int, lr: float, margin: float, loss_sum: Optional[torch.Tensor] = None,
+                active_sum: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One batch-synchronous TransE step (``rgcn_transe_step``, ``include/rgcn_transe.h``): margin loss ``max(0, margin +
+    |h + r - t| - |h' + r - t'|)`` over ``batch`` positives and their corruptions, and the SGD update of ``emb`` (float32
+    ``[N, d]``) and ``rel`` (float32 ``[R, d]``) IN PLACE - every difference from the tables as the call finds them, a
+    row's contributions added in slot order and applied once, the entity rows that moved divided by their norm, all others
+    bit for bit as they were.  ``heads`` / ``tails`` / ``rels`` are the int64 ``[2 * batch]`` vectors of
+    ``sample_batch(num_neg=1)``.  Returns the mean loss (float32 ``[1]``, on the device); ``loss_sum`` (float64 ``[1]``)
+    and ``active_sum`` (int64 ``[1]``) accumulate it and the number of samples with a positive loss over calls.  An id
+    outside its table is clamped and surfaces at the next ``check_indices``.  Deterministic: no float atomics."""
+    _need_gpu("emb", emb, torch.float32)
+    _need_gpu("rel", rel, torch.float32)
+    batch = int(batch)
+    if batch < 0:
+        raise ValueError(f"batch must be >= 0, got {batch}")
+    if emb.dim() != 2 or emb.size(0) == 0 or emb.size(1) == 0 or emb.size(1) % 4:
+        raise ValueError("emb must be [N, d] with N > 0 and d a positive multiple of 4")
+    dev, d = emb.device, emb.size(1)
+    if rel.dim() != 2 or rel.size(0) == 0 or rel.size(1) != d or rel.device != dev:
+        raise ValueError(f"rel must be [R, {d}] with R > 0, on emb's device")
+    for name, t in (("heads", heads), ("tails", tails), ("rels", rels)):
+        _need_gpu(name, t, torch.int64)
+        if t.shape != (2 * batch,) or t.device != dev:
+            raise ValueError(f"{name} must be [{2 * batch}] (batch positives, then their corruptions) on emb's device")
+    for name, t, dtype in (("loss_sum", loss_sum, torch.float64), ("active_sum", active_sum, torch.int64)):
+        if t is not None:
+            _need_gpu(name, t, dtype)
+            if t.numel() != 1 or t.device != dev:
+                raise ValueError(f"{name} must hold one {dtype} on emb's device")
+    lib = _L()
+    with _on(dev):
+        loss_mean = _empty(1, dtype=torch.float32, device=dev)
+        if batch == 0:
+            return loss_mean.fill_(float("nan"))                 # the mean of no losses
+        nbytes = _query("rgcn_transe_step_workspace_bytes", batch, d, rel.size(0))
+        ws = _workspace(nbytes, dev)
+        rc = lib.rgcn_transe_step(_ptr(emb), emb.size(0), _ptr(rel), rel.size(0), d, _ptr(heads), _ptr(tails), _ptr(rels),
+                                  batch, float(lr), float(margin), _ptr(loss_mean), _ptr(loss_sum), _ptr(active_sum),
+                                  _ptr(ws), nbytes, _stream())
+    _lib.check(rc, "rgcn_transe_step")
+    return loss_mean
+
+
+def transe_rank_operands(emb: torch.Tensor, rel: torch.Tensor, anchor_idx: torch.Tensor, rel_idx: torch.Tensor,
+                         side: str = "tail"):
+    """The operands that make the fused ranking and top-k passes order candidates by TransE distance:
+    ``(q [B, D], cand [N, D], true_score_fn)`` with ``D`` the next multiple of 32 past ``d``.  Query rows are
+    ``[h + r, -1/2, 0 ...]`` (``side="tail"``: the tails of ``(anchor, rel, ?)``) or ``[t - r, -1/2, 0 ...]``
+    (``side="head"``), candidate rows ``[e, |e|^2, 0 ...]``, so ``<q_b, cand_n> = (|q_b|^2 - |q_b - e_n|^2) / 2``: per
+    query monotone in minus the squared distance - the device of ``knn``.  ``distmult_rank_masked``,
+    ``distmult_rank_filtered`` and ``distmult_topk_masked`` / ``_filtered`` take ``q`` and ``cand`` as they are, known-triple
+    and node-class masks included; ``true_score_fn(target int64 [B])`` is the score of the true answers."""
+    if side not in ("tail", "head"):
+        raise ValueError("side must be 'tail' or 'head'")
+    _need_gpu("emb", emb, torch.float32)
+    _need_gpu("rel", rel, torch.float32)
+    _need_gpu("anchor_idx", anchor_idx, torch.int64)
+    _need_gpu("rel_idx", rel_idx, torch.int64)
+    if emb.dim() != 2 or rel.dim() != 2 or rel.size(1) != emb.size(1):
+        raise ValueError("emb [N, d] and rel [R, d] expected")
+    if anchor_idx.dim() != 1 or rel_idx.shape != anchor_idx.shape:
+        raise ValueError("anchor_idx [B] and rel_idx [B] expected")
+    dev, (n, d), b = emb.device, emb.shape, anchor_idx.numel()
+    width = (d + 1 + 31) // 32 * 32
+    with _on(dev):
+        q = _empty((b, width), dtype=torch.float32, device=dev).zero_()
+        cand = _empty((n, width), dtype=torch.float32, device=dev).zero_()
+        q[:, :d] = emb[anchor_idx] + rel[rel_idx] if side == "tail" else emb[anchor_idx] - rel[rel_idx]
+        q[:, d] = -0.5
+        cand[:, :d] = emb
+        cand[:, d] = (emb * emb).sum(dim=1)
+
+    def true_score_fn(target: torch.Tensor) -> torch.Tensor:
+        return (q * cand[target]).sum(dim=1)
+
+    return q, cand, true_score_fn
+
+
 CLUSTER_MAX_K = 64            # RGCN_CLUSTER_MAX_K: two 32-column blocks per restart, 32 KB of sums per update workgroup
 CLUSTER_MAX_RESTARTS = 1024   # RGCN_CLUSTER_MAX_RESTARTS
 
