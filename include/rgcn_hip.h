@@ -15,6 +15,35 @@
  *    no host<->device copy (HIP-graph capturable), EXCEPT rgcn_graph_create /
  *    rgcn_graph_destroy, the one-time bucketing of a static graph.
  *  - inputs are borrowed and never written; outputs are caller-allocated.
+ *  - Alignment.  The kernels read and write the caller's memory in pieces of up to 16 bytes (float4, uint4 on the
+ *    fp16 images, 16-byte LDS DMA in the shared tile walk), so a pointer's BASE ADDRESS must be a multiple of the
+ *    widest single access made through it, and at least of its element size.  Every entry point checks this on the
+ *    host - after its other argument checks, before its first HIP runtime call - and returns RGCN_ERR_ALIGN.  NULL
+ *    (an optional operand) always passes.  The same rule covers the headers next to this one.
+ *
+ *      required   operands
+ *      --------   --------------------------------------------------------------------------------------------
+ *         16      every feature / embedding / aggregate table, fp32 or fp16 (x, agg, gagg, g, h, t, r, emb, q, hr,
+ *                 head, rel, rows, hub_agg, hub_partial), every weight, root, bias, basis and ReLU mask, every
+ *                 output or gradient of the same shapes (out, grad_x, t_out, grad_weight, grad_root, grad_bias,
+ *                 grad_h, grad_t, grad_r, grad_basis), `packed` images, every `workspace`, the pointer fields of
+ *                 an rgcn_slab_job, and the entries of the HOST arrays of rgcn_absmax_multi (tensors),
+ *                 rgcn_absmax_pack and rgcn_weights_split_pack_multi (weights, roots, packed)
+ *          8      int64 index vectors and CSR pointers (h_idx, t_idx, r_idx, rel_idx, edge_index, edge_type, order,
+ *                 ptr, ids, seg, target, tail, perm, top_ids, heads, tails, rels), int64 / double scalars and
+ *                 counters (cursor, rng, loss_sum, correct)
+ *          4      amax buffers (their heads are written one word at a time), tile_mask, allow / exclude /
+ *                 query_class / class_of words, int32 CSR arrays (rowptr, col, w_t of the fused layers and of
+ *                 rgcn_graph_import / _export), per-sample float vectors (scores, labels, loss, true_score,
+ *                 grad_scores, top_scores, beaten_by), one-element outputs (mean_loss, grad_mean_loss,
+ *                 total_norm), comp / grad_comp, the [batch, num_entities] scores of distmult_score_all_tails, and
+ *                 EVERYTHING rgcn_adam_clip_step takes: its kernels choose float4 or element-wise access from
+ *                 the address themselves
+ *
+ *    Row pitch: operands read in 16-byte pieces have rows of d * 4 (fp32) or d * 2 (fp16) bytes, and the d % 4 /
+ *    d % 8 / d % 32 checks of each entry point make that a multiple of 16, so every ROW of an aligned table is
+ *    aligned and a row slice table[i:j] qualifies.  Whatever torch.empty (or hipMalloc) returns qualifies; a view
+ *    that starts some ELEMENTS into a flat buffer (flat[1 : 1 + n * d].view(n, d)) does not: copy it first.
  *  - return value: RGCN_OK (0) or a negative RGCN_ERR_* code; rgcn_strerror() names it.
  *    Nothing aborts the process.
  *  - feature dims must be multiples of 4 floats (16-byte rows); fp32 throughout
@@ -65,7 +94,7 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 35
+#define RGCN_ABI_VERSION 36
 
 enum {
   RGCN_OK = 0,
@@ -73,7 +102,8 @@ enum {
   RGCN_ERR_RANGE = -2,        /* node id outside [0,N) or relation id outside [0,R) */
   RGCN_ERR_HIP = -3,          /* a HIP runtime call failed */
   RGCN_ERR_UNSUPPORTED = -4,  /* shape outside what the kernels were built for */
-  RGCN_ERR_WORKSPACE = -5     /* workspace pointer null or too small */
+  RGCN_ERR_WORKSPACE = -5,    /* workspace pointer null or too small */
+  RGCN_ERR_ALIGN = -6         /* a pointer's base address is below the alignment its entry point needs (see Alignment) */
 };
 
 int rgcn_abi_version(void);

@@ -13,7 +13,7 @@ from ctypes import c_double, c_float, POINTER, c_char_p, c_int, c_int64, c_size_
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-ABI_VERSION = 35
+ABI_VERSION = 36
 LIB_NAME = "librgcn_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -23,6 +23,7 @@ RGCN_ERR_RANGE = -2
 RGCN_ERR_HIP = -3
 RGCN_ERR_UNSUPPORTED = -4
 RGCN_ERR_WORKSPACE = -5
+RGCN_ERR_ALIGN = -6
 
 _P = c_void_p      # device pointers travel as integers (tensor.data_ptr())
 _I64 = c_int64
@@ -265,4 +266,8 @@ def check(code: int, what: str) -> None:
         raise IndexError(msg)
     if code in (RGCN_ERR_ARG, RGCN_ERR_UNSUPPORTED):
         raise ValueError(msg)
+    if code == RGCN_ERR_ALIGN:
+        raise ValueError(f"{what}: a tensor's base address is not aligned: {strerror(code)} (code {code}). Every tensor "
+                         f"torch allocates qualifies, and so do row slices of a table whose width is a multiple of 4; a "
+                         f"view that starts some elements into a flat buffer does not - pass tensor.clone()")
     raise RuntimeError(msg)

@@ -465,6 +465,8 @@ int rgcn_kmeans_assign(const float* x, int64_t M, int64_t d, const float* centro
   if (!x || !centroids || !labels || !num_changed) return RGCN_ERR_ARG;
   const KmeansPlan p = plan_kmeans(M, d, R, k);
   if (!ws || ws_bytes < p.bytes) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(16, x, centroids, ws);          // rows and centroids stream in 16-byte DMA pieces
+  RGCN_ALIGN_TRY(4, labels_prev, labels, num_changed, done);
   hipStream_t stream = (hipStream_t)stream_;
   static bool raised[64] = {};
   const int rc = raise_lds(k_assign, STAGE_BYTES, raised);
@@ -495,6 +497,8 @@ int rgcn_kmeans_update(const float* x, int64_t M, int64_t d, float* centroids, i
   if (!x || !centroids || !labels || !num_changed || !counts || !shift2 || !num_iter) return RGCN_ERR_ARG;
   const KmeansPlan p = plan_kmeans(M, d, R, k);
   if (!ws || ws_bytes < p.bytes) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(16, x, centroids, ws);
+  RGCN_ALIGN_TRY(4, labels, num_changed, counts, shift2, num_iter, done);
   hipStream_t stream = (hipStream_t)stream_;
   char* w = (char*)ws;
   float* part = (float*)(w + p.o_part);
@@ -518,6 +522,9 @@ int rgcn_kmeans_inertia(const float* x, int64_t M, int64_t d, const float* centr
   if (!x || !centroids || !labels || !inertia) return RGCN_ERR_ARG;
   const KmeansPlan p = plan_kmeans(M, d, R, k);
   if (!ws || ws_bytes < p.bytes) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(16, x, centroids, ws);
+  RGCN_ALIGN_TRY(8, inertia);
+  RGCN_ALIGN_TRY(4, labels);
   hipStream_t stream = (hipStream_t)stream_;
   double* ipart = (double*)((char*)ws + p.o_ipart);
   k_inertia_partial<<<dim3((unsigned)p.ichunks, (unsigned)R), 256, 0, stream>>>(x, centroids, labels, (int)M, (int)d, (int)k, ipart);
@@ -540,6 +547,9 @@ int rgcn_silhouette_samples(const float* x, const float* xs, const int32_t* col_
   if (!x || !xs || !col_row || !blk_cluster || !counts || !labels || !s || !mean) return RGCN_ERR_ARG;
   const SilPlan p = plan_silhouette(M, Mp, k, slices);
   if (!ws || ws_bytes < p.bytes) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(16, x, xs, ws);
+  RGCN_ALIGN_TRY(8, mean);
+  RGCN_ALIGN_TRY(4, col_row, blk_cluster, counts, labels, s);
   hipStream_t stream = (hipStream_t)stream_;
   static bool raised[64] = {};
   const int rc = raise_lds(k_silhouette, STAGE_BYTES, raised);

@@ -271,6 +271,9 @@ int distmult_fwd(const float* h, const int64_t* h_idx, int64_t h_rows, const flo
   if (batch < 0 || d <= 0 || (d & 3) || h_rows < 0 || t_rows < 0 || r_rows < 0) return RGCN_ERR_ARG;
   if (batch == 0) return RGCN_OK;
   if (!h || !t || !r || !scores) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(16, h, t, r);
+  RGCN_ALIGN_TRY(8, h_idx, t_idx, r_idx);
+  RGCN_ALIGN_TRY(4, scores);
   hipStream_t stream = (hipStream_t)stream_;
   const int g = pick_group(d);
   const unsigned grid = (unsigned)ceil_div64(batch, kThreads / g);
@@ -286,6 +289,9 @@ int distmult_bce_fwd(const float* h, const int64_t* h_idx, int64_t h_rows, const
   if (batch < 0 || d <= 0 || (d & 3) || h_rows < 0 || t_rows < 0 || r_rows < 0) return RGCN_ERR_ARG;
   if (batch == 0) return RGCN_OK;
   if (!h || !t || !r || !labels || !scores || !loss) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(16, h, t, r);
+  RGCN_ALIGN_TRY(8, h_idx, t_idx, r_idx);
+  RGCN_ALIGN_TRY(4, labels, scores, loss);
   hipStream_t stream = (hipStream_t)stream_;
   const int g = pick_group(d);
   const unsigned grid = (unsigned)ceil_div64(batch, kThreads / g);
@@ -299,6 +305,8 @@ int distmult_bce_reduce(const float* loss, const float* scores, const float* lab
                         double* loss_sum, int64_t* correct, int64_t* cursor, int64_t cursor_add, void* stream_) {
   if (batch <= 0 || !loss || !mean_loss || (correct && (!scores || !labels))) return RGCN_ERR_ARG;
   if (batch > INT32_MAX / 2) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(4, loss, scores, labels, mean_loss);
+  RGCN_ALIGN_TRY(8, loss_sum, correct, cursor);
   k_bce_reduce<<<1, 1024, 0, (hipStream_t)stream_>>>(loss, scores, labels, (int)batch, mean_loss, loss_sum,
                                                      reinterpret_cast<long long*>(correct), reinterpret_cast<long long*>(cursor),
                                                      (long long)cursor_add);
@@ -337,6 +345,9 @@ int bwd_impl(const float* gs, const float* scores, const float* labels, const fl
   if (!gs || !h || !t || !r) return RGCN_ERR_ARG;
   if (batch > INT32_MAX / 4 || h_rows > INT32_MAX || t_rows > INT32_MAX || r_rows > INT32_MAX) return RGCN_ERR_UNSUPPORTED;
   if (!workspace || workspace_bytes < distmult_bwd_workspace_bytes(batch, d, r_idx ? r_rows : 0)) return RGCN_ERR_WORKSPACE;
+  RGCN_ALIGN_TRY(16, h, t, r, grad_h, grad_t, grad_r, workspace);
+  RGCN_ALIGN_TRY(8, h_idx, t_idx, r_idx);
+  RGCN_ALIGN_TRY(4, gs, scores, labels);
   float* ws = (float*)workspace;
   const size_t bd = (size_t)batch * d;
   float *ch = ws, *ct = ws + bd, *cr = ws + 2 * bd;
@@ -427,6 +438,8 @@ int rgcn_segment_sum(const float* rows, const int64_t* idx, int64_t batch, int64
   if (!rows || !idx) return RGCN_ERR_ARG;
   if (batch > INT32_MAX / 4 || num_rows > INT32_MAX) return RGCN_ERR_UNSUPPORTED;
   if (!workspace || workspace_bytes < rgcn_segment_sum_workspace_bytes(batch, d, num_rows)) return RGCN_ERR_WORKSPACE;
+  RGCN_ALIGN_TRY(16, rows, out, workspace);
+  RGCN_ALIGN_TRY(8, idx);
   const int64_t nseg = ceil_div64(batch, segment_len(batch));
   float* partial = (float*)workspace;
   int32_t* keys = (int32_t*)(partial + (size_t)nseg * num_rows * d);

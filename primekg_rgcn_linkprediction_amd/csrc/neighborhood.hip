@@ -265,6 +265,9 @@ int rgcn_pair_neighborhood(const int64_t* out_ptr, const int32_t* out_dst, const
   if (nnz > 0 && (!out_dst || !in_src)) return RGCN_ERR_ARG;
   const bool classes = node_class && num_classes > 0;
   if ((classes && !class_count) || (common_cap > 0 && !common_nodes)) return RGCN_ERR_ARG;
+  // every operand is an index or count vector walked one element at a time: natural alignment
+  RGCN_ALIGN_TRY(8, out_ptr, in_ptr, sources, targets, ball, common, union_nodes, union_edges, class_count);
+  RGCN_ALIGN_TRY(4, out_dst, in_src, node_class, distance, common_nodes);
   static bool raised[64] = {};
   const int rc = raise_lds(k_pair_neighborhood, kMaxWords * kBitsets * 4, raised);
   if (rc != RGCN_OK) return rc;

@@ -193,6 +193,9 @@ int rgcn_adam_clip_step(int num_tensors, float* const* params, const float* cons
   L.first_block[num_tensors] = blocks;
   L.count = num_tensors;
   if (!workspace || workspace_bytes < (size_t)blocks * sizeof(float)) return RGCN_ERR_WORKSPACE;
+  // the kernels choose float4 or element-wise access by aligned16() themselves: natural alignment is all they need
+  for (int t = 0; t < num_tensors; ++t) RGCN_ALIGN_TRY(4, L.p[t], L.g[t], L.m[t], L.v[t], L.step[t], L.amax[t]);
+  RGCN_ALIGN_TRY(4, total_norm, workspace);
   hipStream_t stream = (hipStream_t)stream_;
   float* partial = (float*)workspace;
   k_sumsq<<<blocks, kThreads, 0, stream>>>(L, partial);

@@ -389,6 +389,9 @@ int rgcn_edge_cosine(const float* emb, int64_t num_nodes, int d, const int64_t* 
   if (!emb || !out_ptr || !out_dst || !edge_score) return RGCN_ERR_ARG;
   const int64_t blocks = ceil_div64(nnz * kEdgeLanes, kThreads);
   if (blocks > INT32_MAX) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(16, emb);                       // rows as float4
+  RGCN_ALIGN_TRY(8, out_ptr);
+  RGCN_ALIGN_TRY(4, out_dst, edge_score);
   k_edge_cosine<<<(unsigned)blocks, kThreads, 0, (hipStream_t)stream_>>>(emb, (int)num_nodes, d, out_ptr, out_dst, nnz,
                                                                          edge_score);
   RGCN_HIP_TRY(hipGetLastError());
@@ -414,6 +417,9 @@ int rgcn_paths_topk(const int64_t* out_ptr, const int32_t* out_dst, const float*
   hipStream_t stream = (hipStream_t)stream_;
   const int S = plan_slices(num_queries, slices);
   if ((int64_t)S * kWaves * k > INT32_MAX) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(16, ws);
+  RGCN_ALIGN_TRY(8, out_ptr, in_ptr, in_pos, sources, targets, count);
+  RGCN_ALIGN_TRY(4, out_dst, edge_score, in_src, nodes, length, score);
   PathWeights pw;
   pw.w[0] = 0.f;
   for (int L = 1; L <= RGCN_PATHS_MAX_LEN; ++L) pw.w[L] = rgcn_path_weight(L);

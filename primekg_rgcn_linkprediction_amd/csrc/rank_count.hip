@@ -146,6 +146,9 @@ __global__ __launch_bounds__(kThreads) void k_rank_count(const float* __restrict
 int launch_rank_count(const float* q, const float* emb, const float* true_score, const int64_t* target,
                       const uint32_t* allow, const int32_t* query_class, int64_t num_classes, const uint32_t* exclude,
                       int64_t batch, int64_t num_entities, int64_t d, int32_t* beaten_by, void* stream) {
+  RGCN_ALIGN_TRY(16, q, emb);                    // the k-tiles arrive in 16-byte DMA pieces; the epilogue reads words
+  RGCN_ALIGN_TRY(8, target);
+  RGCN_ALIGN_TRY(4, true_score, allow, query_class, exclude, beaten_by);
   dim3 grid((unsigned)ceil_div64(batch, BM), (unsigned)ceil_div64(num_entities, KTile<kRankTN, B_BLK>::BN));
   k_rank_count<<<grid, kThreads, 0, (hipStream_t)stream>>>(q, emb, true_score, target, allow, query_class,
                                                            allow ? (int)num_classes : 0, exclude, beaten_by, (int)batch,

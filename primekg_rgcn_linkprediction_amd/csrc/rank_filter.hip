@@ -69,6 +69,8 @@ int rgcn_rank_exclude_bits(const int64_t* ptr, const int64_t* ids, const int64_t
   if (batch == 0) return RGCN_OK;
   if (!seg || !exclude || (num_segments > 0 && (!ptr || (nnz > 0 && !ids)))) return RGCN_ERR_ARG;
   if (batch > INT32_MAX / 2 || num_entities > INT32_MAX / 2) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(8, ptr, ids, seg);
+  RGCN_ALIGN_TRY(4, exclude);
   hipStream_t stream = (hipStream_t)stream_;
   int* flag = rgcn_index_error_flag();
   if (!flag) return RGCN_ERR_HIP;
@@ -83,6 +85,7 @@ int rgcn_rank_allow_bits(const int32_t* class_of, int64_t num_entities, int64_t 
   if (num_entities <= 0 || num_classes <= 0 || !class_of || !allow) return RGCN_ERR_ARG;
   const int64_t words = ceil_div64(num_entities, 32);
   if (num_entities > INT32_MAX / 2 || num_classes * words > INT32_MAX) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(4, class_of, allow);
   hipStream_t stream = (hipStream_t)stream_;
   int* flag = rgcn_index_error_flag();
   if (!flag) return RGCN_ERR_HIP;

@@ -321,6 +321,9 @@ int distmult_topk_masked(const float* q, const float* emb, const uint32_t* allow
   const int64_t words = ceil_div64(num_entities, 32);
   if (allow && num_classes * words > INT32_MAX) return RGCN_ERR_UNSUPPORTED;   // 32-bit word offsets in the epilogue
   if (!workspace || workspace_bytes < distmult_topk_workspace_bytes(batch, num_entities, k, slices)) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(16, q, emb, workspace);         // 16-byte DMA pieces of the k-tiles; the lists and masks go word by word
+  RGCN_ALIGN_TRY(8, top_ids);
+  RGCN_ALIGN_TRY(4, allow, query_class, exclude, top_scores);
   hipStream_t stream = (hipStream_t)stream_;
   const TopkPlan p = plan_topk(batch, num_entities, slices);
   const size_t lds_bytes = select_lds_bytes((int)k);

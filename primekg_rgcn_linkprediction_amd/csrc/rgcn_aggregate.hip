@@ -386,6 +386,7 @@ int aggregate_levels(const rgcn_graph* g, int transposed, int first, int last, c
   if (tail && (!tail->grad_weight || tail->splits <= 0 || tail->Kc <= 0 || tail->N <= 0 || (tail->N & 3)))
     return RGCN_ERR_ARG;
   if (tail && c->rowptr && c->n_key == 0) {     // nothing to gather: the reduction still has to run
+    RGCN_ALIGN_TRY(16, tail->slab, tail->bias_part, tail->grad_weight, tail->grad_root, tail->grad_bias);
     k_slab_reduce<<<(unsigned)rgcn_slab_reduce_blocks(*tail), 256, 0, stream>>>(*tail);
     RGCN_HIP_TRY(hipGetLastError());
     return RGCN_OK;
@@ -402,6 +403,10 @@ int aggregate_levels(const rgcn_graph* g, int transposed, int first, int last, c
   float* partial = (float*)workspace;
   unsigned* amax_out = reinterpret_cast<unsigned*>(amax);
   if (amax && half_in) return RGCN_ERR_UNSUPPORTED;            // the fp16-table gather feeds the fp16 transform: no scale needed
+  // a lane reads 16 bytes of a table row (four floats, eight halves) and writes float4; amax heads are single words
+  RGCN_ALIGN_TRY(16, x, agg, workspace);
+  RGCN_ALIGN_TRY(4, amax);
+  if (tail) RGCN_ALIGN_TRY(16, tail->slab, tail->bias_part, tail->grad_weight, tail->grad_root, tail->grad_bias);
   const float* cnt = c->weighted ? nullptr : c->val;
   const bool weighted = c->weighted;
   const int q = (int)(d / 4);

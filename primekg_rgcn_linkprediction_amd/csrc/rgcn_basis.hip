@@ -107,6 +107,8 @@ int rgcn_basis_compose(const float* comp, const float* basis, int64_t R, int64_t
                        void* stream_) {
   if (bad(R, B, inner) || !comp || !basis || !weight) return RGCN_ERR_ARG;
   if ((inner & 3) || R * B > kMaxRB * 64 || inner > ((int64_t)1 << 36)) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(16, basis, weight);
+  RGCN_ALIGN_TRY(4, comp);                       // read one coefficient at a time
   const int64_t quads = inner / 4;
   k_basis_compose<<<(unsigned)ceil_div64(quads, kThreads), kThreads, 0, (hipStream_t)stream_>>>(comp, basis, (int)R, (int)B,
                                                                                               quads, weight);
@@ -126,6 +128,8 @@ int rgcn_basis_compose_bwd(const float* grad_weight, const float* comp, const fl
   if ((inner & 3) || R * B > kMaxRB * 64 || inner > ((int64_t)1 << 36)) return RGCN_ERR_UNSUPPORTED;
   if (!grad_comp && !grad_basis) return RGCN_OK;
   if (grad_comp && (!workspace || workspace_bytes < rgcn_basis_compose_bwd_workspace_bytes(R, B, inner))) return RGCN_ERR_WORKSPACE;
+  RGCN_ALIGN_TRY(16, grad_weight, basis, grad_basis, workspace);
+  RGCN_ALIGN_TRY(4, comp, grad_comp);
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t quads = inner / 4;
   const int blocks = (int)ceil_div64(quads, kChunkQuads);

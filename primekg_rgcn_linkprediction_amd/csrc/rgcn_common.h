@@ -11,6 +11,21 @@
     if (err__ != hipSuccess) return RGCN_ERR_HIP; \
   } while (0)
 
+// The alignment contract of the C boundary (include/rgcn_hip.h, "Alignment"): every entry point, once its other
+// argument checks have passed and before its first HIP runtime call, refuses a pointer whose address is not a
+// multiple of the widest single access a kernel makes through it.  `a`: a power of two; NULL passes (optional
+// operands).  A handful of integer ORs and one AND on the host.
+template <class... P>
+static inline bool rgcn_aligned(uintptr_t a, P... p) {
+  uintptr_t bits = 0;
+  ((bits |= (uintptr_t)(const void*)p), ...);
+  return (bits & (a - 1)) == 0;
+}
+#define RGCN_ALIGN_TRY(a, ...)                                       \
+  do {                                                               \
+    if (!rgcn_aligned((a), __VA_ARGS__)) return RGCN_ERR_ALIGN;      \
+  } while (0)
+
 // ---------------------------------------------------------------------------------------------
 // Host scaffolding of the launches, one copy each.
 // ---------------------------------------------------------------------------------------------

@@ -361,6 +361,9 @@ const char* rgcn_strerror(int code) {
     case RGCN_ERR_HIP: return "HIP runtime call failed";
     case RGCN_ERR_UNSUPPORTED: return "shape not supported by this build";
     case RGCN_ERR_WORKSPACE: return "workspace missing or too small";
+    case RGCN_ERR_ALIGN:
+      return "a pointer's base address is not aligned: tables, weights, gradients, workspaces and fp16 images must start "
+             "on a 16-byte boundary, other operands on a multiple of their element size (include/rgcn_hip.h, Alignment)";
     default: return "unknown error code";
   }
 }
@@ -372,6 +375,7 @@ int rgcn_graph_create(const int64_t* edge_index, const int64_t* edge_type, int64
   if (num_edges < 0 || num_nodes < 0 || num_relations <= 0) return RGCN_ERR_ARG;
   if (num_edges > 0 && (!edge_index || !edge_type)) return RGCN_ERR_ARG;
   if (too_big(num_nodes, num_nodes, num_relations, num_edges)) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(8, edge_index, edge_type);
   rgcn_graph* g = new (std::nothrow) rgcn_graph();
   if (!g) return RGCN_ERR_HIP;
   int rc = create_impl(edge_index, edge_type, num_edges, num_nodes, num_relations, (hipStream_t)stream, g);
@@ -392,6 +396,8 @@ int rgcn_graph_create_bipartite(const int64_t* key_node, const int64_t* other_no
   if (num_edges < 0 || num_key_nodes < 0 || num_other_nodes < 0 || num_relations <= 0) return RGCN_ERR_ARG;
   if (num_edges > 0 && (!key_node || !other_node || !edge_type)) return RGCN_ERR_ARG;
   if (too_big(num_key_nodes, num_other_nodes, num_relations, num_edges)) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(8, key_node, other_node, edge_type);
+  RGCN_ALIGN_TRY(4, edge_weight);
   rgcn_graph* g = new (std::nothrow) rgcn_graph();
   if (!g) return RGCN_ERR_HIP;
   int rc = create_bipartite_impl(key_node, other_node, edge_type, num_edges, num_key_nodes, num_other_nodes,
@@ -414,6 +420,8 @@ int rgcn_graph_import(int64_t num_edges, int64_t num_nodes, int64_t num_relation
   if (num_nodes * num_relations > 0 && !cnt) return RGCN_ERR_ARG;
   if (num_edges > 0 && (!col || !perm || !col_t || !perm_t || !w_t)) return RGCN_ERR_ARG;
   if (too_big(num_nodes, num_nodes, num_relations, num_edges)) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(8, perm, perm_t);
+  RGCN_ALIGN_TRY(4, rowptr, col, cnt, rowptr_t, col_t, w_t);
   hipStream_t stream = (hipStream_t)stream_;
   rgcn_graph* g = new (std::nothrow) rgcn_graph();
   if (!g) return RGCN_ERR_HIP;
@@ -479,6 +487,8 @@ int rgcn_graph_export(const rgcn_graph* g, int transposed, int32_t* rowptr, int3
   hipStream_t stream = (hipStream_t)stream_;
   const rgcn_csr* c = &g->dir[transposed ? 1 : 0];
   if (!c->rowptr) return RGCN_ERR_ARG;   // direction not built (bipartite handles have only one)
+  RGCN_ALIGN_TRY(8, perm);               // device-to-device copies: the element size is all a later reader needs
+  RGCN_ALIGN_TRY(4, rowptr, col, val);
   const size_t nr = (size_t)(c->n_key * g->R), e = (size_t)g->E;
   if (rowptr) RGCN_HIP_TRY(hipMemcpyAsync(rowptr, c->rowptr, (nr + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
   if (col && e) RGCN_HIP_TRY(hipMemcpyAsync(col, c->col, e * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));

@@ -408,6 +408,8 @@ int rgcn_layer_fwd_fused(const int32_t* rowptr, const int32_t* col, const uint32
   if (!supported(R, d_in, d_out, false)) return RGCN_ERR_UNSUPPORTED;
   if (N == 0) return RGCN_OK;
   if (N > INT32_MAX / 2) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(16, hub_agg, x, packed, bias, out, agg);
+  RGCN_ALIGN_TRY(4, rowptr, col, tile_mask, x_amax, out_amax);     // ids, mask words and amax heads: one word at a time
   const rgcn_split_frag_view v = rgcn_split_fragment_images(packed, R, d_in, d_out);
   fused_args a{};
   a.x = x; a.rowptr = rowptr; a.col = col; a.hub_agg = hub_agg;
@@ -428,6 +430,8 @@ int rgcn_layer_bwd_input_fused(const int32_t* rowptr_t, const int32_t* col_t, co
   if (!supported(R, d_out, d_in, true)) return RGCN_ERR_UNSUPPORTED;
   if (N == 0) return RGCN_OK;
   if (N > INT32_MAX / 2) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(16, hub_agg, g, packed, relu_mask, grad_x);
+  RGCN_ALIGN_TRY(4, rowptr_t, col_t, w_t, tile_mask_t, g_amax, grad_x_amax, gagg_amax);
   const rgcn_split_frag_view v = rgcn_split_fragment_images(packed, R, d_in, d_out);
   fused_args a{};
   a.x = g; a.rowptr = rowptr_t; a.col = col_t; a.wts = w_t; a.hub_agg = hub_agg;

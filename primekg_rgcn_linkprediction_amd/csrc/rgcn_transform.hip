@@ -792,6 +792,8 @@ int rgcn_transform_fwd(const float* agg, const float* x, const float* weight, co
   if (N == 0) return RGCN_OK;
   if (!agg || !x || !weight) return RGCN_ERR_ARG;
   if (rgcn_gemm_out_of_range(N, (R + 1) * d_in, d_out)) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(16, agg, x, weight, root, bias, out);
+  RGCN_ALIGN_TRY(4, tile_mask);
   hipStream_t stream = (hipStream_t)stream_;
   const int K1 = (int)(R * d_in), K2 = root ? (int)d_in : 0;
   if (relu)
@@ -811,6 +813,8 @@ int rgcn_transform_bwd_input(const float* gagg, const float* g, const float* wei
   if (N == 0) return RGCN_OK;
   if (!gagg || !g || !weight) return RGCN_ERR_ARG;
   if (rgcn_gemm_out_of_range(N, (R + 1) * d_out, d_in)) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(16, gagg, g, weight, root, relu_mask, grad_x);
+  RGCN_ALIGN_TRY(4, tile_mask);
   hipStream_t stream = (hipStream_t)stream_;
   const int K1 = (int)(R * d_out), K2 = root ? (int)d_out : 0;
   if (relu_mask)
@@ -830,6 +834,9 @@ int distmult_score_all_tails(const float* head, const float* rel, const int64_t*
   if (batch == 0) return RGCN_OK;
   if (!head || !rel || !emb || !hr || !scores || (rel_idx && num_relations <= 0)) return RGCN_ERR_ARG;
   if (batch > INT32_MAX / 2 || num_entities > INT32_MAX / 2 || batch * d > INT32_MAX) return RGCN_ERR_UNSUPPORTED;
+  RGCN_ALIGN_TRY(16, head, rel, emb, hr);
+  RGCN_ALIGN_TRY(8, rel_idx);
+  RGCN_ALIGN_TRY(4, scores);                     // [batch, num_entities] for ANY num_entities: stored one score at a time
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t quads = batch * d / 4;
   k_head_times_relation<<<(unsigned)ceil_div64(quads, 256), 256, 0, stream>>>(head, rel, rel_idx, (int)num_relations,
@@ -860,6 +867,8 @@ int rgcn_transform_bwd_params_begin(const float* agg, const float* x, const floa
   rgcn_tn_split p = plan_tn(N, (R + 1) * d_in, d_out);
   const rgcn_slab_layout lay = rgcn_slab_layout_of(p, (R + 1) * d_in, d_out);
   if (!workspace || workspace_bytes < lay.bytes()) return RGCN_ERR_WORKSPACE;
+  RGCN_ALIGN_TRY(16, agg, x, g, grad_weight, grad_root, grad_bias, workspace);
+  RGCN_ALIGN_TRY(4, tile_mask);
   hipStream_t stream = (hipStream_t)stream_;
   if (N == 0) return rgcn_zero_param_grads(grad_weight, grad_root, grad_bias, R, d_in, d_out, stream);
   const int K1 = (int)(R * d_in), K2 = grad_root ? (int)d_in : 0, Kc = K1 + K2;
@@ -893,6 +902,7 @@ int rgcn_slab_reduce(const rgcn_slab_job* job, void* stream) {
   if (!job) return RGCN_ERR_ARG;
   if (!job->slab) return RGCN_OK;                              // nothing pending (empty graph)
   if (!job->grad_weight || job->splits <= 0 || job->Kc <= 0 || job->N <= 0 || (job->N & 3)) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(16, job->slab, job->bias_part, job->grad_weight, job->grad_root, job->grad_bias);
   k_slab_reduce<<<(unsigned)rgcn_slab_reduce_blocks(*job), 256, 0, (hipStream_t)stream>>>(*job);
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;

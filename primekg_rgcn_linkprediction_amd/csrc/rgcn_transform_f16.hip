@@ -227,6 +227,8 @@ int rgcn_transform_fwd_f16(const float* agg, const float* x, const float* weight
   if (d_in % BK) return RGCN_ERR_UNSUPPORTED;                     // a k-tile must not straddle two relations
   if (rgcn_gemm_out_of_range(N, (R + 1) * d_in, d_out)) return RGCN_ERR_UNSUPPORTED;
   if (!workspace || workspace_bytes < rgcn_transform_fwd_f16_workspace_bytes(R, d_in, d_out)) return RGCN_ERR_WORKSPACE;
+  RGCN_ALIGN_TRY(16, agg, x, weight, root, bias, out, workspace);
+  RGCN_ALIGN_TRY(4, tile_mask);
   hipStream_t stream = (hipStream_t)stream_;
   const int K1 = (int)(R * d_in), K2 = root ? (int)d_in : 0, n = (int)d_out;
   __half* bt = (__half*)workspace;

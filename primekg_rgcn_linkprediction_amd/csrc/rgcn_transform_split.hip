@@ -1196,8 +1196,13 @@ int make_hub_fin(const rgcn_graph* g, int transposed, float* partial, int64_t N,
 // picks its B images from `*w`.
 int nt_prepare(nt_call* c, PackedWeights* w, const float* weight, const float* root, const void* packed, int64_t N,
                int64_t R, int64_t d_in, int64_t d_out, int64_t dk, void* workspace, size_t workspace_bytes,
-               const rgcn_graph* hub_graph, int hub_transposed, float* hub_partial, void* stream) {
+               const rgcn_graph* hub_graph, int hub_transposed, float* hub_partial, void* stream, bool operands_aligned) {
   if (!workspace || workspace_bytes < nt_workspace_bytes(R, d_in, d_out)) return RGCN_ERR_WORKSPACE;
+  const int hrc = make_hub_fin(hub_graph, hub_transposed, hub_partial, N, R, dk, &c->fin);
+  if (hrc < 0) return hrc;
+  // `operands_aligned`: the entry point's verdict on its own operands (16 bytes for every table, image and mask, 4 for
+  // amax buffers and occupancy words); reported here, behind the other argument checks and ahead of the first launch
+  if (!operands_aligned || !rgcn_aligned(16, weight, root, packed, workspace, hub_partial)) return RGCN_ERR_ALIGN;
   c->stream = (hipStream_t)stream;
   if (!packed) {
     const int rc = pack_weights(weight, root, R, d_in, d_out, workspace, c->stream);
@@ -1210,8 +1215,7 @@ int nt_prepare(nt_call* c, PackedWeights* w, const float* weight, const float* r
   c->K2 = root ? (int)dk : 0;
   c->kseg = (int)dk;
   c->M = (int)N;
-  const int hrc = make_hub_fin(hub_graph, hub_transposed, hub_partial, N, R, dk, &c->fin);
-  return hrc < 0 ? hrc : RGCN_OK;
+  return RGCN_OK;
 }
 
 // one workgroup per CU (the 128 KB ring leaves no room for a second): as many row splits as that gives
@@ -1270,6 +1274,11 @@ int rgcn_absmax_multi(int count, const float* const* tensors, const int64_t* num
     if (numels[t] < 0 || !outs[t] || (numels[t] > 0 && !tensors[t])) return RGCN_ERR_ARG;
     J.p[t] = tensors[t]; J.n[t] = numels[t]; J.out[t] = outs[t];
   }
+  for (int t = 0; t < count; ++t) {              // a tensor is scanned as float4; amax heads are single words
+    RGCN_ALIGN_TRY(16, tensors[t]);
+    RGCN_ALIGN_TRY(4, outs[t]);
+  }
+  RGCN_ALIGN_TRY(4, zero_buffers);
   k_absmax_multi<<<RGCN_AMAX_HEADS, kPackThreads, 0, (hipStream_t)stream_>>>(J, zero_buffers, zero_count);
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
@@ -1282,6 +1291,9 @@ int rgcn_absmax_pack(const float* x, int64_t numel, float* x_amax, float* zero_b
   const int rc = rgcn_prep_fill(x, numel, x_amax, zero_buffers, zero_count, count, weights, roots, R, d_in, d_out, packed,
                                 packed_bytes_, kPackThreads, &p);
   if (rc != RGCN_OK) return rc;
+  RGCN_ALIGN_TRY(16, x);
+  RGCN_ALIGN_TRY(4, x_amax, zero_buffers);
+  for (int l = 0; l < count; ++l) RGCN_ALIGN_TRY(16, weights[l], roots[l], packed[l]);
   k_absmax_pack<<<(unsigned)(p.pack_blocks * p.layers + RGCN_AMAX_HEADS), kPackThreads, 0, (hipStream_t)stream_>>>(
       p.J, p.zero, p.zero_count, p.JJ, p.pack_blocks, p.layers);
   RGCN_HIP_TRY(hipGetLastError());
@@ -1301,6 +1313,7 @@ int rgcn_weights_split_pack(const float* weight, const float* root, int64_t R, i
                             void* packed, size_t packed_bytes_, void* stream_) {
   const int rc = rgcn_pack_layer_check(R, d_in, d_out, 1, weight, packed, packed_bytes_, packed_bytes(R, d_in, d_out));
   if (rc != RGCN_OK) return rc;
+  RGCN_ALIGN_TRY(16, weight, root, packed);
   return pack_weights(weight, root, R, d_in, d_out, packed, (hipStream_t)stream_);
 }
 
@@ -1321,6 +1334,11 @@ int rgcn_weights_split_pack_multi(int count, const float* const* weights, const 
                             r_amax ? r_amax[l] : nullptr);
     most = std::max<int64_t>(most, (R[l] + (roots[l] ? 1 : 0)) * d_in[l] * d_out[l]);
   }
+  for (int l = 0; l < count; ++l) {
+    RGCN_ALIGN_TRY(16, weights[l], roots[l], packed[l]);
+    RGCN_ALIGN_TRY(4, w_amax ? w_amax[l] : nullptr, r_amax ? r_amax[l] : nullptr);
+  }
+  RGCN_ALIGN_TRY(4, zero_buffers);
   dim3 grid((unsigned)std::min<int64_t>(64, ceil_div64(most, kPackThreads)), (unsigned)count);
   k_pack_split<<<grid, kPackThreads, 0, (hipStream_t)stream_>>>(JJ, zero_buffers, zero_count);
   RGCN_HIP_TRY(hipGetLastError());
@@ -1345,8 +1363,9 @@ int rgcn_transform_fwd_split(const float* agg, const float* x, const float* weig
   if (rgcn_gemm_out_of_range(N, (R + 1) * d_in, d_out)) return RGCN_ERR_UNSUPPORTED;
   nt_call c;
   PackedWeights v;
+  const bool aligned = rgcn_aligned(16, agg, x, bias, out) && rgcn_aligned(4, tile_mask, agg_amax, x_amax, out_amax);
   const int rc = nt_prepare(&c, &v, weight, root, packed, N, R, d_in, d_out, d_in, workspace, workspace_bytes, hub_graph,
-                            hub_transposed, hub_partial, stream_);
+                            hub_transposed, hub_partial, stream_, aligned);
   if (rc != RGCN_OK) return rc;
   c.A1 = agg; c.a1_amax = agg_amax; c.a1_mul = agg_amax_mul; c.tile_mask = tile_mask;
   c.A2 = x; c.a2_amax = x_amax;
@@ -1371,8 +1390,9 @@ int rgcn_transform_bwd_input_split(const float* gagg, const float* g, const floa
   if (rgcn_gemm_out_of_range(N, (R + 1) * d_out, d_in)) return RGCN_ERR_UNSUPPORTED;
   nt_call c;
   PackedWeights v;
+  const bool aligned = rgcn_aligned(16, gagg, g, relu_mask, grad_x) && rgcn_aligned(4, tile_mask, gagg_amax, g_amax, grad_x_amax);
   const int rc = nt_prepare(&c, &v, weight, root, packed, N, R, d_in, d_out, d_out, workspace, workspace_bytes, hub_graph,
-                            hub_transposed, hub_partial, stream_);
+                            hub_transposed, hub_partial, stream_, aligned);
   if (rc != RGCN_OK) return rc;
   c.A1 = gagg; c.a1_amax = gagg_amax; c.a1_mul = gagg_amax_mul; c.tile_mask = tile_mask;
   c.A2 = g; c.a2_amax = g_amax;
@@ -1405,8 +1425,10 @@ int rgcn_transform_bwd_input_chain_split(const float* gagg, const float* g, cons
   if (rgcn_gemm_out_of_range(N, (R + 1) * d_out, (R1 + 1) * d_in1)) return RGCN_ERR_UNSUPPORTED;
   nt_call c;
   PackedWeights v;
+  const bool aligned = rgcn_aligned(16, gagg, g, relu_mask, grad_x, packed1, t_out) &&
+                       rgcn_aligned(4, tile_mask, gagg_amax, g_amax, grad_x_amax);
   const int rc = nt_prepare(&c, &v, weight, root, packed, N, R, d_in, d_out, d_out, workspace, workspace_bytes, hub_graph,
-                            hub_transposed, hub_partial, stream_);
+                            hub_transposed, hub_partial, stream_, aligned);
   if (rc != RGCN_OK) return rc;
   const PackedWeights v1 = packed_view(const_cast<void*>(packed1), R1, d_in1, d_in);     // conv1: d_out1 = d_in of conv2
   c.A1 = gagg; c.a1_amax = gagg_amax; c.a1_mul = gagg_amax_mul; c.tile_mask = tile_mask;
@@ -1429,6 +1451,8 @@ int rgcn_transform_first_split(const float* g, const void* packed, int has_root,
   const int64_t cols = (R + (has_root ? 1 : 0)) * d_in;
   if (rgcn_gemm_out_of_range(N, d_out, cols)) return RGCN_ERR_UNSUPPORTED;
   if (!workspace || workspace_bytes < 2 * kMaxSlots * sizeof(float)) return RGCN_ERR_WORKSPACE;
+  RGCN_ALIGN_TRY(16, g, packed, t_out, workspace);
+  RGCN_ALIGN_TRY(4, g_amax);
   const PackedWeights v = packed_view(const_cast<void*>(packed), R, d_in, d_out);
   nt_call c;                                                   // one operand, no occupancy mask, nothing deferred
   c.A1 = g; c.K1 = (int)d_out; c.a1_amax = g_amax;
@@ -1460,6 +1484,8 @@ int rgcn_transform_bwd_params_split_begin(const float* agg, const float* x, cons
   rgcn_tn_split p = rgcn_tn_plan(N, (R + 1) * d_in, d_out, TN_TKC, kTnBlocks);
   const rgcn_slab_layout lay = rgcn_slab_layout_of(p, (R + 1) * d_in, d_out);
   if (!workspace || workspace_bytes < tn_workspace_bytes(lay)) return RGCN_ERR_WORKSPACE;
+  RGCN_ALIGN_TRY(16, agg, x, g, grad_weight, grad_root, grad_bias, workspace);
+  RGCN_ALIGN_TRY(4, tile_mask, agg_amax, x_amax, g_amax);
   hipStream_t stream = (hipStream_t)stream_;
   if (N == 0) return rgcn_zero_param_grads(grad_weight, grad_root, grad_bias, R, d_in, d_out, stream);
   const int K1 = (int)(R * d_in), K2 = grad_root ? (int)d_in : 0, Kc = K1 + K2;

@@ -70,6 +70,8 @@ extern "C" int rgcn_sample_batch(const int64_t* edge_index, const int64_t* edge_
   if (total == 0) return RGCN_OK;
   if (num_edges == 0 || !edge_index || !edge_type || !heads || !tails || !rels || !labels) return RGCN_ERR_ARG;
   if (num_neg > 0 && !rng) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(8, edge_index, edge_type, order, cursor, rng, heads, tails, rels);
+  RGCN_ALIGN_TRY(4, labels);
   hipStream_t stream = (hipStream_t)stream_;
   k_sample_batch<<<(unsigned)ceil_div64(total, kThreads), kThreads, 0, stream>>>(
       edge_index, edge_type, num_edges, order, cursor, batch, num_neg, num_nodes, rng, heads, tails, rels, labels);

@@ -189,6 +189,9 @@ extern "C" int rgcn_sample_batch_constrained(
   if (total == 0) return RGCN_OK;
   if (num_edges == 0 || !edge_index || !edge_type || !heads || !tails || !rels || !labels) return RGCN_ERR_ARG;
   if (num_neg > 0 && !rng) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(8, edge_index, edge_type, order, cursor, rng, class_ptr, class_members, tail_keys, tail_ptr, tail_ids,
+                 head_keys, head_ptr, head_ids, stats, heads, tails, rels);
+  RGCN_ALIGN_TRY(4, class_of, labels);
   sample_args a;
   a.edge_index = edge_index; a.edge_type = edge_type; a.E = num_edges; a.order = order; a.cursor = cursor;
   a.B = batch; a.k = num_neg; a.num_nodes = num_nodes; a.rng = rng;

@@ -290,6 +290,9 @@ int rgcn_transe_step(float* emb, int64_t num_nodes, float* rel, int64_t num_rela
   if (num_nodes > INT32_MAX || num_relations > INT32_MAX || batch > kMaxBatch || d > INT32_MAX) return RGCN_ERR_UNSUPPORTED;
   const Layout l = layout(batch, d, num_relations);
   if (workspace_bytes < l.bytes) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(16, emb, rel, workspace);       // rows as float4; ids, the loss and the running sums one element at a time
+  RGCN_ALIGN_TRY(8, heads, tails, rels, loss_sum, active_sum);
+  RGCN_ALIGN_TRY(4, loss_mean);
   hipStream_t stream = (hipStream_t)stream_;
   int* flag = index_error_flag();
   if (!flag) return RGCN_ERR_HIP;

@@ -359,6 +359,9 @@ int rgcn_knn_refine(const float* x, int64_t M, int64_t d, const int64_t* cand, i
   if (M < 2 || d <= 0 || k < 1) return RGCN_ERR_ARG;
   if (d % 4 || d > (1 << 20) || k > kMaxK || M >= kMaxM) return RGCN_ERR_UNSUPPORTED;
   if (k + 1 > M || !x || !cand || !ids || !sqdist) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(16, x);                         // rows are read as float4; everything else one element at a time
+  RGCN_ALIGN_TRY(8, cand);
+  RGCN_ALIGN_TRY(4, ids, sqdist);
   hipStream_t stream = (hipStream_t)stream_;
   k_knn_refine<<<(unsigned)ceil_div64(M, 4), 256, 0, stream>>>(x, (int)M, (int)d, cand, (int)k, ids, sqdist);
   RGCN_HIP_TRY(hipGetLastError());
@@ -370,6 +373,7 @@ int rgcn_tsne_affinities(const float* sqdist, int64_t M, int64_t k, double perpl
   if (M < 1 || k < 2) return RGCN_ERR_ARG;
   if (k > kMaxK || M >= kMaxM) return RGCN_ERR_UNSUPPORTED;
   if (!(perplexity > 0.0) || !(perplexity < (double)k) || !sqdist || !cond_p || !beta) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(4, sqdist, cond_p, beta);
   hipStream_t stream = (hipStream_t)stream_;
   k_tsne_affinities<<<(unsigned)ceil_div64(M, 4), 256, 0, stream>>>(sqdist, (int)M, (int)k, log(perplexity), cond_p, beta);
   RGCN_HIP_TRY(hipGetLastError());
@@ -390,6 +394,9 @@ int rgcn_tsne_gradient(const float* y, int64_t M, const int32_t* rowptr, const i
   if (!y || !rowptr || !col || !val || !grad || !z || !kl) return RGCN_ERR_ARG;
   const TsnePlan p = plan_tsne(M, slices);
   if (!ws || ws_bytes < p.bytes) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(16, ws);
+  RGCN_ALIGN_TRY(8, y, grad, z, kl);             // the layout and its gradient go as float2 points
+  RGCN_ALIGN_TRY(4, rowptr, col, val);
   hipStream_t stream = (hipStream_t)stream_;
   char* w = (char*)ws;
   double* klrow = (double*)(w + p.o_klrow);
@@ -425,6 +432,9 @@ int rgcn_tsne_update(const float* grad, int64_t M, float momentum, float learnin
   if (!grad || !y || !update || !gains || !grad_norm2) return RGCN_ERR_ARG;
   const TsnePlan p = plan_tsne(M, 1);
   if (!ws || ws_bytes < p.upd_bytes) return RGCN_ERR_ARG;
+  RGCN_ALIGN_TRY(16, ws);
+  RGCN_ALIGN_TRY(8, grad_norm2);
+  RGCN_ALIGN_TRY(4, grad, y, update, gains);     // one thread per coordinate
   hipStream_t stream = (hipStream_t)stream_;
   double* npart = (double*)((char*)ws + p.o_npart);
   k_tsne_update<<<(unsigned)p.upd_blocks, 256, 0, stream>>>(grad, (int)(2 * M), momentum, learning_rate, min_gain, y, update,

@@ -38,12 +38,18 @@ def bits(t: torch.Tensor) -> torch.Tensor:
 class GuardedAllocator:
     """``empty`` with ``ops._empty``'s signature; every raw buffer is kept until ``check()`` has looked at it"""
 
-    def __init__(self, fill: int, band_bytes: int = BAND_BYTES):
+    def __init__(self, fill: int, band_bytes: int = BAND_BYTES, payload_offset: int = 0):
+        """``payload_offset``: the payload (and the bands around it) start that many bytes later, so a payload begins
+        ``payload_offset`` bytes past a 512-byte boundary instead of on one - the smallest base the 16-byte contract of
+        ``include/rgcn_hip.h`` allows is 16.  0: the payload keeps ``torch.empty``'s alignment."""
         if fill not in (0x00, 0xFF):
             raise ValueError("fill must be 0x00 or 0xFF")
         if band_bytes <= 0 or band_bytes % 512:
             raise ValueError("band_bytes must be a positive multiple of 512 (the payload keeps torch.empty's alignment)")
-        self.fill, self.band_bytes = fill, band_bytes
+        if payload_offset < 0 or payload_offset % 16 or payload_offset >= band_bytes:
+            raise ValueError("payload_offset must be a multiple of 16 (the alignment every entry point accepts), "
+                             "at least 0 and smaller than the band")
+        self.fill, self.band_bytes, self.payload_offset = fill, band_bytes, payload_offset
         self.records = []                     # (call order, shape, dtype, payload bytes, raw uint8 buffer)
         self.calls = 0                        # every request, zero-size ones included
         self._patterns = {}
@@ -67,7 +73,8 @@ class GuardedAllocator:
             return torch.empty(shape, dtype=dtype, device=device)
         nbytes = numel * torch.empty((), dtype=dtype).element_size()
         band = self.band_bytes
-        raw = torch.empty(band + nbytes + band, dtype=torch.uint8, device=device)
+        # [offset bytes nobody looks at | band | payload | band]: the record is the part from the leading band on
+        raw = torch.empty(self.payload_offset + band + nbytes + band, dtype=torch.uint8, device=device)[self.payload_offset:]
         pattern = self._band(raw.device)
         raw[:band] = pattern
         raw[band:band + nbytes] = self.fill

@@ -1,12 +1,16 @@
 """Guard bands and poison fills around every output and workspace the library is handed (``tests/guarded.py``).
 
-Every scenario is a closure over ``ops`` calls on seeded inputs and runs three times: plain, then with every
-``ops._empty`` allocation guarded and pre-filled with 0x00, then with 0xFF.  Asserted for each:
+Every scenario is a closure over ``ops`` calls on seeded inputs and runs four times: plain, then with every
+``ops._empty`` allocation guarded and pre-filled with 0x00, then with 0xFF, then RE-BASED: guarded (0xFF) with every
+allocation AND every input starting 16 bytes past a 512-byte boundary - the smallest base the alignment contract of
+``include/rgcn_hip.h`` admits, where the other runs only ever see multiples of 512.  A 16-byte move selects no other
+code path anywhere, so the re-based run must give the bits of the plain run.  Asserted for each:
 
 * bands   - every band of every allocation of both guarded runs is bit-intact (no store outside an output or
             workspace, so no ``*_workspace_bytes`` query is smaller than the kernel's footprint);
 * inputs  - every input holds the bits it held before (``include/rgcn_hip.h:17``: inputs are borrowed and never written);
-* outputs - every returned tensor holds the same bits in all three runs (no read of memory the call did not write);
+* outputs - every returned tensor holds the same bits in all four runs (no read of memory the call did not write, no
+            assumption about the base address beyond 16 bytes);
 * path    - the scenario first asserts the precondition that puts it on the kernel it is meant for.
 
 Buffers a scenario needs besides the library's own (amax buffers, gradient tables, optimizer state) come from
@@ -20,6 +24,7 @@ written or opaque, and nothing else:
     ``SplitWeights`` images      only through the transforms that consume them            include/rgcn_hip.h:276-279 (fp16
                                                                                           images in the kernels' own orders)
 """
+import contextlib
 import ctypes
 
 import pytest
@@ -102,23 +107,67 @@ def library_amax(buf):
     return Amax(buf, own_fill=False)
 
 
+REBASE_OFFSET = 16            # bytes past a 512-byte boundary: the smallest base a 16-byte operand may have
+
+
+@contextlib.contextmanager
+def rebased(inputs, offset=REBASE_OFFSET):
+    """for the body, every tensor of ``inputs`` lives on a copy of its bits that starts ``offset`` bytes past a 512-byte
+    boundary (same shape, strides and dtype; the tensor OBJECTS are the same, so closures and the objects that hold them
+    need not know); put back afterwards, whatever happened"""
+    done = []                             # (tensor, an alias of what it was)
+    try:
+        for t in inputs:
+            if t.numel() == 0 or any(t is u for u, _ in done):
+                continue
+            span = 1 + sum((n - 1) * st for n, st in zip(t.shape, t.stride()))        # elements from the first to the last
+            raw = torch.empty(512 + span * t.element_size(), dtype=torch.uint8, device=t.device)
+            assert raw.data_ptr() % 512 == 0
+            moved = raw[offset:offset + span * t.element_size()].view(t.dtype).as_strided(tuple(t.shape), t.stride())
+            moved.copy_(t)
+            old = t.detach()              # keeps the original storage alive and remembers the view
+            with torch.no_grad():
+                t.set_(moved)
+            done.append((t, old))
+            assert t.data_ptr() % 512 == offset and t.stride() == old.stride() and t.shape == old.shape
+        yield
+    finally:
+        with torch.no_grad():
+            for t, old in reversed(done):
+                t.set_(old)
+
+
 def protocol(monkeypatch, inputs, fn):
-    """plain / guarded 0x00 / guarded 0xFF; ``inputs``: every tensor the closure only reads"""
+    """plain / guarded 0x00 / guarded 0xFF / re-based; ``inputs``: every tensor the closure only reads"""
     inputs = [t for t in inputs if t is not None]
     before = [bits(t) for t in inputs]
+    homes = [t.data_ptr() for t in inputs]
     torch.cuda.synchronize()
     ctx = Ctx(None)
     runs = [("plain", _snapshot(ctx, fn(ctx)))]
-    for fill in (0x00, 0xFF):
-        alloc, ctx = GuardedAllocator(fill), Ctx(fill)
-        with installed(monkeypatch, alloc):
-            out = fn(ctx)
-            torch.cuda.synchronize()
-            snap = _snapshot(ctx, out)
-        assert alloc.records, "the scenario allocated nothing through ops._empty"
-        alloc.check()
-        runs.append((f"fill 0x{fill:02X}", snap))
+    for fill, offset in ((0x00, 0), (0xFF, 0), (0xFF, REBASE_OFFSET)):
+        alloc, ctx = GuardedAllocator(fill, payload_offset=offset), Ctx(fill)
+        with contextlib.ExitStack() as stack:
+            if offset:
+                stack.enter_context(rebased(inputs, offset))
+                torch.cuda.synchronize()
+            with installed(monkeypatch, alloc):
+                out = fn(ctx)
+                torch.cuda.synchronize()
+                snap = _snapshot(ctx, out)
+            assert alloc.records, "the scenario allocated nothing through ops._empty"
+            alloc.check()
+            if offset:
+                # the run happened where it says: every input and every allocation of the library 16 bytes past a 512-byte
+                # boundary, and the re-based inputs unwritten like the originals
+                for i, (t, b) in enumerate(zip(inputs, before)):
+                    assert t.numel() == 0 or t.data_ptr() % 512 == offset, f"input #{i} was not re-based"
+                    assert torch.equal(bits(t), b), f"re-based input #{i} {tuple(t.shape)} {t.dtype} was written"
+                for order, shape, dtype, nbytes, raw in alloc.records:
+                    assert (raw.data_ptr() + alloc.band_bytes) % 512 == offset, f"allocation #{order} {shape} {dtype}"
+        runs.append((f"fill 0x{fill:02X}" + (f", every base moved by {offset} bytes" if offset else ""), snap))
         del out
+    assert [t.data_ptr() for t in inputs] == homes, "an input was not put back where it lived"
     for i, (t, b) in enumerate(zip(inputs, before)):
         assert torch.equal(bits(t), b), f"input #{i} {tuple(t.shape)} {t.dtype} was written"
     name0, snap0 = runs[0]
@@ -128,7 +177,8 @@ def protocol(monkeypatch, inputs, fn):
             if not torch.equal(a, b):
                 at = torch.nonzero(a != b).view(-1)
                 raise AssertionError(f"{path} ({kind}) differs between the {name0} run and the {name} run in {at.numel()} of "
-                                     f"{a.numel()} words, first at flat word {int(at[0])}: a read of unwritten memory")
+                                     f"{a.numel()} words, first at flat word {int(at[0])}: a read of unwritten memory, or "
+                                     f"(re-based run) a kernel that assumes more of a base address than 16 bytes")
     ops.check_indices(torch.device("cuda", torch.cuda.current_device()))
 
 

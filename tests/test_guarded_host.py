@@ -143,6 +143,65 @@ def test_what_empty_returns_has_the_shape_dtype_and_alignment_of_torch_empty(dty
     alloc.check()
 
 
+@pytest.mark.parametrize("offset", [0, 16, 48, 496])
+def test_the_payload_offset_moves_the_base_by_exactly_that_amount(offset):
+    alloc = GuardedAllocator(0xFF, payload_offset=offset)
+    plain = GuardedAllocator(0xFF)
+    for shape, dtype in (((5, 7), torch.float32), ((13,), torch.uint8), ((3, 8), torch.float16), ((9,), torch.int64)):
+        out, ref = alloc.empty(*shape, dtype=dtype, device=CPU), plain.empty(*shape, dtype=dtype, device=CPU)
+        # torch's CPU allocator aligns to 64 bytes, the device allocator to 512 (asserted in the GPU tier): here the
+        # move is measured against the start of the storage, a multiple of 64 with or without an offset
+        base, ref_base = out.untyped_storage().data_ptr(), ref.untyped_storage().data_ptr()
+        assert base % 64 == 0 and ref_base % 64 == 0
+        assert (out.data_ptr() - base) - (ref.data_ptr() - ref_base) == offset and out.data_ptr() % 64 == offset % 64
+        assert out.shape == ref.shape and out.dtype == ref.dtype and out.is_contiguous() and out.stride() == ref.stride()
+        raw = _raw(alloc)
+        # the record starts at the leading band: the bands sit directly around the payload, as without an offset
+        assert out.data_ptr() - raw.data_ptr() == BAND_BYTES and raw.data_ptr() - base == offset
+        assert raw.numel() == 2 * BAND_BYTES + out.numel() * out.element_size()
+        assert bool((out.view(-1).view(torch.uint8) == 0xFF).all())
+    alloc.check()
+    assert alloc.damage() is None
+
+
+@pytest.mark.parametrize("fill", [0x00, 0xFF])
+def test_bands_detect_strays_on_either_side_at_offset_16(fill):
+    for element, side, where in ((-1, "leading", "4 bytes before the payload"), (35, "trailing", "0 bytes past the payload's end")):
+        alloc = GuardedAllocator(fill, payload_offset=16)
+        alloc.empty(3, dtype=torch.int64, device=CPU)                 # allocation #0 stays clean
+        out = alloc.empty(5, 7, dtype=torch.float32, device=CPU)
+        assert out.data_ptr() % 64 == 16
+        out.copy_(torch.arange(35.0).view(5, 7))
+        alloc.check()
+        _stray_store(out, element)
+        with pytest.raises(AssertionError) as err:
+            alloc.check()
+        msg = str(err.value)
+        assert "allocation #1" in msg and f"{side} band" in msg and where in msg
+    # the far edge of the leading band: the 16 bytes in front of it belong to the raw buffer, not to the band
+    alloc = GuardedAllocator(fill, payload_offset=16)
+    out = alloc.empty(16, 4, dtype=torch.float32, device=CPU)
+    _stray_store(out, -(BAND_BYTES // 4))
+    with pytest.raises(AssertionError, match="leading band damaged at band byte 0 "):
+        alloc.check()
+
+
+def test_an_unwritten_element_differs_between_the_fills_at_offset_16():
+    want = torch.randn(6, 5, generator=torch.Generator().manual_seed(0))
+    results = {}
+    for fill in (0x00, 0xFF):
+        alloc = GuardedAllocator(fill, payload_offset=16)
+        out = alloc.empty(6, 5, dtype=torch.float32, device=CPU)
+        assert out.data_ptr() % 64 == 16
+        flat = out.view(-1)
+        flat[:17] = want.view(-1)[:17]
+        flat[18:] = want.view(-1)[18:]                                # element 17 is left as the allocator filled it
+        alloc.check()
+        results[fill] = bits(out)
+    a, b = results[0x00], results[0xFF]
+    assert torch.nonzero(a != b).view(-1).tolist() == [17]
+
+
 def test_zero_size_requests_are_plain_tensors():
     alloc = GuardedAllocator(0x00)
     for call in ((0,), (0, 8), ((3, 0),), (torch.Size([0]),)):
@@ -159,6 +218,12 @@ def test_bad_parameters_are_refused():
         GuardedAllocator(0x5A)
     with pytest.raises(ValueError):
         GuardedAllocator(0x00, band_bytes=1000)
+    for offset in (-16, 1, 4, 8, 24, BAND_BYTES, BAND_BYTES + 16):    # not a multiple of 16, or not inside the band
+        with pytest.raises(ValueError, match="multiple of 16"):
+            GuardedAllocator(0x00, payload_offset=offset)
+    with pytest.raises(ValueError, match="multiple of 16"):
+        GuardedAllocator(0x00, band_bytes=512, payload_offset=512)
+    assert GuardedAllocator(0x00, band_bytes=512, payload_offset=496).payload_offset == 496
 
 
 def test_installed_swaps_the_seam_and_puts_it_back(monkeypatch):
