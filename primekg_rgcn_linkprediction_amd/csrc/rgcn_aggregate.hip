@@ -19,6 +19,16 @@
 // of a segment with a whole workgroup per item (up to 512 rows: 256/G row slots in parallel, LDS
 // combine in slot order), so even a 100k-edge hub costs one extra short launch and the result is
 // run-to-run deterministic.
+//
+// The grid of the level-0 launch has three parts, in dispatch order:
+//   1. the gather proper: the workgroups that walk the live item slots;
+//   2. zero-fill workgroups: a (node, relation) segment without an edge (half of C2's 92,778) is an item too, and the
+//      plan's order makes these items the suffix of level 0.  Their rows are +0.0f and depend on nothing the walk
+//      computes, so they are not walked (item, flags, id window, cnt and four divides for one zero row, in workgroups
+//      dispatched after the walk has drained): a workgroup reads the `dst` of RGCN_ZERO_ROWS of them and stores;
+//   3. riders: the workgroups of a pending parameter-gradient slab reduction (rgcn_slab_reduce.h).
+// The parts share nothing: no counter, no ticket, no workgroup waits for another.  Behind the walk is where the zero
+// rows measured fastest (in front of it, behind the riders, interleaved with the walk: profiles/gather_empty_rows.txt).
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -35,6 +45,9 @@ constexpr int kThreads = 256;
 constexpr int kUnroll = RGCN_HEAD;   // rows in flight per lane group = ids that travel with an item
 #ifndef RGCN_REDUCE_UNROLL
 #define RGCN_REDUCE_UNROLL 16
+#endif
+#ifndef RGCN_ZERO_ROWS
+#define RGCN_ZERO_ROWS 64            // rows of a zero-fill workgroup (32, 128 and 256 measured no better)
 #endif
 
 __device__ inline float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
@@ -196,6 +209,34 @@ __device__ inline void aggregate_block(
   if (amax_out) rgcn_amax_publish(amax_out, lmax, seen);
 }
 
+// Rows of one zero-fill workgroup: whole passes of its 256 / G row slots.
+template <int G>
+constexpr int zero_rows() { return RGCN_ZERO_ROWS > kThreads / G ? RGCN_ZERO_ROWS : kThreads / G; }
+
+// Zero-fill workgroup `zb`: the items [first + zb * zero_rows, ...) are segments without an edge (rgcn_csr::
+// empty_items0), whose rows of `agg` are +0.0f whatever the table holds (0 / cnt, or a sum of nothing).  It reads their
+// `dst` and stores the rows: no id window, no cnt, no amax (a zero never raises a maximum), nothing shared with any
+// other workgroup.  1-D grids only (d <= 4 * G).
+template <int G>
+__device__ inline void zero_rows_block(const int64_t zb, const rgcn_item* __restrict__ items, int64_t first,
+                                       int64_t nitems, float* __restrict__ agg, int d) {
+  constexpr int kSlots = kThreads / G, kPasses = zero_rows<G>() / kSlots;
+  const int c4 = ((int)threadIdx.x % G) * 4;
+  const int64_t base = first + zb * zero_rows<G>() + (int)threadIdx.x / G;
+  int32_t dst[kPasses];
+#pragma unroll
+  for (int p = 0; p < kPasses; ++p) {            // all the item loads first: one round trip, then stores only
+    const int64_t i = base + (int64_t)p * kSlots;
+    dst[p] = i < nitems ? items[i].dst : -1;
+  }
+  if (c4 >= d) return;
+#pragma unroll
+  for (int p = 0; p < kPasses; ++p)
+    if (dst[p] >= 0) *reinterpret_cast<float4*>(agg + (size_t)dst[p] * d + c4) = f4zero();
+}
+
+// Grid of the level-0 launch, in dispatch order: `gather_blocks` workgroups of the gather proper, `zero_blocks`
+// zero-fill workgroups, then the riders of a pending slab reduction (see the file header).
 // (The weighted body takes 68 registers, one granule over the 64 that let eight waves share a SIMD; holding it to 64
 // with amdgpu_waves_per_eu(8) costs three spilled registers and measured ~1 us on the d = 128 transposed gather, inside
 // the box-to-box spread: left alone.)
@@ -204,13 +245,19 @@ __global__ __launch_bounds__(kThreads) void k_aggregate(
     const float* __restrict__ src, const rgcn_item* __restrict__ items, int64_t nitems,
     const int32_t* __restrict__ col, const float* __restrict__ w, const float* __restrict__ cnt,
     float* __restrict__ agg, float* __restrict__ partial, int d, const int32_t* __restrict__ head_col,
-    const float* __restrict__ head_w, const rgcn_slab_job job, int gather_blocks, unsigned* __restrict__ amax_out) {
+    const float* __restrict__ head_w, const rgcn_slab_job job, int gather_blocks, int zero_blocks,
+    unsigned* __restrict__ amax_out) {
   __shared__ float4 red[kThreads];               // pack combine (see rgcn_common.h)
-  if ((int)blockIdx.x >= gather_blocks) {        // workgroups past the gather: a pending slab reduction rides along
-    rgcn_slab_reduce_block<RGCN_SLAB_OUTS, RGCN_SLAB_GROUPS>(job, (int64_t)blockIdx.x - gather_blocks, red);
+  const int bx = (int)blockIdx.x, zb = bx - gather_blocks, rb = zb - zero_blocks;
+  if (rb >= 0) {                                // workgroups past both: a pending slab reduction rides along
+    rgcn_slab_reduce_block<RGCN_SLAB_OUTS, RGCN_SLAB_GROUPS>(job, (int64_t)rb, red);
     return;
   }
-  aggregate_block<G, WEIGHTED>((int)blockIdx.x, red, src, items, nitems, col, w, cnt, agg, partial, d, head_col, head_w, amax_out);
+  if (zb >= 0) {
+    zero_rows_block<G>(zb, items, (int64_t)gather_blocks * (kThreads / G), nitems, agg, d);
+    return;
+  }
+  aggregate_block<G, WEIGHTED>(bx, red, src, items, nitems, col, w, cnt, agg, partial, d, head_col, head_w, amax_out);
 }
 
 // fp16 feature table, fp32 accumulate (BASELINE.json configs[4]): the same walk with 8 halves
@@ -347,15 +394,24 @@ void launch_level(const rgcn_csr* c, int level, bool weighted, const float* x, c
   if (nitems == 0) return;
   const unsigned gy = (unsigned)ceil_div64(d, 4 * G);
   if (level == 0) {
-    const unsigned gather_blocks = (unsigned)ceil_div64(nitems, kThreads / G);
+    // Segments without an edge (the suffix of the item order, rgcn_csr::empty_items0) only need their zero rows: the
+    // gather proper covers the live slots rounded up to whole workgroups - the few empty items inside the last of them
+    // go the walk's way - and zero-fill workgroups store the rest.  Where the slab rider is allowed (can_ride below):
+    // the fp32 gather on a 1-D grid, d <= 256.  A 2-D grid (d > 256) and k_aggregate_h walk every item as before.
+    const int64_t slots = kThreads / G;
+    const int64_t walked = gy == 1 ? std::min(nitems, ceil_div64(nitems - c->empty_items0, slots) * slots) : nitems;
+    const unsigned gather_blocks = (unsigned)ceil_div64(walked, slots);
+    const unsigned zero_blocks = (unsigned)ceil_div64(nitems - walked, zero_rows<G>());
     const rgcn_slab_job job = tail ? *tail : rgcn_slab_job{};
-    dim3 grid(gather_blocks + (tail ? (unsigned)rgcn_slab_reduce_blocks(job) : 0u), gy);   // tail only with gy == 1
+    dim3 grid(gather_blocks + zero_blocks + (tail ? (unsigned)rgcn_slab_reduce_blocks(job) : 0u), gy);   // tail only with gy == 1
     if (weighted)
       k_aggregate<G, true><<<grid, kThreads, 0, stream>>>(x, c->items[0], nitems, c->col, c->val, cnt, agg, partial, d,
-                                                          c->head_col, c->head_w, job, (int)gather_blocks, amax_out);
+                                                          c->head_col, c->head_w, job, (int)gather_blocks,
+                                                          (int)zero_blocks, amax_out);
     else
       k_aggregate<G, false><<<grid, kThreads, 0, stream>>>(x, c->items[0], nitems, c->col, nullptr, cnt, agg, partial, d,
-                                                           c->head_col, nullptr, job, (int)gather_blocks, amax_out);
+                                                           c->head_col, nullptr, job, (int)gather_blocks,
+                                                           (int)zero_blocks, amax_out);
   } else {
     dim3 grid((unsigned)nitems, gy);
     k_reduce_partials<G><<<grid, kThreads, 0, stream>>>(c->items[level], cnt, agg, partial, d, amax_out);

@@ -1,6 +1,7 @@
 // Shared declarations for librgcn_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/rgcn_hip.h"
 #include "rgcn_plan.h"
@@ -83,6 +84,12 @@ struct rgcn_csr {
   int64_t n_key = 0;          // nodes that own segments (rows of agg = n_key * R)
   int64_t n_other = 0;        // nodes the col[] ids refer to (rows of x)
   int num_levels = 0;
+  // Where the live level-0 slots end, counted from the back: the plan orders level 0 as packs, then singles by
+  // descending length, so the segments without an edge are exactly the last empty_items0 items and the slots in front
+  // of the first empty single are num_items[0] - empty_items0.  The gather launch walks those and only stores zero
+  // rows for the rest (rgcn_aggregate.hip).  At most n_key * R < 2^31; an int32 here leaves every other field where
+  // it was (the mirror of this struct in tests/test_alignment_host.py).
+  int32_t empty_items0 = 0;
   rgcn_item* items[RGCN_MAX_LEVELS] = {};
   int64_t num_items[RGCN_MAX_LEVELS] = {};
   int64_t num_partials = 0;   // rows of partial-sum workspace (all levels)
@@ -107,6 +114,8 @@ struct rgcn_csr {
   // The split-precision transforms scale the aggregate operand by this bound instead of scanning it.
   float weight_bound = 1.f;
 };
+
+static_assert(offsetof(rgcn_csr, items) == offsetof(rgcn_csr, num_levels) + 8, "empty_items0 sits behind num_levels");
 
 struct rgcn_graph {
   int64_t E = 0, N = 0, R = 0;

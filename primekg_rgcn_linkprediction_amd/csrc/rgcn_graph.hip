@@ -93,6 +93,13 @@ int build_plan(const std::vector<int32_t>& rowptr, int64_t NR, int64_t R, rgcn_c
 
   csr->num_levels = (int)levels.size();
   csr->num_partials = partial_rows;
+  csr->empty_items0 = 0;
+  if (!levels.empty()) {                         // the empty singles are the suffix of level 0 (order: rgcn_plan.h)
+    const std::vector<rgcn_item>& v0 = levels[0];
+    size_t live = v0.size();
+    while (live > 0 && !(v0[live - 1].flags & RGCN_ITEM_PACK) && v0[live - 1].begin == v0[live - 1].end) --live;
+    csr->empty_items0 = (int32_t)(v0.size() - live);
+  }
   for (int l = 0; l < csr->num_levels; ++l) {
     auto& v = levels[l];
     csr->num_items[l] = (int64_t)v.size();
