@@ -26,9 +26,13 @@
 //      plan's order makes these items the suffix of level 0.  Their rows are +0.0f and depend on nothing the walk
 //      computes, so they are not walked (item, flags, id window, cnt and four divides for one zero row, in workgroups
 //      dispatched after the walk has drained): a workgroup reads the `dst` of RGCN_ZERO_ROWS of them and stores;
-//   3. riders: the workgroups of a pending parameter-gradient slab reduction (rgcn_slab_reduce.h).
+//   3. riders: the workgroups of a pending parameter-gradient slab reduction (rgcn_slab_reduce.h).  They are the last
+//      to start, so what each of them takes is the tail of the launch: one batch of loads (all the slabs of its group
+//      at C2), the adds in slab order, one barrier.
 // The parts share nothing: no counter, no ticket, no workgroup waits for another.  Behind the walk is where the zero
-// rows measured fastest (in front of it, behind the riders, interleaved with the walk: profiles/gather_empty_rows.txt).
+// rows measured fastest (in front of it, behind the riders, interleaved with the walk: profiles/gather_empty_rows.txt),
+// and behind the zero rows the riders: between the walk and the zero rows is 0.3 us slower at d = 128, in front of the
+// walk 0.4 us faster at d = 128 and 0.75 us slower on the merged d = 64 gather (profiles/slab_riders.txt).
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>

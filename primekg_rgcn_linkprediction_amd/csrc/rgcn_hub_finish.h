@@ -23,6 +23,17 @@ __device__ inline float rgcn_reduce_item(const rgcn_item it, const float* __rest
   const int gl = (int)threadIdx.x % G, slot = (int)threadIdx.x / G;
   const int c4 = (gl + col0) * 4;
   const bool live = c4 < d;
+  // The divisor of a mean structure's FINAL row, requested in front of the first batch of rows (slot 0 alone uses it,
+  // after the LDS combine): behind the barrier it would be one more dependent round trip at the end of every item.
+  // `it` is the same in every lane, and a load from a wave-uniform address is compiled to a scalar load that is waited
+  // for on the spot (scalar loads return out of order: their only wait is "all of them"), in front of the rows instead
+  // of beside them.  The zero the compiler cannot see through keeps it a vector load, which the rows' own wait covers.
+  const bool mean = cnt && slot == 0 && live && (it.flags & RGCN_ITEM_FINAL);
+  int lane_zero = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(lane_zero));            // (no instruction: only the register class and the lost constant)
+#endif
+  const float c = mean ? cnt[it.dst + lane_zero] : 1.f;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   if (live) {
     for (int r0 = it.begin + slot; r0 < it.end; r0 += SLOTS * RGCN_REDUCE_UNROLL) {
@@ -50,8 +61,7 @@ __device__ inline float rgcn_reduce_item(const rgcn_item it, const float* __rest
       s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
     }
     if (it.flags & RGCN_ITEM_FINAL) {
-      if (cnt) {
-        const float c = cnt[it.dst];
+      if (cnt) {                                   // (`mean` holds here: a true division, where it always was)
         s.x /= c; s.y /= c; s.z /= c; s.w /= c;
       }
       *reinterpret_cast<float4*>(agg + (size_t)it.dst * d + c4) = s;
