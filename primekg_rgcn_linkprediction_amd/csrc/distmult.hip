@@ -25,15 +25,6 @@ __device__ inline float bce_with_logits(float x, float y) {
 // in the same situation, asynchronously; an error CODE would need a host sync per call).
 __device__ int g_index_error = 0;
 
-__device__ inline int64_t checked_row(const int64_t* __restrict__ idx, int64_t b, int64_t rows) {
-  int64_t v = idx ? idx[b] : b;
-  if ((uint64_t)v >= (uint64_t)rows) {
-    g_index_error = 1;
-    v = 0;
-  }
-  return v;
-}
-
 template <int G, bool BCE = false>
 __global__ __launch_bounds__(kThreads) void k_distmult_fwd(const float* __restrict__ h, const int64_t* __restrict__ hi,
                                                            int64_t h_rows, const float* __restrict__ t,
@@ -47,9 +38,9 @@ __global__ __launch_bounds__(kThreads) void k_distmult_fwd(const float* __restri
   const bool live = b < B;
   float s = 0.f;
   if (live) {
-    const float* hp = h + (size_t)checked_row(hi, b, h_rows) * d;
-    const float* tp = t + (size_t)checked_row(ti, b, t_rows) * d;
-    const float* rp = r + (size_t)checked_row(ri, b, r_rows) * d;
+    const float* hp = h + (size_t)rgcn_checked_row(hi, b, h_rows, &g_index_error) * d;
+    const float* tp = t + (size_t)rgcn_checked_row(ti, b, t_rows, &g_index_error) * d;
+    const float* rp = r + (size_t)rgcn_checked_row(ri, b, r_rows, &g_index_error) * d;
     for (int c = gl * 4; c < d; c += G * 4) {
       const float4 a = ld4(hp + c), m = ld4(rp + c), z = ld4(tp + c);
       s += a.x * m.x * z.x;
@@ -80,7 +71,8 @@ __global__ __launch_bounds__(kThreads) void k_distmult_fwd(const float* __restri
 //   3. k_segment_partials / k_segment_combine: the relation table (few rows, hundreds of occurrences
 //      each) as a fixed two-level tree: one wave per (row, segment of >= 64 samples) adds its occurrences in
 //      order, one wave per row adds the segments in order.
-// Every sum has a fixed order: two runs give the same bits.
+// Every sum has a fixed order: two runs give the same bits.  The pieces of launches 2 and 3 - and the two tree
+// kernels themselves - live in rgcn_ordered_match.h, shared with the TransE step (transe.hip).
 // ---------------------------------------------------------------------------------------
 template <int G, bool BCE = false>
 __global__ __launch_bounds__(kThreads) void k_distmult_contrib(
@@ -102,7 +94,8 @@ __global__ __launch_bounds__(kThreads) void k_distmult_contrib(
   const int64_t b = ((int64_t)blockIdx.x * kThreads + threadIdx.x) / G;
   const int gl = threadIdx.x % G;
   if (b >= B) return;
-  const int64_t hr = checked_row(hi, b, h_rows), tr = checked_row(ti, b, t_rows), rr = checked_row(ri, b, r_rows);
+  const int64_t hr = rgcn_checked_row(hi, b, h_rows, &g_index_error), tr = rgcn_checked_row(ti, b, t_rows, &g_index_error),
+                rr = rgcn_checked_row(ri, b, r_rows, &g_index_error);
   if (gl == 0) {
     if (key_h) key_h[b] = (int32_t)hr;
     if (key_t) key_t[b] = (int32_t)tr;
@@ -124,7 +117,7 @@ constexpr int kKeysInLds = 16384;                // key count up to which the ke
 // rows[S, d] (workspace), keys[S] -> out[key] = sum of the rows with that key, in slot order; one wave per slot, sixteen
 // slots per workgroup (one staging of the keys serves them all).  A slot that finds an equal key BEFORE itself
 // retires; the first occurrence of a row adds the rows of all its occurrences in slot order.  A template on where the
-// keys are: the scans then read LDS with ds_read_b32, not through a flat pointer.
+// keys are (stage_keys).
 // (Round 3 tried a chunked two-pass form - every 16th occurrence adds its chunk, a second launch adds the chunk sums
 // of the rows with more than 16 occurrences - to shorten the chain of a hub with 100+ occurrences: 15 + 18 us against
 // this kernel's 27 us.  The launch is bound by the scans over the keys, not by the hub's additions.)
@@ -134,59 +127,18 @@ __global__ __launch_bounds__(64 * kScatterWaves) void k_scatter_rows(const int32
                                                                               float* __restrict__ out) {
   __shared__ int32_t skeys[IN_LDS ? kKeysInLds : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (IN_LDS) {
-    for (int i = threadIdx.x; i < S; i += 64 * kScatterWaves) skeys[i] = keys[i];
-    __syncthreads();
-  }
-  const int32_t* k = IN_LDS ? skeys : keys;
+  const int32_t* k = stage_keys<IN_LDS, 64 * kScatterWaves>(keys, S, skeys);
   const int s = blockIdx.x * kScatterWaves + wave;
   if (s >= S) return;
   const int my = k[s];
-  for (int c = 0; c < s; c += 64) {              // an earlier occurrence owns the row
-    const int p = c + lane;
-    if (__ballot(p < s && k[p] == my)) return;
-  }
+  for (int c = 0; c < s; c += 64)               // an earlier occurrence owns the row
+    if (earlier_slot_has(k, my, s, c, lane)) return;
   for (int c0 = lane * 4; c0 < ((d + 255) & ~255); c0 += 256) {
     MatchIter it;
     it.start(k, my, s, S, lane);
     const int cc = min(c0, d - 4);
     const float4 acc = ordered_row_sum(it, rows, d, cc, lane);
     if (c0 < d) *reinterpret_cast<float4*>(out + (size_t)my * d + c0) = acc;
-  }
-}
-
-// partial[(seg * R + row), :] = sum of rows[b] over b in segment seg with keys[b] == row, in order
-__global__ __launch_bounds__(64) void k_segment_partials(const int32_t* __restrict__ keys, int B,
-                                                         const float* __restrict__ rows, int d, int R, int seg_len,
-                                                         float* __restrict__ partial) {
-  const int lane = threadIdx.x, row = blockIdx.x, seg = blockIdx.y;
-  const int lo = seg * seg_len, hi = min(B, lo + seg_len);
-  for (int c0 = lane * 4; c0 < ((d + 255) & ~255); c0 += 256) {
-    MatchIter it;
-    it.start(keys, row, lo, hi, lane);
-    const int cc = min(c0, d - 4);
-    const float4 acc = ordered_row_sum(it, rows, d, cc, lane);
-    if (c0 < d) *reinterpret_cast<float4*>(partial + ((size_t)seg * R + row) * d + c0) = acc;
-  }
-}
-
-// out[row, :] = sum over segments, in order
-__global__ __launch_bounds__(64) void k_segment_combine(const float* __restrict__ partial, int nseg, int R, int d,
-                                                        float* __restrict__ out) {
-  const int lane = threadIdx.x, row = blockIdx.x;
-  for (int c0 = lane * 4; c0 < d; c0 += 256) {
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int s0 = 0; s0 < nseg; s0 += 16) {      // sixteen loads in flight, added in segment order
-      float4 v[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u)
-        v[u] = s0 + u < nseg ? ld4(partial + ((size_t)(s0 + u) * R + row) * d + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w;
-      }
-    }
-    *reinterpret_cast<float4*>(out + (size_t)row * d + c0) = acc;
   }
 }
 
@@ -202,49 +154,18 @@ __global__ __launch_bounds__(1024) void k_bce_reduce(const float* __restrict__ l
                                                      const float* __restrict__ labels, int B, float* __restrict__ mean_loss,
                                                      double* __restrict__ loss_sum, long long* __restrict__ correct,
                                                      long long* __restrict__ cursor, long long cursor_add) {
-  __shared__ float red[1024];
-  __shared__ int hits[1024];
-  float s = 0.f;
-  int c = 0;
-  for (int b = threadIdx.x; b < B; b += 1024) {
+  const SumTally total = block1024_sum_tally(B, [&](int b, float& s, int& hits) {
     s += loss[b];
-    if (correct) c += ((scores[b] > 0.f) == (labels[b] > 0.5f)) ? 1 : 0;
-  }
-  red[threadIdx.x] = s;
-  hits[threadIdx.x] = c;
-  __syncthreads();
-  for (int w = 512; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      red[threadIdx.x] += red[threadIdx.x + w];
-      hits[threadIdx.x] += hits[threadIdx.x + w];
-    }
-    __syncthreads();
-  }
+    if (correct) hits += ((scores[b] > 0.f) == (labels[b] > 0.5f)) ? 1 : 0;
+  });
   if (threadIdx.x == 0) {
-    const float mean = red[0] / (float)B;
+    const float mean = total.sum / (float)B;
     mean_loss[0] = mean;
     if (loss_sum) loss_sum[0] += (double)mean * (double)B;
-    if (correct) correct[0] += hits[0];
+    if (correct) correct[0] += total.tally;
     if (cursor) cursor[0] += cursor_add;
   }
 }
-
-int pick_group(int64_t d) {
-  int g = 1;
-  while (g < 64 && g * 4 < d) g <<= 1;
-  return g;
-}
-
-#define DISPATCH_G(G_, CALL)                  \
-  switch (G_) {                               \
-    case 1: { constexpr int G = 1; CALL; } break;   \
-    case 2: { constexpr int G = 2; CALL; } break;   \
-    case 4: { constexpr int G = 4; CALL; } break;   \
-    case 8: { constexpr int G = 8; CALL; } break;   \
-    case 16: { constexpr int G = 16; CALL; } break; \
-    case 32: { constexpr int G = 32; CALL; } break; \
-    default: { constexpr int G = 64; CALL; } break; \
-  }
 
 }  // namespace
 
@@ -275,9 +196,9 @@ int distmult_fwd(const float* h, const int64_t* h_idx, int64_t h_rows, const flo
   RGCN_ALIGN_TRY(8, h_idx, t_idx, r_idx);
   RGCN_ALIGN_TRY(4, scores);
   hipStream_t stream = (hipStream_t)stream_;
-  const int g = pick_group(d);
+  const int g = rgcn_pick_group(d);
   const unsigned grid = (unsigned)ceil_div64(batch, kThreads / g);
-  DISPATCH_G(g, (k_distmult_fwd<G><<<grid, kThreads, 0, stream>>>(h, h_idx, h_rows, t, t_idx, t_rows, r, r_idx, r_rows,
+  RGCN_DISPATCH_G(g, (k_distmult_fwd<G><<<grid, kThreads, 0, stream>>>(h, h_idx, h_rows, t, t_idx, t_rows, r, r_idx, r_rows,
                                                                     batch, (int)d, scores)));
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
@@ -293,9 +214,9 @@ int distmult_bce_fwd(const float* h, const int64_t* h_idx, int64_t h_rows, const
   RGCN_ALIGN_TRY(8, h_idx, t_idx, r_idx);
   RGCN_ALIGN_TRY(4, labels, scores, loss);
   hipStream_t stream = (hipStream_t)stream_;
-  const int g = pick_group(d);
+  const int g = rgcn_pick_group(d);
   const unsigned grid = (unsigned)ceil_div64(batch, kThreads / g);
-  DISPATCH_G(g, (k_distmult_fwd<G, true><<<grid, kThreads, 0, stream>>>(h, h_idx, h_rows, t, t_idx, t_rows, r, r_idx,
+  RGCN_DISPATCH_G(g, (k_distmult_fwd<G, true><<<grid, kThreads, 0, stream>>>(h, h_idx, h_rows, t, t_idx, t_rows, r, r_idx,
                                                                          r_rows, batch, (int)d, scores, labels, loss)));
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
@@ -359,7 +280,7 @@ int bwd_impl(const float* gs, const float* scores, const float* labels, const fl
   float* out_h = grad_h ? (h_idx ? ch : grad_h) : nullptr;
   float* out_t = grad_t ? (t_idx ? ct : grad_t) : nullptr;
   float* out_r = grad_r ? (r_idx ? cr : grad_r) : nullptr;
-  const int g = pick_group(d);
+  const int g = rgcn_pick_group(d);
   const unsigned grid = (unsigned)ceil_div64(batch, kThreads / g);
   const bool sh = grad_h && h_idx, st = grad_t && t_idx;
   // zero_tables: the tables the scatter below writes rows into are cleared by riders of this launch (the relation
@@ -371,7 +292,7 @@ int bwd_impl(const float* gs, const float* scores, const float* labels, const fl
     if (st && !(sh && grad_h == grad_t)) { zb = grad_t; zbq = t_rows * d / 4; }
   }
   const unsigned riders = (zaq + zbq) > 0 ? (unsigned)std::min<int64_t>(1024, ceil_div64(zaq + zbq, 4 * kThreads)) : 0u;
-  DISPATCH_G(g, (k_distmult_contrib<G, BCE><<<grid + riders, kThreads, 0, stream>>>(
+  RGCN_DISPATCH_G(g, (k_distmult_contrib<G, BCE><<<grid + riders, kThreads, 0, stream>>>(
                     gs, h, h_idx, h_rows, t, t_idx, t_rows, r, r_idx, r_rows, batch, (int)d, out_h, out_t, out_r,
                     (grad_h && h_idx) ? kh : nullptr, (grad_t && t_idx) ? kt : nullptr, (grad_r && r_idx) ? kr : nullptr,
                     scores, labels, (int)grid, za, zaq, zb, zbq)));
@@ -389,7 +310,7 @@ int bwd_impl(const float* gs, const float* scores, const float* labels, const fl
   if (grad_r && r_idx && r_rows > 0) {
     dim3 pg((unsigned)r_rows, (unsigned)nseg);
     k_segment_partials<<<pg, 64, 0, stream>>>(kr, (int)batch, cr, (int)d, (int)r_rows, (int)segment_len(batch), partial);
-    k_segment_combine<<<(unsigned)r_rows, 64, 0, stream>>>(partial, (int)nseg, (int)r_rows, (int)d, grad_r);
+    k_segment_combine<false><<<(unsigned)r_rows, 64, 0, stream>>>(partial, (int)nseg, (int)r_rows, (int)d, grad_r);
   }
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
@@ -397,7 +318,7 @@ int bwd_impl(const float* gs, const float* scores, const float* labels, const fl
 
 __global__ void k_keys32(const int64_t* __restrict__ idx, int64_t B, int64_t rows, int32_t* __restrict__ keys) {
   const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) keys[b] = (int32_t)checked_row(idx, b, rows);
+  if (b < B) keys[b] = (int32_t)rgcn_checked_row(idx, b, rows, &g_index_error);
 }
 
 }  // namespace
@@ -446,7 +367,7 @@ int rgcn_segment_sum(const float* rows, const int64_t* idx, int64_t batch, int64
   k_keys32<<<(unsigned)ceil_div64(batch, 256), 256, 0, stream>>>(idx, batch, num_rows, keys);
   dim3 pg((unsigned)num_rows, (unsigned)nseg);
   k_segment_partials<<<pg, 64, 0, stream>>>(keys, (int)batch, rows, (int)d, (int)num_rows, (int)segment_len(batch), partial);
-  k_segment_combine<<<(unsigned)num_rows, 64, 0, stream>>>(partial, (int)nseg, (int)num_rows, (int)d, out);
+  k_segment_combine<false><<<(unsigned)num_rows, 64, 0, stream>>>(partial, (int)nseg, (int)num_rows, (int)d, out);
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }

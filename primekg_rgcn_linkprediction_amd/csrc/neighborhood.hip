@@ -37,14 +37,6 @@ constexpr int kMaxWords = (kLdsBytes - kStaticReserve) / (kBitsets * 4);
 constexpr int64_t kMaxNodes = (int64_t)kMaxWords * 32;
 static_assert(kMaxNodes >= 262144, "twice the full PrimeKG node count must fit (include/rgcn_neighborhood.h)");
 
-__device__ inline int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ inline int lane_int(int v, int src) { return __builtin_amdgcn_readfirstlane(__shfl(v, src)); }
-__device__ inline int64_t lane_i64(int64_t v, int src) {
-  const unsigned lo = (unsigned)lane_int((int)(unsigned)(v & 0xffffffffll), src);
-  const int hi = lane_int((int)(v >> 32), src);
-  return ((int64_t)hi << 32) | (int64_t)lo;
-}
-
 // The sum of v over the workgroup, in every thread.  `red` may still be read by the previous call's stragglers: the
 // first barrier waits for them.  (It is also the barrier that makes the caller's LDS stores before the call visible.)
 __device__ inline unsigned long long block_sum(unsigned long long v, unsigned long long* red, int tid) {

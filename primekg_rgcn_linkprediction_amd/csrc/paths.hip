@@ -130,15 +130,6 @@ __device__ inline void list_offer(WaveList& l, int k, int lane, bool has, const 
   }
 }
 
-__device__ inline int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ inline int lane_int(int v, int src) { return __builtin_amdgcn_readfirstlane(__shfl(v, src)); }
-__device__ inline float lane_float(float v, int src) { return __int_as_float(lane_int(__float_as_int(v), src)); }
-__device__ inline int64_t lane_i64(int64_t v, int src) {
-  const unsigned lo = (unsigned)lane_int((int)(unsigned)(v & 0xffffffffll), src);
-  const int hi = lane_int((int)(v >> 32), src);
-  return ((int64_t)hi << 32) | (int64_t)lo;
-}
-
 struct PathWeights {
   float w[RGCN_PATHS_MAX_LEN + 1];
 };

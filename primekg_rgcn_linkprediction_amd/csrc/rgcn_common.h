@@ -146,6 +146,16 @@ static_assert(RGCN_AMAX_HEADS * RGCN_AMAX_HEAD_STRIDE == RGCN_AMAX_FLOATS && RGC
               "amax buffer layout");
 
 #if defined(__HIPCC__)
+// v held to [lo, hi]: the bounds of a CSR row read from memory that may be damaged
+__device__ inline int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// lane src's value of v as a wave-uniform (scalar) value
+__device__ inline int lane_int(int v, int src) { return __builtin_amdgcn_readfirstlane(__shfl(v, src)); }
+__device__ inline float lane_float(float v, int src) { return __int_as_float(lane_int(__float_as_int(v), src)); }
+__device__ inline int64_t lane_i64(int64_t v, int src) {
+  const unsigned lo = (unsigned)lane_int((int)(unsigned)(v & 0xffffffffll), src);
+  const int hi = lane_int((int)(v >> 32), src);
+  return ((int64_t)hi << 32) | (int64_t)lo;
+}
 // The ReLU of every fused epilogue.  fmaxf returns its non-NaN operand, so fmaxf(NaN, 0) is 0 and a diverged
 // pre-activation would leave the layer looking healthy; torch.relu(NaN) is NaN.  The select puts the NaN back and
 // leaves every other input with the bits fmaxf(v, 0.f) gives it (-0 included; +inf stays +inf, -inf becomes 0).

@@ -28,27 +28,13 @@
 // (it must not alias another anchor's key), and segment bounds are clamped to the id array.
 #include "rgcn_common.h"
 #include "../../include/rgcn_sampling.h"
+#include "rgcn_sample_core.h"
 #include "rgcn_sorted_search.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxTries = 16;
-
-__device__ inline void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  c[1] = (uint32_t)p1; c[3] = (uint32_t)p0; c[0] = n0; c[2] = n2;
-}
-
-__device__ inline void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
 
 struct known_side {
   const int64_t* keys;
@@ -91,18 +77,13 @@ __global__ __launch_bounds__(kThreads) void k_sample_batch_constrained(const sam
   const bool live = i < B * (1 + k);         // no early return: every lane takes part in the wave sums below
   int rejected = 0, gave_up = 0;
   if (live) {
-    const int64_t start = a.cursor ? a.cursor[0] : 0;
-    const int64_t p = i < B ? i : (i - B) / k;                       // the positive this sample comes from
-    int64_t pos = start + p;
-    pos = pos < 0 ? 0 : (pos >= E ? E - 1 : pos);                    // never read outside the columns
-    int64_t colm = a.order ? a.order[pos] : pos;
-    colm = colm < 0 ? 0 : (colm >= E ? E - 1 : colm);
-    int64_t h = a.edge_index[colm], t = a.edge_index[E + colm];
-    const int64_t rel = a.edge_type[colm];
+    const rgcn_positive s = rgcn_sample_positive(a.edge_index, E, a.order, a.cursor, B, k, i);
+    int64_t h = s.h, t = s.t;
+    const int64_t rel = a.edge_type[s.colm];
     if (i >= B) {
       const uint32_t k0 = (uint32_t)a.rng[0], k1 = (uint32_t)((uint64_t)a.rng[0] >> 32);
       const uint32_t e0 = (uint32_t)a.rng[1], e1 = (uint32_t)((uint64_t)a.rng[1] >> 32);
-      const uint64_t ctr = (uint64_t)start * (uint64_t)k + (uint64_t)(i - B);   // unique per negative of the epoch
+      const uint64_t ctr = rgcn_sample_counter(s.start, B, k, i);
       uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), e0, e1};
       philox4x32_10(c, k0, k1);
       const bool replace_head = (c[0] >> 31) != 0;
@@ -138,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void k_sample_batch_constrained(const sam
           c[0] = (uint32_t)ctr; c[1] = (uint32_t)(ctr >> 32); c[2] = e0; c[3] = e1 ^ ((uint32_t)tr << 24);
           philox4x32_10(c, k0, k1);
         }
-        const int64_t draw = (int64_t)(((uint64_t)c[1] * (uint64_t)range) >> 32);   // uniform on [0, range)
+        const int64_t draw = rgcn_sample_draw(c[1], range);
         entity = base < 0 ? draw : a.class_members[base + draw];
         bool known = false;
         if (seg_hi > seg_lo) {

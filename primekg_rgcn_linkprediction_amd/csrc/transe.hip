@@ -4,17 +4,17 @@
 // the margin loss, the Python loop `for i in range(len(batch_indices)): if loss[i] > 0: ...` with its five row updates
 // per sample, and `self.embeddings / np.linalg.norm(...)` over the whole table.  The reference's loop is serial (a later
 // sample sees the rows an earlier one moved); here every difference is taken from the tables as the step finds them and
-// a row's contributions are added in slot order and applied once - the structure of the DistMult backward
-// (distmult.hip), whose ordered-match iterator this file shares (rgcn_ordered_match.h):
+// a row's contributions are added in slot order and applied once - the ordered scatter of the DistMult backward
+// (distmult.hip), taken from the header both files share (rgcn_ordered_match.h).  This file defines:
 //   1. k_transe_contrib: one lane group of d/4 lanes per sample, float4 per lane, butterfly reduction of the two norms.
 //      Writes the scaled rows 2 lr dp_i, 2 lr dn_i, the sample's loss, four int32 entity keys (-1 when the sample is
 //      not active), the relation key and the relation row 2 lr (dp_i - dn_i) (exact zeros when not active).
 //   2. k_transe_apply: one wave per slot.  A slot whose key occurs BEFORE it retires; the first occurrence adds the
 //      signed rows of all occurrences in slot order, adds the sum to the table row, normalises it and writes it once.
 //      A launch of its own: launch 1 reads the rows this one writes.
-//   3. k_transe_rel_partials / k_transe_rel_combine: the relation table as the fixed two-level tree of
-//      rgcn_segment_sum, the combine pass subtracting the sum from the row.
-//   4. k_transe_loss: the mean loss in a fixed order and the two device-side accumulators.
+//   3. k_transe_loss: the mean loss in a fixed order and the two device-side accumulators.
+// Between 2 and 3 the step launches the header's relation tree (k_segment_partials, k_segment_combine<true>: the
+// combine pass subtracts the sum from the row).
 // No floating-point atomics; two runs from the same tables give the same bits.
 #include "rgcn_common.h"
 #include "rgcn_ordered_match.h"
@@ -25,16 +25,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kApplyWaves = 16;                  // slots per workgroup of the apply launch: one staging of the keys serves sixteen
 constexpr int kKeysInLds = 8192;                 // key count (4 per sample) up to which the apply launch stages the keys in LDS
-
-// an id outside its table: clamped to row 0, the library's sticky flag raised (rgcn_index_error_fetch)
-__device__ inline int64_t clamped_row(const int64_t* __restrict__ idx, int64_t b, int64_t rows, int* __restrict__ flag) {
-  int64_t v = idx[b];
-  if ((uint64_t)v >= (uint64_t)rows) {
-    *flag = 1;
-    v = 0;
-  }
-  return v;
-}
 
 __device__ inline float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ inline float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
@@ -53,12 +43,15 @@ __global__ __launch_bounds__(kThreads) void k_transe_contrib(
   const bool live = b < B;                       // lanes past the batch stay for the butterflies
   int64_t h = 0, t = 0, hn = 0, tn = 0, r = 0;
   float sp = 0.f, sn = 0.f;
+  // the host refuses a step without its id vectors: rgcn_checked_row's "no index vector, row b itself" cannot occur
+  // here, and said so it costs no register
+  __builtin_assume(heads != nullptr && tails != nullptr && rels != nullptr);
   if (live) {
-    h = clamped_row(heads, b, num_nodes, flag);
-    t = clamped_row(tails, b, num_nodes, flag);
-    hn = clamped_row(heads, B + b, num_nodes, flag);
-    tn = clamped_row(tails, B + b, num_nodes, flag);
-    r = clamped_row(rels, b, num_relations, flag);
+    h = rgcn_checked_row(heads, b, num_nodes, flag);
+    t = rgcn_checked_row(tails, b, num_nodes, flag);
+    hn = rgcn_checked_row(heads, B + b, num_nodes, flag);
+    tn = rgcn_checked_row(tails, B + b, num_nodes, flag);
+    r = rgcn_checked_row(rels, b, num_relations, flag);
     for (int c = gl * 4; c < d; c += G * 4) {
       const float4 rv = ld4(rel + (size_t)r * d + c);
       const float4 dp = sub4(add4(ld4(emb + (size_t)h * d + c), rv), ld4(emb + (size_t)t * d + c));
@@ -98,34 +91,6 @@ __global__ __launch_bounds__(kThreads) void k_transe_contrib(
   }
 }
 
-// the signed rows of the slots the iterator yields, added in slot order, eight loads in flight: slot p belongs to sample
-// p / 4; kinds 0 and 3 (positive head, negative tail) subtract their row, kinds 1 and 2 add it; kinds 0, 1 read
-// dpn[2i], kinds 2, 3 read dpn[2i + 1]
-__device__ inline float4 signed_row_sum(MatchIter& it, const float* __restrict__ dpn, int d, int c0, int lane) {
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  while (true) {
-    int p[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) p[u] = it.next(lane);
-    if (p[0] < 0) break;
-    float4 v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      // slot p reads row p >> 1 of dpn (kinds 0, 1 -> 2i, kinds 2, 3 -> 2i + 1).  The sign is a bit flipped for kinds
-      // 0 and 3, not a select between a row and its negation: written as `neg ? -w : w` inside the `p >= 0` branch,
-      // the compiler at hand dropped the negation of the first of the eight rows for kind 0 (seen in the ISA)
-      const float4 w = p[u] >= 0 ? ld4(dpn + (size_t)(p[u] >> 1) * d + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
-      const unsigned flip = (~((unsigned)p[u] ^ ((unsigned)p[u] >> 1)) & 1u) << 31;
-      v[u] = make_float4(__uint_as_float(__float_as_uint(w.x) ^ flip), __uint_as_float(__float_as_uint(w.y) ^ flip),
-                         __uint_as_float(__float_as_uint(w.z) ^ flip), __uint_as_float(__float_as_uint(w.w) ^ flip));
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc = add4(acc, v[u]);
-    if (p[7] < 0) break;
-  }
-  return acc;
-}
-
 // keys[S] (S = 4B, -1: not active), dpn[2B, d] -> emb[key] = normalised(emb[key] + signed sum), once per key
 template <bool IN_LDS>
 __global__ __launch_bounds__(64 * kApplyWaves) void k_transe_apply(const int32_t* __restrict__ keys, int S,
@@ -133,26 +98,20 @@ __global__ __launch_bounds__(64 * kApplyWaves) void k_transe_apply(const int32_t
                                                                    float* __restrict__ emb) {
   __shared__ int32_t skeys[IN_LDS ? kKeysInLds : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (IN_LDS) {
-    for (int i = threadIdx.x; i < S; i += 64 * kApplyWaves) skeys[i] = keys[i];
-    __syncthreads();
-  }
-  const int32_t* k = IN_LDS ? skeys : keys;
+  const int32_t* k = stage_keys<IN_LDS, 64 * kApplyWaves>(keys, S, skeys);
   const int s = blockIdx.x * kApplyWaves + wave;
   if (s >= S) return;
   const int my = k[s];
   if (my < 0) return;                            // a slot of a sample that is not active
-  for (int c = 0; c < s; c += 64) {              // an earlier occurrence owns the row
-    const int p = c + lane;
-    if (__ballot(p < s && k[p] == my)) return;
-  }
+  for (int c = 0; c < s; c += 64)               // an earlier occurrence owns the row
+    if (earlier_slot_has(k, my, s, c, lane)) return;
   float* row = emb + (size_t)my * d;
   float ss = 0.f;
   for (int c0 = lane * 4; c0 < ((d + 255) & ~255); c0 += 256) {
     MatchIter it;
     it.start(k, my, s, S, lane);
     const int cc = min(c0, d - 4);               // lanes past the row stay for the iterator's ballots
-    const float4 acc = signed_row_sum(it, dpn, d, cc, lane);
+    const float4 acc = ordered_row_sum<TranseRows>(it, dpn, d, cc, lane);
     if (c0 < d) {
       const float4 v = add4(ld4(row + c0), acc);
       ss += dot4(v);
@@ -168,75 +127,21 @@ __global__ __launch_bounds__(64 * kApplyWaves) void k_transe_apply(const int32_t
   }
 }
 
-// partial[(seg * R + row), :] = sum of relrow[b] over b in segment seg with rkeys[b] == row, in order
-__global__ __launch_bounds__(64) void k_transe_rel_partials(const int32_t* __restrict__ rkeys, int B,
-                                                            const float* __restrict__ relrow, int d, int R, int seg_len,
-                                                            float* __restrict__ partial) {
-  const int lane = threadIdx.x, row = blockIdx.x, seg = blockIdx.y;
-  const int lo = seg * seg_len, hi = min(B, lo + seg_len);
-  for (int c0 = lane * 4; c0 < ((d + 255) & ~255); c0 += 256) {
-    MatchIter it;
-    it.start(rkeys, row, lo, hi, lane);
-    const int cc = min(c0, d - 4);
-    const float4 acc = ordered_row_sum(it, relrow, d, cc, lane);
-    if (c0 < d) *reinterpret_cast<float4*>(partial + ((size_t)seg * R + row) * d + c0) = acc;
-  }
-}
-
-// rel[row, :] -= sum over segments, in order
-__global__ __launch_bounds__(64) void k_transe_rel_combine(const float* __restrict__ partial, int nseg, int R, int d,
-                                                           float* __restrict__ rel) {
-  const int lane = threadIdx.x, row = blockIdx.x;
-  for (int c0 = lane * 4; c0 < d; c0 += 256) {
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int s0 = 0; s0 < nseg; s0 += 16) {      // sixteen loads in flight, added in segment order
-      float4 v[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u)
-        v[u] = s0 + u < nseg ? ld4(partial + ((size_t)(s0 + u) * R + row) * d + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int u = 0; u < 16; ++u) acc = add4(acc, v[u]);
-    }
-    float* out = rel + (size_t)row * d + c0;
-    *reinterpret_cast<float4*>(out) = sub4(ld4(out), acc);
-  }
-}
-
 // mean of the per-sample losses (thread i adds elements i, i + 1024, ..., then a fixed tree), the active count (a sample
 // is active iff its first key is not -1) and the two running sums
 __global__ __launch_bounds__(1024) void k_transe_loss(const float* __restrict__ loss, const int32_t* __restrict__ keys, int B,
                                                       float* __restrict__ loss_mean, double* __restrict__ loss_sum,
                                                       long long* __restrict__ active_sum) {
-  __shared__ float red[1024];
-  __shared__ int act[1024];
-  float s = 0.f;
-  int c = 0;
-  for (int b = threadIdx.x; b < B; b += 1024) {
+  const SumTally total = block1024_sum_tally(B, [&](int b, float& s, int& active) {
     s += loss[b];
-    c += keys[4 * b] >= 0 ? 1 : 0;
-  }
-  red[threadIdx.x] = s;
-  act[threadIdx.x] = c;
-  __syncthreads();
-  for (int w = 512; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      red[threadIdx.x] += red[threadIdx.x + w];
-      act[threadIdx.x] += act[threadIdx.x + w];
-    }
-    __syncthreads();
-  }
+    active += keys[4 * b] >= 0 ? 1 : 0;
+  });
   if (threadIdx.x == 0) {
-    const float mean = red[0] / (float)B;
+    const float mean = total.sum / (float)B;
     loss_mean[0] = mean;
     if (loss_sum) loss_sum[0] += (double)mean;
-    if (active_sum) active_sum[0] += act[0];
+    if (active_sum) active_sum[0] += total.tally;
   }
-}
-
-int pick_group(int64_t d) {
-  int g = 1;
-  while (g < 64 && g * 4 < d) g <<= 1;
-  return g;
 }
 
 // the workspace's sections, each on a 256-byte boundary
@@ -303,29 +208,19 @@ int rgcn_transe_step(float* emb, int64_t num_nodes, float* rel, int64_t num_rela
   float* loss = (float*)(ws + l.loss);
   int32_t* keys = (int32_t*)(ws + l.keys);
   int32_t* rkeys = (int32_t*)(ws + l.rkeys);
-  const int g = pick_group(d);
+  const int g = rgcn_pick_group(d);
   const unsigned grid = (unsigned)ceil_div64(batch, kThreads / g);
-#define TRANSE_CONTRIB(G_)                                                                                             \
-  k_transe_contrib<G_><<<grid, kThreads, 0, stream>>>(emb, num_nodes, rel, num_relations, (int)d, heads, tails, rels,  \
-                                                      batch, 2.f * lr, margin, dpn, relrow, loss, keys, rkeys, flag)
-  switch (g) {
-    case 1: TRANSE_CONTRIB(1); break;
-    case 2: TRANSE_CONTRIB(2); break;
-    case 4: TRANSE_CONTRIB(4); break;
-    case 8: TRANSE_CONTRIB(8); break;
-    case 16: TRANSE_CONTRIB(16); break;
-    case 32: TRANSE_CONTRIB(32); break;
-    default: TRANSE_CONTRIB(64); break;
-  }
-#undef TRANSE_CONTRIB
+  RGCN_DISPATCH_G(g, (k_transe_contrib<G><<<grid, kThreads, 0, stream>>>(emb, num_nodes, rel, num_relations, (int)d, heads,
+                                                                        tails, rels, batch, 2.f * lr, margin, dpn, relrow,
+                                                                        loss, keys, rkeys, flag)));
   const int S = (int)(4 * batch);
   const unsigned ag = (unsigned)ceil_div64(S, kApplyWaves);
   if (S <= kKeysInLds) k_transe_apply<true><<<ag, 64 * kApplyWaves, 0, stream>>>(keys, S, dpn, (int)d, emb);
   else k_transe_apply<false><<<ag, 64 * kApplyWaves, 0, stream>>>(keys, S, dpn, (int)d, emb);
   dim3 pg((unsigned)num_relations, (unsigned)l.nseg);
-  k_transe_rel_partials<<<pg, 64, 0, stream>>>(rkeys, (int)batch, relrow, (int)d, (int)num_relations,
-                                               (int)segment_len(batch), partial);
-  k_transe_rel_combine<<<(unsigned)num_relations, 64, 0, stream>>>(partial, (int)l.nseg, (int)num_relations, (int)d, rel);
+  k_segment_partials<<<pg, 64, 0, stream>>>(rkeys, (int)batch, relrow, (int)d, (int)num_relations, (int)segment_len(batch),
+                                            partial);
+  k_segment_combine<true><<<(unsigned)num_relations, 64, 0, stream>>>(partial, (int)l.nseg, (int)num_relations, (int)d, rel);
   k_transe_loss<<<1, 1024, 0, stream>>>(loss, keys, (int)batch, loss_mean, loss_sum,
                                         reinterpret_cast<long long*>(active_sum));
   RGCN_HIP_TRY(hipGetLastError());
