@@ -94,7 +94,7 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 36
+#define RGCN_ABI_VERSION 37
 
 enum {
   RGCN_OK = 0,

@@ -13,7 +13,7 @@ from ctypes import c_double, c_float, POINTER, c_char_p, c_int, c_int64, c_size_
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-ABI_VERSION = 36
+ABI_VERSION = 37
 LIB_NAME = "librgcn_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -210,6 +210,20 @@ TRANSE_PROTOTYPES = {
                                  _P, _P, _P, _P, c_size_t, _P]),                   # loss outputs, workspace, stream
 }
 
+# include/rgcn_resample.h, one to one: bootstrap resampling of the evaluation metrics (csrc/resample.hip; not part of
+# rgcn_hip.h, never forwarded by rgcn_sequence_run - an analysis call, outside any recorded Region)
+RESAMPLE_PROTOTYPES = {
+    "rgcn_resample_weights": (c_int, [_I64, _I64, _I64, _P, _P]),
+    "rgcn_resample_curves": (c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64,     # sorted samples, cut, units, replicates, seed
+                                     _P, _P, _P, _P, _P, _P, _P]),                 # wp, wn, auc2, ap, tp, fp, stream
+    "rgcn_resample_ranks": (c_int, [_P, _P, _I64, _P, c_int, _I64, _I64, _I64,     # ranks, k_values, units, replicates, seed
+                                    _P, _P, _P, _P, _P]),                          # w_sum, rank_sum, hits, rr_sum, stream
+}
+RESAMPLE_TILE = 1024             # RGCN_RESAMPLE_TILE
+RESAMPLE_MAX_SAMPLES = 1 << 28   # RGCN_RESAMPLE_MAX_SAMPLES
+RESAMPLE_MAX_REPLICATES = 65535  # RGCN_RESAMPLE_MAX_REPLICATES
+RESAMPLE_MAX_K = 8               # RGCN_RESAMPLE_MAX_K
+
 _lib = None
 
 
@@ -231,7 +245,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise RGCNLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

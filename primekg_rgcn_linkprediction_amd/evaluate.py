@@ -235,17 +235,19 @@ class ModelEvaluator:
     def compare_methods(self, train_data: Dict, methods: Sequence[str] = ("random", "degree", "transe", "rgcn"),
                         k_values: Sequence[int] = (1, 5, 10, 20, 50), filtered: bool = False, type_constrained: bool = False,
                         both_sides: bool = False, transe_epochs: int = 50, seed: int = 0, drug_class: Optional[int] = None,
-                        disease_class: Optional[int] = None, **transe_kwargs) -> Dict:
+                        disease_class: Optional[int] = None, bootstrap: int = 0, bootstrap_seed: int = 0,
+                        by_frequency: bool = False, **transe_kwargs) -> Dict:
         """this model next to the Random, Node Degree and TransE baselines (``baselines.py``, fitted on ``train_data``),
         every method under one ranking protocol on the test triples and one set of labelled per-triple scores:
-        ``compare.compare_methods`` on the evaluator's test set, full graph and node classes"""
+        ``compare.compare_methods`` on the evaluator's test set, full graph and node classes.  ``bootstrap`` > 0 adds
+        intervals per method and paired p-values per pair of methods, ``by_frequency`` the split by disease degree."""
         from . import compare
         test = {"edge_index": self.test_edge_index, "edge_type": self.test_edge_type}
         full = {"edge_index": self.full_edge_index, "edge_type": self.full_edge_type, "num_nodes": self.num_nodes,
                 "num_relations": self.model.decoder.num_relations}
         return compare.compare_methods(train_data, test, full, self.device, self.model, self.node_class, methods, k_values,
                                        filtered, type_constrained, both_sides, transe_epochs, seed, drug_class,
-                                       disease_class, transe_kwargs or None)
+                                       disease_class, transe_kwargs or None, bootstrap, bootstrap_seed, by_frequency)
 
     @torch.no_grad()
     def reduce_dimensions(self, method: str = "tsne", sample_size: Optional[int] = None, random_state: int = 42, **tsne_kw):
@@ -277,12 +279,49 @@ class ModelEvaluator:
                 "precision": float(precision_score(labels, pred)), "recall": float(recall_score(labels, pred)),
                 "f1_score": float(f1_score(labels, pred)), "threshold": threshold}
 
+    def _sample_units(self, num_neg_samples: int) -> torch.Tensor:
+        """int32: the test triple of every entry of ``compute_scores_and_labels`` - per batch its positives, then
+        ``num_neg_samples`` corruptions of each, one after the other"""
+        units = []
+        for lo in range(0, self.num_test_edges, self.batch_size):
+            own = torch.arange(lo, min(lo + self.batch_size, self.num_test_edges), dtype=torch.int32, device=self.device)
+            units += [own, own.repeat_interleave(num_neg_samples)]
+        return torch.cat(units) if units else torch.zeros(0, dtype=torch.int32, device=self.device)
+
+    @torch.no_grad()
+    def bootstrap(self, replicates: int, seed: int = 0, filtered: bool = False, type_constrained: bool = False,
+                  both_sides: bool = False, num_neg_samples: int = 1, k_values: Sequence[int] = (10, 50)) -> Dict:
+        """Intervals for the metrics of ``evaluate`` from ``replicates`` Poisson bootstrap resamples of the test
+        triples, on the device (``ops.classification_counts`` / ``ops.rank_sums``): per metric (``auc_roc``,
+        ``auc_pr``, ``f1_score``, ``mrr``, ``mean_rank``, each ``hits@k``) the point estimate, the standard error and
+        the 2.5 / 97.5 percentile interval, plus ``replicates``, ``seed`` and ``degenerate_replicates`` (dropped: a
+        class had no weight).  A triple keeps its corruptions, and its tail query its head query: they share a weight.
+        The scores are those of the last ``evaluate`` under the same options when there was one.  The median rank is
+        not a sum over queries and is not resampled."""
+        from . import bootstrap as BS
+        key = (num_neg_samples, bool(filtered), bool(type_constrained))
+        if getattr(self, "_scores_key", None) != key:
+            self.scores, self.labels = self.compute_scores_and_labels(num_neg_samples, filtered, type_constrained)
+            self._scores_key = key
+        ranks = self.tail_ranks(filtered, type_constrained)
+        if both_sides:
+            ranks = torch.cat([ranks, self.head_ranks(filtered, type_constrained)])
+        scores, labels = (torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in (self.scores, self.labels))
+        vectors, degenerate, w_sum = BS.replicate_vectors(scores, labels, self._sample_units(num_neg_samples), ranks,
+                                                          BS.query_units(self.num_test_edges, ranks.numel(), self.device),
+                                                          k_values, replicates, seed)
+        out = BS.block(vectors, degenerate, replicates, seed, w_sum)
+        out["protocol"] = {"filtered": bool(filtered), "type_constrained": bool(type_constrained),
+                           "sides": "both" if both_sides else "tail", "num_neg_samples": num_neg_samples}
+        return out
+
     def evaluate(self, num_neg_samples: int = 1, k_values: List[int] = (10, 50), filtered: bool = False,
                  type_constrained: bool = False, both_sides: bool = False) -> Dict:
         """the reference's four keys; with any of the three protocol options one more, ``"ranking_filtered"``: the
         same metric names under that protocol plus ``"protocol"`` saying which it was"""
         scores, labels = self.compute_scores_and_labels(num_neg_samples, filtered, type_constrained)
         self.scores, self.labels = scores, labels          # kept for plotting code, as the reference does
+        self._scores_key = (num_neg_samples, bool(filtered), bool(type_constrained))
         metrics = {"classification": self.compute_classification_metrics(scores, labels),
                    "ranking": self.compute_ranking_metrics(k_values),
                    "test_edges": self.num_test_edges, "num_nodes": self.num_nodes}
@@ -388,12 +427,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--both_sides", action="store_true", help="also rank the heads and average over both sides")
     p.add_argument("--node_types", type=str, default=None,
                    help="the preprocessing's mappings.pt, or an .npz / .pt holding an int vector [num_nodes]")
+    p.add_argument("--bootstrap", type=int, default=0,
+                   help="bootstrap replicates over the test triples: a \"bootstrap\" block with intervals in results.json (0: off)")
+    p.add_argument("--bootstrap_seed", type=int, default=0)
     return p
 
 
 def parse_args(argv=None) -> argparse.Namespace:
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.bootstrap < 0 or args.bootstrap > 65535:
+        parser.error("--bootstrap must be in [0, 65535]")
     if args.type_constrained and not args.node_types:
         parser.error("--type_constrained needs --node_types PATH (mappings.pt, or an .npz / .pt int vector [num_nodes])")
     return args
@@ -428,6 +472,9 @@ def main(argv=None) -> Dict:
     evaluator = ModelEvaluator(model, test_data, full_graph, device, batch_size=args.batch_size, node_class=node_class)
     metrics = evaluator.evaluate(num_neg_samples=args.num_neg_samples, k_values=args.k_values, filtered=args.filtered,
                                  type_constrained=args.type_constrained, both_sides=args.both_sides)
+    if args.bootstrap:
+        metrics["bootstrap"] = evaluator.bootstrap(args.bootstrap, args.bootstrap_seed, args.filtered, args.type_constrained,
+                                                   args.both_sides, args.num_neg_samples, args.k_values)
     save_results(metrics, Path(args.output_dir), info)
     logger.info("Results saved to: %s", args.output_dir)
     return metrics

@@ -2307,7 +2307,173 @@ def transe_rank_operands(emb: torch.Tensor, rel: torch.Tensor, anchor_idx: torch
     return q, cand, true_score_fn
 
 
-CLUSTER_MAX_K = 64            # RGCN_CLUSTER_MAX_K: two 32-column blocks per restart, 32 KB of sums per update workgroup
+# ----------------------------------------------------------------------------------
+# bootstrap resampling of the evaluation metrics (include/rgcn_resample.h, csrc/resample.hip)
+# ----------------------------------------------------------------------------------
+def _ratio(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
+    """float64 ``num / den`` with NaN where ``den`` is 0 (the metric is undefined in that replicate)"""
+    num, den = num.double(), den.double()
+    return torch.where(den > 0, num / den.clamp(min=1), torch.full_like(den, float("nan")))
+
+
+class ClassificationCounts(NamedTuple):
+    """per replicate ``0 .. replicates`` (row 0: the point estimate): the sufficient statistics of the ROC / PR
+    metrics under the resampling weights, and the metrics as float64 tensors with NaN where a replicate leaves one
+    undefined (a class without weight, or nothing predicted positive)"""
+    wp: torch.Tensor        # int64: total positive weight
+    wn: torch.Tensor        # int64: total negative weight
+    auc2: torch.Tensor      # int64: 2 wp wn AUC-ROC, ties counted half
+    ap: torch.Tensor        # float64: step-wise average precision (0 where wp or wn is 0)
+    tp: torch.Tensor        # int64: positive weight with score >= threshold
+    fp: torch.Tensor        # int64: negative weight with score >= threshold
+
+    def degenerate(self) -> torch.Tensor:
+        return (self.wp == 0) | (self.wn == 0)
+
+    def auc_roc(self) -> torch.Tensor:
+        return _ratio(self.auc2, 2 * self.wp * self.wn)         # 2 wp wn < 2^63 (wp + wn < 2^32)
+
+    def auc_pr(self) -> torch.Tensor:
+        return torch.where(self.degenerate(), torch.full_like(self.ap, float("nan")), self.ap)
+
+    def precision(self) -> torch.Tensor:
+        return _ratio(self.tp, self.tp + self.fp)
+
+    def recall(self) -> torch.Tensor:
+        return _ratio(self.tp, self.wp)
+
+    def f1(self) -> torch.Tensor:
+        return _ratio(2 * self.tp, self.tp + self.fp + self.wp)
+
+    def accuracy(self) -> torch.Tensor:
+        return _ratio(self.tp + self.wn - self.fp, self.wp + self.wn)
+
+
+class RankSums(NamedTuple):
+    """per replicate ``0 .. replicates``: the weighted sums behind MRR, mean rank and Hits@k"""
+    w_sum: torch.Tensor     # int64
+    rank_sum: torch.Tensor  # int64
+    hit_sums: torch.Tensor  # int64 [replicates + 1, len(k_values)]
+    rr_sum: torch.Tensor    # float64
+    k_values: Tuple[int, ...]
+
+    def mrr(self) -> torch.Tensor:
+        return _ratio(self.rr_sum, self.w_sum)
+
+    def mean_rank(self) -> torch.Tensor:
+        return _ratio(self.rank_sum, self.w_sum)
+
+    def hits(self, k: int) -> torch.Tensor:
+        return _ratio(self.hit_sums[:, self.k_values.index(int(k))], self.w_sum)
+
+
+def _resample_sizes(num_units: int, replicates: int, seed: int) -> Tuple[int, int, int]:
+    num_units, replicates, seed = int(num_units), int(replicates), int(seed) & 0xFFFFFFFFFFFFFFFF
+    if num_units <= 0 or num_units > 0x7FFFFFFF:
+        raise ValueError(f"num_units must be in [1, 2^31 - 1], got {num_units}")
+    if replicates < 0 or replicates > _lib.RESAMPLE_MAX_REPLICATES:
+        raise ValueError(f"replicates must be in [0, {_lib.RESAMPLE_MAX_REPLICATES}], got {replicates}")
+    return num_units, replicates, seed - (1 << 64) if seed >> 63 else seed        # the C side takes the bits as an int64
+
+
+def _resample_units(unit: Optional[torch.Tensor], count: int, device) -> Tuple[torch.Tensor, int]:
+    """``(unit int32 [count], num_units)``; ``None``: every sample is its own unit"""
+    if unit is None:
+        return torch.arange(count, dtype=torch.int32, device=device), max(count, 1)
+    _need_gpu("unit", unit, torch.int32)
+    if unit.shape != (count,) or unit.device != device:
+        raise ValueError(f"unit must be [{count}], one id per sample, on the samples' device")
+    return unit, (int(unit.max()) + 1 if count else 1)
+
+
+def resample_weights(num_units: int, replicates: int, seed: int, device="cuda") -> torch.Tensor:
+    """uint8 ``[replicates + 1, num_units]``: the resampling weight of every unit in every replicate
+    (``rgcn_resample_weights``) - row 0 all ones, row ``b >= 1`` the Poisson(1) draws of ``include/rgcn_resample.h``,
+    a pure function of ``(seed, b, unit)``"""
+    num_units, replicates, seed = _resample_sizes(num_units, replicates, seed)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"resample_weights on {device}: the resampling runs on MI355X (HIP) only; there is no CPU "
+                           f"fallback in this package")
+    lib = _L()
+    with _on(device):
+        out = _empty((replicates + 1, num_units), dtype=torch.uint8, device=device)
+        rc = lib.rgcn_resample_weights(num_units, replicates, seed, _ptr(out), _stream())
+    _lib.check(rc, "rgcn_resample_weights")
+    return out
+
+
+def classification_counts(scores: torch.Tensor, labels: torch.Tensor, unit: Optional[torch.Tensor] = None,
+                          replicates: int = 0, seed: int = 0, threshold: float = 0.5) -> ClassificationCounts:
+    """The ROC / PR statistics of ``scores`` (float32 or float64 ``[n]``) against ``labels`` (``[n]``, non-zero =
+    positive) in ``replicates`` paired Poisson bootstrap resamples plus the point estimate (``rgcn_resample_curves``).
+    ``unit`` (int32 ``[n]``, default: every sample its own) names the resampling unit of each sample: samples of one
+    unit share their weight.  A NaN score counts as ``-inf``: it never ranks above a number.  One stable descending
+    sort here; every replicate is then a walk of that order.  The integers are exact, ``ap`` is within
+    ``(n + 2) 2^-53`` of the exact value, and the same call gives the same bits."""
+    if not isinstance(scores, torch.Tensor) or not isinstance(labels, torch.Tensor):
+        raise TypeError("scores and labels must be torch.Tensors")
+    if scores.device.type != "cuda":
+        raise RuntimeError(f"scores is on {scores.device}: the resampling runs on MI355X (HIP) tensors only; there is no "
+                           f"CPU fallback in this package")
+    if scores.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"scores must be float32 or float64, got {scores.dtype}")
+    if scores.dim() != 1 or labels.shape != scores.shape or labels.device != scores.device:
+        raise ValueError("scores [n] and labels [n] on one device expected")
+    dev, n = scores.device, scores.numel()
+    if n > _lib.RESAMPLE_MAX_SAMPLES:
+        raise IndexError(f"at most 2^28 samples, got {n}")
+    unit, num_units = _resample_units(unit, n, dev)
+    num_units, replicates, seed = _resample_sizes(num_units, replicates, seed)
+    lib = _L()
+    with _on(dev):
+        clean = torch.where(torch.isnan(scores), torch.full_like(scores, float("-inf")), scores)
+        ordered, order = torch.sort(clean, descending=True, stable=True)
+        label_s = _empty(n, dtype=torch.uint8, device=dev).copy_(labels[order] != 0)
+        unit_s = _empty(n, dtype=torch.int32, device=dev).copy_(unit[order])
+        tie_end = _empty(n, dtype=torch.uint8, device=dev)
+        if n:
+            tie_end[:-1] = ordered[:-1] != ordered[1:]
+            tie_end[-1] = 1
+        cut = int((ordered.double() >= float(threshold)).sum())
+        out = [_empty(replicates + 1, dtype=torch.float64 if name == "ap" else torch.int64, device=dev)
+               for name in ClassificationCounts._fields]
+        rc = lib.rgcn_resample_curves(_ptr(label_s), _ptr(unit_s), _ptr(tie_end), n, cut, num_units, replicates, seed,
+                                      *[_ptr(t) for t in out], _stream())
+    _lib.check(rc, "rgcn_resample_curves")
+    return ClassificationCounts(*out)
+
+
+def rank_sums(ranks: torch.Tensor, unit: Optional[torch.Tensor], k_values, replicates: int = 0, seed: int = 0) -> RankSums:
+    """The weighted sums behind MRR, mean rank and Hits@k of ``ranks`` (int64 ``[m]``, 1-based) in ``replicates``
+    paired Poisson bootstrap resamples plus the point estimate (``rgcn_resample_ranks``); ``unit`` as in
+    ``classification_counts`` - with both sides ranked, the tail query and the head query of a triple share its unit.
+    At most 8 ``k_values``.  The median rank is not a sum and is not resampled."""
+    _need_gpu("ranks", ranks, torch.int64)
+    if ranks.dim() != 1:
+        raise ValueError("ranks [m] expected")
+    k_values = tuple(int(k) for k in k_values)
+    if len(k_values) > _lib.RESAMPLE_MAX_K:
+        raise ValueError(f"at most {_lib.RESAMPLE_MAX_K} k_values, got {len(k_values)}")
+    dev, m, nk = ranks.device, ranks.numel(), len(k_values)
+    if m > _lib.RESAMPLE_MAX_SAMPLES:
+        raise IndexError(f"at most 2^28 queries, got {m}")
+    unit, num_units = _resample_units(unit, m, dev)
+    num_units, replicates, seed = _resample_sizes(num_units, replicates, seed)
+    lib = _L()
+    with _on(dev):
+        ks = _empty(max(nk, 1), dtype=torch.int32, device=dev).copy_(
+            torch.tensor(list(k_values) or [0], dtype=torch.int32), non_blocking=False)
+        w_sum, rank_sum = (_empty(replicates + 1, dtype=torch.int64, device=dev) for _ in range(2))
+        hit_sums = _empty((replicates + 1, nk), dtype=torch.int64, device=dev)
+        rr_sum = _empty(replicates + 1, dtype=torch.float64, device=dev)
+        rc = lib.rgcn_resample_ranks(_ptr(ranks), _ptr(unit), m, _ptr(ks), nk, num_units, replicates, seed, _ptr(w_sum),
+                                     _ptr(rank_sum), _ptr(hit_sums) if nk else None, _ptr(rr_sum), _stream())
+    _lib.check(rc, "rgcn_resample_ranks")
+    return RankSums(w_sum, rank_sum, hit_sums, rr_sum, k_values)
+
+
+CLUSTER_MAX_K = 64           # RGCN_CLUSTER_MAX_K: two 32-column blocks per restart, 32 KB of sums per update workgroup
 CLUSTER_MAX_RESTARTS = 1024   # RGCN_CLUSTER_MAX_RESTARTS
 
 
