@@ -94,7 +94,7 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 37
+#define RGCN_ABI_VERSION 38
 
 enum {
   RGCN_OK = 0,

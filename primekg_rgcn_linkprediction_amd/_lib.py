@@ -13,7 +13,7 @@ from ctypes import c_double, c_float, POINTER, c_char_p, c_int, c_int64, c_size_
 
 import torch  # noqa: F401  (loads the HIP runtime first)
 
-ABI_VERSION = 37
+ABI_VERSION = 38
 LIB_NAME = "librgcn_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -224,6 +224,18 @@ RESAMPLE_MAX_SAMPLES = 1 << 28   # RGCN_RESAMPLE_MAX_SAMPLES
 RESAMPLE_MAX_REPLICATES = 65535  # RGCN_RESAMPLE_MAX_REPLICATES
 RESAMPLE_MAX_K = 8               # RGCN_RESAMPLE_MAX_K
 
+# include/rgcn_complex.h, one to one: the ComplEx scoring head (csrc/complex.hip; not part of rgcn_hip.h, never forwarded
+# by rgcn_sequence_run - the head runs outside any recorded Region).  Parameter for parameter the DistMult head's rows.
+COMPLEX_PROTOTYPES = {
+    "complex_fwd": (c_int, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P]),
+    "complex_bce_fwd": (c_int, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _P, _P]),
+    "complex_bwd_workspace_bytes": (c_size_t, [_I64, _I64, _I64]),
+    "complex_bwd": (c_int, [_P, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, c_size_t, c_int, _P]),
+    "complex_bce_bwd": (c_int, [_P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P,
+                                c_size_t, c_int, _P]),
+    "rgcn_complex_query": (c_int, [c_int, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P]),
+}
+
 _lib = None
 
 
@@ -245,7 +257,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise RGCNLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + list(COMPLEX_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -6,6 +6,10 @@ short launches instead of a Python loop over every sample.  Its embeddings go to
 matrix (``predict`` / ``predict_all``: the reference's ``(cos + 1) / 2``), and - what the reference's comparison cannot do -
 it is ranked by TransE distance under the project's own filtered, type-constrained, two-sided protocol through the fused
 ranking and top-k passes (``ops.transe_rank_operands``).  ``NodeDegree`` and ``Random`` are a few lines of torch.
+
+``ComplEx`` is not in the reference's comparison (its README asks for it under "Advanced Baselines"): a free entity table
+under the project's own ComplEx head (``LinkPredictor(decoder="complex")``), trained like the model - device sampler, fused
+BCE, fused clip + Adam - with ``TransE``'s surface.
 """
 from __future__ import annotations
 
@@ -16,6 +20,7 @@ import torch
 from torch import Tensor
 
 from . import consumers, ops
+from .head import LinkPredictor
 
 logger = logging.getLogger("primekg_rgcn_linkprediction_amd.baselines")
 
@@ -203,6 +208,159 @@ class TransE:
                   candidate_class=None, max_mask_bytes: int = 256 << 20):
         """the ``k`` nearest heads of every ``(?, relation, tail)`` query"""
         return self._top("head", tails, relations, k, known, node_class, candidate_class, max_mask_bytes)
+
+
+class ComplEx:
+    """A free entity table ``[N, d]`` scored by ``LinkPredictor(decoder="complex")``: ``Re <h, r, conj(t)>`` over d / 2
+    complex numbers per row, so it tells ``(h, r, t)`` from ``(t, r, h)`` (DistMult and the cosine of ``TransE.predict``
+    cannot).  ``fit`` trains on the device: per batch one sampler launch (``num_neg`` corruptions per positive), the
+    fused BCE head forward and backward, and the fused clip + Adam step (``ops.adam_clip_step``); one read-back per
+    epoch.  ``embeddings`` float32 ``[N, d]`` and ``relation_embeddings`` ``[R, d]`` stay on the device."""
+
+    name = "ComplEx"
+
+    def __init__(self, embedding_dim: int = 64, num_epochs: int = 50, learning_rate: float = 0.01, batch_size: int = 1024,
+                 num_neg: int = 1, grad_clip: float = 1.0, seed: int = 0, device=None):
+        if embedding_dim <= 0 or embedding_dim % 8:
+            raise ValueError("embedding_dim must be a positive multiple of 8")
+        if batch_size <= 0 or num_epochs < 0 or num_neg <= 0:
+            raise ValueError("batch_size and num_neg must be positive and num_epochs >= 0")
+        self.embedding_dim, self.num_epochs, self.learning_rate = int(embedding_dim), int(num_epochs), float(learning_rate)
+        self.batch_size, self.num_neg, self.grad_clip, self.seed = int(batch_size), int(num_neg), float(grad_clip), int(seed)
+        self.device = torch.device("cuda" if device is None else device)
+        self.embeddings: Optional[Tensor] = None
+        self.decoder: Optional[LinkPredictor] = None
+        self.epoch_losses = []          # mean BCE per sample, per epoch
+
+    @property
+    def relation_embeddings(self) -> Optional[Tensor]:
+        return None if self.decoder is None else self.decoder.relation_embeddings.weight.detach()
+
+    # ------------------------------------------------------------------------------------------------- training
+    def fit(self, edge_index: Tensor, edge_type: Tensor, num_nodes: int, num_relations: int) -> "ComplEx":
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("ComplEx.fit trains on the MI355X (HIP) only; there is no CPU fallback in this package")
+        edge_index = edge_index.to(device=dev, dtype=torch.int64).contiguous()
+        edge_type = edge_type.to(device=dev, dtype=torch.int64).contiguous()
+        if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_type.shape != (edge_index.size(1),):
+            raise ValueError("edge_index must be [2, E] and edge_type [E]")
+        num_edges = edge_index.size(1)
+        gen = torch.Generator().manual_seed(self.seed)
+        table = torch.nn.init.xavier_uniform_(torch.empty(num_nodes, self.embedding_dim), generator=gen)
+        rel = torch.nn.init.xavier_uniform_(torch.empty(num_relations, self.embedding_dim), generator=gen)
+        self.decoder = LinkPredictor(num_relations, self.embedding_dim, decoder="complex").to(dev)
+        with torch.no_grad():
+            self.decoder.relation_embeddings.weight.copy_(rel)
+        table = table.to(dev).requires_grad_(True)
+        self.embeddings, self.epoch_losses = table.detach(), []
+        if num_edges == 0 or self.num_epochs == 0:
+            self.decoder.eval()
+            return self
+        params = [table, self.decoder.relation_embeddings.weight]
+        exp_avgs, exp_avg_sqs = ([torch.zeros_like(p) for p in params] for _ in range(2))
+        steps = [torch.zeros(1, dtype=torch.float32, device=dev) for _ in params]
+        batch = min(self.batch_size, num_edges)
+        sizes = [min(batch, num_edges - lo) for lo in range(0, num_edges, batch)]
+        self.decoder.train()
+        with torch.cuda.device(dev):
+            dev_gen = torch.Generator(device=dev).manual_seed(self.seed)
+            cursor = torch.zeros(1, dtype=torch.int64, device=dev)
+            rng = torch.tensor([self.seed & 0x7FFFFFFFFFFFFFFF, 0], dtype=torch.int64).to(dev)
+            loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
+            for ep in range(self.num_epochs):
+                order = torch.randperm(num_edges, device=dev, generator=dev_gen)
+                cursor.zero_()
+                rng[1] = ep
+                loss_sum.zero_()
+                for size in sizes:
+                    h, t, r, labels = ops.sample_batch(edge_index, edge_type, order, cursor, size, self.num_neg, num_nodes, rng)
+                    # the launch that forms the mean also adds it to the epoch's sum and moves the cursor on
+                    loss, _ = self.decoder.bce_loss(table, h, t, r, labels, stats=(loss_sum, None, cursor, size))
+                    loss.backward()
+                    ops.adam_clip_step([p.data for p in params], [p.grad for p in params], exp_avgs, exp_avg_sqs, steps,
+                                       self.learning_rate, 0.9, 0.999, 1e-8, max_norm=self.grad_clip)
+                    for p in params:
+                        p.grad = None
+                self.epoch_losses.append(float(loss_sum.item()) / (num_edges * (1 + self.num_neg)))   # the epoch's one read-back
+                logger.info("ComplEx epoch %d/%d, loss %.4f", ep + 1, self.num_epochs, self.epoch_losses[-1])
+            ops.check_indices(dev)
+        self.decoder.eval()
+        return self
+
+    def _fitted(self) -> Tensor:
+        if self.embeddings is None:
+            raise RuntimeError("ComplEx: fit() first")
+        return self.embeddings
+
+    def _ids(self, *vectors):
+        dev = self._fitted().device
+        return [torch.as_tensor(x, dtype=torch.int64).to(dev).contiguous().view(-1) for x in vectors]
+
+    # ------------------------------------------------------------------------------------------- per-triple scores
+    @torch.no_grad()
+    def predict(self, heads, tails, relations) -> Tensor:
+        """``sigmoid(score(head_b, relation_b, tail_b))`` per triple: the order of head and tail matters"""
+        emb = self._fitted()
+        heads, tails, relations = self._ids(heads, tails, relations)
+        return torch.sigmoid(self.decoder.score_triples(emb, heads, tails, relations))
+
+    @torch.no_grad()
+    def predict_all(self, heads, tails, relation: int) -> Tensor:
+        """the ``[n_heads, n_tails]`` matrix of the same score under one relation"""
+        emb = self._fitted()
+        heads, tails = self._ids(heads, tails)
+        rels = torch.full_like(heads, int(relation))
+        return torch.sigmoid(self.decoder.score_all_tails(emb[heads], rels, emb).index_select(1, tails))
+
+    # ------------------------------------------------------------------------------------------- ranking and top-k
+    @torch.no_grad()
+    def rank_tails(self, heads, relations, tails, *, known: Optional["ops.KnownTriples"] = None, node_class=None,
+                   max_mask_bytes: int = 256 << 20) -> Tensor:
+        """int64 ``[B]``: 1-based rank of ``tails[b]`` among all entities for ``(head, relation, ?)`` - the pass, the
+        masks and the tie rule of ``LinkPredictor.rank_tails``"""
+        emb = self._fitted()
+        heads, relations, tails = self._ids(heads, relations, tails)
+        return self.decoder.rank_tails(emb[heads], relations, emb, tails, known=known, head_indices=heads,
+                                       node_class=self._classes(node_class), max_mask_bytes=max_mask_bytes)
+
+    @torch.no_grad()
+    def rank_heads(self, tails, relations, heads, *, known: Optional["ops.KnownTriples"] = None, node_class=None,
+                   max_mask_bytes: int = 256 << 20) -> Tensor:
+        """the other side, ``(?, relation, tail)``: the query operand carries the conjugate (``LinkPredictor.rank_heads``)"""
+        emb = self._fitted()
+        tails, relations, heads = self._ids(tails, relations, heads)
+        return self.decoder.rank_heads(emb[tails], relations, emb, heads, known=known, tail_indices=tails,
+                                       node_class=self._classes(node_class), max_mask_bytes=max_mask_bytes)
+
+    def _classes(self, node_class):
+        if node_class is None:
+            return None
+        node_class = torch.as_tensor(node_class)
+        if getattr(self, "_class_key", None) is not node_class:                 # the head caches the allow rows by tensor
+            self._class_key, self._class_dev = node_class, node_class.to(self._fitted().device)
+        return self._class_dev
+
+    @torch.no_grad()
+    def top_tails(self, heads, relations, k: int, *, known: Optional["ops.KnownTriples"] = None, node_class=None,
+                  candidate_class=None, max_mask_bytes: int = 256 << 20):
+        """``(ids int64 [B, k], scores [B, k])``: the ``k`` best tails of every ``(head, relation)`` query, score
+        descending, equal scores by id ascending, id -1 / score -inf past the number of candidates"""
+        emb = self._fitted()
+        heads, relations = self._ids(heads, relations)
+        return self.decoder.top_tails(emb[heads], relations, emb, k, known=known, head_indices=heads,
+                                      node_class=self._classes(node_class), candidate_class=candidate_class,
+                                      max_mask_bytes=max_mask_bytes)
+
+    @torch.no_grad()
+    def top_heads(self, tails, relations, k: int, *, known: Optional["ops.KnownTriples"] = None, node_class=None,
+                  candidate_class=None, max_mask_bytes: int = 256 << 20):
+        """the ``k`` best heads of every ``(?, relation, tail)`` query"""
+        emb = self._fitted()
+        tails, relations = self._ids(tails, relations)
+        return self.decoder.top_heads(emb[tails], relations, emb, k, known=known, tail_indices=tails,
+                                      node_class=self._classes(node_class), candidate_class=candidate_class,
+                                      max_mask_bytes=max_mask_bytes)
 
 
 class NodeDegree:

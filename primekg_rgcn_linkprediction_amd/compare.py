@@ -9,9 +9,12 @@ fused ranking pass, known triples filtered and candidates type-constrained as as
 ``ModelEvaluator.compute_classification_metrics`` is applied to per-triple scores of the test triples and one seeded
 corruption of each.  How a method orders candidates:
 
-* ``rgcn``    the DistMult score on the encoder's embeddings (``ModelEvaluator.tail_ranks`` / ``head_ranks``);
+* ``rgcn``    the checkpoint's decoder (DistMult, or ComplEx when it was trained with ``--decoder complex``) on the
+              encoder's embeddings (``ModelEvaluator.tail_ranks`` / ``head_ranks``);
 * ``transe``  the TransE distance ``|h + r - t|`` (``ops.transe_rank_operands``); its per-triple score is the reference's
               ``(cos + 1) / 2``;
+* ``complex`` the ComplEx score ``Re <h, r, conj(t)>`` on a free entity table (``baselines.ComplEx``: the project's own head,
+              ``ops.complex_query`` for the query rows of each side); its per-triple score is ``sigmoid`` of it;
 * ``degree``  ``sqrt(deg_drug(head) * deg_disease(tail))`` (``NodeDegreeBaseline``), ranked as the product of the two
               factors - a one-column inner product, so it goes through the same pass and masks;
 * ``random``  the inner product of two seeded Gaussian tables: a different random order per query.
@@ -41,7 +44,7 @@ from . import evaluate as E
 
 logger = logging.getLogger("primekg_rgcn_linkprediction_amd.compare")
 
-METHODS = ("random", "degree", "transe", "rgcn")
+METHODS = ("random", "degree", "transe", "complex", "rgcn")
 K_VALUES = (1, 5, 10, 20, 50)
 TYPE_NAMES = {"drug": "drug", "disease": "disease"}          # PrimeKG's node type names
 NEGATIVE_STREAM = (1 << 55) + 2                               # Philox stream of the comparison's corruptions
@@ -113,7 +116,8 @@ def compare_methods(train_data: Dict, test_data: Dict, full_graph: Dict, device,
                     filtered: bool = False, type_constrained: bool = False, both_sides: bool = False,
                     transe_epochs: int = 50, seed: int = 0, drug_class: Optional[int] = None,
                     disease_class: Optional[int] = None, transe_kwargs: Optional[Dict] = None, bootstrap: int = 0,
-                    bootstrap_seed: int = 0, by_frequency: bool = False) -> Dict:
+                    bootstrap_seed: int = 0, by_frequency: bool = False, complex_epochs: int = 50,
+                    complex_kwargs: Optional[Dict] = None) -> Dict:
     """-> ``{"protocol": ..., "methods": {name: {"ranking": ..., "classification": ..., "fit_seconds": ...}}}``.
     ``bootstrap`` > 0: every method also gets a ``"bootstrap"`` block (``bootstrap.block``: estimate, standard error and
     95 % interval per metric over that many paired resamples of the test triples, on the device) and the result a
@@ -167,6 +171,15 @@ def compare_methods(train_data: Dict, test_data: Dict, full_graph: Dict, device,
             ranks = proto.ranks(lambda side, a, r: ops.transe_rank_operands(method.embeddings, method.relation_embeddings,
                                                                             a, r, side)[:2])
             scores = method.predict(heads, tails)
+        elif name == "complex":
+            kw = dict(num_epochs=complex_epochs, seed=seed, device=device)
+            kw.update(complex_kwargs or {})
+            method = baselines.ComplEx(**kw).fit(train_ei, train_et, num_nodes, num_relations)
+            torch.cuda.synchronize(device)
+            fit_s = time.perf_counter() - t0
+            ranks = proto.ranks(lambda side, a, r: (ops.complex_query(method.embeddings, a, method.relation_embeddings, r, side),
+                                                    method.embeddings))
+            scores = method.predict(heads, tails, torch.cat([proto.rel, proto.rel]))
         elif name == "degree":
             method = baselines.NodeDegree().fit(train_ei, proto.node_class, drug_class, disease_class)
             fit_s = time.perf_counter() - t0
@@ -184,7 +197,7 @@ def compare_methods(train_data: Dict, test_data: Dict, full_graph: Dict, device,
                          "classification": E.ModelEvaluator.compute_classification_metrics(
                              scores.detach().double().cpu().numpy(), labels),
                          "fit_seconds": fit_s}
-        if name == "transe":
+        if name in ("transe", "complex"):
             results[name]["epoch_losses"] = method.epoch_losses
         scores = scores.detach().double().to(device)         # the Random baseline scores on the host
         if bootstrap_n:
@@ -197,9 +210,11 @@ def compare_methods(train_data: Dict, test_data: Dict, full_graph: Dict, device,
         logger.info("%s: MRR %.4f, Hits@10 %.4f, AUC-ROC %.4f", name, results[name]["ranking"]["mrr"],
                     results[name]["ranking"].get("hits@10", float("nan")), results[name]["classification"]["auc_roc"])
     ops.check_indices(device)
+    decoder_name = {"distmult": "DistMult", "complex": "ComplEx"}[getattr(getattr(model, "decoder", None), "decoder", "distmult")]
     protocol = dict(proto.describe(), k_values=list(k_values), seed=seed, transe_epochs=transe_epochs,
+                    complex_epochs=complex_epochs,
                     classification="test triples (label 1) and one seeded corruption of each (label 0); per-triple scores: "
-                                   "rgcn sigmoid(DistMult), transe (cos + 1) / 2, degree sqrt(deg_drug * deg_disease), "
+                                   f"rgcn sigmoid({decoder_name}), transe (cos + 1) / 2, complex sigmoid(ComplEx), degree sqrt(deg_drug * deg_disease), "
                                    "random uniform; threshold 0.5")
     result = {"protocol": protocol, "methods": results}
     if bootstrap_n:
@@ -295,7 +310,7 @@ def save_comparison(result: Dict, output_dir) -> Path:
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="Compare the R-GCN with the Random, Node Degree and TransE baselines on MI355X")
+    p = argparse.ArgumentParser(description="Compare the R-GCN with the Random, Node Degree, TransE and ComplEx baselines on MI355X")
     p.add_argument("--data_dir", type=str, default="data/processed")
     p.add_argument("--model_path", type=str, default=None, help="the trained R-GCN checkpoint (method rgcn)")
     p.add_argument("--output_dir", type=str, default="results/comparison")
@@ -306,6 +321,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--type_constrained", action="store_true", help="rank among the entities of the true answer's node type")
     p.add_argument("--both_sides", action="store_true", help="rank the heads too and average over both sides")
     p.add_argument("--transe_epochs", type=int, default=50)
+    p.add_argument("--complex_epochs", type=int, default=50)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--k_values", type=int, nargs="+", default=list(K_VALUES))
     p.add_argument("--drug_class", type=int, default=None, help="class id of drugs (default: by name from mappings.pt)")
@@ -330,8 +346,8 @@ def parse_args(argv=None) -> argparse.Namespace:
         parser.error("method rgcn needs --model_path")
     if (args.type_constrained or args.by_frequency or "degree" in args.methods) and not args.node_types:
         parser.error("--type_constrained, --by_frequency and method degree need --node_types PATH")
-    if args.transe_epochs < 0:
-        parser.error("--transe_epochs must be >= 0")
+    if args.transe_epochs < 0 or args.complex_epochs < 0:
+        parser.error("--transe_epochs and --complex_epochs must be >= 0")
     return args
 
 
@@ -358,7 +374,8 @@ def main(argv=None) -> Dict:
     result = compare_methods(train_data, test_data, full_graph, device, model, node_class, args.methods, args.k_values,
                              args.filtered, args.type_constrained, args.both_sides, args.transe_epochs, args.seed,
                              _class_id(args.drug_class, "drug", names), _class_id(args.disease_class, "disease", names),
-                             bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed, by_frequency=args.by_frequency)
+                             bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed, by_frequency=args.by_frequency,
+                             complex_epochs=args.complex_epochs)
     path = save_comparison(result, args.output_dir)
     print(table_markdown(result))
     logger.info("Comparison saved to: %s", path)

@@ -111,37 +111,6 @@ __global__ __launch_bounds__(kThreads) void k_distmult_contrib(
   }
 }
 
-constexpr int kScatterWaves = 16;                // waves (slots) per workgroup: one staging of the keys serves sixteen slots
-constexpr int kKeysInLds = 16384;                // key count up to which the keys are staged in LDS
-
-// rows[S, d] (workspace), keys[S] -> out[key] = sum of the rows with that key, in slot order; one wave per slot, sixteen
-// slots per workgroup (one staging of the keys serves them all).  A slot that finds an equal key BEFORE itself
-// retires; the first occurrence of a row adds the rows of all its occurrences in slot order.  A template on where the
-// keys are (stage_keys).
-// (Round 3 tried a chunked two-pass form - every 16th occurrence adds its chunk, a second launch adds the chunk sums
-// of the rows with more than 16 occurrences - to shorten the chain of a hub with 100+ occurrences: 15 + 18 us against
-// this kernel's 27 us.  The launch is bound by the scans over the keys, not by the hub's additions.)
-template <bool IN_LDS>
-__global__ __launch_bounds__(64 * kScatterWaves) void k_scatter_rows(const int32_t* __restrict__ keys, int S,
-                                                                              const float* __restrict__ rows, int d,
-                                                                              float* __restrict__ out) {
-  __shared__ int32_t skeys[IN_LDS ? kKeysInLds : 1];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int32_t* k = stage_keys<IN_LDS, 64 * kScatterWaves>(keys, S, skeys);
-  const int s = blockIdx.x * kScatterWaves + wave;
-  if (s >= S) return;
-  const int my = k[s];
-  for (int c = 0; c < s; c += 64)               // an earlier occurrence owns the row
-    if (earlier_slot_has(k, my, s, c, lane)) return;
-  for (int c0 = lane * 4; c0 < ((d + 255) & ~255); c0 += 256) {
-    MatchIter it;
-    it.start(k, my, s, S, lane);
-    const int cc = min(c0, d - 4);
-    const float4 acc = ordered_row_sum(it, rows, d, cc, lane);
-    if (c0 < d) *reinterpret_cast<float4*>(out + (size_t)my * d + c0) = acc;
-  }
-}
-
 // The step's bookkeeping in ONE launch (one 1,024-thread workgroup): mean of the per-sample losses (fixed order: thread i
 // adds elements i, i + 1024, ... , then a fixed tree - two runs give the same bits), the epoch's running sums
 // (src/train.py:321-326: `predictions = sigmoid(scores) > 0.5`, `correct += (predictions == labels).sum()`,
@@ -296,11 +265,7 @@ int bwd_impl(const float* gs, const float* scores, const float* labels, const fl
                     gs, h, h_idx, h_rows, t, t_idx, t_rows, r, r_idx, r_rows, batch, (int)d, out_h, out_t, out_r,
                     (grad_h && h_idx) ? kh : nullptr, (grad_t && t_idx) ? kt : nullptr, (grad_r && r_idx) ? kr : nullptr,
                     scores, labels, (int)grid, za, zaq, zb, zbq)));
-  auto scatter = [&](const int32_t* k, int S, const float* rows, float* out) {
-    const unsigned sg = (unsigned)ceil_div64(S, kScatterWaves);
-    if (S <= kKeysInLds) k_scatter_rows<true><<<sg, 64 * kScatterWaves, 0, stream>>>(k, S, rows, (int)d, out);
-    else k_scatter_rows<false><<<sg, 64 * kScatterWaves, 0, stream>>>(k, S, rows, (int)d, out);
-  };
+  auto scatter = [&](const int32_t* k, int S, const float* rows, float* out) { rgcn_scatter_rows(k, S, rows, (int)d, out, stream); };
   if (sh && st && grad_h == grad_t) {            // one table, one key space: head slots then tail slots
     scatter(kh, (int)(2 * batch), ch, grad_h);
   } else {

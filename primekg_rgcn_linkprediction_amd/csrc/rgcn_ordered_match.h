@@ -1,11 +1,13 @@
 // The ordered scatter, whole: contribution rows plus int32 keys in, one row per key out, every sum in slot order, so two
-// runs give the same bits.  Users: distmult.hip (the DistMult backward, rgcn_segment_sum) and transe.hip (the TransE step).
+// runs give the same bits.  Users: distmult.hip (the DistMult backward, rgcn_segment_sum), complex.hip (the ComplEx
+// backward) and transe.hip (the TransE step).
 //   - rgcn_pick_group / RGCN_DISPATCH_G: the lane group of d/4 lanes per sample of the contribution launches.
 //   - rgcn_checked_row: an id outside its table is clamped to row 0 and the library's sticky flag raised.
 //   - stage_keys / earlier_slot_has: the prologue of the one-wave-per-slot kernels (k_scatter_rows, k_transe_apply): the
 //     keys into LDS, and one step of the ballot scan that retires every occurrence of a key but the first.
 //   - MatchIter / ordered_row_sum: the wave-uniform iterator over the slots that carry one key, and the sum of their rows
 //     in slot order, eight loads in flight; a policy maps a slot to its row and sign (PlainRows, TranseRows).
+//   - k_scatter_rows / rgcn_scatter_rows: the scatter launch of the two heads' backward, decoder-independent.
 //   - segment_len / k_segment_partials / k_segment_combine<SUBTRACT>: the fixed two-level tree of a table of few rows.
 //   - block1024_sum_tally: the float sum and int tally of the loss reductions (k_bce_reduce, k_transe_loss).
 // Everything sits in an anonymous namespace: each translation unit gets its own copies, the kernels included, and no
@@ -136,6 +138,44 @@ __device__ inline float4 ordered_row_sum(MatchIter& it, const float* __restrict_
     if (p[7] < 0) break;
   }
   return acc;
+}
+
+constexpr int kScatterWaves = 16;                // waves (slots) per workgroup: one staging of the keys serves sixteen slots
+constexpr int kKeysInLds = 16384;                // key count up to which the keys are staged in LDS
+
+// rows[S, d] (workspace), keys[S] -> out[key] = sum of the rows with that key, in slot order; one wave per slot, sixteen
+// slots per workgroup (one staging of the keys serves them all).  A slot that finds an equal key BEFORE itself
+// retires; the first occurrence of a row adds the rows of all its occurrences in slot order.  A template on where the
+// keys are (stage_keys).
+// (Round 3 tried a chunked two-pass form - every 16th occurrence adds its chunk, a second launch adds the chunk sums
+// of the rows with more than 16 occurrences - to shorten the chain of a hub with 100+ occurrences: 15 + 18 us against
+// this kernel's 27 us.  The launch is bound by the scans over the keys, not by the hub's additions.)
+template <bool IN_LDS>
+__global__ __launch_bounds__(64 * kScatterWaves) void k_scatter_rows(const int32_t* __restrict__ keys, int S,
+                                                                              const float* __restrict__ rows, int d,
+                                                                              float* __restrict__ out) {
+  __shared__ int32_t skeys[IN_LDS ? kKeysInLds : 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int32_t* k = stage_keys<IN_LDS, 64 * kScatterWaves>(keys, S, skeys);
+  const int s = blockIdx.x * kScatterWaves + wave;
+  if (s >= S) return;
+  const int my = k[s];
+  for (int c = 0; c < s; c += 64)               // an earlier occurrence owns the row
+    if (earlier_slot_has(k, my, s, c, lane)) return;
+  for (int c0 = lane * 4; c0 < ((d + 255) & ~255); c0 += 256) {
+    MatchIter it;
+    it.start(k, my, s, S, lane);
+    const int cc = min(c0, d - 4);
+    const float4 acc = ordered_row_sum(it, rows, d, cc, lane);
+    if (c0 < d) *reinterpret_cast<float4*>(out + (size_t)my * d + c0) = acc;
+  }
+}
+
+// the scatter launch of a head's backward (distmult.hip, complex.hip): the instance by where the S keys fit
+inline void rgcn_scatter_rows(const int32_t* keys, int S, const float* rows, int d, float* out, hipStream_t stream) {
+  const unsigned grid = (unsigned)((S + kScatterWaves - 1) / kScatterWaves);
+  if (S <= kKeysInLds) k_scatter_rows<true><<<grid, 64 * kScatterWaves, 0, stream>>>(keys, S, rows, d, out);
+  else k_scatter_rows<false><<<grid, 64 * kScatterWaves, 0, stream>>>(keys, S, rows, d, out);
 }
 
 // samples per segment of the relation-table tree: 64 for the training batch (a wave then adds ~20 rows in order instead

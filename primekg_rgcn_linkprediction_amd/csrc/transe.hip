@@ -24,7 +24,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kApplyWaves = 16;                  // slots per workgroup of the apply launch: one staging of the keys serves sixteen
-constexpr int kKeysInLds = 8192;                 // key count (4 per sample) up to which the apply launch stages the keys in LDS
+constexpr int kApplyKeysInLds = 8192;            // key count (4 per sample) up to which the apply launch stages the keys in LDS
 
 __device__ inline float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ inline float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
@@ -96,7 +96,7 @@ template <bool IN_LDS>
 __global__ __launch_bounds__(64 * kApplyWaves) void k_transe_apply(const int32_t* __restrict__ keys, int S,
                                                                    const float* __restrict__ dpn, int d,
                                                                    float* __restrict__ emb) {
-  __shared__ int32_t skeys[IN_LDS ? kKeysInLds : 1];
+  __shared__ int32_t skeys[IN_LDS ? kApplyKeysInLds : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int32_t* k = stage_keys<IN_LDS, 64 * kApplyWaves>(keys, S, skeys);
   const int s = blockIdx.x * kApplyWaves + wave;
@@ -215,7 +215,7 @@ int rgcn_transe_step(float* emb, int64_t num_nodes, float* rel, int64_t num_rela
                                                                         loss, keys, rkeys, flag)));
   const int S = (int)(4 * batch);
   const unsigned ag = (unsigned)ceil_div64(S, kApplyWaves);
-  if (S <= kKeysInLds) k_transe_apply<true><<<ag, 64 * kApplyWaves, 0, stream>>>(keys, S, dpn, (int)d, emb);
+  if (S <= kApplyKeysInLds) k_transe_apply<true><<<ag, 64 * kApplyWaves, 0, stream>>>(keys, S, dpn, (int)d, emb);
   else k_transe_apply<false><<<ag, 64 * kApplyWaves, 0, stream>>>(keys, S, dpn, (int)d, emb);
   dim3 pg((unsigned)num_relations, (unsigned)l.nseg);
   k_segment_partials<<<pg, 64, 0, stream>>>(rkeys, (int)batch, relrow, (int)d, (int)num_relations, (int)segment_len(batch),

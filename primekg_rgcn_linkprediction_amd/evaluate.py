@@ -363,12 +363,13 @@ def load_model(model_path: str, device: torch.device, trust_pickle: bool = False
     model = DrugDiseaseModel(num_nodes=num_nodes, num_relations=num_relations, embedding_dim=args.embedding_dim,
                              hidden_dim=args.hidden_dim, dropout=args.dropout,
                              decoder_dropout=getattr(args, "decoder_dropout", 0.0),
-                             num_bases=getattr(args, "num_bases", None))
+                             num_bases=getattr(args, "num_bases", None),
+                             decoder=getattr(args, "decoder", "distmult"))
     model.load_state_dict(state)
     model = model.to(device).eval()
     info = {"checkpoint_path": str(model_path), "epoch": checkpoint.get("epoch", "unknown"), "num_nodes": num_nodes,
             "num_relations": num_relations, "embedding_dim": args.embedding_dim, "hidden_dim": args.hidden_dim,
-            "num_parameters": sum(p.numel() for p in model.parameters())}
+            "decoder": model.decoder.decoder, "num_parameters": sum(p.numel() for p in model.parameters())}
     for key in ("best_val_loss", "best_val_acc"):
         if key in checkpoint:
             info[key] = checkpoint[key]

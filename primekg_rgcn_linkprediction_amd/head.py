@@ -1,4 +1,4 @@
-"""DistMult scoring head on the HIP library.
+"""DistMult and ComplEx scoring heads on the HIP library.
 
 Mirror of the reference's ``LinkPredictor`` (``src/models/rgcn.py:145-243``): same
 constructor ``(num_relations, embedding_dim, dropout=0.0)``, same parameter
@@ -8,6 +8,10 @@ constructor ``(num_relations, embedding_dim, dropout=0.0)``, same parameter
 
 Extra entry ``score_triples(node_embeddings, head_idx, tail_idx, relation_types)`` fuses
 the two row gathers of ``rgcn.py:325-326`` into the scoring kernel (SURVEY row C1 + C2).
+
+``LinkPredictor(..., decoder="complex")`` scores with ComplEx, ``Re <h, r, conj(t)>`` (``include/rgcn_complex.h``): a
+row of width d is d / 2 complex numbers, real parts first, so the parameter and the checkpoint keys are DistMult's.
+Unlike DistMult it tells ``(h, r, t)`` from ``(t, r, h)``: the tail enters conjugated.
 """
 from __future__ import annotations
 
@@ -151,15 +155,104 @@ class _ScoreAllTailsFunction(torch.autograd.Function):
         return grad_head, grad_rel, None, grad_emb
 
 
+class _ComplExFunction(torch.autograd.Function):
+    """scores[b] = Re <H[hi(b)], Rm[ri(b)], conj(T[ti(b)])>; an index of None means row b."""
+
+    @staticmethod
+    def forward(ctx, h: Tensor, h_idx: Optional[Tensor], t: Tensor, t_idx: Optional[Tensor],
+                r: Tensor, r_idx: Optional[Tensor]) -> Tensor:
+        h, t, r = h.contiguous(), t.contiguous(), r.contiguous()
+        h_idx, t_idx, r_idx = (i.contiguous() if i is not None else None for i in (h_idx, t_idx, r_idx))
+        batch = (h_idx if h_idx is not None else h).size(0)
+        scores = ops.complex_fwd(h, h_idx, t, t_idx, r, r_idx, batch)
+        ctx.batch = batch
+        ctx.same_ht = h.data_ptr() == t.data_ptr() and h.shape == t.shape
+        ctx.save_for_backward(h, h_idx, t, t_idx, r, r_idx)
+        return scores
+
+    @staticmethod
+    def backward(ctx, gs: Tensor):
+        h, h_idx, t, t_idx, r, r_idx = ctx.saved_tensors
+        need_h, _, need_t, _, need_r, _ = ctx.needs_input_grad
+        gh = torch.empty_like(h) if need_h else None
+        # head and tail gathered from one table: accumulate both into one buffer
+        shared = ctx.same_ht and need_h and need_t and h_idx is not None and t_idx is not None
+        gt = gh if shared else (torch.empty_like(t) if need_t else None)
+        gr = torch.empty_like(r) if need_r else None
+        ops.complex_bwd(gs.contiguous(), h, h_idx, t, t_idx, r, r_idx, ctx.batch, gh, gt, gr, zero_tables=True)
+        return gh, None, (None if shared else gt), None, gr, None
+
+
+class _ComplExBCEFunction(torch.autograd.Function):
+    """``_DistMultBCEFunction`` with the ComplEx score: the scoring launch emits the per-sample loss, the mean and the
+    step's bookkeeping are ``distmult_bce_reduce``'s (decoder-independent), and one backward call turns the gradient of
+    the mean loss into the head / tail / relation gradients."""
+
+    @staticmethod
+    def forward(ctx, h, h_idx, t, t_idx, r, r_idx, labels, stats=None):
+        h, t, r = h.contiguous(), t.contiguous(), r.contiguous()
+        h_idx, t_idx, r_idx = (i.contiguous() if i is not None else None for i in (h_idx, t_idx, r_idx))
+        labels = labels.contiguous()
+        batch = (h_idx if h_idx is not None else h).size(0)
+        scores, per_sample = ops.complex_bce_fwd(h, h_idx, t, t_idx, r, r_idx, labels, batch)
+        ctx.batch = batch
+        ctx.same_ht = h.data_ptr() == t.data_ptr() and h.shape == t.shape
+        ctx.save_for_backward(h, h_idx, t, t_idx, r, r_idx, labels, scores)
+        ctx.mark_non_differentiable(scores)
+        ctx.set_materialize_grads(False)
+        loss_sum, correct, cursor, cursor_add = stats if stats is not None else (None, None, None, 0)
+        mean = ops.distmult_bce_reduce(per_sample, scores, labels, loss_sum, correct, cursor, cursor_add)
+        return mean.reshape(()), scores
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_scores):
+        h, h_idx, t, t_idx, r, r_idx, labels, scores = ctx.saved_tensors
+        need_h, _, need_t, _, need_r, _, _, _ = ctx.needs_input_grad
+        if g_loss is None:                           # nothing downstream used the loss
+            return (None,) * 8
+        gh = torch.empty_like(h) if need_h else None
+        shared = ctx.same_ht and need_h and need_t and h_idx is not None and t_idx is not None
+        gt = gh if shared else (torch.empty_like(t) if need_t else None)
+        gr = torch.empty_like(r) if need_r else None
+        ops.complex_bce_bwd(g_loss.reshape(1).contiguous(), scores, labels, h, h_idx, t, t_idx, r, r_idx,
+                            ctx.batch, gh, gt, gr, zero_tables=True)
+        return gh, None, (None if shared else gt), None, gr, None, None, None
+
+
+def complex_query_rows(x: Tensor, rel_rows: Tensor, side: str) -> Tensor:
+    """``ops.complex_query`` on gathered rows, in torch ops - the differentiable form (``score_all_tails`` when a
+    gradient is required); same grouping as the kernel"""
+    m = x.size(1) // 2
+    x_re, x_im, r_re, r_im = x[:, :m], x[:, m:], rel_rows[:, :m], rel_rows[:, m:]
+    if side == "tail":
+        return torch.cat([x_re * r_re - x_im * r_im, x_re * r_im + x_im * r_re], dim=1)
+    return torch.cat([r_re * x_re + r_im * x_im, r_re * x_im - r_im * x_re], dim=1)
+
+
+DECODERS = ("distmult", "complex")
+
+
 def distmult(h, h_idx, t, t_idx, r, r_idx) -> Tensor:
     return _DistMultFunction.apply(h, h_idx, t, t_idx, r, r_idx)
 
 
-class LinkPredictor(nn.Module):
-    """DistMult decoder: ``score(h, r, t) = sum_d h_d * r_d * t_d``."""
+def complex_score(h, h_idx, t, t_idx, r, r_idx) -> Tensor:
+    return _ComplExFunction.apply(h, h_idx, t, t_idx, r, r_idx)
 
-    def __init__(self, num_relations: int, embedding_dim: int, dropout: float = 0.0):
+
+class LinkPredictor(nn.Module):
+    """``decoder="distmult"`` (the default): ``score(h, r, t) = sum_d h_d * r_d * t_d``, symmetric in h and t.
+    ``decoder="complex"``: ``score(h, r, t) = Re <h, r, conj(t)>`` over d / 2 complex numbers per row (real parts in
+    columns [0, d / 2), imaginary parts behind them; d a multiple of 8), which is not: the tail enters conjugated, so
+    the head side of every ranking call takes another query operand than the tail side.  Same parameter either way."""
+
+    def __init__(self, num_relations: int, embedding_dim: int, dropout: float = 0.0, decoder: str = "distmult"):
         super().__init__()
+        if decoder not in DECODERS:
+            raise ValueError(f"decoder must be one of {DECODERS}, got {decoder!r}")
+        if decoder == "complex" and embedding_dim % 8:
+            raise ValueError("embedding dim must be a multiple of 8")
+        self.decoder = decoder
         self.num_relations = num_relations
         self.embedding_dim = embedding_dim
         self.relation_embeddings = nn.Embedding(num_relations, embedding_dim)
@@ -181,14 +274,16 @@ class LinkPredictor(nn.Module):
     def forward(self, head_embeddings: Tensor, tail_embeddings: Tensor,
                 relation_types: Tensor) -> Tensor:
         r, r_idx = self._relation_operand(relation_types)
-        return distmult(head_embeddings, None, tail_embeddings, None, r, r_idx)
+        score = complex_score if self.decoder == "complex" else distmult
+        return score(head_embeddings, None, tail_embeddings, None, r, r_idx)
 
     def score_triples(self, node_embeddings: Tensor, head_indices: Tensor, tail_indices: Tensor,
                       relation_types: Tensor) -> Tensor:
         """``forward(node_embeddings[head], node_embeddings[tail], rel)`` without
         materialising the two [B, d] gathers."""
         r, r_idx = self._relation_operand(relation_types)
-        return distmult(node_embeddings, head_indices, node_embeddings, tail_indices, r, r_idx)
+        score = complex_score if self.decoder == "complex" else distmult
+        return score(node_embeddings, head_indices, node_embeddings, tail_indices, r, r_idx)
 
     def bce_loss(self, node_embeddings: Tensor, head_indices: Tensor, tail_indices: Tensor,
                  relation_types: Tensor, labels: Tensor, stats=None):
@@ -196,8 +291,16 @@ class LinkPredictor(nn.Module):
         device-resident running sums and batch cursor ``(loss_sum, correct, cursor, cursor_add)``, updated by the launch
         that forms the mean (``Trainer``: ``src/train.py:321-326`` without nine elementwise launches per step)."""
         r, r_idx = self._relation_operand(relation_types)
-        return _DistMultBCEFunction.apply(node_embeddings, head_indices, node_embeddings, tail_indices,
-                                          r, r_idx, labels, stats)
+        fn = _ComplExBCEFunction if self.decoder == "complex" else _DistMultBCEFunction
+        return fn.apply(node_embeddings, head_indices, node_embeddings, tail_indices, r, r_idx, labels, stats)
+
+    def _query(self, side: str, anchor_embeddings: Tensor, relation_types: Tensor) -> Tensor:
+        """the query rows ``q`` with ``score = <q[b], E[n]>`` for the candidates of ``side``.  DistMult: ``anchor * rel`` on
+        both sides.  ComplEx: ``ops.complex_query`` - on the head side the operand with the conjugate."""
+        if self.decoder == "complex":
+            return ops.complex_query(anchor_embeddings.contiguous(), None, self.relation_embeddings.weight,
+                                     relation_types.contiguous(), side)
+        return (anchor_embeddings * self.relation_embeddings(relation_types)).contiguous()
 
     @torch.no_grad()
     def rank_tails(self, head_embeddings: Tensor, relation_types: Tensor, all_tail_embeddings: Tensor,
@@ -220,7 +323,7 @@ class LinkPredictor(nn.Module):
         tail's row, in the head's row or in the relation's - is beaten by every eligible candidate: rank ``1 +
         #eligible``, raw that is ``N``, where the reference's argsort would put the missing value first.  A model whose
         table is all NaN ranks every triple last, never first."""
-        hr = (head_embeddings * self.relation_embeddings(relation_types)).contiguous()
+        hr = self._query("tail", head_embeddings, relation_types)
         emb = all_tail_embeddings.contiguous()
         true_score = (hr * emb[tail_indices]).sum(1)
         if known is None and node_class is None:
@@ -234,12 +337,14 @@ class LinkPredictor(nn.Module):
                    tail_indices: Optional[Tensor] = None, node_class: Optional[Tensor] = None,
                    max_mask_bytes: int = 256 << 20) -> Tensor:
         """1-based rank of ``head_indices[b]`` among all entities for ``(?, relation, tail)``.  DistMult is symmetric
-        in head and tail, so this is ``rank_tails``'s pass with ``q = tail * rel``; ``known`` filters by the
+        in head and tail, so this is ``rank_tails``'s pass with ``q = tail * rel``.  ComplEx is not: the query operand is
+        ``q = [r_re t_re + r_im t_im | r_re t_im - r_im t_re]``, the tail rotated by the CONJUGATE of the relation
+        (``ops.complex_query(side="head")``), so that ``score(n, r, t) = <q, E[n]>``.  ``known`` filters by the
         ``(tail, relation)`` sets (``tail_indices``: the node ids of the tails), ``node_class`` restricts the
         candidates to the true head's class.  Non-finite values as in ``rank_tails``: an eligible candidate counts
         unless its score is ``<=`` the true score, so a NaN candidate counts against every query and a NaN true score
         ranks ``1 + #eligible``."""
-        tr = (tail_embeddings * self.relation_embeddings(relation_types)).contiguous()
+        tr = self._query("head", tail_embeddings, relation_types)
         emb = all_head_embeddings.contiguous()
         true_score = (tr * emb[head_indices]).sum(1)
         return self._rank_filtered("head", tr, emb, true_score, head_indices.contiguous(), relation_types, known,
@@ -281,7 +386,7 @@ class LinkPredictor(nn.Module):
         ``known`` (with ``head_indices``): only novel tails - no ``n`` with ``(head, relation, n)`` among the known
         triples.  ``node_class`` (int ``[N]``) with ``candidate_class`` (an int, or an int ``[B]`` tensor): only tails
         of that class ("drugs").  ``min_score``: only scores ``>=`` it."""
-        hr = (head_embeddings * self.relation_embeddings(relation_types)).contiguous()
+        hr = self._query("tail", head_embeddings, relation_types)
         return self._top_filtered("tail", hr, all_tail_embeddings.contiguous(), k, relation_types, known, head_indices,
                                   node_class, candidate_class, min_score, max_mask_bytes)
 
@@ -291,8 +396,9 @@ class LinkPredictor(nn.Module):
                   node_class: Optional[Tensor] = None, candidate_class=None, min_score: Optional[float] = None,
                   max_mask_bytes: int = 256 << 20):
         """The ``k`` best heads of every ``(?, relation, tail)`` query.  DistMult is symmetric in head and tail, so
-        this is ``top_tails``'s pass with ``q = tail * rel``; ``known`` filters by the ``(tail, relation)`` sets."""
-        tr = (tail_embeddings * self.relation_embeddings(relation_types)).contiguous()
+        this is ``top_tails``'s pass with ``q = tail * rel``; ComplEx takes the conjugate operand of ``rank_heads``.
+        ``known`` filters by the ``(tail, relation)`` sets."""
+        tr = self._query("head", tail_embeddings, relation_types)
         return self._top_filtered("head", tr, all_head_embeddings.contiguous(), k, relation_types, known, tail_indices,
                                   node_class, candidate_class, min_score, max_mask_bytes)
 
@@ -321,7 +427,23 @@ class LinkPredictor(nn.Module):
         """``(h * r) @ E^T`` -> [B, num_entities] (rgcn.py:215-243): the ranking kernel's GEMM with a store
         epilogue (``distmult_score_all_tails``), so ``score_all_tails(...)[b, n]`` and the score ``rank_tails``
         compares are the same bits.  Differentiable like the reference's expression.  An embedding width that is not a
-        multiple of the kernel's 32-wide k step (the reference's is 128) takes the library GEMM on the GPU."""
+        multiple of the kernel's 32-wide k step (the reference's is 128) takes the library GEMM on the GPU.
+
+        ComplEx: the same kernel on the query rows ``q`` (``ops.complex_query``, or torch ops when a gradient is
+        required) with a one-row relation table of ones - ``x * 1.0f`` is exact, so the entries, the scores the ranking
+        pass compares and the scores the top-k pass lists are the same bits."""
+        if self.decoder == "complex":
+            needs_grad = torch.is_grad_enabled() and (head_embeddings.requires_grad or all_tail_embeddings.requires_grad
+                                                      or self.relation_embeddings.weight.requires_grad)
+            if needs_grad or not head_embeddings.is_cuda:
+                q = complex_query_rows(head_embeddings, self.relation_embeddings(relation_types), "tail")
+            else:
+                q = self._query("tail", head_embeddings, relation_types)
+            if q.size(1) % 32 and q.is_cuda:
+                return q @ all_tail_embeddings.t()
+            ones = torch.ones(1, q.size(1), dtype=q.dtype, device=q.device)
+            zero = torch.zeros(q.size(0), dtype=torch.int64, device=q.device)
+            return _ScoreAllTailsFunction.apply(q, ones, zero, all_tail_embeddings)
         if head_embeddings.size(1) % 32 and head_embeddings.is_cuda:
             return (head_embeddings * self.relation_embeddings(relation_types)) @ all_tail_embeddings.t()
         return _ScoreAllTailsFunction.apply(head_embeddings, self.relation_embeddings.weight, relation_types,

@@ -65,11 +65,11 @@ class DrugDiseaseRGCN(nn.Module):
 
 
 class DrugDiseaseModel(nn.Module):
-    """R-GCN encoder + DistMult decoder."""
+    """R-GCN encoder + scoring head: DistMult (the default) or ComplEx (``decoder="complex"``, ``LinkPredictor``)."""
 
     def __init__(self, num_nodes: int, num_relations: int, embedding_dim: int = 64,
                  hidden_dim: int = 128, dropout: float = 0.5, decoder_dropout: float = 0.0,
-                 num_bases: Optional[int] = None, gather_dtype=None):
+                 num_bases: Optional[int] = None, gather_dtype=None, decoder: str = "distmult"):
         super().__init__()
         self.num_nodes = num_nodes
         self.num_relations = num_relations
@@ -78,7 +78,7 @@ class DrugDiseaseModel(nn.Module):
                                        embedding_dim=embedding_dim, hidden_dim=hidden_dim,
                                        dropout=dropout, num_bases=num_bases, gather_dtype=gather_dtype)
         self.decoder = LinkPredictor(num_relations=num_relations, embedding_dim=hidden_dim,
-                                     dropout=decoder_dropout)
+                                     dropout=decoder_dropout, decoder=decoder)
 
     def forward(self, edge_index: Tensor, edge_type: Tensor, head_indices: Tensor,
                 tail_indices: Tensor, relation_types: Tensor) -> Tensor:

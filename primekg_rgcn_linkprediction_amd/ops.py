@@ -1634,6 +1634,117 @@ def distmult_bwd(gs, h, h_idx, t, t_idx, r, r_idx, batch: int, grad_h, grad_t, g
     _lib.check(rc, "distmult_bwd")
 
 
+# ----------------------------------------------------------------------------------
+# ComplEx head (include/rgcn_complex.h, csrc/complex.hip): score(h, r, t) = Re <h, r, conj(t)>, asymmetric in h and t.
+# A row of width d is d / 2 complex numbers, real parts in columns [0, d / 2), imaginary parts in [d / 2, d).
+# ----------------------------------------------------------------------------------
+def _check_complex_operands(h, h_idx, t, t_idx, r, r_idx, batch: int) -> int:
+    d = h.size(1)
+    for name, m, i in (("head", h, h_idx), ("tail", t, t_idx), ("rel", r, r_idx)):
+        _check_operand(name, m, i, batch)
+        if m.size(1) != d:
+            raise ValueError("head / tail / relation embedding dims differ")
+    if d % 8:
+        raise ValueError("embedding dim must be a multiple of 8")
+    return d
+
+
+def complex_fwd(h, h_idx, t, t_idx, r, r_idx, batch: int) -> torch.Tensor:
+    """``scores[b] = Re <H[hi(b)], R[ri(b)], conj(T[ti(b)])>`` (``complex_fwd``); an index of None means row b."""
+    d = _check_complex_operands(h, h_idx, t, t_idx, r, r_idx, batch)
+    lib = _L()
+    with _on(h.device):
+        scores = _empty(batch, dtype=torch.float32, device=h.device)
+        rc = lib.complex_fwd(_ptr(h), _ptr(h_idx), h.size(0), _ptr(t), _ptr(t_idx), t.size(0), _ptr(r), _ptr(r_idx),
+                             r.size(0), batch, d, _ptr(scores), _stream())
+    _lib.check(rc, "complex_fwd")
+    return scores
+
+
+def complex_bce_fwd(h, h_idx, t, t_idx, r, r_idx, labels, batch: int):
+    """-> (scores [B], per-sample binary_cross_entropy_with_logits(scores, labels) [B]) in one launch; the mean is
+    ``distmult_bce_reduce``'s (decoder-independent)."""
+    d = _check_complex_operands(h, h_idx, t, t_idx, r, r_idx, batch)
+    _need_gpu("labels", labels, torch.float32)
+    if labels.shape != (batch,):
+        raise ValueError(f"labels must be [{batch}], got {tuple(labels.shape)}")
+    lib = _L()
+    with _on(h.device):
+        scores = _empty(batch, dtype=torch.float32, device=h.device)
+        loss = _empty(batch, dtype=torch.float32, device=h.device)
+        rc = lib.complex_bce_fwd(_ptr(h), _ptr(h_idx), h.size(0), _ptr(t), _ptr(t_idx), t.size(0), _ptr(r), _ptr(r_idx),
+                                 r.size(0), _ptr(labels), batch, d, _ptr(scores), _ptr(loss), _stream())
+    _lib.check(rc, "complex_bce_fwd")
+    return scores, loss
+
+
+def _complex_bwd_workspace(lib, batch: int, d: int, r, r_idx, device):
+    nbytes = lib.complex_bwd_workspace_bytes(batch, d, r.size(0) if r_idx is not None else 0)
+    return _workspace(nbytes, device), nbytes
+
+
+def complex_bce_bwd(grad_mean_loss, scores, labels, h, h_idx, t, t_idx, r, r_idx, batch: int,
+                    grad_h, grad_t, grad_r, zero_tables: bool = False) -> None:
+    """Backward of ``mean(bce_with_logits(complex(...), labels))``; ``grad_mean_loss`` is a one-element device tensor.
+    Writes like ``complex_bwd`` (``zero_tables`` as there)."""
+    _need_gpu("grad_mean_loss", grad_mean_loss, torch.float32)
+    if grad_mean_loss.numel() != 1:
+        raise ValueError("grad_mean_loss must hold one float")
+    d = h.size(1)
+    if d % 8:
+        raise ValueError("embedding dim must be a multiple of 8")
+    lib = _L()
+    with _on(h.device):
+        ws, nbytes = _complex_bwd_workspace(lib, batch, d, r, r_idx, h.device)
+        rc = lib.complex_bce_bwd(_ptr(grad_mean_loss), _ptr(scores), _ptr(labels), _ptr(h), _ptr(h_idx), h.size(0),
+                                 _ptr(t), _ptr(t_idx), t.size(0), _ptr(r), _ptr(r_idx), r.size(0), batch, d,
+                                 _ptr(grad_h), _ptr(grad_t), _ptr(grad_r), _ptr(ws), nbytes, int(bool(zero_tables)),
+                                 _stream())
+    _lib.check(rc, "complex_bce_bwd")
+
+
+def complex_bwd(gs, h, h_idx, t, t_idx, r, r_idx, batch: int, grad_h, grad_t, grad_r, zero_tables: bool = False) -> None:
+    """Deterministic backward of ``complex_fwd``, with the write rules of ``distmult_bwd``: rows reached through an index
+    vector are WRITTEN with the ordered sum of their samples' contributions, the rows nobody touches are cleared by the
+    first launch (``zero_tables``) or must come zeroed, ``grad_h is grad_t`` (one table) is one key space."""
+    _need_gpu("grad_scores", gs, torch.float32)
+    d = h.size(1)
+    if d % 8:
+        raise ValueError("embedding dim must be a multiple of 8")
+    lib = _L()
+    with _on(h.device):
+        ws, nbytes = _complex_bwd_workspace(lib, batch, d, r, r_idx, h.device)
+        rc = lib.complex_bwd(_ptr(gs), _ptr(h), _ptr(h_idx), h.size(0), _ptr(t), _ptr(t_idx), t.size(0), _ptr(r),
+                             _ptr(r_idx), r.size(0), batch, d, _ptr(grad_h), _ptr(grad_t), _ptr(grad_r), _ptr(ws),
+                             nbytes, int(bool(zero_tables)), _stream())
+    _lib.check(rc, "complex_bwd")
+
+
+def complex_query(x, x_idx, rel, rel_idx, side: str = "tail") -> torch.Tensor:
+    """The query rows ``q [B, d]`` with ``score = <q[b], E[n]>`` for every entity row - what the ranking, top-k and
+    score-matrix passes take (``rgcn_complex_query``: the gathers and the rotation in one launch).  ``side="tail"``: the
+    tails of ``(x, rel, ?)``, ``q = [x_re r_re - x_im r_im | x_re r_im + x_im r_re]``.  ``side="head"``: the heads of
+    ``(?, rel, x)``, ``q = [r_re x_re + r_im x_im | r_re x_im - r_im x_re]`` - the conjugate operand; the two differ.
+    An index of None means row b."""
+    if side not in ("tail", "head"):
+        raise ValueError("side must be 'tail' or 'head'")
+    batch = (x_idx if x_idx is not None else x).size(0)
+    for name, m, i in (("x", x, x_idx), ("rel", rel, rel_idx)):
+        _check_operand(name, m, i, batch)
+    d = x.size(1)
+    if rel.size(1) != d:
+        raise ValueError("entity / relation embedding dims differ")
+    if d % 8:
+        raise ValueError("embedding dim must be a multiple of 8")
+    lib = _L()
+    with _on(x.device):
+        q = _empty((batch, d), dtype=torch.float32, device=x.device)
+        rc = lib.rgcn_complex_query(0 if side == "tail" else 1, _ptr(x), _ptr(x_idx), x.size(0), _ptr(rel), _ptr(rel_idx),
+                                    rel.size(0), batch, d, _ptr(q), _stream())
+    _lib.check(rc, "rgcn_complex_query")
+    return q
+
+
 def distmult_rank_tails(hr: torch.Tensor, emb: torch.Tensor, true_score: torch.Tensor,
                         tail: torch.Tensor) -> torch.Tensor:
     """``rank[b] = 1 + #{n != tail[b] : not (<hr[b], emb[n]> <= true_score[b])}`` (int64 [B]): the

@@ -469,7 +469,8 @@ def create_model(num_nodes: int, num_relations: int, args: argparse.Namespace) -
                              embedding_dim=args.embedding_dim, hidden_dim=args.hidden_dim,
                              dropout=args.dropout, decoder_dropout=args.decoder_dropout,
                              num_bases=args.num_bases,
-                             gather_dtype=torch.float16 if getattr(args, "fp16_gather", False) else None)
+                             gather_dtype=torch.float16 if getattr(args, "fp16_gather", False) else None,
+                             decoder=getattr(args, "decoder", "distmult"))
     logger.info("Model created with %s parameters",
                 f"{sum(p.numel() for p in model.parameters() if p.requires_grad):,}")
     return model
@@ -484,6 +485,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--hidden_dim", type=int, default=128)
     p.add_argument("--dropout", type=float, default=0.5)
     p.add_argument("--decoder_dropout", type=float, default=0.1)
+    p.add_argument("--decoder", type=str, default="distmult", choices=["distmult", "complex"],
+                   help="scoring head: distmult (symmetric in head and tail) or complex (Re <h, r, conj(t)>: tells a "
+                        "directed edge from its reverse; hidden_dim must be a multiple of 8)")
     p.add_argument("--num_bases", type=int, default=None)
     p.add_argument("--epochs", type=int, default=100)
     p.add_argument("--batch_size", type=int, default=1024)
