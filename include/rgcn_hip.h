@@ -214,7 +214,12 @@ typedef struct rgcn_slab_job {
  * levels, no job, no amax):
  *   x_f16 != 0   the gathered table is IEEE fp16 (x: half[N, d], d % 8 == 0): half the bytes per gathered row
  *                (BASELINE.json configs[4], "fp16 features + fp32 accumulate").  Sums, agg and the workspace stay
- *                fp32.  amax must be NULL (RGCN_ERR_UNSUPPORTED otherwise).
+ *                fp32.  amax must be NULL (RGCN_ERR_UNSUPPORTED otherwise).  (Bit 0 of x_f16; 0 and 1 mean what they did.)
+ *   x_f16 & RGCN_MODE_SPARSE_ROWS
+ *                the rows of segments with no edge are NOT written (fp32 table, R <= 32, d <= 256 only:
+ *                RGCN_ERR_UNSUPPORTED otherwise): agg is a SPARSE aggregate, whose dead rows hold whatever the buffer
+ *                held and may only be read by the split-precision transforms called with the same bit, which never load
+ *                them.  amax is unaffected (a zero never raises a maximum).  rgcn_aggregate never sets it.
  *   first_level, last_level
  *                only the launches (tree levels) [first_level, last_level) of rgcn_graph_num_levels are issued;
  *                last_level < 0: all from first_level on.  The levels called in order equal one call, which lets a
@@ -236,6 +241,15 @@ typedef struct rgcn_slab_job {
  * such a producer runs (rgcn_absmax clears buffers on the side).  The split-precision transforms below scale
  * their operands by it. */
 #define RGCN_AMAX_FLOATS 2048
+/* Sparse aggregates (training passes; include/rgcn_sparse.h has the row-granular occupancy they rest on).  One bit,
+ * the same value in every `int` option word that takes it - x_f16 of rgcn_aggregate_ex, `half` of
+ * rgcn_transform_fwd_split / _bwd_input_split / _bwd_params_split_begin, has_root1 of
+ * rgcn_transform_bwd_input_chain_split (bit 0 of each keeps its meaning; the values 0 and 1 behave as they always
+ * did).  On a transform it says: the aggregate operand (agg / gagg) is sparse, `tile_mask` is the rgcn_graph_tile_mask
+ * of the structure it was gathered over (required: RGCN_ERR_ARG without it), and a row of it whose (row, relation)
+ * segment has no edge is never loaded - the lane's LDS-DMA reads a zero row kept by the library instead.  x / g and
+ * the other operands are read as ever; results are bit-identical to the dense call. */
+#define RGCN_MODE_SPARSE_ROWS 2
 size_t rgcn_aggregate_workspace_bytes(const rgcn_graph* g, int transposed, int64_t d);
 int rgcn_aggregate_deferrable(const rgcn_graph* g, int transposed, int64_t d);
 int rgcn_aggregate(const rgcn_graph* g, int transposed, const float* x, int64_t d, float* agg,

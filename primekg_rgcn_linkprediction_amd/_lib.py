@@ -236,6 +236,15 @@ COMPLEX_PROTOTYPES = {
     "rgcn_complex_query": (c_int, [c_int, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P]),
 }
 
+# include/rgcn_sparse.h, one to one: the row-granular occupancy behind sparse aggregates (csrc/rgcn_graph.hip; queries,
+# never forwarded by rgcn_sequence_run).  MODE_SPARSE_ROWS: RGCN_MODE_SPARSE_ROWS of rgcn_hip.h, the bit a training pass
+# sets in the `int` option word of its gathers and of the split transforms that read their aggregates.
+SPARSE_PROTOTYPES = {
+    "rgcn_graph_row_mask": (c_void_p, [c_void_p, c_int, POINTER(c_int64)]),
+    "rgcn_occupancy_host": (_I64, [_P, _I64, _I64, _P, POINTER(c_int64)]),
+}
+MODE_SPARSE_ROWS = 2
+
 _lib = None
 
 
@@ -257,7 +266,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise RGCNLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + list(COMPLEX_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + list(COMPLEX_PROTOTYPES.items()) + list(SPARSE_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -122,6 +122,26 @@ def _transform_first(graph: "ops.BucketedGraph", weight: Tensor, root: Optional[
     return d_out >= ratio * d_in and root is not None and not graph.bipartite
 
 
+# Sparse aggregates: about half of the (node, relation) segments of a typed knowledge graph have no edge (46,756 of C2's
+# 92,778, on the source side too), and an aggregate that stays inside a training pass - agg1, agg2, the transposed
+# aggregate of conv2's input gradient - needs neither their zero rows stored by the gather nor read back by the
+# transforms (ops.aggregate_sparse; the NT / chained NT / TN kernels redirect those lanes to one row of zeros: same
+# bits).  Where the split kernels consume the aggregate and its scale is known beforehand; everything else - fp32 and
+# one-pass fp16 transforms, the fp16 table, shards, the fused layers, the eval path - keeps every row written.
+# profiles/sparse_aggregate.txt.  A module attribute (tests patch it); part of _policy_key().
+_SPARSE_AGG = True
+
+
+def _sparse_agg(graph: "ops.BucketedGraph", transposed: bool, half: bool, packed, amax, d: int, precision=None) -> bool:
+    """is the d-wide aggregate of this layer a sparse one (see above)?  The consumers' own conditions: split precision
+    with the step's split images, the operand's maximum in a buffer (a sparse operand cannot be scanned), rows the
+    parameter-gradient kernel tiles (d % 64), a square graph of at most 32 relations."""
+    return bool(_SPARSE_AGG and not half and packed is not None and amax is not None and ops.GEMM_PRECISION == "split"
+                and precision in (None, "half") and d % 64 == 0 and d <= 256 and not graph.bipartite
+                and not graph.weighted_shard and graph.num_relations <= 32
+                and graph.row_mask_ptr(transposed) is not None)
+
+
 def _gagg_scale(graph: "ops.BucketedGraph", gagg_amax: Optional[Tensor], g_amax: Optional[Tensor]):
     """``(amax, amax_mul)`` of the transform reading a transposed aggregate of ``g``: its OWN maximum, which its gather
     publishes - the bound weight_bound * max |g| is hundreds of times looser on hub graphs and would cost its ordinary
@@ -177,17 +197,23 @@ def _input_grad(graph: "ops.BucketedGraph", g: Tensor, weight: Tensor, root: Opt
             gx = ops.layer_bwd_input_fused(graph, g, packed, relu_mask, g_amax, amax_out=amax_out, tail=tail,
                                            inline_limit=_EVAL_INLINE_LIMIT, out_scale=out_scale, gagg_amax=gagg_amax)
         else:
-            gagg = ops.aggregate(graph, g, transposed=True, tail=tail, amax_out=gagg_amax)   # autograd of A3 + A4
+            # (the transposed aggregate lives from this launch to the next one: sparse where that one can take it)
+            sparse = gagg_amax is not None and _sparse_agg(graph, True, False, packed, g_amax, d_out, precision)
+            if sparse:
+                gagg = ops.aggregate_sparse(graph, g, transposed=True, tail=tail, amax_out=gagg_amax)[0]
+            else:
+                gagg = ops.aggregate(graph, g, transposed=True, tail=tail, amax_out=gagg_amax)   # autograd of A3 + A4
             amax, mul = _gagg_scale(graph, gagg_amax, g_amax)
             if (lower is not None and packed is not None and g_amax is not None
                     and _from_packed(lower[0], lower[2], precision) and _transform_first(graph, *lower, precision)
                     and ops.chain_supported(weight, lower[0])):
                 gx, t = ops.transform_bwd_input_chain(gagg, g, weight, root, relu_mask, packed, lower[2], graph=graph,
-                                                      amax=amax, amax_mul=mul, amax_out=amax_out, out_scale=out_scale)
+                                                      amax=amax, amax_mul=mul, amax_out=amax_out, out_scale=out_scale,
+                                                      sparse=sparse)
             else:
                 gx = ops.transform_bwd_input(gagg, g, weight, root, relu_mask=relu_mask, graph=graph, amax=amax,
                                              amax_mul=mul, amax_out=amax_out, packed=packed, precision=precision,
-                                             out_scale=out_scale)                   # autograd of A6 wrt x
+                                             out_scale=out_scale, sparse=sparse)    # autograd of A6 wrt x
     return (gx, t) if lower is not None else gx
 
 
@@ -197,10 +223,16 @@ def _backward_scales(g: Tensor, layers: int) -> _Scales:
     return _Scales(g, slots=2 * layers)
 
 
-def _deferred_params(graph: "ops.BucketedGraph", agg, x, g, x_amax, g_amax, has_root: bool, has_bias: bool, prec):
-    """a layer's parameter gradients, their slab reduction left pending: it rides in the gather that follows"""
+def _deferred_params(graph: "ops.BucketedGraph", agg, x, g, x_amax, g_amax, has_root: bool, has_bias: bool, prec,
+                     packed=None):
+    """a layer's parameter gradients, their slab reduction left pending: it rides in the gather that follows.  ``agg``
+    is the forward's aggregate: a sparse one wherever _layer_train_forward made it so, and this asks _sparse_agg the
+    same question with the same answers (the step's images ``packed``, the table's maximum, the width).  The one
+    thing the backward does not know is the forward's table type; with an fp16 table the aggregate is dense and the
+    kernel merely skips the loads of its stored zeros - the same bits."""
+    sparse = _sparse_agg(graph, False, False, packed, x_amax, x.size(1), prec)
     return ops.transform_bwd_params(agg, x, g, graph.num_relations, want_root=has_root, want_bias=has_bias, graph=graph,
-                                    defer=True, amax=(x_amax, x_amax, g_amax), precision=prec)
+                                    defer=True, amax=(x_amax, x_amax, g_amax), precision=prec, sparse=sparse)
 
 
 # Training forward of one layer: gather -> transform (two launches, the aggregate written by one and read by the
@@ -241,13 +273,17 @@ def _layer_train_forward(graph: "ops.BucketedGraph", x: Tensor, gather_dtype, we
         out = ops.layer_fwd_fused(graph, x, packed, bias, relu, x_amax, amax_out, inline_limit=_EVAL_INLINE_LIMIT,
                                   agg_out=agg)
         return agg, out
-    if _defer_hubs(half, packed, x_amax, d_in, d_out):
+    sparse = n == graph.num_other_nodes and _sparse_agg(graph, False, half, packed, x_amax, d_in)
+    if sparse:
+        # no zero rows stored, none read: by the transform below and by the parameter gradients (_deferred_params)
+        agg, hubs = ops.aggregate_sparse(graph, x, defer=_defer_hubs(half, packed, x_amax, d_in, d_out))
+    elif _defer_hubs(half, packed, x_amax, d_in, d_out):
         # the gather leaves its hub tails to the transform (one launch less); `agg` is complete once that has run
         agg, hubs = ops.aggregate_deferred(graph, x)
     else:
         agg, hubs = ops.aggregate(graph, _table(x, gather_dtype)), None
     out = ops.transform_fwd(agg, x, weight, root, bias, relu=relu, graph=graph, half=half, amax=(x_amax, x_amax),
-                            amax_out=amax_out, packed=packed, hubs=hubs)
+                            amax_out=amax_out, packed=packed, hubs=hubs, sparse=sparse)
     return agg, out
 
 
@@ -269,7 +305,8 @@ def _conv_backward(x, agg, weight, root, x_amax, pkbuf, g, *, graph, has_root, h
     """one layer's backward as a pass -> (gx | None, gw | None, groot | None, gbias | None)"""
     packed = _packs([pkbuf], [(weight, root)])[0]
     scales = _backward_scales(g, 1)
-    pending = _deferred_params(graph, agg, x, g, x_amax, scales.first, has_root, has_bias, prec) if need_p else None
+    pending = (_deferred_params(graph, agg, x, g, x_amax, scales.first, has_root, has_bias, prec, packed)
+               if need_p else None)
     gx = _input_grad(graph, g, weight, root, pending, scales.first, scales, packed, prec) if need_x else None
     if pending is None:
         return gx, None, None, None
@@ -368,14 +405,14 @@ def _enc2_backward(x, agg1, h, agg2, w1, root1, w2, root2, x_amax, h_amax, pk1bu
     scales = _backward_scales(g, 2)
     g_amax, gz_amax = scales.first, scales.slot()
     # the slab reductions of the parameter gradients ride in the transposed gathers that follow them
-    red2 = _deferred_params(graph, agg2, h, g, h_amax, g_amax, has_root2, has_b2, prec)
+    red2 = _deferred_params(graph, agg2, h, g, h_amax, g_amax, has_root2, has_b2, prec, pk2)
     # gz = d loss / d (pre-ReLU of conv1): ReLU mask h (positive exactly where a unit is active and kept), the dropout
     # factor 1 / (1 - p) one more epilogue scalar; where conv1's gradient is wanted, the launch may form its T too
     gz = _input_grad(graph, g, w2, root2, red2, g_amax, scales, pk2, prec, relu_mask=h,
                      out_scale=1.0 / (1.0 - p) if p > 0 else 1.0, amax_out=gz_amax,
                      lower=(w1, root1, pk1) if need_x else None)
     gz, t_first = gz if need_x else (gz, None)
-    red1 = _deferred_params(graph, agg1, x, gz, x_amax, gz_amax, has_root1, has_b1, prec)
+    red1 = _deferred_params(graph, agg1, x, gz, x_amax, gz_amax, has_root1, has_b1, prec, pk1)
     gx = _input_grad(graph, gz, w1, root1, red1, gz_amax, scales, pk1, prec, t_first) if need_x else None
     red2.finish()
     red1.finish()
@@ -389,7 +426,7 @@ _R_BACKWARD = ops.Region("encoder2.backward", _enc2_backward)
 
 
 def _policy_key():
-    return (_TRAIN_FUSED, _DEFER_HUBS, _TRANSFORM_FIRST_RATIO, _EVAL_INLINE_LIMIT, _TRAIN_FUSED_MIN_BYTES)
+    return (_TRAIN_FUSED, _DEFER_HUBS, _TRANSFORM_FIRST_RATIO, _EVAL_INLINE_LIMIT, _TRAIN_FUSED_MIN_BYTES, _SPARSE_AGG)
 
 
 def _enc2_train_forward(graph, params, gather_dtype, half_backward: bool, hints, p: float = 0.0):

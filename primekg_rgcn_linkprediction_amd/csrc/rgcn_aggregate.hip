@@ -25,7 +25,9 @@
 //   2. zero-fill workgroups: a (node, relation) segment without an edge (half of C2's 92,778) is an item too, and the
 //      plan's order makes these items the suffix of level 0.  Their rows are +0.0f and depend on nothing the walk
 //      computes, so they are not walked (item, flags, id window, cnt and four divides for one zero row, in workgroups
-//      dispatched after the walk has drained): a workgroup reads the `dst` of RGCN_ZERO_ROWS of them and stores;
+//      dispatched after the walk has drained): a workgroup reads the `dst` of RGCN_ZERO_ROWS of them and stores.  A
+//      SPARSE aggregate (RGCN_MODE_SPARSE_ROWS: one that stays inside a training pass, read only by the split transforms,
+//      which never load those rows) has no part 2 at all, and its walk ends at the last live slot;
 //   3. riders: the workgroups of a pending parameter-gradient slab reduction (rgcn_slab_reduce.h).  They are the last
 //      to start, so what each of them takes is the tail of the launch: one batch of loads (all the slabs of its group
 //      at C2), the adds in slab order, one barrier.
@@ -393,8 +395,8 @@ __global__ __launch_bounds__(kThreads) void k_reduce_partials(const rgcn_item* _
 template <int G>
 void launch_level(const rgcn_csr* c, int level, bool weighted, const float* x, const float* cnt, float* agg,
                   float* partial, int d, hipStream_t stream, const rgcn_slab_job* tail = nullptr,
-                  unsigned* amax_out = nullptr) {
-  const int64_t nitems = c->num_items[level];
+                  unsigned* amax_out = nullptr, bool sparse = false) {
+  int64_t nitems = c->num_items[level];
   if (nitems == 0) return;
   const unsigned gy = (unsigned)ceil_div64(d, 4 * G);
   if (level == 0) {
@@ -405,9 +407,13 @@ void launch_level(const rgcn_csr* c, int level, bool weighted, const float* x, c
     const int64_t slots = kThreads / G;
     const int64_t walked = gy == 1 ? std::min(nitems, ceil_div64(nitems - c->empty_items0, slots) * slots) : nitems;
     const unsigned gather_blocks = (unsigned)ceil_div64(walked, slots);
-    const unsigned zero_blocks = (unsigned)ceil_div64(nitems - walked, zero_rows<G>());
+    // A sparse aggregate (RGCN_MODE_SPARSE_ROWS; gy == 1 is the caller's check) gets no zero-fill workgroups, and the
+    // walk's last workgroup ends at the last live slot: no row of a segment without an edge is written at all.
+    if (sparse) nitems -= c->empty_items0;
+    const unsigned zero_blocks = sparse ? 0u : (unsigned)ceil_div64(nitems - walked, zero_rows<G>());
     const rgcn_slab_job job = tail ? *tail : rgcn_slab_job{};
     dim3 grid(gather_blocks + zero_blocks + (tail ? (unsigned)rgcn_slab_reduce_blocks(job) : 0u), gy);   // tail only with gy == 1
+    if (grid.x == 0) return;                     // (a sparse aggregate of a structure without any edge)
     if (weighted)
       k_aggregate<G, true><<<grid, kThreads, 0, stream>>>(x, c->items[0], nitems, c->col, c->val, cnt, agg, partial, d,
                                                           c->head_col, c->head_w, job, (int)gather_blocks,
@@ -438,7 +444,7 @@ void launch_level0_h(const rgcn_csr* c, bool weighted, const __half* x, const fl
 
 int aggregate_levels(const rgcn_graph* g, int transposed, int first, int last, const float* x, int64_t d,
                      float* agg, void* workspace, size_t workspace_bytes, void* stream_, bool half_in,
-                     const rgcn_slab_job* tail, float* amax) {
+                     const rgcn_slab_job* tail, float* amax, bool sparse) {
   if (!g) return RGCN_ERR_ARG;
   const rgcn_csr* c = &g->dir[transposed ? 1 : 0];
   hipStream_t stream = (hipStream_t)stream_;
@@ -463,6 +469,8 @@ int aggregate_levels(const rgcn_graph* g, int transposed, int first, int last, c
   float* partial = (float*)workspace;
   unsigned* amax_out = reinterpret_cast<unsigned*>(amax);
   if (amax && half_in) return RGCN_ERR_UNSUPPORTED;            // the fp16-table gather feeds the fp16 transform: no scale needed
+  // no zero rows: only where the zero-fill workgroups exist (fp32 table, 1-D grid) and the consumers can tell the rows
+  if (sparse && (half_in || d > 256 || !c->tile_mask)) return RGCN_ERR_UNSUPPORTED;
   // a lane reads 16 bytes of a table row (four floats, eight halves) and writes float4; amax heads are single words
   RGCN_ALIGN_TRY(16, x, agg, workspace);
   RGCN_ALIGN_TRY(4, amax);
@@ -491,13 +499,13 @@ int aggregate_levels(const rgcn_graph* g, int transposed, int first, int last, c
       else launch_level0_h<64>(c, weighted, xh, cnt, agg, partial, (int)d, stream);
       continue;
     }
-    if (q <= 1) launch_level<1>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out);
-    else if (q <= 2) launch_level<2>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out);
-    else if (q <= 4) launch_level<4>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out);
-    else if (q <= 8) launch_level<8>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out);
-    else if (q <= 16) launch_level<16>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out);
-    else if (q <= 32) launch_level<32>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out);
-    else launch_level<64>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out);
+    if (q <= 1) launch_level<1>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out, sparse);
+    else if (q <= 2) launch_level<2>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out, sparse);
+    else if (q <= 4) launch_level<4>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out, sparse);
+    else if (q <= 8) launch_level<8>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out, sparse);
+    else if (q <= 16) launch_level<16>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out, sparse);
+    else if (q <= 32) launch_level<32>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out, sparse);
+    else launch_level<64>(c, l, weighted, x, cnt, agg, partial, (int)d, stream, t0, amax_out, sparse);
   }
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
@@ -517,8 +525,8 @@ int rgcn_aggregate_ex(const rgcn_graph* g, int transposed, const void* x, int x_
                       float* amax, void* stream) {
   if (!g) return RGCN_ERR_ARG;
   return aggregate_levels(g, transposed, first_level, last_level < 0 ? g->dir[transposed ? 1 : 0].num_levels : last_level,
-                          reinterpret_cast<const float*>(x), d, agg, workspace, workspace_bytes, stream, x_f16 != 0, job,
-                          amax);
+                          reinterpret_cast<const float*>(x), d, agg, workspace, workspace_bytes, stream, (x_f16 & 1) != 0, job,
+                          amax, (x_f16 & RGCN_MODE_SPARSE_ROWS) != 0);
 }
 
 int rgcn_aggregate(const rgcn_graph* g, int transposed, const float* x, int64_t d, float* agg,

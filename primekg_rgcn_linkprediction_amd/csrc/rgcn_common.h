@@ -101,6 +101,10 @@ struct rgcn_csr {
   // bit r of tile_mask[t]: some row of rows [32t, 32t+32) has a non-empty (row, r) segment.
   // Typed relations leave whole row ranges without a relation (drug-gene edges never reach a
   // disease row): the transforms skip the all-zero k/m-tiles these bits expose.  NULL if R > 32.
+  // The SAME allocation carries the occupancy row by row behind the tile words (rgcn_row_mask_offset): bit r of
+  // row_mask[i] says segment (i, r) has an edge, so tile_mask[t] is the OR of its 32 rows; zero words pad it for
+  // the rows a consumer's last tiles reach past n_key.  A consumer of a sparse aggregate (rgcn_hip.h,
+  // RGCN_MODE_SPARSE_ROWS) finds it from tile_mask and its own row count - no field of this struct moves.
   uint32_t* tile_mask = nullptr;
   int64_t num_row_tiles = 0;
   // Deferred hub tails: when the plan has exactly ONE reduce level (every segment <= RGCN_CHUNK * RGCN_PACK *
@@ -116,6 +120,25 @@ struct rgcn_csr {
 };
 
 static_assert(offsetof(rgcn_csr, items) == offsetof(rgcn_csr, num_levels) + 8, "empty_items0 sits behind num_levels");
+
+// Layout of the occupancy allocation of a structure with n_key rows: ceil(n_key / 32) tile words, padded to a
+// 16-byte boundary, then n_key row words and RGCN_ROW_MASK_PAD zero words (a consumer stages up to two 32-row tiles
+// past its last row and reads four words at a time).
+constexpr int64_t RGCN_ROW_MASK_PAD = 96;
+static inline int64_t rgcn_row_mask_offset(int64_t n_key) { return ((n_key + 31) / 32 + 3) / 4 * 4; }
+static inline int64_t rgcn_occupancy_words(int64_t n_key) { return rgcn_row_mask_offset(n_key) + n_key + RGCN_ROW_MASK_PAD; }
+// Host side of both masks, from a host copy of rowptr [n_key * R + 1]: `words` = rgcn_occupancy_words(n_key), zeroed here.
+static inline void rgcn_fill_occupancy(const int32_t* rowptr, int64_t n_key, int64_t R, uint32_t* words) {
+  const int64_t off = rgcn_row_mask_offset(n_key), total = rgcn_occupancy_words(n_key);
+  for (int64_t i = 0; i < total; ++i) words[i] = 0u;
+  for (int64_t i = 0; i < n_key; ++i) {
+    uint32_t m = 0u;
+    for (int64_t r = 0; r < R; ++r)
+      if (rowptr[i * R + r + 1] > rowptr[i * R + r]) m |= 1u << r;
+    words[off + i] = m;
+    words[i >> 5] |= m;
+  }
+}
 
 struct rgcn_graph {
   int64_t E = 0, N = 0, R = 0;

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "rgcn_common.h"
+#include "../../include/rgcn_sparse.h"
 
 namespace {
 
@@ -213,12 +214,10 @@ int plan_structure(rgcn_csr* c, int64_t R, hipStream_t stream) {
   std::vector<int32_t> rp((size_t)NR + 1);
   RGCN_HIP_TRY(hipMemcpyAsync(rp.data(), c->rowptr, (NR + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   RGCN_HIP_TRY(hipStreamSynchronize(stream));
-  if (R <= 32 && c->n_key > 0) {          // relation occupancy per 32-row tile
+  if (R <= 32 && c->n_key > 0) {          // relation occupancy per 32-row tile and, behind it, per row
     c->num_row_tiles = ceil_div64(c->n_key, 32);
-    std::vector<uint32_t> mask((size_t)c->num_row_tiles, 0u);
-    for (int64_t i = 0; i < c->n_key; ++i)
-      for (int64_t r = 0; r < R; ++r)
-        if (rp[i * R + r + 1] > rp[i * R + r]) mask[(size_t)(i >> 5)] |= 1u << r;
+    std::vector<uint32_t> mask((size_t)rgcn_occupancy_words(c->n_key));
+    rgcn_fill_occupancy(rp.data(), c->n_key, R, mask.data());
     RGCN_HIP_TRY(hipMalloc((void**)&c->tile_mask, mask.size() * sizeof(uint32_t)));
     RGCN_HIP_TRY(hipMemcpy(c->tile_mask, mask.data(), mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
@@ -475,6 +474,27 @@ const uint32_t* rgcn_graph_tile_mask(const rgcn_graph* g, int transposed, int64_
   const rgcn_csr* c = &g->dir[transposed ? 1 : 0];
   if (num_row_tiles) *num_row_tiles = c->num_row_tiles;
   return c->tile_mask;
+}
+
+const uint32_t* rgcn_graph_row_mask(const rgcn_graph* g, int transposed, int64_t* num_rows) {
+  if (num_rows) *num_rows = 0;
+  if (!g) return nullptr;
+  const rgcn_csr* c = &g->dir[transposed ? 1 : 0];
+  if (!c->tile_mask) return nullptr;
+  if (num_rows) *num_rows = c->n_key;
+  return c->tile_mask + rgcn_row_mask_offset(c->n_key);
+}
+
+int64_t rgcn_occupancy_host(const int32_t* rowptr, int64_t num_rows, int64_t num_relations, uint32_t* words,
+                            int64_t* row_offset) {
+  if (num_rows < 0 || num_relations <= 0) return -1;
+  if (row_offset) *row_offset = rgcn_row_mask_offset(num_rows);
+  if (num_relations > 32) return 0;              // no occupancy words: the consumers read every row
+  if (words) {
+    if (!rowptr) return -1;
+    rgcn_fill_occupancy(rowptr, num_rows, num_relations, words);
+  }
+  return rgcn_occupancy_words(num_rows);
 }
 
 int rgcn_graph_arrays(const rgcn_graph* g, int transposed, const int32_t** rowptr, const int32_t** col,

@@ -218,6 +218,11 @@ struct nt_chain {
   int N2;
 };
 
+// What a lane's LDS-DMA reads in place of a row of a SPARSE aggregate (RGCN_MODE_SPARSE_ROWS) whose (row, relation)
+// segment has no edge: 16 bytes of this row of zeros (never written; 512 bytes, hot in every L2).  The gather stored
+// nothing there and the buffer may hold anything - the kernels below never issue a load from it.
+__device__ __attribute__((aligned(16))) float g_zero_row[128];
+
 template <int WM, int WN, int TN, int EPI, bool LO, bool CHAIN = false>
 __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __restrict__ A1, int K1,
                                                             const float* __restrict__ A2, int K2,
@@ -229,7 +234,8 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
                                                             const float* __restrict__ mask, float* __restrict__ C,
                                                             int M, int N, const uint32_t* __restrict__ tile_mask,
                                                             int kseg, unsigned* __restrict__ amax_out,
-                                                            const hub_fin fin, float out_scale, const nt_chain chain) {
+                                                            const hub_fin fin, float out_scale, const nt_chain chain,
+                                                            const uint32_t* __restrict__ row_mask) {
   static_assert(!CHAIN || (WM == 2 && WN == 2 && TN == 2 && LO), "the chained product is built for the 64 x 128 tile");
   constexpr int WAVES = WM * WN;                 // WM wave rows (32 output rows each) x WN wave columns (32 TN columns each)
   constexpr int BM = 32 * WM, BN = 32 * TN * WN, NBUF = WM == 2 ? 3 : 4, D = NBUF - 1;   // D k-tiles in flight
@@ -264,6 +270,16 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
       if ((t32 + q) * 32 < M) rel_mask |= tile_mask[t32 + q];
     rel_mask = __builtin_amdgcn_readfirstlane(rel_mask);
   }
+  int a_m[A_PW], a_c4[A_PW];                                     // source row and (swizzled) column of this lane
+  unsigned a_rm[A_PW];                                           // relations the row has in a sparse A1 (row_mask; else all)
+#pragma unroll
+  for (int j = 0; j < A_PW; ++j) {
+    const int row = (wave * A_PW + j) * 8 + (lane >> 3);
+    a_m[j] = min(m0 + row, M - 1);                               // rows past M read a valid row; never stored
+    a_c4[j] = ((lane & 7) ^ ((row >> 1) & 7)) * 4;
+    a_rm[j] = row_mask ? row_mask[a_m[j]] : 0xffffffffu;         // the lane's rows are fixed for the whole k loop
+  }
+  const float* a_zero = g_zero_row + (lane & 7) * 4;
   int fin_b = 0, fin_e = 0;                      // this row tile's range of deferred hub items (below): the same round trip
   if (WAVES == 4 && fin.ptr) {
     fin_b = fin.ptr[min(m0 >> 5, fin.tiles)];
@@ -302,13 +318,6 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
 
-  int a_m[A_PW], a_c4[A_PW];                                     // source row and (swizzled) column of this lane
-#pragma unroll
-  for (int j = 0; j < A_PW; ++j) {
-    const int row = (wave * A_PW + j) * 8 + (lane >> 3);
-    a_m[j] = min(m0 + row, M - 1);                               // rows past M read a valid row; never stored
-    a_c4[j] = ((lane & 7) ^ ((row >> 1) & 7)) * 4;
-  }
   size_t b_off[B_PW];
 #pragma unroll
   for (int j = 0; j < B_PW; ++j) {
@@ -325,9 +334,12 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
     const bool first = kt < K1;                                  // a k-tile lies in one A operand (K1 % 32 == 0)
     const float* abase = first ? A1 + kt : A2 + (kt - K1);
     const int lda = first ? K1 : K2;
+    // a row of a sparse A1 without this k-tile's relation is not there: the lane reads zeros instead (A2 always is)
+    const bool masked = first && row_mask != nullptr;            // (uniform)
+    const unsigned rbit = masked ? 1u << (kt / kseg) : 0u;
 #pragma unroll
     for (int j = 0; j < A_PW; ++j)
-      glds16(abase + ((size_t)a_m[j] * lda + a_c4[j]), sA + (wave * A_PW + j) * 8 * BK * 4);
+      glds16((!masked || (a_rm[j] & rbit)) ? abase + ((size_t)a_m[j] * lda + a_c4[j]) : a_zero, sA + (wave * A_PW + j) * 8 * BK * 4);
 #pragma unroll
     for (int j = 0; j < B_PW; ++j) {
       glds16(Bh + kt + b_off[j], sBh + (wave * B_PW + j) * 16 * BK * 2);
@@ -766,7 +778,8 @@ __global__ __launch_bounds__(2 * kThreads) void k_gemm_tn_coop(const float* __re
                                                                amax_ref amax1, float a1_mul, amax_ref amax2, amax_ref gmax,
                                                                float* __restrict__ slab,
                                                                float* __restrict__ bias_part,
-                                                               const uint32_t* __restrict__ tile_mask, int kseg) {
+                                                               const uint32_t* __restrict__ tile_mask, int kseg,
+                                                               const uint32_t* __restrict__ row_mask) {
   constexpr int TKC = TN_TKC, RING = 3, A_FLOATS = 32 * TKC, G_FLOATS = 32 * 128;
   constexpr int SLOT_BYTES = (A_FLOATS + G_FLOATS) * 4;          // 32 KB: one fp32 m-tile of both operands
   constexpr int PLANE = 4 * 128 * 16;                            // 8 KB: one fp16 image of one operand's m-tile
@@ -826,14 +839,34 @@ __global__ __launch_bounds__(2 * kThreads) void k_gemm_tn_coop(const float* __re
   const float* a_src = a_first ? A1 + acol : A2 + (acol - K1);
   const int lda = a_first ? K1 : K2;
   const int gcol = min(n0 + d_col, N - 4);                       // as for A: every lane issues every DMA (the counted waits rely on it)
-  auto stage = [&](int mt, int slot) {
+  // A sparse A1 (row_mask): a row without the relation of this lane's columns is not there - the lane reads zeros
+  // instead.  The lane's columns are fixed, the rows change per m-tile: the occupancy words of the wave's four rows
+  // of a tile (two per DMA instruction) are wave-uniform loads, requested when the tile is looked up - a tile ahead
+  // of its stage() in the loop, where the lgkmcnt(0) at its top covers them - and never counted by vmcnt.
+  struct row_words { unsigned w[2 * A_PW]; };
+  const bool a_masked = row_mask != nullptr && a_first;          // (A2 - x - is always read)
+  const unsigned a_bit = a_masked ? 1u << (acol / kseg) : 0u;
+  const float* a_zero = g_zero_row + d_col;
+  auto words_of = [&](int mt) {                                  // mt <= mend + 31: inside the padded words
+    row_words q;
+#pragma unroll
+    for (int i = 0; i < 2 * A_PW; ++i) q.w[i] = 0xffffffffu;
+    if (row_mask) {                                              // (uniform; four consecutive words: one scalar load)
+      const uint32_t* p = row_mask + mt + wave * 2 * A_PW;
+#pragma unroll
+      for (int i = 0; i < 2 * A_PW; ++i) q.w[i] = p[i];
+    }
+    return q;
+  };
+  auto stage = [&](int mt, int slot, const row_words& rw) {
     char* sA = lds + slot * SLOT_BYTES;
     char* sG = sA + A_FLOATS * 4;
 #pragma unroll
     for (int j = 0; j < A_PW; ++j) {
       const int r0 = (wave * A_PW + j) * 2;
       const int m = min(mt + r0 + d_row, M - 1);                 // rows past mend are zeroed by the conversion
-      glds16(a_src + (size_t)m * lda, sA + r0 * TKC * 4);
+      const unsigned word = d_row ? rw.w[2 * j + 1] : rw.w[2 * j];
+      glds16((!a_masked || (word & a_bit)) ? a_src + (size_t)m * lda : a_zero, sA + r0 * TKC * 4);
     }
 #pragma unroll
     for (int j = 0; j < G_PW; ++j) {
@@ -847,11 +880,16 @@ __global__ __launch_bounds__(2 * kThreads) void k_gemm_tn_coop(const float* __re
   // (each tile's DMAs leave as soon as the tile is known: looking a tile up can be a dependent read of the occupancy
   // words, and three of those ahead of the first DMA were a microsecond of the prologue)
   int cur = next_mt(mbeg - 32);
-  stage(cur, 0);
+  row_words rw = words_of(cur);
   int nxt = cur < mend ? next_mt(cur) : mend;
-  stage(nxt, 1);
+  stage(cur, 0, rw);
+  rw = words_of(nxt);
   int aft = nxt < mend ? next_mt(nxt) : mend;
-  stage(aft, 2);
+  stage(nxt, 1, rw);
+  rw = words_of(aft);
+  int fut = aft < mend ? next_mt(aft) : mend;                    // tile t + 3: looked up a tile ahead, with its words
+  stage(aft, 2, rw);
+  rw = words_of(fut);
 
   // operand scales.  Conversion: waves 0-3 convert A - thread (column pair cp, row group mg) - waves 4-7 convert G;
   // a column pair lies in one A operand (K1 even).
@@ -929,8 +967,7 @@ __global__ __launch_bounds__(2 * kThreads) void k_gemm_tn_coop(const float* __re
     if (aft < mend) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(P) : "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    const int fut = aft < mend ? next_mt(aft) : mend;            // tile t + 3 -> the ring slot tile t has just left
-    if (fut < mend) stage(fut, t % RING);
+    if (fut < mend) stage(fut, t % RING, rw);                    // tile t + 3 -> the ring slot tile t has just left
     // fragments of tile t (plane buffer t % 2): per 16-row step A hi / lo and two column blocks of G hi / lo
     const unsigned pl = kPlanes + (unsigned)((t & 1) * PBUF_BYTES);
     f32x4 qa[2][2], qg[2][2][2];                 // [step][hi | lo], [step][block][hi | lo]
@@ -972,6 +1009,8 @@ __global__ __launch_bounds__(2 * kThreads) void k_gemm_tn_coop(const float* __re
     cur = nxt;
     nxt = aft;
     aft = fut;
+    fut = aft < mend ? next_mt(aft) : mend;                      // (its occupancy words land behind the next barrier's wait)
+    rw = words_of(fut);
   }
 
   RGCN_STAMP(2);
@@ -1099,6 +1138,7 @@ struct nt_call {
   int M = 0, N = 0;
   const uint32_t* tile_mask = nullptr;         // relation occupancy of A1's row tiles, `kseg` columns per relation
   int kseg = 0;
+  const uint32_t* row_mask = nullptr;          // A1 is a sparse aggregate: its rows' relation occupancy (behind tile_mask)
   const float *a1_amax = nullptr, *a2_amax = nullptr;   // amax buffers of the A operands; NULL: scanned into scan_slots
   float a1_mul = 1.f, out_scale = 1.f;
   float* c_amax = nullptr;                     // amax buffer that receives max |C|
@@ -1117,7 +1157,7 @@ void nt_launch(const nt_call& c) {
   const dim3 grid((unsigned)ceil_div64(c.M, 64), CHAIN ? 1u : (unsigned)ceil_div64(c.N, 64 * TN));
   k_gemm_nt_split<2, 2, TN, EPI, LO, CHAIN><<<grid, 256, 0, c.stream>>>(
       c.A1, c.K1, c.A2, c.K2, c.Bh, c.Bl, c.b_inv, c.r1, c.a1_mul, c.r2, c.bias, c.mask, c.C, c.M, c.N, c.tile_mask, c.kseg,
-      reinterpret_cast<unsigned*>(c.c_amax), c.fin, c.out_scale, CHAIN ? c.chain : nt_chain{});
+      reinterpret_cast<unsigned*>(c.c_amax), c.fin, c.out_scale, CHAIN ? c.chain : nt_chain{}, c.row_mask);
 }
 
 int launch_nt_split(nt_call c) {
@@ -1128,6 +1168,7 @@ int launch_nt_split(nt_call c) {
   const hub_fin& fin = c.fin;
   if (fin.ptr && fin.d != 64 && fin.d != 128 && fin.d != 256) return RGCN_ERR_UNSUPPORTED;
   if (fin.ptr && (!c.a1_amax || fin.d != c.kseg)) return RGCN_ERR_ARG;   // an unfinished A1 cannot be scanned for its maximum
+  if (c.row_mask && (!c.a1_amax || c.kseg <= 0 || c.kseg % BK != 0)) return RGCN_ERR_ARG;   // nor can a sparse one
   const int K1 = c.K1, K2 = c.K2;
   if (K1 % BK || K2 % BK || K1 + K2 <= 0) return RGCN_ERR_UNSUPPORTED;
   // maxima of the A operands: from their producers, or scanned here (one launch over what is missing)
@@ -1358,7 +1399,7 @@ int rgcn_transform_fwd_split(const float* agg, const float* x, const float* weig
                              float* hub_partial) {
   if (rgcn_layer_bad_dims(N, R, d_in, d_out) || !out) return RGCN_ERR_ARG;
   if (N == 0) return RGCN_OK;
-  if (!agg || !x || !weight) return RGCN_ERR_ARG;
+  if (!agg || !x || !weight || ((half & RGCN_MODE_SPARSE_ROWS) && !tile_mask)) return RGCN_ERR_ARG;
   if (d_in % BK) return RGCN_ERR_UNSUPPORTED;
   if (rgcn_gemm_out_of_range(N, (R + 1) * d_in, d_out)) return RGCN_ERR_UNSUPPORTED;
   nt_call c;
@@ -1368,11 +1409,12 @@ int rgcn_transform_fwd_split(const float* agg, const float* x, const float* weig
                             hub_transposed, hub_partial, stream_, aligned);
   if (rc != RGCN_OK) return rc;
   c.A1 = agg; c.a1_amax = agg_amax; c.a1_mul = agg_amax_mul; c.tile_mask = tile_mask;
+  if (half & RGCN_MODE_SPARSE_ROWS) c.row_mask = tile_mask + rgcn_row_mask_offset(N);
   c.A2 = x; c.a2_amax = x_amax;
   c.Bh = v.Bh_f; c.Bl = v.Bl_f; c.b_inv = v.inv_scale;
   c.bias = bias; c.epi = relu ? EPI_RELU : EPI_NONE;
   c.C = out; c.N = (int)d_out; c.c_amax = out_amax;
-  c.half = half != 0;
+  c.half = (half & 1) != 0;
   return launch_nt_split(c);
 }
 
@@ -1385,7 +1427,7 @@ int rgcn_transform_bwd_input_split(const float* gagg, const float* g, const floa
                                    float out_scale) {
   if (rgcn_layer_bad_dims(N, R, d_in, d_out) || !grad_x || !(out_scale > 0.f)) return RGCN_ERR_ARG;
   if (N == 0) return RGCN_OK;
-  if (!gagg || !g || !weight) return RGCN_ERR_ARG;
+  if (!gagg || !g || !weight || ((half & RGCN_MODE_SPARSE_ROWS) && !tile_mask)) return RGCN_ERR_ARG;
   if (d_out % BK) return RGCN_ERR_UNSUPPORTED;
   if (rgcn_gemm_out_of_range(N, (R + 1) * d_out, d_in)) return RGCN_ERR_UNSUPPORTED;
   nt_call c;
@@ -1395,11 +1437,12 @@ int rgcn_transform_bwd_input_split(const float* gagg, const float* g, const floa
                             hub_transposed, hub_partial, stream_, aligned);
   if (rc != RGCN_OK) return rc;
   c.A1 = gagg; c.a1_amax = gagg_amax; c.a1_mul = gagg_amax_mul; c.tile_mask = tile_mask;
+  if (half & RGCN_MODE_SPARSE_ROWS) c.row_mask = tile_mask + rgcn_row_mask_offset(N);
   c.A2 = g; c.a2_amax = g_amax;
   c.Bh = v.Bh_b; c.Bl = v.Bl_b; c.b_inv = v.inv_scale;
   c.mask = relu_mask; c.epi = relu_mask ? EPI_MASK : EPI_NONE;
   c.C = grad_x; c.N = (int)d_in; c.c_amax = grad_x_amax; c.out_scale = out_scale;
-  c.half = half != 0;
+  c.half = (half & 1) != 0;
   return launch_nt_split(c);
 }
 
@@ -1422,6 +1465,9 @@ int rgcn_transform_bwd_input_chain_split(const float* gagg, const float* g, cons
   if (!rgcn_transform_bwd_input_chain_supported(R, d_in, d_out, R1, d_in1)) return RGCN_ERR_UNSUPPORTED;
   if (N == 0) return RGCN_OK;
   if (!gagg || !g || !weight || !gagg_amax || !g_amax) return RGCN_ERR_ARG;
+  const bool sparse = (has_root1 & RGCN_MODE_SPARSE_ROWS) != 0;
+  has_root1 &= 1;
+  if (sparse && !tile_mask) return RGCN_ERR_ARG;
   if (rgcn_gemm_out_of_range(N, (R + 1) * d_out, (R1 + 1) * d_in1)) return RGCN_ERR_UNSUPPORTED;
   nt_call c;
   PackedWeights v;
@@ -1432,6 +1478,7 @@ int rgcn_transform_bwd_input_chain_split(const float* gagg, const float* g, cons
   if (rc != RGCN_OK) return rc;
   const PackedWeights v1 = packed_view(const_cast<void*>(packed1), R1, d_in1, d_in);     // conv1: d_out1 = d_in of conv2
   c.A1 = gagg; c.a1_amax = gagg_amax; c.a1_mul = gagg_amax_mul; c.tile_mask = tile_mask;
+  if (sparse) c.row_mask = tile_mask + rgcn_row_mask_offset(N);
   c.A2 = g; c.a2_amax = g_amax;
   c.Bh = v.Bh_b; c.Bl = v.Bl_b; c.b_inv = v.inv_scale;
   c.mask = relu_mask; c.epi = relu_mask ? EPI_MASK : EPI_NONE;
@@ -1480,6 +1527,7 @@ int rgcn_transform_bwd_params_split_begin(const float* agg, const float* x, cons
   // (64: a 64-column half of a kc tile lies in one operand / relation)
   const int rc = rgcn_params_begin_check(job, agg, x, g, N, R, d_in, d_out, grad_weight, 64);
   if (rc != RGCN_OK) return rc;
+  if ((half & RGCN_MODE_SPARSE_ROWS) && (!tile_mask || !agg_amax)) return RGCN_ERR_ARG;   // a sparse agg cannot be scanned
   // the slab layout is sized for (R+1)*d_in rows; with grad_root == NULL only K1 are used
   rgcn_tn_split p = rgcn_tn_plan(N, (R + 1) * d_in, d_out, TN_TKC, kTnBlocks);
   const rgcn_slab_layout lay = rgcn_slab_layout_of(p, (R + 1) * d_in, d_out);
@@ -1506,10 +1554,11 @@ int rgcn_transform_bwd_params_split_begin(const float* agg, const float* x, cons
   dim3 grid((unsigned)(p.kc_tiles * p.n_tiles), (unsigned)p.splits);
   const uint32_t* tmask = (d_in % 64 == 0) ? tile_mask : nullptr;
   float* bp = grad_bias ? bias_part : nullptr;
+  const uint32_t* rmask = (half & RGCN_MODE_SPARSE_ROWS) ? tile_mask + rgcn_row_mask_offset(N) : nullptr;
 #define RGCN_TN_LAUNCH(KERNEL, LO_)                                                                              \
   KERNEL<LO_><<<grid, 2 * kThreads, 0, stream>>>(agg, K1, x, K2, g, (int)N, (int)d_out, p.n_tiles, p.rows_per_split, \
-                                                 r1, a1_mul, r2, rg, slab, bp, tmask, (int)d_in)
-  if (half) RGCN_TN_LAUNCH(k_gemm_tn_coop, false);
+                                                 r1, a1_mul, r2, rg, slab, bp, tmask, (int)d_in, rmask)
+  if (half & 1) RGCN_TN_LAUNCH(k_gemm_tn_coop, false);
   else RGCN_TN_LAUNCH(k_gemm_tn_coop, true);
 #undef RGCN_TN_LAUNCH
   RGCN_HIP_TRY(hipGetLastError());

@@ -540,6 +540,17 @@ class BucketedGraph:
             cache[transposed] = _L().rgcn_graph_tile_mask(handle, int(transposed), None) or None
         return cache[transposed]
 
+    def row_mask_ptr(self, transposed: bool) -> Optional[int]:
+        """device pointer (as int) of the relation occupancy ROW BY ROW (bit r of word i: segment (i, r) has an edge;
+        ``include/rgcn_sparse.h``), or None (more than 32 relations, no rows).  What a sparse aggregate rests on."""
+        if self.bipartite and transposed:
+            raise ValueError("a shard structure has one direction only (transposed=False)")
+        handle = self.handle                                         # raises once the graph is destroyed
+        cache = self.__dict__.setdefault("_row_mask_ptrs", {})      # fixed for the life of the handle
+        if transposed not in cache:
+            cache[transposed] = _L().rgcn_graph_row_mask(handle, int(transposed), None) or None
+        return cache[transposed]
+
     def workspace_bytes(self, transposed: bool, d: int) -> int:
         """bytes of partial-sum workspace ``aggregate`` needs for rows of width d (memoised)"""
         handle = self.handle
@@ -832,10 +843,13 @@ class PendingParamGrads:
 
 
 def _gather(graph: BucketedGraph, x: torch.Tensor, transposed: bool, tail: Optional[PendingParamGrads],
-            amax_out: Optional[torch.Tensor], out: Optional[torch.Tensor], levels=(0, -1)):
+            amax_out: Optional[torch.Tensor], out: Optional[torch.Tensor], levels=(0, -1), sparse: bool = False):
     """The one ``rgcn_aggregate_ex`` call behind ``aggregate`` and ``aggregate_deferred``: launches ``levels`` =
-    [first, last) of the gather (last < 0: all) -> (agg, workspace).  A pending ``tail`` goes along as the call's job."""
+    [first, last) of the gather (last < 0: all) -> (agg, workspace).  A pending ``tail`` goes along as the call's job.
+    ``sparse``: the rows of segments without an edge are not written (``aggregate_sparse``)."""
     half_in = isinstance(x, torch.Tensor) and x.dtype == torch.float16
+    if sparse and (half_in or graph.row_mask_ptr(transposed) is None or x.dim() != 2 or x.size(1) > 256):
+        raise ValueError("a sparse aggregate needs an fp32 table of rows up to 256 wide and a structure of <= 32 relations")
     _need_gpu("x", x, torch.float16 if half_in else torch.float32)
     if graph.bipartite and transposed:
         raise ValueError("a shard structure has one direction only (transposed=False)")
@@ -870,7 +884,8 @@ def _gather(graph: BucketedGraph, x: torch.Tensor, transposed: bool, tail: Optio
             if measure and first == 0:
                 beg, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 beg.record()
-            rc = rc or lib.rgcn_aggregate_ex(graph.handle, int(transposed), _ptr(x), int(half_in), d, _ptr(out), _ptr(ws),
+            rc = rc or lib.rgcn_aggregate_ex(graph.handle, int(transposed), _ptr(x),
+                                             int(half_in) | (_lib.MODE_SPARSE_ROWS if sparse else 0), d, _ptr(out), _ptr(ws),
                                              nbytes, first, last, ctypes.byref(job) if job is not None else None,
                                              _ptr(amax_out), _stream())
             if measure and first == 0:
@@ -895,6 +910,23 @@ def aggregate(graph: BucketedGraph, x: torch.Tensor, transposed: bool = False,
     buffer, fp32 table only): receives ``max |result|``, the scale the split-precision
     transforms need for this operand."""
     return _gather(graph, x, transposed, tail, amax_out, out)[0]
+
+
+def aggregate_sparse(graph: BucketedGraph, x: torch.Tensor, transposed: bool = False,
+                     tail: Optional[PendingParamGrads] = None, amax_out: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None, defer: bool = False):
+    """``aggregate`` / ``aggregate_deferred`` (``defer``) for an aggregate that stays inside a training pass -> ``(agg,
+    hubs | None)``: the rows of the (node, relation) segments without an edge - half of them on a typed knowledge
+    graph - are NOT written, they hold whatever the buffer held.  Only the split-precision transforms called with
+    ``sparse=True`` and the same ``graph`` may read such an aggregate: they never load those rows
+    (``graph.row_mask_ptr``).  Live rows and ``amax_out`` are the bits ``aggregate`` gives."""
+    if defer:
+        d = x.size(1) if x.dim() == 2 else 0
+        if (x.dtype == torch.float32 and GATHER_EVENTS is None and graph.num_levels(transposed) == 2
+                and graph.deferrable(transposed, d)):
+            agg, ws = _gather(graph, x, transposed, tail, amax_out, out, levels=(0, 1), sparse=True)
+            return agg, DeferredHubs(graph, transposed, ws)
+    return _gather(graph, x, transposed, tail, amax_out, out, sparse=True)[0], None
 
 
 def fused_bwd_supported(num_relations: int, d_in: int, d_out: int) -> bool:
@@ -1098,11 +1130,23 @@ def _mask_for(graph: Optional[BucketedGraph], transposed: bool, n: int, r: int) 
     return graph.tile_mask_ptr(transposed and not graph.bipartite)
 
 
+def _sparse_bit(sparse: bool, graph: Optional[BucketedGraph], transposed: bool, split, amax) -> int:
+    """the option bit of a split transform whose aggregate operand is sparse (``aggregate_sparse``): the kernel then
+    never loads the rows ``graph.row_mask_ptr`` says are not there"""
+    if not sparse:
+        return 0
+    if not split or graph is None or graph.bipartite or graph.row_mask_ptr(transposed) is None or amax is None:
+        raise ValueError("a sparse aggregate needs the split-precision transform, the graph it was gathered over "
+                         "(<= 32 relations, not a shard) and the operand's amax buffer (it cannot be scanned)")
+    return _lib.MODE_SPARSE_ROWS
+
+
 def transform_fwd(agg, x, weight, root=None, bias=None, relu: bool = False,
                   graph: Optional[BucketedGraph] = None, half: bool = False, amax=None,
                   amax_out: Optional[torch.Tensor] = None, precision: Optional[str] = None,
                   packed: Optional[SplitWeights] = None, amax_mul: float = 1.0,
-                  out: Optional[torch.Tensor] = None, hubs: Optional[DeferredHubs] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, hubs: Optional[DeferredHubs] = None,
+                  sparse: bool = False) -> torch.Tensor:
     """``sum_r agg[:, r] @ weight[r] + x @ root + bias`` as one fp32-MFMA GEMM; ``relu``
     fuses the activation that follows conv1 (``rgcn.py:124``) into the epilogue.  ``graph``
     (the structure ``agg`` was aggregated over) lets the kernel skip the k-tiles of relations
@@ -1117,7 +1161,8 @@ def transform_fwd(agg, x, weight, root=None, bias=None, relu: bool = False,
     the bound ``amax_mul * value(agg_amax)`` - pass the buffer of the table ``agg`` was gathered from
     and the structure's ``weight_bound`` (a mean of rows cannot exceed the table's maximum: 1) - and
     ``x`` by its own maximum; a missing buffer is scanned here (one more pass over that operand).
-    ``amax_out`` (a ZEROED amax buffer): receives ``max |out|``."""
+    ``amax_out`` (a ZEROED amax buffer): receives ``max |out|``.  ``sparse``: ``agg`` came from
+    ``aggregate_sparse`` over ``graph`` (split precision only)."""
     n, r, d_in, d_out = _check_layer(agg, x, weight, root, bias)
     lib = _L()
     _check_amax("amax_out", amax_out, x.device)
@@ -1136,6 +1181,7 @@ def transform_fwd(agg, x, weight, root=None, bias=None, relu: bool = False,
             raise ValueError("packed does not belong to these weights")
     elif hubs is not None:
         raise ValueError("deferred hub tails need the split-precision transform (finish them with aggregate instead)")
+    mode = _sparse_bit(sparse, graph, False, split, _pair(amax, 2)[0] if split else None)
     k = (r + (root is not None)) * d_in
     with _on(x.device):
         if out is None:
@@ -1148,7 +1194,7 @@ def transform_fwd(agg, x, weight, root=None, bias=None, relu: bool = False,
                 rc = lib.rgcn_transform_fwd_split(_ptr(agg), _ptr(x), _ptr(weight), _ptr(root),
                                                   _ptr(packed.buf) if packed is not None else None, _ptr(bias),
                                                   int(relu), _mask_for(graph, False, n, r), n, r, d_in, d_out,
-                                                  _ptr(a1), float(amax_mul), _ptr(a2), int(split == 2), _ptr(out),
+                                                  _ptr(a1), float(amax_mul), _ptr(a2), int(split == 2) | mode, _ptr(out),
                                                   _ptr(amax_out), _ptr(ws), nbytes, _stream(), *_hub_args(hubs, n, r))
         elif half and d_in % 32 == 0:
             name = "rgcn_transform_fwd_f16"
@@ -1173,7 +1219,7 @@ def transform_bwd_input(gagg, g, weight, root=None, relu_mask=None,
                         graph: Optional[BucketedGraph] = None, amax=None, amax_out: Optional[torch.Tensor] = None,
                         precision: Optional[str] = None, packed: Optional[SplitWeights] = None,
                         amax_mul: float = 1.0, hubs: Optional[DeferredHubs] = None,
-                        out_scale: float = 1.0) -> torch.Tensor:
+                        out_scale: float = 1.0, sparse: bool = False) -> torch.Tensor:
     """``grad_x = out_scale * (sum_r gagg[:, r] @ weight[r]^T + g @ root^T)``; with ``relu_mask`` (the
     layer's input, when that input is the output of a fused-ReLU layer) the result is
     additionally multiplied by ``relu_mask > 0``.  ``out_scale`` (the ``1 / (1 - p)`` of a dropout whose
@@ -1185,6 +1231,7 @@ def transform_bwd_input(gagg, g, weight, root=None, relu_mask=None,
     if d_in % 4 or d_out % 4:
         raise ValueError("in/out channels must be multiples of 4")
     split = _use_split(precision, d_out, 32)
+    mode = _sparse_bit(sparse, graph, True, split and n > 0, _pair(amax, 2)[0])
     if split and n > 0:
         a1, a2 = _pair(amax, 2)
         _check_amax("gagg_amax", a1, g.device)
@@ -1199,8 +1246,8 @@ def transform_bwd_input(gagg, g, weight, root=None, relu_mask=None,
                 rc = lib.rgcn_transform_bwd_input_split(_ptr(gagg), _ptr(g), _ptr(weight), _ptr(root),
                                                         _ptr(packed.buf) if packed is not None else None,
                                                         _ptr(relu_mask), _mask_for(graph, True, n, r), n, r, d_in,
-                                                        d_out, _ptr(a1), float(amax_mul), _ptr(a2), int(split == 2),
-                                                        _ptr(gx), _ptr(amax_out), _ptr(ws), nbytes, _stream(),
+                                                        d_out, _ptr(a1), float(amax_mul), _ptr(a2),
+                                                        int(split == 2) | mode, _ptr(gx), _ptr(amax_out), _ptr(ws), nbytes, _stream(),
                                                         *_hub_args(hubs, n, r), float(out_scale))
         _lib.check(rc, "rgcn_transform_bwd_input_split")
         return gx
@@ -1231,7 +1278,8 @@ def chain_supported(weight: torch.Tensor, weight1: torch.Tensor) -> bool:
 
 def transform_bwd_input_chain(gagg, g, weight, root, relu_mask, packed: SplitWeights, packed1: SplitWeights,
                               graph: Optional[BucketedGraph] = None, amax=None, amax_out: Optional[torch.Tensor] = None,
-                              amax_mul: float = 1.0, hubs: Optional[DeferredHubs] = None, out_scale: float = 1.0):
+                              amax_mul: float = 1.0, hubs: Optional[DeferredHubs] = None, out_scale: float = 1.0,
+                              sparse: bool = False):
     """``(gz, T)``: ``gz = transform_bwd_input(gagg, g, weight, root, relu_mask, ...)`` - the same bits - and
     ``T = transform_first(gz, packed1)``, conv1's transform-first product (``[N, (R1 + 1) * d_in1]``), computed by the
     SAME launch: every workgroup keeps its 64-row tile of ``gz`` as fp16 hi / lo fragments and multiplies it by conv1's
@@ -1246,6 +1294,7 @@ def transform_bwd_input_chain(gagg, g, weight, root, relu_mask, packed: SplitWei
     _check_amax("amax_out", amax_out, g.device)
     if a1 is None or a2 is None:
         raise ValueError("the chained transform needs the operand maxima (amax=)")
+    mode = _sparse_bit(sparse, graph, True, True, a1)
     lib = _L()
     cols = (r1 + (1 if packed1.has_root else 0)) * d_in1
     with _on(g.device):
@@ -1259,7 +1308,7 @@ def transform_bwd_input_chain(gagg, g, weight, root, relu_mask, packed: SplitWei
                                                           _ptr(relu_mask), _mask_for(graph, True, n, r), n, r, d_in, d_out,
                                                           _ptr(a1), float(amax_mul), _ptr(a2), _ptr(gz), _ptr(amax_out), _ptr(ws),
                                                           nbytes, _stream(), *_hub_args(hubs, n, r), float(out_scale),
-                                                          _ptr(packed1.buf), int(packed1.has_root), r1, d_in1, _ptr(t))
+                                                          _ptr(packed1.buf), int(packed1.has_root) | mode, r1, d_in1, _ptr(t))
     _lib.check(rc, "rgcn_transform_bwd_input_chain_split")
     return gz, t
 
@@ -1291,7 +1340,7 @@ def transform_first(g: torch.Tensor, packed: SplitWeights, amax: Optional[torch.
 
 def transform_bwd_params(agg, x, g, num_relations: int, want_root: bool = True, want_bias: bool = True,
                          graph: Optional[BucketedGraph] = None, defer: bool = False, amax=None,
-                         precision: Optional[str] = None, amax_mul: float = 1.0):
+                         precision: Optional[str] = None, amax_mul: float = 1.0, sparse: bool = False):
     """``(grad_weight[R, d_in, d_out], grad_root | None, grad_bias | None)``; with ``defer=True`` a
     ``PendingParamGrads`` whose reduction the caller attaches to the next gather (or finishes).
     Split precision: ``amax = (agg_amax, x_amax, g_amax)``, any of them None (scanned here)."""
@@ -1309,6 +1358,7 @@ def transform_bwd_params(agg, x, g, num_relations: int, want_root: bool = True, 
         groot = _empty(d_in, d_out, dtype=torch.float32, device=x.device) if want_root else None
         gbias = _empty(d_out, dtype=torch.float32, device=x.device) if want_bias else None
         split = _use_split(precision, d_in, 64)
+        mode = _sparse_bit(sparse, graph, False, split and n > 0, _pair(amax, 3)[0])
         if split and n > 0:
             a1, a2, a3 = _pair(amax, 3)
             for nm, t in (("agg_amax", a1), ("x_amax", a2), ("g_amax", a3)):
@@ -1320,7 +1370,7 @@ def transform_bwd_params(agg, x, g, num_relations: int, want_root: bool = True, 
                 rc = lib.rgcn_transform_bwd_params_split_begin(_ptr(agg), _ptr(x), _ptr(g),
                                                                _mask_for(graph, False, n, r), n, r, d_in, d_out,
                                                                _ptr(a1), float(amax_mul), _ptr(a2), _ptr(a3),
-                                                               int(split == 2), _ptr(gw), _ptr(groot),
+                                                               int(split == 2) | mode, _ptr(gw), _ptr(groot),
                                                                _ptr(gbias), _ptr(ws), nbytes, _stream(),
                                                                ctypes.byref(job))
             _lib.check(rc, "rgcn_transform_bwd_params_split_begin")
@@ -3242,7 +3292,7 @@ class _NotRecordable(Exception):
 
 
 _SEQ_INDEX = {name: i for i, name in enumerate(_lib.SEQ_FUNCTIONS)}
-_SEQ_PURE = ("rgcn_graph_tile_mask", "rgcn_graph_num_levels", "rgcn_graph_weight_bound", "rgcn_aggregate_deferrable",
+_SEQ_PURE = ("rgcn_graph_tile_mask", "rgcn_graph_row_mask", "rgcn_graph_num_levels", "rgcn_graph_weight_bound", "rgcn_aggregate_deferrable",
              "rgcn_graph_num_edges", "rgcn_graph_num_nodes", "rgcn_graph_num_relations", "rgcn_abi_version", "rgcn_strerror")
 REGIONS = True      # False: always through the wrappers (tests, tools/host_profile.py)
 
