@@ -236,6 +236,17 @@ COMPLEX_PROTOTYPES = {
     "rgcn_complex_query": (c_int, [c_int, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P]),
 }
 
+# include/rgcn_softmax.h, one to one: the 1-vs-all softmax loss over every candidate (csrc/softmax_loss.hip; not part of
+# rgcn_hip.h, never forwarded by rgcn_sequence_run - the softmax step runs eagerly, outside any recorded Region)
+SOFTMAX_PROTOTYPES = {
+    "rgcn_softmax_workspace_bytes": (c_size_t, [_I64, _I64, _I64, _I64]),
+    "rgcn_softmax_lse": (c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _I64,     # operands, masks, sizes, slices
+                                 _P, _P, _P, _P, _P, _P, c_size_t, _P]),                   # outputs, workspace, stream
+    "rgcn_softmax_grad": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64,
+                                  _P, _P, c_int, _P, c_size_t, _P]),                       # dq, dE, accumulate, workspace, stream
+}
+SOFTMAX_MAX_D = 256              # widest row the backward keeps in accumulators (csrc/softmax_loss.hip)
+
 # include/rgcn_sparse.h, one to one: the row-granular occupancy behind sparse aggregates (csrc/rgcn_graph.hip; queries,
 # never forwarded by rgcn_sequence_run).  MODE_SPARSE_ROWS: RGCN_MODE_SPARSE_ROWS of rgcn_hip.h, the bit a training pass
 # sets in the `int` option word of its gathers and of the split transforms that read their aggregates.
@@ -266,7 +277,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise RGCNLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + list(COMPLEX_PROTOTYPES.items()) + list(SPARSE_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + list(COMPLEX_PROTOTYPES.items()) + list(SPARSE_PROTOTYPES.items()) + list(SOFTMAX_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -219,6 +219,60 @@ class _ComplExBCEFunction(torch.autograd.Function):
         return gh, None, (None if shared else gt), None, gr, None, None, None
 
 
+class _SoftmaxLossFunction(torch.autograd.Function):
+    """Per-sample 1-vs-all softmax loss of one side, ``(loss [B], hit [B])``: ``loss[b] = logsumexp over the eligible
+    candidates of <q[b], E[n]>`` minus the target's score (``ops.softmax_lse_filtered``: no ``[B, N]`` matrix), with the
+    query rows of the decoder - ``anchor * rel`` (DistMult) or ``ops.complex_query`` (ComplEx; the head side carries the
+    conjugate).  The backward is ``ops.softmax_grad_filtered``: ``demb`` is the candidates' share of the gradient of the
+    node embeddings, and ``dq`` goes through the query by the backward entry points that exist - the query is the
+    score's gradient with respect to the free end, so ``sum_b <q(x_b, r_b), dq_b>`` is the decoder's score with ``dq``
+    as an un-indexed operand and ``grad_scores = 1``: ``distmult_bwd`` / ``complex_bwd`` with that operand's gradient
+    left out scatter ``r o dq`` into the anchors' rows and ``x o dq`` into the relations' in their deterministic
+    sample order.  ``r_idx`` None: ``r`` holds one (dropped-out) relation row per sample."""
+
+    @staticmethod
+    def forward(ctx, emb, r, r_idx, rel_ids, anchor_idx, target_idx, decoder, side, known, allow, query_class,
+                max_mask_bytes):
+        emb, r = emb.contiguous(), r.contiguous()
+        anchor_idx, target_idx = anchor_idx.contiguous(), target_idx.contiguous()
+        r_idx = r_idx.contiguous() if r_idx is not None else None
+        if decoder == "complex":
+            q = ops.complex_query(emb, anchor_idx, r, r_idx, side)
+        else:
+            q = (emb[anchor_idx] * (r[r_idx] if r_idx is not None else r)).contiguous()
+        rel_ids = rel_ids.contiguous()                         # the samples' relations: what the known triples are keyed by
+        lse, _, _, loss, hit = ops.softmax_lse_filtered(q, emb, target_idx, known, side, anchor_idx, rel_ids, allow,
+                                                        query_class, max_mask_bytes)
+        ctx.save_for_backward(emb, r, r_idx, rel_ids, anchor_idx, target_idx, q, lse, allow, query_class)
+        ctx.decoder, ctx.side, ctx.known, ctx.max_mask_bytes = decoder, side, known, max_mask_bytes
+        ctx.mark_non_differentiable(hit)
+        ctx.set_materialize_grads(False)
+        return loss, hit
+
+    @staticmethod
+    def backward(ctx, g, _g_hit):
+        emb, r, r_idx, rel_ids, anchor_idx, target_idx, q, lse, allow, query_class = ctx.saved_tensors
+        need_emb, need_r = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g is None or not (need_emb or need_r):
+            return (None,) * 12
+        batch = anchor_idx.size(0)
+        dq, demb = ops.softmax_grad_filtered(g.contiguous(), q, emb, target_idx, lse, ctx.known, ctx.side, anchor_idx,
+                                             rel_ids, allow, query_class, ctx.max_mask_bytes, need_dq=True,
+                                             need_demb=need_emb)
+        ones = torch.ones(batch, dtype=torch.float32, device=emb.device)
+        gx = torch.empty_like(emb) if need_emb else None         # the anchors' rows; cleared by the backward's first launch
+        gr = torch.empty_like(r) if need_r else None
+        if ctx.decoder == "complex" and ctx.side == "head":
+            ops.complex_bwd(ones, dq, None, emb, anchor_idx, r, r_idx, batch, None, gx, gr, zero_tables=True)
+        elif ctx.decoder == "complex":
+            ops.complex_bwd(ones, emb, anchor_idx, dq, None, r, r_idx, batch, gx, None, gr, zero_tables=True)
+        else:
+            ops.distmult_bwd(ones, emb, anchor_idx, dq, None, r, r_idx, batch, gx, None, gr, zero_tables=True)
+        if need_emb:
+            demb.add_(gx)
+        return (demb, gr) + (None,) * 10
+
+
 def complex_query_rows(x: Tensor, rel_rows: Tensor, side: str) -> Tensor:
     """``ops.complex_query`` on gathered rows, in torch ops - the differentiable form (``score_all_tails`` when a
     gradient is required); same grouping as the kernel"""
@@ -227,6 +281,17 @@ def complex_query_rows(x: Tensor, rel_rows: Tensor, side: str) -> Tensor:
     if side == "tail":
         return torch.cat([x_re * r_re - x_im * r_im, x_re * r_im + x_im * r_re], dim=1)
     return torch.cat([r_re * x_re + r_im * x_im, r_re * x_im - r_im * x_re], dim=1)
+
+
+def known_mask(known, side: str, anchor_idx: Tensor, rel_idx: Tensor) -> Tensor:
+    """bool ``[B, N]``: entry ``(b, n)`` set iff ``(anchor[b], relation[b], n)`` is a known triple of ``side`` - the dense
+    form of ``KnownTriples.exclude_bits``, in torch ops on whatever device the structure is on"""
+    keys, ptr, ids = known.csr(side)
+    seg = known.segments(side, anchor_idx.to(keys.device), rel_idx.to(keys.device))
+    mask = torch.zeros(seg.numel(), known.num_nodes, dtype=torch.bool, device=keys.device)
+    for b in torch.nonzero(seg >= 0).view(-1).tolist():
+        mask[b, ids[int(ptr[seg[b]]):int(ptr[seg[b] + 1])]] = True
+    return mask.to(anchor_idx.device)
 
 
 DECODERS = ("distmult", "complex")
@@ -293,6 +358,71 @@ class LinkPredictor(nn.Module):
         r, r_idx = self._relation_operand(relation_types)
         fn = _ComplExBCEFunction if self.decoder == "complex" else _DistMultBCEFunction
         return fn.apply(node_embeddings, head_indices, node_embeddings, tail_indices, r, r_idx, labels, stats)
+
+    def softmax_loss(self, node_embeddings: Tensor, head_indices: Tensor, tail_indices: Tensor,
+                     relation_types: Tensor, *, sides=("tail", "head"), known: Optional["ops.KnownTriples"] = None,
+                     node_class: Optional[Tensor] = None, stats=None, max_mask_bytes: int = 256 << 20):
+        """``(mean loss, hits)``: the 1-vs-all softmax cross-entropy of the true entity against EVERY candidate - what
+        ``rank_tails`` / ``rank_heads`` ask afterwards, as a loss.  Per side of ``sides`` (``"tail"``: the tails of
+        ``(head, relation, ?)`` with the true tail as target; ``"head"``: the heads of ``(?, relation, tail)``) and
+        sample, ``loss = logsumexp over the eligible candidates of score - score of the target``; the mean is over sides
+        and samples, ``hits`` (int64 scalar) counts the samples whose target is a best eligible candidate.  Eligible: every
+        entity, minus - with ``known`` - the other known answers of the query (the filtered protocol), restricted - with
+        ``node_class`` (int ``[N]``) - to the target's class (the type-constrained protocol); the target itself always.
+        ``stats``: ``(loss_sum, correct)`` device tensors the step's sums are added to.
+
+        On the GPU this is one fused pass per side that never stores the ``[B, N]`` scores (``ops.softmax_lse``) and a
+        backward that recomputes them (``ops.softmax_grad``).  On CPU tensors it is the torch expression below, which is
+        the specification."""
+        if isinstance(sides, str):
+            sides = (sides,)
+        if not sides or any(s not in ("tail", "head") for s in sides):
+            raise ValueError("sides must name 'tail', 'head' or both")
+        if not node_embeddings.is_cuda:
+            losses, hits = zip(*(self._softmax_loss_torch(node_embeddings, head_indices, tail_indices, relation_types, s,
+                                                          known, node_class) for s in sides))
+        else:
+            r, r_idx = self._relation_operand(relation_types)
+            allow = cls = None
+            if node_class is not None:
+                cls, allow = self._allow_rows(node_class, node_embeddings)
+            losses, hits = [], []
+            for s in sides:
+                anchor, target = (head_indices, tail_indices) if s == "tail" else (tail_indices, head_indices)
+                query_class = cls[target].contiguous() if cls is not None else None
+                loss, hit = _SoftmaxLossFunction.apply(node_embeddings, r, r_idx, relation_types, anchor, target, self.decoder, s, known,
+                                                       allow, query_class, max_mask_bytes)
+                losses.append(loss)
+                hits.append(hit)
+        loss = torch.cat(losses).mean()
+        hit_count = torch.cat([h.reshape(-1) for h in hits]).to(torch.int64).sum()
+        if stats is not None:
+            with torch.no_grad():
+                stats[0].add_(torch.cat(losses).sum().to(stats[0].dtype))
+                stats[1].add_(hit_count.to(stats[1].dtype))
+        return loss, hit_count
+
+    def _softmax_loss_torch(self, emb, head_indices, tail_indices, relation_types, side, known, node_class):
+        """the specification of one side: ``(loss [B], hit [B])`` in torch ops, any dtype, differentiable"""
+        anchor, target = (head_indices, tail_indices) if side == "tail" else (tail_indices, head_indices)
+        r, r_idx = self._relation_operand(relation_types)
+        rel_rows = (r[r_idx] if r_idx is not None else r).to(emb.dtype)
+        x = emb[anchor]
+        q = complex_query_rows(x, rel_rows, side) if self.decoder == "complex" else x * rel_rows
+        scores = q @ emb.t()                                                     # [B, N]
+        b, n = scores.shape
+        rows = torch.arange(b, device=emb.device)
+        eligible = torch.ones(b, n, dtype=torch.bool, device=emb.device)
+        if node_class is not None:
+            cls = node_class.to(emb.device)
+            eligible &= (cls[None, :] == cls[target][:, None]) & (cls[target] >= 0)[:, None]
+        if known is not None:
+            eligible &= ~known_mask(known, side, anchor, relation_types)
+        eligible[rows, target] = True                                            # the target always counts
+        masked = scores.masked_fill(~eligible, float("-inf"))
+        true_score = scores[rows, target]
+        loss = torch.logsumexp(masked, dim=1) - true_score
+        return loss, true_score >= masked.max(dim=1).values
 
     def _query(self, side: str, anchor_embeddings: Tensor, relation_types: Tensor) -> Tensor:
         """the query rows ``q`` with ``score = <q[b], E[n]>`` for the candidates of ``side``.  DistMult: ``anchor * rel`` on

@@ -94,6 +94,14 @@ class DrugDiseaseModel(nn.Module):
         node_embeddings = self.encoder(edge_index, edge_type)
         return self.decoder.bce_loss(node_embeddings, head_indices, tail_indices, relation_types, labels, stats)
 
+    def softmax_loss(self, edge_index: Tensor, edge_type: Tensor, head_indices: Tensor, tail_indices: Tensor,
+                     relation_types: Tensor, **kwargs):
+        """``(mean loss, hits)``: the 1-vs-all softmax loss of the positives against every entity, the twin of
+        ``bce_loss``; ``kwargs``: ``sides=``, ``known=``, ``node_class=``, ``stats=``, ``max_mask_bytes=`` of
+        ``LinkPredictor.softmax_loss``."""
+        node_embeddings = self.encoder(edge_index, edge_type)
+        return self.decoder.softmax_loss(node_embeddings, head_indices, tail_indices, relation_types, **kwargs)
+
     def predict(self, edge_index: Tensor, edge_type: Tensor, head_indices: Tensor,
                 tail_indices: Tensor, relation_types: Tensor) -> Tensor:
         self.eval()

@@ -2184,6 +2184,189 @@ def distmult_topk_filtered(q: torch.Tensor, emb: torch.Tensor, k: int, known: Op
     return ids, scores
 
 
+# ----------------------------------------------------------------------------------
+# 1-vs-all softmax loss over every candidate (include/rgcn_softmax.h, csrc/softmax_loss.hip): the log-sum-exp of the
+# ranking pass's scores under the ranking pass's masks, and its two gradients, without the [B, N] score matrix.
+# ----------------------------------------------------------------------------------
+SOFTMAX_MAX_D = _lib.SOFTMAX_MAX_D
+
+
+def _softmax_check(q, emb, target, allow, query_class, exclude, slices: int, g=None, lse=None):
+    """the argument checks of ``softmax_lse`` / ``softmax_grad``, shapes before devices (a wrong shape is a ``ValueError``
+    wherever the tensors live) -> (B, N, d, classes)"""
+    if not all(isinstance(t, torch.Tensor) for t in (q, emb, target)):
+        raise TypeError("q, emb and target must be torch.Tensors")
+    if q.dim() != 2 or emb.dim() != 2 or emb.size(1) != q.size(1) or emb.size(0) == 0 or target.shape != (q.size(0),):
+        raise ValueError("q [B, d], emb [N, d] (N > 0), target [B] expected")
+    b, d = q.shape
+    if d % 32:
+        raise ValueError(f"embedding dim must be a multiple of 32 for the fused softmax kernels, got {d}")
+    if d > SOFTMAX_MAX_D:
+        raise ValueError(f"embedding dim must be at most {SOFTMAX_MAX_D} (the backward keeps a 64 x d output tile in "
+                         f"accumulators), got {d}")
+    if int(slices) < 0:
+        raise ValueError("slices must be >= 0 (0: chosen from the batch and the number of entities)")
+    w, classes = mask_words(emb.size(0)), 0
+    if (allow is None) != (query_class is None):
+        raise ValueError("allow and query_class go together")
+    if allow is not None:
+        classes = allow.size(0) if allow.dim() == 2 else 0
+        if allow.dim() != 2 or allow.size(1) != w or classes == 0 or query_class.shape != (b,):
+            raise ValueError(f"allow [C, {w}] and query_class [B] expected")
+    if exclude is not None and exclude.shape != (b, w):
+        raise ValueError(f"exclude [{b}, {w}] expected")
+    for name, t in (("g", g), ("lse", lse)):
+        if t is not None and t.shape != (b,):
+            raise ValueError(f"{name} [{b}] expected")
+    _need_gpu("q", q, torch.float32)
+    _need_gpu("emb", emb, torch.float32)
+    _need_gpu("target", target, torch.int64)
+    if allow is not None:
+        _need_gpu("allow", allow, torch.int32)
+        _need_gpu("query_class", query_class, torch.int32)
+    if exclude is not None:
+        _need_gpu("exclude", exclude, torch.int32)
+    for name, t in (("g", g), ("lse", lse)):
+        if t is not None:
+            _need_gpu(name, t, torch.float32)
+    return b, emb.size(0), d, classes
+
+
+def softmax_lse(q: torch.Tensor, emb: torch.Tensor, target: torch.Tensor, allow: Optional[torch.Tensor] = None,
+                query_class: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None, slices: int = 0,
+                with_loss: bool = False):
+    """``(lse, true_score, row_max)``, float32 ``[B]`` each (``rgcn_softmax_lse``): over the candidates that
+    ``allow[query_class[b]]`` admits and ``exclude[b]`` does not strike (the masks of ``distmult_rank_masked``) PLUS the
+    target itself, always, ``row_max = max s``, ``lse = row_max + log(sum exp(s - row_max))`` with ``s[b, n] =
+    <q[b], emb[n]>`` - the bits ``distmult_score_all_tails`` stores; ``true_score[b] = s[b, target[b]]`` from the same
+    accumulator.  The loss is ``lse - true_score``, a hit is ``true_score >= row_max``; ``with_loss=True`` appends
+    ``(loss float32 [B], hit int32 [B])``, formed by the launch that merges the slices.  ``slices``: into how many
+    ranges the entities are cut (0: chosen from ``B`` and ``N`` alone); the result may depend on it in the last bits
+    and on nothing else - two calls give the same bits."""
+    b, n, d, classes = _softmax_check(q, emb, target, allow, query_class, exclude, slices)
+    lib = _L()
+    with _on(q.device):
+        lse = _empty(b, dtype=torch.float32, device=q.device)
+        true_score = _empty(b, dtype=torch.float32, device=q.device)
+        row_max = _empty(b, dtype=torch.float32, device=q.device)
+        loss = _empty(b, dtype=torch.float32, device=q.device) if with_loss else None
+        hit = _empty(b, dtype=torch.int32, device=q.device) if with_loss else None
+        if b:
+            nbytes = int(lib.rgcn_softmax_workspace_bytes(b, n, d, int(slices)))
+            ws = _empty(nbytes, dtype=torch.uint8, device=q.device)
+            rc = lib.rgcn_softmax_lse(_ptr(q), _ptr(emb), _ptr(target), _ptr(allow), _ptr(query_class), classes,
+                                      _ptr(exclude), b, n, d, int(slices), _ptr(lse), _ptr(true_score), _ptr(row_max),
+                                      _ptr(loss), _ptr(hit), _ptr(ws), nbytes, _stream())
+            _lib.check(rc, "rgcn_softmax_lse")
+    return (lse, true_score, row_max, loss, hit) if with_loss else (lse, true_score, row_max)
+
+
+def softmax_grad(g: torch.Tensor, q: torch.Tensor, emb: torch.Tensor, target: torch.Tensor, lse: torch.Tensor,
+                 allow: Optional[torch.Tensor] = None, query_class: Optional[torch.Tensor] = None,
+                 exclude: Optional[torch.Tensor] = None, slices: int = 0, need_dq: bool = True, need_demb: bool = True,
+                 demb: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """``(dq [B, d], demb [N, d])`` for ``g[b] = d(...) / d loss[b]`` (``rgcn_softmax_grad``): with ``c[b, n] = g[b] *
+    ([n eligible] exp(s[b, n] - lse[b]) - [n == target[b]])``, ``dq = c @ emb`` and ``demb = c.T @ q`` - the score tile
+    is recomputed, the coefficient never leaves the chip.  ``demb`` is written whole (rows no query finds eligible are
+    exact zeros); ``demb=`` names the buffer to write, ``accumulate=True`` adds to what it holds (the chunked caller).
+    A gradient that is not needed is ``None``.  No floating-point atomics: two calls give the same bits."""
+    b, n, d, classes = _softmax_check(q, emb, target, allow, query_class, exclude, slices, g, lse)
+    if demb is not None:
+        _need_gpu("demb", demb, torch.float32)
+        if demb.shape != emb.shape:
+            raise ValueError(f"demb {tuple(emb.shape)} expected")
+    elif accumulate:
+        raise ValueError("accumulate=True needs the demb buffer to add to")
+    lib = _L()
+    with _on(q.device):
+        dq = _empty((b, d), dtype=torch.float32, device=q.device) if need_dq else None
+        if need_demb and demb is None:
+            demb = _empty((n, d), dtype=torch.float32, device=q.device)
+        if not need_demb:
+            demb = None
+        nbytes = int(lib.rgcn_softmax_workspace_bytes(b, n, d, int(slices))) if need_dq else 0
+        ws = _empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes else None
+        rc = lib.rgcn_softmax_grad(_ptr(g), _ptr(q), _ptr(emb), _ptr(target), _ptr(allow), _ptr(query_class), classes,
+                                   _ptr(exclude), _ptr(lse), b, n, d, int(slices), _ptr(dq), _ptr(demb),
+                                   int(bool(accumulate)), _ptr(ws), nbytes, _stream())
+    _lib.check(rc, "rgcn_softmax_grad")
+    return dq, demb
+
+
+def _softmax_chunk_rows(b: int, w: int, max_mask_bytes: int) -> int:
+    rows = max(1, int(max_mask_bytes) // (4 * w))
+    if rows >= 128:
+        rows -= rows % 128                                       # whole query tiles of both passes
+    return min(rows, b)
+
+
+def softmax_lse_filtered(q, emb, target, known: Optional[KnownTriples] = None, side: str = "tail",
+                         anchor_idx: Optional[torch.Tensor] = None, rel_idx: Optional[torch.Tensor] = None,
+                         allow: Optional[torch.Tensor] = None, query_class: Optional[torch.Tensor] = None,
+                         max_mask_bytes: int = 256 << 20, slices: int = 0):
+    """``softmax_lse(..., with_loss=True)`` with the exclude mask of ``known`` built chunk by chunk through one buffer,
+    as ``distmult_rank_filtered`` does (a mask row costs ``W * 4`` bytes): the forward is chunkable by rows, a row's
+    result does not depend on the chunking.  -> ``(lse, true_score, row_max, loss, hit)``."""
+    b = q.size(0)
+    if known is None or b == 0:
+        return softmax_lse(q, emb, target, allow, query_class, None, slices, with_loss=True)
+    if anchor_idx is None or rel_idx is None:
+        raise ValueError("a filtered softmax needs the anchor node ids and relation ids of the queries")
+    if known.num_nodes != emb.size(0):
+        raise ValueError(f"known triples are over {known.num_nodes} nodes, the candidates are {emb.size(0)}")
+    w = mask_words(emb.size(0))
+    rows = _softmax_chunk_rows(b, w, max_mask_bytes)
+    if rows >= b:
+        return softmax_lse(q, emb, target, allow, query_class, known.exclude_bits(side, anchor_idx, rel_idx), slices,
+                           with_loss=True)
+    outs = [_empty(b, dtype=dt, device=q.device) for dt in (torch.float32,) * 4 + (torch.int32,)]
+    buf = _empty((rows, w), dtype=torch.int32, device=q.device)
+    for lo in range(0, b, rows):
+        hi = min(lo + rows, b)
+        excl = known.exclude_bits(side, anchor_idx[lo:hi], rel_idx[lo:hi], out=buf)
+        part = softmax_lse(q[lo:hi], emb, target[lo:hi], allow, None if query_class is None else query_class[lo:hi],
+                           excl, slices, with_loss=True)
+        for o, p in zip(outs, part):
+            o[lo:hi] = p
+    return tuple(outs)
+
+
+def softmax_grad_filtered(g, q, emb, target, lse, known: Optional[KnownTriples] = None, side: str = "tail",
+                          anchor_idx: Optional[torch.Tensor] = None, rel_idx: Optional[torch.Tensor] = None,
+                          allow: Optional[torch.Tensor] = None, query_class: Optional[torch.Tensor] = None,
+                          max_mask_bytes: int = 256 << 20, slices: int = 0, need_dq: bool = True,
+                          need_demb: bool = True, demb: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """``softmax_grad`` with the exclude mask of ``known`` rebuilt chunk by chunk through one buffer, the chunks of
+    ``softmax_lse_filtered``.  ``dq`` is chunkable by rows.  ``demb`` accumulates over the chunks in chunk order - chunk
+    0 writes it (or adds to it: ``accumulate``), every later chunk adds - so the same chunking (the same
+    ``max_mask_bytes``) gives the same bits, and another chunking the same values to rounding."""
+    b = q.size(0)
+    if known is None or b == 0:
+        return softmax_grad(g, q, emb, target, lse, allow, query_class, None, slices, need_dq, need_demb, demb, accumulate)
+    if anchor_idx is None or rel_idx is None:
+        raise ValueError("a filtered softmax needs the anchor node ids and relation ids of the queries")
+    if known.num_nodes != emb.size(0):
+        raise ValueError(f"known triples are over {known.num_nodes} nodes, the candidates are {emb.size(0)}")
+    w = mask_words(emb.size(0))
+    rows = _softmax_chunk_rows(b, w, max_mask_bytes)
+    if rows >= b:
+        return softmax_grad(g, q, emb, target, lse, allow, query_class, known.exclude_bits(side, anchor_idx, rel_idx),
+                            slices, need_dq, need_demb, demb, accumulate)
+    dq = _empty((b, q.size(1)), dtype=torch.float32, device=q.device) if need_dq else None
+    if need_demb and demb is None:
+        demb = _empty(tuple(emb.shape), dtype=torch.float32, device=q.device)
+    buf = _empty((rows, w), dtype=torch.int32, device=q.device)
+    for lo in range(0, b, rows):
+        hi = min(lo + rows, b)
+        excl = known.exclude_bits(side, anchor_idx[lo:hi], rel_idx[lo:hi], out=buf)
+        part, _ = softmax_grad(g[lo:hi], q[lo:hi], emb, target[lo:hi], lse[lo:hi], allow,
+                               None if query_class is None else query_class[lo:hi], excl, slices, need_dq, need_demb,
+                               demb if need_demb else None, need_demb and (accumulate or lo > 0))
+        if need_dq:
+            dq[lo:hi] = part
+    return dq, (demb if need_demb else None)
+
+
 PATHS_MAX_K = 64          # one list entry per lane of the inserting wave (csrc/paths.hip)
 PATHS_MAX_LEN = 4         # edges of the longest path
 PATHS_LDS_IDS = 2048      # in-neighbours of a target the enumeration stages in LDS; more are read from global memory

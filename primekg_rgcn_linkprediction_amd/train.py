@@ -81,7 +81,20 @@ class Trainer:
         # from the class of the node they replace, by the constrained device sampler - there is no other path to them
         self.filtered_negatives = bool(getattr(args, "filtered_negatives", False))
         self.type_constrained_negatives = bool(getattr(args, "type_constrained_negatives", False))
-        self.constrained_negatives = self.filtered_negatives or self.type_constrained_negatives
+        # --loss softmax: the 1-vs-all softmax cross-entropy of the true entity against every candidate; no negatives are
+        # sampled, and the two protocol switches choose the denominator's candidates instead of the sampler's draws
+        self.softmax = getattr(args, "loss", "bce") == "softmax"
+        self.softmax_sides = ("tail",) if getattr(args, "softmax_sides", "both") == "tail" else ("tail", "head")
+        if self.softmax:
+            if getattr(args, "num_neg_samples", 1) != 1:
+                raise ValueError("--loss softmax scores every entity against the true one and samples no negatives: "
+                                 "--num_neg_samples has no meaning with it, leave it at 1")
+            if getattr(args, "torch_sampler", False):
+                raise ValueError("--loss softmax draws no negatives, so there is no sampler to choose: drop --torch_sampler")
+            if self.type_constrained_negatives and not getattr(args, "node_types", None):
+                raise ValueError("--type_constrained_negatives needs --node_types PATH (mappings.pt, or an .npz / .pt "
+                                 "int vector [num_nodes])")
+        self.constrained_negatives = (self.filtered_negatives or self.type_constrained_negatives) and not self.softmax
         if self.constrained_negatives:
             if getattr(args, "torch_sampler", False):
                 raise ValueError("--filtered_negatives / --type_constrained_negatives need the device sampler: drop --torch_sampler")
@@ -113,7 +126,7 @@ class Trainer:
         # whole-step HIP graph (sampler -> encoder -> head -> BCE -> backward -> clip -> Adam ->
         # running metrics) for the full-size batches of an epoch; needs a device-side Adam step count
         self.use_hip_graph = (device.type == "cuda" and not getattr(args, "no_hip_graph", False)
-                              and max(1, getattr(args, "gradient_accumulation_steps", 1)) == 1)
+                              and max(1, getattr(args, "gradient_accumulation_steps", 1)) == 1 and not self.softmax)
         # on the GPU: the single-kernel update (same rule; the default one runs ~10 list kernels
         # per step, ~125 us here), with its step count on the device when the step is captured
         extra = {"fused": True, "capturable": self.use_hip_graph} if device.type == "cuda" else {}
@@ -143,6 +156,19 @@ class Trainer:
                 self._neg_known = ops.KnownTriples(self.train_edge_index, self.train_edge_type, n, r)
                 self._neg_known_full = ops.KnownTriples(self.full_edge_index, self.full_edge_type, n, r)
             self._neg_stats = torch.zeros(2, dtype=torch.int64, device=device)
+        self._sm_known = self._sm_known_full = self._sm_node_class = None
+        if self.softmax:
+            from . import ops
+            n, r = train_data["num_nodes"], train_data["num_relations"]
+            logger.info("--loss softmax (%s): every step runs eagerly - the mask chunking and the known-triple lookup are "
+                        "torch ops that have never been captured into a HIP graph", " + ".join(self.softmax_sides))
+            if self.type_constrained_negatives:
+                from .evaluate import load_node_classes
+                self._sm_node_class = load_node_classes(args.node_types, n).to(device)
+            if self.filtered_negatives:
+                # what training may know: the train graph; validate() scores over the full graph and filters against it
+                self._sm_known = ops.KnownTriples(self.train_edge_index, self.train_edge_type, n, r)
+                self._sm_known_full = ops.KnownTriples(self.full_edge_index, self.full_edge_type, n, r)
         self.best_val_loss, self.best_val_acc = float("inf"), 0.0
         self.train_losses, self.val_losses, self.train_accs, self.val_accs = [], [], [], []
         self.output_dir = Path(args.output_dir)
@@ -196,6 +222,8 @@ class Trainer:
         """One batch: assembly, forward over the train graph, BCE, backward and (when
         ``update``) clip + optimizer step; running loss / hits stay on the device.  ``lo`` is
         only documentation here - the position is whatever ``self._cursor`` holds."""
+        if self.softmax:
+            return self._softmax_step(lo, size, accum, update)
         heads, tails, rels, labels = self._make_batch(lo, size)
         fused = self._fused_bookkeeping
         if fused:
@@ -219,6 +247,20 @@ class Trainer:
                 self._loss_sum += loss.detach().double() * labels.numel()
                 self._correct += ((scores.detach() > 0) == (labels > 0.5)).sum()
         return heads, tails, rels, labels, loss.detach()
+
+    def _softmax_step(self, lo: int, size: int, accum: int = 1, update: bool = True):
+        """``_step`` with ``--loss softmax``: the batch is ``size`` positives of the permutation and nothing else; the
+        loss is the mean over sides and samples, the running sums take the summed loss and the number of hits (the
+        target is a best eligible candidate).  Eager: ``lo`` is the position."""
+        idx = self._order[lo:lo + size]
+        heads, tails, rels = self.train_edge_index[0, idx], self.train_edge_index[1, idx], self.train_edge_type[idx]
+        loss, _ = self.model.softmax_loss(self.train_edge_index, self.train_edge_type, heads, tails, rels,
+                                          sides=self.softmax_sides, known=self._sm_known, node_class=self._sm_node_class,
+                                          stats=(self._loss_sum, self._correct))
+        (loss / accum if accum != 1 else loss).backward()
+        if update:
+            self._clip_and_update()
+        return heads, tails, rels, None, loss.detach()
 
     def _clip_and_update(self) -> None:
         """``clip_grad_norm_`` + ``optimizer.step()`` (train.py:311-317).  On the GPU: two launches
@@ -317,13 +359,14 @@ class Trainer:
                 out = self._step(lo, hi - lo, accum=accum, update=last)
                 if last:
                     self.optimizer.zero_grad(set_to_none=True)
-            seen += (hi - lo) * (1 + self.neg_sampler.num_neg_samples)
+            seen += (hi - lo) * (len(self.softmax_sides) if self.softmax else 1 + self.neg_sampler.num_neg_samples)
             if on_step is not None:
                 on_step(*out)
         result = (self._loss_sum / max(seen, 1)).item(), self._correct.item() / max(seen, 1)
         if self._neg_stats is not None:      # read back once per epoch, with the loss
             self.negative_stats = tuple(self._neg_stats.tolist())
-        ops.check_indices(self.device)       # an id outside the embedding table anywhere in the epoch: IndexError, here
+        if not (self.softmax and self.device.type != "cuda"):   # (--loss softmax on the CPU indexes through torch, which raises itself)
+            ops.check_indices(self.device)   # an id outside the embedding table anywhere in the epoch: IndexError, here
         return result
 
     @torch.no_grad()
@@ -338,6 +381,17 @@ class Trainer:
         # batch is the head's two launches (scores + loss, then mean / running sums).  Negatives: the reference's
         # sampler on torch's RNG stream, as there.
         fused = self._fused_bookkeeping and hasattr(self.model, "encoder") and hasattr(self.model, "decoder")
+        if self.softmax:
+            # the same loss over the full graph's embeddings, computed once; filtered against the full graph
+            emb = self.model.encoder(self.full_edge_index, self.full_edge_type)
+            for heads, tails, rels in self._batches(self.val_edge_index, self.val_edge_type, shuffle=False):
+                self.model.decoder.softmax_loss(emb, heads, tails, rels, sides=self.softmax_sides,
+                                                known=self._sm_known_full, node_class=self._sm_node_class,
+                                                stats=(loss_sum, correct))
+                seen += heads.numel() * len(self.softmax_sides)
+            if self.device.type == "cuda":
+                ops.check_indices(self.device)
+            return (loss_sum / max(seen, 1)).item(), correct.item() / max(seen, 1)
         emb = self.model.encoder(self.full_edge_index, self.full_edge_type) if fused else None
         for heads, tails, rels, labels in self._validation_batches():
             if fused:
@@ -495,6 +549,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adamw"])
     p.add_argument("--num_neg_samples", type=int, default=1)
+    p.add_argument("--loss", type=str, default="bce", choices=["bce", "softmax"],
+                   help="bce: binary cross-entropy against sampled negatives (the reference's); softmax: the 1-vs-all "
+                        "softmax cross-entropy of the true entity against every candidate, fused (no sampled negatives; "
+                        "--filtered_negatives / --type_constrained_negatives then choose the denominator's candidates)")
+    p.add_argument("--softmax_sides", type=str, default="both", choices=["tail", "both"],
+                   help="--loss softmax: predict the tail of (head, relation, ?) only, or also the head of (?, relation, tail)")
     p.add_argument("--grad_clip", type=float, default=1.0)
     p.add_argument("--gradient_accumulation_steps", type=int, default=1)
     p.add_argument("--save_every", type=int, default=10)
