@@ -1,0 +1,94 @@
+/* rgcn_edge_dropout.h - edge dropout and hidden batch edges for the training encoder of librgcn_hip.so (plain C,
+ * gfx950 only).
+ *
+ * The error codes, the ABI version and the conventions (device pointers, `stream` a hipStream_t passed as void*,
+ * nothing aborts, inputs never written) are those of rgcn_hip.h.
+ *
+ * Why.  A link-prediction trainer that encodes over the train graph and scores positives taken from that same graph
+ * asks the model to predict an edge the encoder has just averaged into both of its endpoints.  Schlichtkrull et al.
+ * (2018) name edge dropout as the regulariser that makes the R-GCN encoder work for this task, and later trainers
+ * also take the batch's own edges out of the message-passing graph.  The reference has neither.  The bucketed
+ * structure is built once by a sort that synchronises and allocates, so it cannot change per step; what can change
+ * per step is the per-edge weight the weighted gathers already multiply by.  Hence: a VIEW of a graph handle whose
+ * two directions are both weighted, and a DRAW that rewrites the view's weights in place.
+ *
+ * THE VIEW.  rgcn_edge_dropout_create takes a square handle with a mean forward direction (what rgcn_graph_create and
+ * rgcn_graph_import return; anything else: RGCN_ERR_UNSUPPORTED) and builds an rgcn_graph whose two directions are
+ * weighted-sum structures.  The view SHARES rowptr, col, perm, the work items, the hub index, the item heads' column
+ * ids and the occupancy masks with the parent - it does not own them, and the parent must outlive the view.  The
+ * view OWNS, per direction, val (float[E]) and head_w (float[level-0 items * 8]), one int32[N * R] array of kept
+ * counts (and the int32[N * R] counters a draw adds into), and two int32[E] index arrays (the forward segment of
+ * every forward position and of every transposed position), which make the draw a flat walk of the edges.  Ownership lives in the wrapper, not in the structure:
+ * rgcn_edge_dropout_destroy frees only what the view owns.  After create the view holds the draw p = 0,
+ * position = NULL, so it is usable at once.  create may allocate and synchronise.
+ *
+ * Every entry point that takes an rgcn_graph takes rgcn_edge_dropout_graph(ed):
+ *   rgcn_aggregate(view, 0, x)   agg[i * R + r] = sum over the in-edges of (i, r) of w_fwd * x[src], in the weighted
+ *                                gather's order (runs, packs and the hub tree included) = the mean over the KEPT
+ *                                in-edges up to rounding; a segment without a kept edge gives zeros.  This is RGCNConv
+ *                                on edge_index[:, kept], edge_type[kept].
+ *   rgcn_aggregate(view, 1, g)   its adjoint.
+ *   rgcn_graph_weight_bound      a true bound for EVERY draw: forward 1 + 1e-6 (a segment's weights sum to
+ *                                k * fl(1 / k) <= 1 + 2^-23), transposed the edge count of the longest (source,
+ *                                relation) segment (every weight is <= 1).
+ *   tile / row occupancy masks   the parent's: supersets under every draw (a tile they skip is zero under every draw).
+ *
+ * THE DRAW - the contract; tests restate it on the host (tests/edge_dropout_reference.py).  With e the ORIGINAL
+ * column of an edge (perm[] of either direction), c0 = cursor[0] (0 without a cursor), seed = rng[0], epoch = rng[1]:
+ *   hidden(e)  = position != NULL  and  c0 <= position[e] < c0 + batch
+ *   c          = philox4x32_10(counter = (low32(e), low32(c0), low32(epoch), RGCN_EDGE_DROPOUT_STREAM),
+ *                              key = (low32(seed), high32(seed)))
+ *   dropped(e) = c[0] < T,   T = floor(p * 2^32) as uint32            - an integer compare: the host restates it exactly
+ *   kept(e)    = not hidden(e) and not dropped(e)
+ *   k[i, r]    = number of kept edges of forward segment (i, r)      - int32, exact (integer atomics: order-free)
+ *   w_fwd[pos] = kept ? 1.0f / (float)k[dst, r] : 0.0f               - one IEEE division, as the transposed weights of
+ *   w_t[pos]   = kept ? 1.0f / (float)k[dst, r] : 0.0f                 rgcn_graph_create (dst = col_t[pos], r = segment % R)
+ *   head_w     = the copies of the first weights of every level-0 item, refreshed for both directions
+ *   stats[0]  += kept edges,  stats[1] += hidden edges               - accumulated, never cleared here
+ * p = 0 without a position reproduces the parent's transposed weights bit for bit.  The word depends on (seed, epoch,
+ * cursor, column) only: the same step draws the same mask whatever ran before it, and a replayed HIP graph whose device
+ * cursor has moved draws that cursor's mask.
+ *
+ * Non-finite values - a deliberate deviation.  A dropped or hidden edge contributes 0 * x: it is MULTIPLIED by a zero
+ * weight, not skipped, so a non-finite source row still reaches the aggregate of a segment it was dropped from
+ * (0 * NaN = NaN), where RGCNConv on the kept subgraph would not see it.  The hot gather is not changed for it.
+ */
+#ifndef RGCN_EDGE_DROPOUT_H
+#define RGCN_EDGE_DROPOUT_H
+
+#include "rgcn_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define RGCN_EDGE_DROPOUT_STREAM 0x45444F50u   /* counter word 3 of every edge-dropout draw ("EDOP"; not RGCN_RESAMPLE_STREAM) */
+
+typedef struct rgcn_edge_dropout rgcn_edge_dropout;
+
+/* RGCN_ERR_ARG: g or out NULL.  RGCN_ERR_UNSUPPORTED: g is not a square handle with a mean forward direction and a
+ * weighted transposed one (a shard, another view).  Synchronises `stream` and allocates device memory owned by the view. */
+int rgcn_edge_dropout_create(const rgcn_graph* g, void* stream, rgcn_edge_dropout** out);
+void rgcn_edge_dropout_destroy(rgcn_edge_dropout* ed);
+/* the view; owned by ed, valid until rgcn_edge_dropout_destroy */
+const rgcn_graph* rgcn_edge_dropout_graph(const rgcn_edge_dropout* ed);
+/* DEVICE int32[N * R]: k of the last draw; owned by ed */
+const int32_t* rgcn_edge_dropout_kept(const rgcn_edge_dropout* ed);
+/* the same array copied (device to device, async on `stream`) into the caller's int32[N * R], as rgcn_graph_export
+ * copies the structure's arrays.  RGCN_ERR_ARG: ed NULL, or out NULL while N * R > 0; RGCN_ERR_ALIGN: out needs 4. */
+int rgcn_edge_dropout_kept_export(const rgcn_edge_dropout* ed, int32_t* out, void* stream);
+
+/* One draw: asynchronous on `stream`, no allocation, no host synchronisation, capturable into a HIP graph (three
+ * kernels, no memset node: the draw's last launch clears the counters the next one adds into).  rng: DEVICE int64[2] =
+ * {seed, epoch}; cursor: DEVICE int64[1] or NULL (= 0); batch >= 0;
+ * position: DEVICE int64[E] or NULL, position[e] = where column e stands in the epoch's order; stats: DEVICE int64[2]
+ * or NULL.  RGCN_ERR_ARG: ed or rng NULL, batch < 0, p outside [0, 1) (NaN included).  RGCN_ERR_ALIGN: rng, cursor,
+ * position, stats need 8. */
+int rgcn_edge_dropout_draw(rgcn_edge_dropout* ed, double p, const int64_t* rng, const int64_t* cursor, int64_t batch,
+                           const int64_t* position, int64_t* stats, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RGCN_EDGE_DROPOUT_H */

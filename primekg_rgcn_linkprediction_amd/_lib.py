@@ -247,6 +247,18 @@ SOFTMAX_PROTOTYPES = {
 }
 SOFTMAX_MAX_D = 256              # widest row the backward keeps in accumulators (csrc/softmax_loss.hip)
 
+# include/rgcn_edge_dropout.h, one to one: edge dropout and hidden batch edges (csrc/edge_dropout.hip; not part of
+# rgcn_hip.h, never forwarded by rgcn_sequence_run - the draw happens outside any recorded Region, before the forward)
+EDGE_DROPOUT_PROTOTYPES = {
+    "rgcn_edge_dropout_create": (c_int, [c_void_p, _P, POINTER(c_void_p)]),
+    "rgcn_edge_dropout_destroy": (None, [c_void_p]),
+    "rgcn_edge_dropout_graph": (c_void_p, [c_void_p]),
+    "rgcn_edge_dropout_kept": (c_void_p, [c_void_p]),
+    "rgcn_edge_dropout_kept_export": (c_int, [c_void_p, _P, _P]),
+    "rgcn_edge_dropout_draw": (c_int, [c_void_p, c_double, _P, _P, _I64, _P, _P, _P]),   # p, rng, cursor, batch, position, stats
+}
+EDGE_DROPOUT_STREAM = 0x45444F50   # RGCN_EDGE_DROPOUT_STREAM
+
 # include/rgcn_sparse.h, one to one: the row-granular occupancy behind sparse aggregates (csrc/rgcn_graph.hip; queries,
 # never forwarded by rgcn_sequence_run).  MODE_SPARSE_ROWS: RGCN_MODE_SPARSE_ROWS of rgcn_hip.h, the bit a training pass
 # sets in the `int` option word of its gathers and of the split transforms that read their aggregates.
@@ -277,7 +289,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise RGCNLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + list(COMPLEX_PROTOTYPES.items()) + list(SPARSE_PROTOTYPES.items()) + list(SOFTMAX_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + list(COMPLEX_PROTOTYPES.items()) + list(SPARSE_PROTOTYPES.items()) + list(SOFTMAX_PROTOTYPES.items()) + list(EDGE_DROPOUT_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -107,6 +107,7 @@ def _fused_backward(graph, g, r, d_in, d_out, g_amax, packed, precision) -> bool
     the transposed aggregate [N, R * d_out] would no longer fit the Infinity Cache (or RGCN_TRAIN_FUSED=1)"""
     fused = _TRAIN_FUSED == "1" or (_TRAIN_FUSED == "auto" and g.size(0) * r * d_out * 4 >= _TRAIN_FUSED_MIN_BYTES)
     return (fused and precision is None and packed is not None and g_amax is not None and not graph.bipartite
+            and not graph.edge_dropout                     # (its walked CSR would be a stale copy of the weights)
             and ops.GEMM_PRECISION == "split" and ops.fused_bwd_supported(r, d_in, d_out))
 
 
@@ -119,7 +120,8 @@ def _transform_first(graph: "ops.BucketedGraph", weight: Tensor, root: Optional[
     """does the layer's input gradient take the transform-first order (see _input_grad)?"""
     r, d_in, d_out = weight.shape
     ratio = _TRANSFORM_FIRST_RATIO if _from_packed(weight, packed, precision) else max(_TRANSFORM_FIRST_RATIO, 4.0)
-    return d_out >= ratio * d_in and root is not None and not graph.bipartite
+    # (an edge-dropout view: the merged structure would be a copy of weights that the next draw rewrites)
+    return d_out >= ratio * d_in and root is not None and not graph.bipartite and not graph.edge_dropout
 
 
 # Sparse aggregates: about half of the (node, relation) segments of a typed knowledge graph have no edge (46,756 of C2's
@@ -145,7 +147,10 @@ def _sparse_agg(graph: "ops.BucketedGraph", transposed: bool, half: bool, packed
 def _gagg_scale(graph: "ops.BucketedGraph", gagg_amax: Optional[Tensor], g_amax: Optional[Tensor]):
     """``(amax, amax_mul)`` of the transform reading a transposed aggregate of ``g``: its OWN maximum, which its gather
     publishes - the bound weight_bound * max |g| is hundreds of times looser on hub graphs and would cost its ordinary
-    rows that many binades of the lo half (tests/test_split_rows.py); the bound only without it (fp32: no slots)"""
+    rows that many binades of the lo half (tests/test_split_rows.py); the bound only without it (fp32: no slots).  An
+    edge-dropout view's transposed bound is the longest (source, relation) segment's edge count (every weight <= 1: 61,716
+    at C2; the parent's is that segment's sum of 1 / cnt) - looser still, and reached on the fp32 route alone, whose
+    kernels scale nothing by it"""
     if gagg_amax is not None:
         return (gagg_amax, g_amax), 1.0
     return (g_amax, g_amax), graph.weight_bound(True)
@@ -232,7 +237,8 @@ def _deferred_params(graph: "ops.BucketedGraph", agg, x, g, x_amax, g_amax, has_
     kernel merely skips the loads of its stored zeros - the same bits."""
     sparse = _sparse_agg(graph, False, False, packed, x_amax, x.size(1), prec)
     return ops.transform_bwd_params(agg, x, g, graph.num_relations, want_root=has_root, want_bias=has_bias, graph=graph,
-                                    defer=True, amax=(x_amax, x_amax, g_amax), precision=prec, sparse=sparse)
+                                    defer=True, amax=(x_amax, x_amax, g_amax), precision=prec, sparse=sparse,
+                                    amax_mul=_agg_bound(graph))
 
 
 # Training forward of one layer: gather -> transform (two launches, the aggregate written by one and read by the
@@ -245,16 +251,22 @@ _TRAIN_FUSED = _os.environ.get("RGCN_TRAIN_FUSED", "auto")
 _TRAIN_FUSED_MIN_BYTES = 256 << 20
 
 
-def _defer_hubs(half: bool, packed, amax, k: int, n_out: int) -> bool:
+def _defer_hubs(half: bool, packed, amax, k: int, n_out: int, graph=None) -> bool:
     """may a gather of k-wide rows leave its hub tails to the transform (n_out columns) that follows it?  Split
     precision with the operand's scale known beforehand; rows up to 128 wide and ONE column block of workgroups
     (at 256 the workgroups of every column block would each finish the same rows, with four row slots: measured
     1 % slower at C3)."""
     return (_DEFER_HUBS and not half and packed is not None and amax is not None and ops.GEMM_PRECISION == "split"
-            and k in (64, 128) and n_out <= 128)
+            and k in (64, 128) and n_out <= 128 and not (graph is not None and graph.edge_dropout))
 
 
 _DEFER_HUBS = True
+
+
+def _agg_bound(graph: "ops.BucketedGraph") -> float:
+    """what max |table| is multiplied by to bound a FORWARD aggregate: 1 for a mean (it cannot exceed the table's
+    maximum), the structure's weight bound for the weighted sums of an edge-dropout view - true for every draw"""
+    return graph.weight_bound(False) if graph.edge_dropout else 1.0
 
 
 def _train_fused(graph, n, r, d_in, d_out, half) -> bool:
@@ -276,14 +288,14 @@ def _layer_train_forward(graph: "ops.BucketedGraph", x: Tensor, gather_dtype, we
     sparse = n == graph.num_other_nodes and _sparse_agg(graph, False, half, packed, x_amax, d_in)
     if sparse:
         # no zero rows stored, none read: by the transform below and by the parameter gradients (_deferred_params)
-        agg, hubs = ops.aggregate_sparse(graph, x, defer=_defer_hubs(half, packed, x_amax, d_in, d_out))
-    elif _defer_hubs(half, packed, x_amax, d_in, d_out):
+        agg, hubs = ops.aggregate_sparse(graph, x, defer=_defer_hubs(half, packed, x_amax, d_in, d_out, graph))
+    elif _defer_hubs(half, packed, x_amax, d_in, d_out, graph):
         # the gather leaves its hub tails to the transform (one launch less); `agg` is complete once that has run
         agg, hubs = ops.aggregate_deferred(graph, x)
     else:
         agg, hubs = ops.aggregate(graph, _table(x, gather_dtype)), None
     out = ops.transform_fwd(agg, x, weight, root, bias, relu=relu, graph=graph, half=half, amax=(x_amax, x_amax),
-                            amax_out=amax_out, packed=packed, hubs=hubs, sparse=sparse)
+                            amax_out=amax_out, packed=packed, hubs=hubs, sparse=sparse, amax_mul=_agg_bound(graph))
     return agg, out
 
 
@@ -583,17 +595,40 @@ def _check_gather_dtype(gather_dtype) -> None:
         raise ValueError(f"gather_dtype must be None, torch.float32 or torch.float16, got {gather_dtype}")
 
 
+def _resolve_graph(graph: Optional["ops.BucketedGraph"], edge_index: Tensor, edge_type: Tensor, num_nodes: int,
+                   num_relations: int, differentiating: bool) -> "ops.BucketedGraph":
+    """the structure a layer runs over: the cached bucketing of its columns, or the caller's ``graph=`` override - the
+    view of an ``ops.EdgeDropout`` on that bucketing.  A view stands for its parent wherever nothing is differentiated
+    (eval mode, no_grad without dropout): dropout regularises training, scoring sees the whole graph."""
+    if graph is None:
+        return ops.bucket(edge_index, edge_type, num_nodes, num_relations)
+    if not isinstance(graph, ops.BucketedGraph) or graph.bipartite:
+        raise ValueError("graph= takes a whole bucketed graph or the view of an ops.EdgeDropout")
+    if graph.num_nodes != num_nodes or graph.num_relations != num_relations:
+        raise ValueError(f"graph= has {graph.num_nodes} nodes and {graph.num_relations} relations; x has {num_nodes} rows "
+                         f"and the layer {num_relations} relations")
+    if graph.edge_dropout and not differentiating:
+        return graph.parent
+    return graph
+
+
+def _differentiating(*tensors) -> bool:
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
 def rgcn_conv(x: Tensor, edge_index: Tensor, edge_type: Tensor, weight: Tensor,
               root: Optional[Tensor], bias: Optional[Tensor], num_relations: int,
-              activation: Optional[str] = None, gather_dtype=None, half_backward: bool = False) -> Tensor:
+              activation: Optional[str] = None, gather_dtype=None, half_backward: bool = False,
+              graph: Optional["ops.BucketedGraph"] = None) -> Tensor:
     """Functional form on effective weights ``[R, d_in, d_out]``; ``activation='relu'`` fuses
     the ReLU into the layer; ``gather_dtype=torch.float16`` makes the forward gather read an fp16
-    copy of the feature table (fp32 accumulate; BASELINE configs[4]); gradients stay fp32."""
+    copy of the feature table (fp32 accumulate; BASELINE configs[4]); gradients stay fp32.  ``graph``: run over this
+    structure instead of the bucketing of ``edge_index`` (``_resolve_graph``)."""
     _check_x(x)
     _check_gather_dtype(gather_dtype)
     if activation not in (None, "relu"):
         raise ValueError(f"activation must be None or 'relu', got {activation!r}")
-    graph = ops.bucket(edge_index, edge_type, x.size(0), num_relations)
+    graph = _resolve_graph(graph, edge_index, edge_type, x.size(0), num_relations, _differentiating(x, weight, root, bias))
     return _RGCNConvFunction.apply(x, weight, root, bias, graph, activation == "relu", gather_dtype, half_backward)
 
 
@@ -611,14 +646,16 @@ def _encoder_hints(x: Tensor, conv1: "RGCNConv", conv2: "RGCNConv"):
 
 
 def rgcn_encoder2(x: Tensor, edge_index: Tensor, edge_type: Tensor, conv1: "RGCNConv",
-                  conv2: "RGCNConv", dropout_p: float = 0.0) -> Tensor:
+                  conv2: "RGCNConv", dropout_p: float = 0.0, graph: Optional["ops.BucketedGraph"] = None) -> Tensor:
     """``conv2(dropout(relu(conv1(x)), dropout_p))`` through the fused two-layer autograd node
-    (``dropout_p`` = 0: no dropout, e.g. eval mode)."""
+    (``dropout_p`` = 0: no dropout, e.g. eval mode).  ``graph``: run over this structure instead of the bucketing of
+    ``edge_index`` (``_resolve_graph``: an edge-dropout view counts only where something is differentiated or dropped)."""
     _check_x(x)
     if not 0.0 <= dropout_p < 1.0:
         raise ValueError(f"dropout_p must be in [0, 1), got {dropout_p}")
-    graph = ops.bucket(edge_index, edge_type, x.size(0), conv1.num_relations)
     tensors = [x] + list(conv1.parameters()) + list(conv2.parameters())
+    graph = _resolve_graph(graph, edge_index, edge_type, x.size(0), conv1.num_relations,
+                           dropout_p > 0.0 or _differentiating(*tensors))
     if dropout_p == 0.0 and not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors)):
         return encoder2_eval(x, graph, conv1.effective_weight(), conv1.root, conv1.bias, conv2.effective_weight(),
                              conv2.root, conv2.bias, conv1.gather_dtype)       # nothing to differentiate, no dropout
@@ -743,9 +780,13 @@ class RGCNConv(nn.Module):
         return _BasisCompose.apply(self.comp, self.weight)
 
     def forward(self, x: Tensor, edge_index: Tensor, edge_type: Optional[Tensor] = None,
-                activation: Optional[str] = None) -> Tensor:
+                activation: Optional[str] = None, graph: Optional["ops.BucketedGraph"] = None) -> Tensor:
         """PyG's ``forward(x, edge_index, edge_type)``; the extra keyword ``activation='relu'``
-        returns ``relu(out)`` with the ReLU fused into the transform's epilogue."""
+        returns ``relu(out)`` with the ReLU fused into the transform's epilogue; ``graph``: the view of an
+        ``ops.EdgeDropout`` on this graph.  A view counts only where something is differentiated: in ``eval()``, under
+        ``no_grad``, and also in training mode with grad enabled when neither ``x`` nor any parameter requires grad
+        (all frozen), the layer runs over the view's PARENT, the whole graph - a caller who drew on purpose and wants
+        the dropped graph there calls ``ops.aggregate`` / ``ops.transform_fwd`` on the view itself."""
         if isinstance(x, (tuple, list)) or x is None:
             raise NotImplementedError("x must be a float tensor [N, in_channels]")
         if not isinstance(edge_index, Tensor):
@@ -753,8 +794,10 @@ class RGCNConv(nn.Module):
         assert edge_type is not None, "edge_type is required"
         if x.dim() != 2 or x.size(1) != self.in_channels_l:
             raise ValueError(f"x must be [N, {self.in_channels_l}], got {tuple(x.shape)}")
+        if graph is not None and graph.edge_dropout and not self.training:
+            graph = graph.parent
         return rgcn_conv(x, edge_index, edge_type, self.effective_weight(), self.root, self.bias,
-                         self.num_relations, activation, self.gather_dtype, self.half_backward)
+                         self.num_relations, activation, self.gather_dtype, self.half_backward, graph=graph)
 
     def __repr__(self) -> str:
         return (f"{self.__class__.__name__}({self.in_channels_l}, {self.out_channels}, "

@@ -1,0 +1,302 @@
+// Edge dropout and hidden batch edges (include/rgcn_edge_dropout.h).
+//
+// The bucketed structure of a graph is built once, by a sort that synchronises and allocates; a training step cannot
+// rebuild it, least of all inside a captured HIP graph.  What a step CAN change is the per-edge weight the weighted
+// body of k_aggregate already multiplies by.  So a draw is three flat launches over arrays that never move:
+//   k_ed_mark     one thread per forward position: kept or not (Philox word of the edge's original column, the batch
+//                 window), the mark left in w_fwd as 1 / 0, and the kept count of every (destination, relation) segment.
+//                 The bucketed order puts a segment in consecutive positions, so a workgroup reduces its runs of equal
+//                 segments (wave ballots, then LDS) and issues ONE integer atomic per segment it touches - a hub of
+//                 300,000 edges receives 300 adds, not 300,000 (the note above RGCN_AMAX_SLOTS in rgcn_common.h).
+//   k_ed_weights  w = kept ? 1 / k[destination, relation] : 0 for every position of both directions (the transposed
+//                 half recomputes the mark from the same word: no E-sized mask travels between the directions).
+//   k_ed_heads    the copies of the first RGCN_HEAD weights that ride with every level-0 item, both directions.
+// The counts are added into counters that are zero between two draws: k_ed_weights copies them out (what
+// rgcn_edge_dropout_kept shows) and k_ed_heads, the last launch, clears them - no memset node in a captured step.
+// Integer sums are order-free, so two draws with the same (seed, epoch, cursor) leave the same bits.
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "rgcn_common.h"
+#include "rgcn_sample_core.h"
+#include "../../include/rgcn_edge_dropout.h"
+#include "../../include/rgcn_resample.h"
+
+static_assert(RGCN_EDGE_DROPOUT_STREAM != RGCN_RESAMPLE_STREAM, "every generator of the library has its own stream word");
+
+struct rgcn_edge_dropout {
+  const rgcn_graph* parent = nullptr;
+  rgcn_graph view;              // shares everything but val / head_w with the parent
+  float* val[2] = {nullptr, nullptr};
+  float* head_w[2] = {nullptr, nullptr};
+  int32_t* kept = nullptr;      // [N * R] k of the last draw
+  int32_t* count = nullptr;     // [N * R] the counters a draw adds into: all zero between two draws (k_ed_heads clears them)
+  int32_t* seg_f = nullptr;     // [E] forward segment of every forward position
+  int32_t* seg_t = nullptr;     // [E] forward segment (dst * R + rel) of every transposed position
+};
+
+namespace {
+
+constexpr int kMarkThreads = 1024, kMarkWaves = kMarkThreads / 64, kThreads = 256;
+
+inline unsigned grid_for(int64_t n, int threads) { return (unsigned)std::max<int64_t>(1, ceil_div64(n, threads)); }
+
+struct draw_params {
+  const int64_t* position;
+  const int64_t* cursor;
+  const int64_t* rng;
+  int64_t batch;
+  uint32_t threshold;
+};
+
+// (c0, key, epoch) of a draw, read once per thread
+struct draw_state {
+  int64_t c0;
+  uint32_t k0, k1, epoch;
+};
+__device__ inline draw_state draw_begin(const draw_params& p) {
+  draw_state s;
+  s.c0 = p.cursor ? p.cursor[0] : 0;
+  const uint64_t seed = (uint64_t)p.rng[0];
+  s.k0 = (uint32_t)seed;
+  s.k1 = (uint32_t)(seed >> 32);
+  s.epoch = (uint32_t)(uint64_t)p.rng[1];
+  return s;
+}
+__device__ inline bool edge_hidden(const draw_params& p, const draw_state& s, int64_t e) {
+  if (!p.position) return false;
+  const int64_t at = p.position[e];
+  return at >= s.c0 && at < s.c0 + p.batch;
+}
+__device__ inline bool edge_dropped(const draw_params& p, const draw_state& s, int64_t e) {
+  uint32_t c[4] = {(uint32_t)(uint64_t)e, (uint32_t)(uint64_t)s.c0, s.epoch, RGCN_EDGE_DROPOUT_STREAM};
+  philox4x32_10(c, s.k0, s.k1);
+  return c[0] < p.threshold;
+}
+
+// seg[pos] = the segment whose [rowptr[s], rowptr[s + 1]) holds pos: the last s with rowptr[s] <= pos.  With `col`
+// (the transposed structure) the FORWARD segment of that edge instead: col[pos] * R + s % R.
+__global__ void k_ed_segments(const int32_t* __restrict__ rowptr, int64_t NR, int64_t E, int64_t R,
+                              const int32_t* __restrict__ col, int32_t* __restrict__ seg) {
+  const int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (pos >= E) return;
+  int64_t lo = 0, hi = NR;                       // rowptr[lo] <= pos < rowptr[hi] throughout
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((int64_t)rowptr[mid] <= pos) lo = mid; else hi = mid;
+  }
+  seg[pos] = col ? (int32_t)((int64_t)col[pos] * R + lo % R) : (int32_t)lo;
+}
+
+__global__ __launch_bounds__(kMarkThreads) void k_ed_mark(const int64_t* __restrict__ perm,
+                                                          const int32_t* __restrict__ seg_f, int64_t E, draw_params p,
+                                                          float* __restrict__ w_fwd, int32_t* __restrict__ kept,
+                                                          unsigned long long* __restrict__ stats) {
+  __shared__ int32_t s_seg[kMarkThreads], s_cnt[kMarkThreads], s_rseg[kMarkThreads];
+  __shared__ int32_t s_heads[kMarkWaves], s_stat[2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t pos = (int64_t)blockIdx.x * kMarkThreads + tid;
+  const bool valid = pos < E;
+  const draw_state st = draw_begin(p);
+  bool keep = false, hide = false;
+  int32_t seg = -1;                              // the positions past the end form one run that counts nothing
+  if (valid) {
+    const int64_t e = perm[pos];
+    seg = seg_f[pos];
+    hide = edge_hidden(p, st, e);
+    keep = !hide && !edge_dropped(p, st, e);
+    w_fwd[pos] = keep ? 1.f : 0.f;               // the mark; k_ed_weights turns it into the weight
+  }
+  s_seg[tid] = seg;
+  s_cnt[tid] = 0;
+  if (tid < 2) s_stat[tid] = 0;
+  __syncthreads();
+  const bool head = tid == 0 || s_seg[tid - 1] != seg;
+  const unsigned long long heads = __ballot(head), keeps = __ballot(keep), hides = __ballot(hide);
+  if (lane == 0) s_heads[wave] = __popcll(heads);
+  __syncthreads();
+  int run = -1, runs = 0;                        // index of this thread's run inside the workgroup
+  for (int w = 0; w < kMarkWaves; ++w) {
+    if (w == wave) run += runs;
+    runs += s_heads[w];
+  }
+  const unsigned long long upto = lane == 63 ? ~0ull : ((1ull << (lane + 1)) - 1);
+  run += __popcll(heads & upto);
+  if (head || lane == 0) {                       // first lane of a run's stretch inside this wave
+    const unsigned long long above = heads & ~upto;
+    const int next = above ? __ffsll((long long)above) - 1 : 64;
+    const unsigned long long stretch = (next == 64 ? ~0ull : ((1ull << next) - 1)) & ~(upto >> 1);
+    const int n = __popcll(keeps & stretch);
+    if (n) atomicAdd(&s_cnt[run], n);
+    if (head) s_rseg[run] = seg;
+  }
+  if (lane == 0) {
+    const int nk = __popcll(keeps), nh = __popcll(hides);
+    if (nk) atomicAdd(&s_stat[0], nk);
+    if (nh) atomicAdd(&s_stat[1], nh);
+  }
+  __syncthreads();
+  if (tid < runs && s_cnt[tid] > 0) atomicAdd(&kept[s_rseg[tid]], s_cnt[tid]);   // a run with a kept edge is no padding
+  if (stats && tid < 2 && s_stat[tid] > 0) atomicAdd(&stats[tid], (unsigned long long)s_stat[tid]);
+}
+
+__global__ __launch_bounds__(kThreads) void k_ed_weights(const int64_t* __restrict__ perm_t,
+                                                         const int32_t* __restrict__ seg_f,
+                                                         const int32_t* __restrict__ seg_t, int64_t E, draw_params p,
+                                                         const int32_t* __restrict__ kept, float* __restrict__ w_fwd,
+                                                         float* __restrict__ w_t, int64_t NR, int32_t* __restrict__ kept_out) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i < NR) kept_out[i] = kept[i];             // what rgcn_edge_dropout_kept shows until the next draw
+  if (i < E) {
+    const bool keep = w_fwd[i] != 0.f;
+    w_fwd[i] = keep ? 1.0f / (float)kept[seg_f[i]] : 0.f;
+  } else if (i < 2 * E) {
+    const int64_t pos = i - E, e = perm_t[pos];
+    const draw_state st = draw_begin(p);
+    const bool keep = !edge_hidden(p, st, e) && !edge_dropped(p, st, e);
+    w_t[pos] = keep ? 1.0f / (float)kept[seg_t[pos]] : 0.f;   // a kept edge is counted in its own segment: k >= 1
+  }
+}
+
+// head_w of both directions, as k_item_heads (rgcn_graph.hip) fills it
+__global__ __launch_bounds__(kThreads) void k_ed_heads(const rgcn_item* __restrict__ items0, int64_t n0,
+                                                       const float* __restrict__ w0, float* __restrict__ head0,
+                                                       const rgcn_item* __restrict__ items1, int64_t n1,
+                                                       const float* __restrict__ w1, float* __restrict__ head1,
+                                                       int64_t NR, int32_t* __restrict__ count) {
+  int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i < NR) count[i] = 0;                      // every reader of this draw's counters has finished: ready for the next
+  const rgcn_item* items = items0;
+  const float* w = w0;
+  float* head = head0;
+  if (i >= n0 * RGCN_HEAD) {
+    i -= n0 * RGCN_HEAD;
+    if (i >= n1 * RGCN_HEAD) return;
+    items = items1; w = w1; head = head1;
+  }
+  const rgcn_item it = items[i / RGCN_HEAD];
+  const int e = it.begin + (int)(i % RGCN_HEAD);
+  head[i] = e < it.end ? w[e] : 0.f;
+}
+
+int draw_impl(rgcn_edge_dropout* ed, const draw_params& p, int64_t* stats, hipStream_t stream) {
+  const rgcn_graph& v = ed->view;
+  const int64_t E = v.E, NR = v.N * v.R;
+  if (E <= 0) return RGCN_OK;                    // no edge: kept holds the zeros rgcn_edge_dropout_create left
+  // kernels only, no memset node: the counters are zero on entry (create, then every draw's last launch clears them)
+  k_ed_mark<<<grid_for(E, kMarkThreads), kMarkThreads, 0, stream>>>(v.dir[0].perm, ed->seg_f, E, p, ed->val[0], ed->count,
+                                                                   reinterpret_cast<unsigned long long*>(stats));
+  k_ed_weights<<<grid_for(std::max(2 * E, NR), kThreads), kThreads, 0, stream>>>(v.dir[1].perm, ed->seg_f, ed->seg_t, E, p,
+                                                                                ed->count, ed->val[0], ed->val[1], NR, ed->kept);
+  const int64_t n0 = v.dir[0].num_items[0], n1 = v.dir[1].num_items[0];
+  k_ed_heads<<<grid_for(std::max((n0 + n1) * RGCN_HEAD, NR), kThreads), kThreads, 0, stream>>>(
+      v.dir[0].items[0], n0, ed->val[0], ed->head_w[0], v.dir[1].items[0], n1, ed->val[1], ed->head_w[1], NR, ed->count);
+  RGCN_HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+int create_impl(const rgcn_graph* g, hipStream_t stream, rgcn_edge_dropout* ed) {
+  const int64_t E = g->E, NR = g->N * g->R;
+  ed->parent = g;
+  ed->view = *g;                                 // every pointer shared ...
+  RGCN_HIP_TRY(hipMalloc((void**)&ed->kept, (size_t)std::max<int64_t>(NR, 1) * sizeof(int32_t)));
+  RGCN_HIP_TRY(hipMalloc((void**)&ed->count, (size_t)std::max<int64_t>(NR, 1) * sizeof(int32_t)));
+  RGCN_HIP_TRY(hipMemsetAsync(ed->kept, 0, (size_t)std::max<int64_t>(NR, 1) * sizeof(int32_t), stream));
+  RGCN_HIP_TRY(hipMemsetAsync(ed->count, 0, (size_t)std::max<int64_t>(NR, 1) * sizeof(int32_t), stream));
+  for (int d = 0; d < 2; ++d) {                  // ... but the weights and their item-head copies
+    rgcn_csr& c = ed->view.dir[d];
+    c.weighted = true;
+    c.val = nullptr;
+    c.head_w = nullptr;
+    if (E > 0) RGCN_HIP_TRY(hipMalloc((void**)&ed->val[d], (size_t)E * sizeof(float)));
+    if (c.num_items[0] > 0)
+      RGCN_HIP_TRY(hipMalloc((void**)&ed->head_w[d], (size_t)c.num_items[0] * RGCN_HEAD * sizeof(float)));
+    c.val = ed->val[d];
+    c.head_w = ed->head_w[d];
+  }
+  // bounds that hold for every draw: a forward segment's weights sum to k * fl(1 / k) <= 1 + 2^-23 (the margin
+  // plan_structure gives a weighted structure); a transposed weight is <= 1, so a segment's sum is at most its length
+  ed->view.dir[0].weight_bound = (float)(1.0 + 1e-6);
+  std::vector<int32_t> rp((size_t)NR + 1);
+  RGCN_HIP_TRY(hipMemcpyAsync(rp.data(), g->dir[1].rowptr, (size_t)(NR + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  RGCN_HIP_TRY(hipStreamSynchronize(stream));
+  int32_t longest = 1;
+  for (int64_t s = 0; s < NR; ++s) longest = std::max(longest, rp[(size_t)s + 1] - rp[(size_t)s]);
+  ed->view.dir[1].weight_bound = (float)longest;
+  if (E > 0) {
+    RGCN_HIP_TRY(hipMalloc((void**)&ed->seg_f, (size_t)E * sizeof(int32_t)));
+    RGCN_HIP_TRY(hipMalloc((void**)&ed->seg_t, (size_t)E * sizeof(int32_t)));
+    k_ed_segments<<<grid_for(E, kThreads), kThreads, 0, stream>>>(g->dir[0].rowptr, NR, E, g->R, nullptr, ed->seg_f);
+    k_ed_segments<<<grid_for(E, kThreads), kThreads, 0, stream>>>(g->dir[1].rowptr, NR, E, g->R, g->dir[1].col, ed->seg_t);
+    RGCN_HIP_TRY(hipGetLastError());
+  }
+  // the draw p = 0 without a window: usable at once (threshold 0 drops nothing, whatever the key)
+  int64_t* rng = nullptr;
+  RGCN_HIP_TRY(hipMalloc((void**)&rng, 2 * sizeof(int64_t)));
+  int rc = hipMemsetAsync(rng, 0, 2 * sizeof(int64_t), stream) == hipSuccess ? RGCN_OK : RGCN_ERR_HIP;
+  if (rc == RGCN_OK) rc = draw_impl(ed, draw_params{nullptr, nullptr, rng, 0, 0u}, nullptr, stream);
+  if (rc == RGCN_OK && hipStreamSynchronize(stream) != hipSuccess) rc = RGCN_ERR_HIP;
+  (void)hipFree(rng);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rgcn_edge_dropout_create(const rgcn_graph* g, void* stream, rgcn_edge_dropout** out) {
+  if (!out) return RGCN_ERR_ARG;
+  *out = nullptr;
+  if (!g) return RGCN_ERR_ARG;
+  const rgcn_csr &f = g->dir[0], &t = g->dir[1];
+  if (!f.rowptr || !t.rowptr || f.weighted || !t.weighted || f.n_key != g->N || f.n_other != g->N || t.n_key != g->N ||
+      t.n_other != g->N)
+    return RGCN_ERR_UNSUPPORTED;
+  rgcn_edge_dropout* ed = new (std::nothrow) rgcn_edge_dropout();
+  if (!ed) return RGCN_ERR_HIP;
+  const int rc = create_impl(g, (hipStream_t)stream, ed);
+  if (rc != RGCN_OK) {
+    rgcn_edge_dropout_destroy(ed);
+    return rc;
+  }
+  *out = ed;
+  return RGCN_OK;
+}
+
+void rgcn_edge_dropout_destroy(rgcn_edge_dropout* ed) {
+  if (!ed) return;
+  for (int d = 0; d < 2; ++d) {
+    (void)hipFree(ed->val[d]);
+    (void)hipFree(ed->head_w[d]);
+  }
+  (void)hipFree(ed->kept);
+  (void)hipFree(ed->count);
+  (void)hipFree(ed->seg_f);
+  (void)hipFree(ed->seg_t);
+  delete ed;                                     // the shared arrays stay the parent's
+}
+
+const rgcn_graph* rgcn_edge_dropout_graph(const rgcn_edge_dropout* ed) { return ed ? &ed->view : nullptr; }
+
+const int32_t* rgcn_edge_dropout_kept(const rgcn_edge_dropout* ed) { return ed ? ed->kept : nullptr; }
+
+int rgcn_edge_dropout_kept_export(const rgcn_edge_dropout* ed, int32_t* out, void* stream) {
+  if (!ed) return RGCN_ERR_ARG;
+  const size_t nr = (size_t)(ed->view.N * ed->view.R);
+  if (nr && !out) return RGCN_ERR_ARG;           // (a graph without nodes has nothing to copy)
+  RGCN_ALIGN_TRY(4, out);
+  if (nr) RGCN_HIP_TRY(hipMemcpyAsync(out, ed->kept, nr * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return RGCN_OK;
+}
+
+int rgcn_edge_dropout_draw(rgcn_edge_dropout* ed, double p, const int64_t* rng, const int64_t* cursor, int64_t batch,
+                           const int64_t* position, int64_t* stats, void* stream) {
+  if (!ed || !rng || batch < 0) return RGCN_ERR_ARG;
+  if (!(p >= 0.0 && p < 1.0)) return RGCN_ERR_ARG;            // NaN fails both compares
+  RGCN_ALIGN_TRY(8, rng, cursor, position, stats);
+  const uint32_t threshold = (uint32_t)(uint64_t)(p * 4294967296.0);   // floor(p * 2^32) <= 2^32 - 1 for p < 1
+  return draw_impl(ed, draw_params{position, cursor, rng, batch, threshold}, stats, (hipStream_t)stream);
+}
+
+}  // extern "C"

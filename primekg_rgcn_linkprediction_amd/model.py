@@ -48,17 +48,21 @@ class DrugDiseaseRGCN(nn.Module):
         nn.init.xavier_uniform_(self.node_embeddings.weight)
 
     def forward(self, edge_index: Tensor, edge_type: Tensor,
-                node_indices: Optional[Tensor] = None) -> Tensor:
+                node_indices: Optional[Tensor] = None, graph=None) -> Tensor:
+        """``graph``: the view of an ``ops.EdgeDropout`` on this graph - messages then pass over the edges its last draw
+        kept.  Training mode only: in ``eval()`` (and under ``no_grad`` without dropout) the whole graph is used."""
         # the whole table is the layer-1 input (no lookup) unless a subset is asked for
         x = self.node_embeddings.weight if node_indices is None else self.node_embeddings(node_indices)
         p = self.dropout.p if self.training else 0.0
+        if graph is not None and graph.edge_dropout and not self.training:
+            graph = graph.parent
         if p < 1.0:
             # conv1 -> relu -> dropout -> conv2 (rgcn.py:123-128) as one fused autograd node; the
             # mask comes from torch's dropout kernel and RNG stream, as in the reference
-            return rgcn_encoder2(x, edge_index, edge_type, self.conv1, self.conv2, dropout_p=p)
-        x = self.conv1(x, edge_index, edge_type, activation="relu")      # p == 1: everything dropped
+            return rgcn_encoder2(x, edge_index, edge_type, self.conv1, self.conv2, dropout_p=p, graph=graph)
+        x = self.conv1(x, edge_index, edge_type, activation="relu", graph=graph)      # p == 1: everything dropped
         x = self.dropout(x)
-        return self.conv2(x, edge_index, edge_type)
+        return self.conv2(x, edge_index, edge_type, graph=graph)
 
     def get_node_embeddings(self, node_indices: Tensor) -> Tensor:
         return self.node_embeddings(node_indices)
@@ -81,25 +85,31 @@ class DrugDiseaseModel(nn.Module):
                                      dropout=decoder_dropout, decoder=decoder)
 
     def forward(self, edge_index: Tensor, edge_type: Tensor, head_indices: Tensor,
-                tail_indices: Tensor, relation_types: Tensor) -> Tensor:
-        node_embeddings = self.encoder(edge_index, edge_type)
+                tail_indices: Tensor, relation_types: Tensor, graph=None) -> Tensor:
+        node_embeddings = self._encode(edge_index, edge_type, graph)
         # rgcn.py:325-329: two row gathers + decoder, fused into one scoring kernel
         return self.decoder.score_triples(node_embeddings, head_indices, tail_indices, relation_types)
 
+    def _encode(self, edge_index: Tensor, edge_type: Tensor, graph=None) -> Tensor:
+        """the encoder's call, unchanged when no ``graph=`` override is given (an encoder without the keyword keeps working)"""
+        if graph is None:
+            return self.encoder(edge_index, edge_type)
+        return self.encoder(edge_index, edge_type, graph=graph)
+
     def bce_loss(self, edge_index: Tensor, edge_type: Tensor, head_indices: Tensor, tail_indices: Tensor,
-                 relation_types: Tensor, labels: Tensor, stats=None):
+                 relation_types: Tensor, labels: Tensor, stats=None, graph=None):
         """``(nn.BCEWithLogitsLoss()(self(...), labels), scores)`` - what ``Trainer`` needs per
         step (``train.py:291-300``) with the loss fused into the head kernels; ``stats``: see
-        ``LinkPredictor.bce_loss``."""
-        node_embeddings = self.encoder(edge_index, edge_type)
+        ``LinkPredictor.bce_loss``; ``graph``: see ``DrugDiseaseRGCN.forward``."""
+        node_embeddings = self._encode(edge_index, edge_type, graph)
         return self.decoder.bce_loss(node_embeddings, head_indices, tail_indices, relation_types, labels, stats)
 
     def softmax_loss(self, edge_index: Tensor, edge_type: Tensor, head_indices: Tensor, tail_indices: Tensor,
-                     relation_types: Tensor, **kwargs):
+                     relation_types: Tensor, graph=None, **kwargs):
         """``(mean loss, hits)``: the 1-vs-all softmax loss of the positives against every entity, the twin of
         ``bce_loss``; ``kwargs``: ``sides=``, ``known=``, ``node_class=``, ``stats=``, ``max_mask_bytes=`` of
-        ``LinkPredictor.softmax_loss``."""
-        node_embeddings = self.encoder(edge_index, edge_type)
+        ``LinkPredictor.softmax_loss``; ``graph``: see ``DrugDiseaseRGCN.forward``."""
+        node_embeddings = self._encode(edge_index, edge_type, graph)
         return self.decoder.softmax_loss(node_embeddings, head_indices, tail_indices, relation_types, **kwargs)
 
     def predict(self, edge_index: Tensor, edge_type: Tensor, head_indices: Tensor,

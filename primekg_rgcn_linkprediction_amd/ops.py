@@ -407,6 +407,8 @@ class BucketedGraph:
     """Owner of one ``rgcn_graph`` handle: the CSR-by-relation structures (forward and
     transposed) of a static multigraph, built once on the device."""
 
+    edge_dropout = False        # True on the view of an ``EdgeDropout``: weights rewritten in place by every draw
+
     def __init__(self, edge_index: torch.Tensor, edge_type: torch.Tensor, num_nodes: int,
                  num_relations: int):
         self._handle = None
@@ -788,6 +790,122 @@ def clear_graph_cache() -> None:
 
 
 # ----------------------------------------------------------------------------------
+# edge dropout + hidden batch edges (include/rgcn_edge_dropout.h)
+# ----------------------------------------------------------------------------------
+class _EdgeDropoutView(BucketedGraph):
+    """The graph an ``EdgeDropout`` draws into: both directions weighted, the structure shared with the parent, the
+    weights rewritten in place by every draw.  The gathers and transforms take it like any bucketed graph; everything
+    that would COPY weights out of the handle at build time is refused - such a copy goes stale at the next draw."""
+
+    edge_dropout = True
+
+    def _stale(self, what: str):
+        raise ValueError(f"{what} copies edge weights out of the structure when it is built; the weights of an edge-dropout "
+                         f"view change with every draw - use the parent graph")
+
+    def state(self) -> dict:
+        self._stale("state() / save()")
+
+    def row_blocks(self, block_rows: int):
+        self._stale("row_blocks()")
+
+    def fused_plan(self, inline_limit: int = 16, transposed: bool = False):
+        self._stale("fused_plan() (the one-kernel layers)")
+
+    def merged_transposed(self):
+        self._stale("merged_transposed() (the transform-first input gradient)")
+
+    def destroy(self) -> None:
+        self.__dict__.pop("_regions", None)       # recorded passes hold addresses of the view's arrays
+        self._handle = None                        # owned by the EdgeDropout, not by this object
+
+    def __del__(self):  # pragma: no cover
+        pass
+
+
+class EdgeDropout:
+    """Per-step edge dropout and hidden batch edges on ``graph`` (a whole graph: ``BucketedGraph(...)``, ``bucket``,
+    ``from_state``), drawn on the device (``rgcn_edge_dropout_*``).  ``.view`` is a bucketed graph of stable identity
+    whose per-edge weights every ``draw`` rewrites in place: ``aggregate(view, x)`` is the mean over the KEPT in-edges
+    of every (node, relation) - ``RGCNConv`` on ``edge_index[:, kept]`` - and ``aggregate(view, g, transposed=True)``
+    its adjoint.  ``graph`` must outlive this object; the draw happens outside any recorded pass, before the forward."""
+
+    def __init__(self, graph: BucketedGraph):
+        self._handle = None
+        if not isinstance(graph, BucketedGraph) or graph.bipartite or graph.weighted_shard or graph.edge_dropout:
+            raise ValueError("edge dropout views a whole graph (not a shard structure, not another view)")
+        handle = ctypes.c_void_p()
+        with _on(graph.device):
+            rc = _lib.load().rgcn_edge_dropout_create(graph.handle, _stream(), ctypes.byref(handle))
+        _lib.check(rc, "rgcn_edge_dropout_create")
+        self._handle, self.graph, self.device = handle, graph, graph.device
+        view = _EdgeDropoutView.__new__(_EdgeDropoutView)
+        view.device = graph.device
+        view.num_nodes, view.num_relations, view.num_other_nodes = graph.num_nodes, graph.num_relations, graph.num_nodes
+        view.num_edges = graph.num_edges
+        view.bipartite, view.weighted_shard = False, True
+        view.parent = graph
+        view._handle = ctypes.c_void_p(_lib.load().rgcn_edge_dropout_graph(handle))
+        self.view = view
+
+    @property
+    def handle(self) -> ctypes.c_void_p:
+        if self._handle is None:
+            raise RuntimeError("EdgeDropout was destroyed")
+        return self._handle
+
+    def draw(self, p: float, rng: torch.Tensor, cursor: Optional[torch.Tensor] = None, batch: int = 0,
+             position: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None) -> None:
+        """One draw into the view (asynchronous, capturable): every edge is dropped with probability ``p`` by the Philox
+        word of (its original column, ``cursor``, epoch); with ``position`` (int64[E]: where each column stands in the
+        epoch's order) the columns at positions ``[cursor, cursor + batch)`` - the batch's own edges - are hidden
+        too.  ``rng``: int64[2] = {seed, epoch}; ``cursor``: int64[1] or None (0); ``stats``: int64[2] or None,
+        accumulates (kept, hidden).  All on the graph's device."""
+        if not 0.0 <= float(p) < 1.0:
+            raise ValueError(f"edge dropout p must be in [0, 1), got {p}")
+        for name, t, n in (("rng", rng, 2), ("cursor", cursor, 1), ("position", position, self.graph.num_edges),
+                           ("stats", stats, 2)):
+            if t is None:
+                if name == "rng":
+                    raise ValueError("rng (int64[2] = {seed, epoch} on the device) is required")
+                continue
+            _need_gpu(name, t, torch.int64)
+            if t.numel() != n or t.device != self.device:
+                raise ValueError(f"{name} must be int64[{n}] on the graph's device")
+        if int(batch) < 0:
+            raise ValueError("batch must be >= 0")
+        with _on(self.device):
+            rc = _lib.load().rgcn_edge_dropout_draw(self.handle, float(p), _ptr(rng), _ptr(cursor), int(batch),
+                                                    _ptr(position), _ptr(stats), _stream())
+        _lib.check(rc, "rgcn_edge_dropout_draw")
+
+    def kept_counts(self) -> torch.Tensor:
+        """int32[N * R]: the kept edges of every (destination, relation) segment under the last draw (a copy)"""
+        nr = self.graph.num_nodes * self.graph.num_relations
+        with _on(self.device):
+            out = _empty(nr, dtype=torch.int32, device=self.device)
+            rc = _lib.load().rgcn_edge_dropout_kept_export(self.handle, _ptr(out), _stream())
+        _lib.check(rc, "rgcn_edge_dropout_kept_export")
+        return out
+
+    def destroy(self) -> None:
+        view = self.__dict__.get("view")
+        if view is not None:
+            view.destroy()
+        if self._handle is not None:
+            try:
+                _lib.load().rgcn_edge_dropout_destroy(self._handle)
+            finally:
+                self._handle = None
+
+    def __del__(self):  # pragma: no cover - interpreter teardown order
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+# ----------------------------------------------------------------------------------
 # aggregate (rows A3 + A4 / their autograd)
 # ----------------------------------------------------------------------------------
 # bench.py sets this to a list to collect (weighted, d, edges, segments, table rows, start_event, end_event) per
@@ -890,7 +1008,7 @@ def _gather(graph: BucketedGraph, x: torch.Tensor, transposed: bool, tail: Optio
                                              _ptr(amax_out), _stream())
             if measure and first == 0:
                 end.record()
-                weighted = bool(transposed) or (graph.bipartite and graph.weighted_shard)
+                weighted = bool(transposed) or (graph.weighted_shard and (graph.bipartite or graph.edge_dropout))
                 GATHER_EVENTS.append((weighted, d, graph.num_edges, graph.num_nodes * graph.num_relations,
                                       graph.num_other_nodes, beg, end))
         if rc == 0 and job is not None:

@@ -105,6 +105,23 @@ class Trainer:
                                  "int vector [num_nodes])")
             if not 1 <= int(getattr(args, "negative_tries", 8)) <= 16:
                 raise ValueError("--negative_tries must be in 1..16")
+        # --edge_dropout P / --hide_batch_edges (both off by default): per step, on the device, every train edge is
+        # dropped from the message-passing graph with probability P and / or the batch's own columns are hidden from it, so
+        # that a positive is not an edge the encoder has just averaged into both of its endpoints (ops.EdgeDropout)
+        self.edge_dropout_p = float(getattr(args, "edge_dropout", 0.0) or 0.0)
+        self.hide_batch_edges = bool(getattr(args, "hide_batch_edges", False))
+        self._edge_dropout = self._ed_stats = self._ed_position = None
+        self.edge_dropout_stats = (0, 0)       # (kept edges, hidden edges) summed over the steps of the last training epoch
+        self._ed_steps = 0                     # steps of that epoch: kept fraction = kept / (steps * train columns)
+        if self.edge_dropout_p or self.hide_batch_edges:
+            if not 0.0 <= self.edge_dropout_p < 1.0:
+                raise ValueError(f"--edge_dropout must be in [0, 1), got {self.edge_dropout_p}")
+            if device.type != "cuda":
+                raise ValueError("--edge_dropout / --hide_batch_edges run on the GPU only (the draw is a device kernel)")
+            from .model import DrugDiseaseRGCN
+            if not isinstance(getattr(model, "encoder", None), DrugDiseaseRGCN):
+                raise ValueError("--edge_dropout / --hide_batch_edges need the single-GPU encoder (DrugDiseaseRGCN): the "
+                                 "partitioned and replicated encoders of dist.py hold shard structures, which have no view")
         self.model = model.to(device)
         self.device, self.args = device, args
         self.train_data, self.val_data, self.full_graph = train_data, val_data, full_graph
@@ -120,6 +137,10 @@ class Trainer:
             for d, ei, et in ((train_data, self.train_edge_index, self.train_edge_type),
                               (full_graph, self.full_edge_index, self.full_edge_type)):
                 ops.bucket(ei, et, d["num_nodes"], d["num_relations"], sidecar=d.get("sidecar"))
+        if self.edge_dropout_p or self.hide_batch_edges:
+            self._edge_dropout = ops.EdgeDropout(ops.bucket(self.train_edge_index, self.train_edge_type,
+                                                            train_data["num_nodes"], train_data["num_relations"]))
+            self._ed_stats = torch.zeros(2, dtype=torch.int64, device=device)
         opt = {"adam": torch.optim.Adam, "adamw": torch.optim.AdamW}.get(args.optimizer)
         if opt is None:
             raise ValueError(f"Unknown optimizer: {args.optimizer}")
@@ -224,15 +245,16 @@ class Trainer:
         only documentation here - the position is whatever ``self._cursor`` holds."""
         if self.softmax:
             return self._softmax_step(lo, size, accum, update)
+        view = self._draw_edges(size)                   # before the sampler: both read the cursor of THIS batch
         heads, tails, rels, labels = self._make_batch(lo, size)
         fused = self._fused_bookkeeping
         if fused:
             # the criterion fused into the head; the launch that forms the mean also keeps the epoch's running sums
             # and moves the batch cursor on (device-side bookkeeping, no host sync, no elementwise launches)
             loss, scores = self.model.bce_loss(self.train_edge_index, self.train_edge_type, heads, tails, rels, labels,
-                                               stats=(self._loss_sum, self._correct, self._cursor, size))
+                                               stats=(self._loss_sum, self._correct, self._cursor, size), **view)
         else:
-            scores = self.model(self.train_edge_index, self.train_edge_type, heads, tails, rels)
+            scores = self.model(self.train_edge_index, self.train_edge_type, heads, tails, rels, **view)
             loss = self.criterion(scores, labels)
         # d(loss / accum) / d loss as a kept device scalar: `.backward()` would launch a fill for its implicit ones
         # tensor (and a division for the accumulation) in every step
@@ -248,15 +270,28 @@ class Trainer:
                 self._correct += ((scores.detach() > 0) == (labels > 0.5)).sum()
         return heads, tails, rels, labels, loss.detach()
 
+    def _draw_edges(self, size: int) -> dict:
+        """This step's message-passing graph: one draw into the trainer's edge-dropout view at the device cursor, keyed by
+        the sampler's ``(seed, epoch)`` -> the ``graph=`` keyword of the model's loss (empty without the flags).  Part of
+        the captured step: a replay draws at whatever the cursor then holds."""
+        if self._edge_dropout is None:
+            return {}
+        self._edge_dropout.draw(self.edge_dropout_p, self._rng, cursor=self._cursor, batch=size if self.hide_batch_edges else 0,
+                                position=self._ed_position if self.hide_batch_edges else None, stats=self._ed_stats)
+        return {"graph": self._edge_dropout.view}
+
     def _softmax_step(self, lo: int, size: int, accum: int = 1, update: bool = True):
         """``_step`` with ``--loss softmax``: the batch is ``size`` positives of the permutation and nothing else; the
         loss is the mean over sides and samples, the running sums take the summed loss and the number of hits (the
         target is a best eligible candidate).  Eager: ``lo`` is the position."""
         idx = self._order[lo:lo + size]
         heads, tails, rels = self.train_edge_index[0, idx], self.train_edge_index[1, idx], self.train_edge_type[idx]
+        if self._edge_dropout is not None:
+            self._cursor.fill_(lo)                      # (nothing else moves the cursor of an eager softmax step)
+        view = self._draw_edges(size)
         loss, _ = self.model.softmax_loss(self.train_edge_index, self.train_edge_type, heads, tails, rels,
                                           sides=self.softmax_sides, known=self._sm_known, node_class=self._sm_node_class,
-                                          stats=(self._loss_sum, self._correct))
+                                          stats=(self._loss_sum, self._correct), **view)
         (loss / accum if accum != 1 else loss).backward()
         if update:
             self._clip_and_update()
@@ -339,6 +374,12 @@ class Trainer:
             self._neg_stats.zero_()
         # the permutation is drawn on the host like the reference's torch.randperm(num_edges)
         self._order.copy_(torch.randperm(e))
+        if self._edge_dropout is not None:
+            self._ed_stats.zero_()
+            if self.hide_batch_edges:                # where every column stands in this epoch's order: one scatter per epoch
+                if self._ed_position is None:
+                    self._ed_position = torch.empty(e, device=self.device, dtype=torch.int64)
+                self._ed_position[self._order] = torch.arange(e, device=self.device)
         steps = -(-e // bsz)
         if max_steps is not None:
             steps = min(steps, max_steps)
@@ -365,6 +406,9 @@ class Trainer:
         result = (self._loss_sum / max(seen, 1)).item(), self._correct.item() / max(seen, 1)
         if self._neg_stats is not None:      # read back once per epoch, with the loss
             self.negative_stats = tuple(self._neg_stats.tolist())
+        if self._ed_stats is not None:
+            self.edge_dropout_stats = tuple(self._ed_stats.tolist())
+            self._ed_steps = steps
         if not (self.softmax and self.device.type != "cuda"):   # (--loss softmax on the CPU indexes through torch, which raises itself)
             ops.check_indices(self.device)   # an id outside the embedding table anywhere in the epoch: IndexError, here
         return result
@@ -450,6 +494,10 @@ class Trainer:
             self.val_losses.append(va_loss); self.val_accs.append(va_acc)
             negatives = ("" if not self.constrained_negatives else
                          " | Neg Rejected: %d | Neg Gave Up: %d" % self.negative_stats)
+            if self._edge_dropout is not None:
+                kept, hidden = self.edge_dropout_stats
+                drawn = max(1, self._ed_steps * self.train_edge_index.size(1))
+                negatives += " | Edges Kept: %.4f | Edges Hidden: %d" % (kept / drawn, hidden)
             logger.info("Epoch %d/%d | Time: %.2fs | Train Loss: %.4f | Train Acc: %.4f | Val Loss: %.4f | "
                         "Val Acc: %.4f%s", epoch, self.args.epochs, time.time() - t0, tr_loss, tr_acc, va_loss, va_acc,
                         negatives)
@@ -579,6 +627,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="the preprocessing's mappings.pt, or an .npz / .pt holding an int vector [num_nodes]")
     p.add_argument("--negative_tries", type=int, default=8,
                    help="draws per filtered negative before the last one is kept (1..16)")
+    p.add_argument("--edge_dropout", type=float, default=0.0, metavar="P",
+                   help="drop every train edge from the message-passing graph with probability P in every step (drawn on "
+                        "the device; Schlichtkrull et al. 2018); validation and evaluation use the whole graph")
+    p.add_argument("--hide_batch_edges", action="store_true",
+                   help="hide the batch's own columns from the message-passing graph of its step, so that a positive is "
+                        "not an edge the encoder can see (the reverse column of a pair stays)")
     p.add_argument("--no_hip_graph", action="store_true",
                    help="launch every training step eagerly instead of replaying one captured HIP graph")
     p.add_argument("--synthetic", action="store_true",
