@@ -164,20 +164,38 @@ __device__ inline float amax_reduce(const amax_loads& q) {
 // scans the (small, L2-resident) weights for their maximum itself - a second launch for it would cost more
 // than the redundant reads; scale_out[0] = 2^-eb for the consumers' epilogues.
 // ---------------------------------------------------------------------------------------
-constexpr int kPackThreads = 1024, kPackJobs = RGCN_PACK_JOBS;
+// Workgroup sizes, chosen by measurement (profiles/first_launch.txt; tools/pack_probe.hip builds the other sizes):
+// kPackThreads where a workgroup scans its layer's weights for their maximum (one round of 16,384 / threads float4 per
+// thread) and then packs kPackTiles tiles, kSplitThreads where every maximum is given (nothing to scan: a tile per
+// workgroup), kScanThreads for the launch that only takes maxima.
+#ifndef RGCN_PACK_THREADS
+#define RGCN_PACK_THREADS 512
+#endif
+#ifndef RGCN_PACK_TILES
+#define RGCN_PACK_TILES 1
+#endif
+#ifndef RGCN_SPLIT_THREADS
+#define RGCN_SPLIT_THREADS 256
+#endif
+#ifndef RGCN_SCAN_THREADS
+#define RGCN_SCAN_THREADS 1024
+#endif
+constexpr int kPackThreads = RGCN_PACK_THREADS, kSplitThreads = RGCN_SPLIT_THREADS, kScanThreads = RGCN_SCAN_THREADS;
+constexpr int kPackTiles = RGCN_PACK_TILES;
+constexpr int kPackJobs = RGCN_PACK_JOBS, kZeroMax = RGCN_PREP_ZERO_MAX;
+constexpr int kPackCapScan = 64, kPackCapGiven = 256;    // workgroups per layer: each scanning one repeats the layer's scan
 using pack_job = rgcn_pack_job;                  // (definitions and device bodies: rgcn_prep.h - the first gather of a
 using pack_jobs = rgcn_pack_jobs;                //  pass can carry this work as extra workgroups)
-__device__ inline void pack_body(const pack_job& J, float* red, int nblocks, int bid) {
-  rgcn_pack_body<kPackThreads>(J, red, nblocks, bid);
-}
 
-__global__ __launch_bounds__(kPackThreads) void k_pack_split(const pack_jobs JJ, float* __restrict__ zero, int zero_count) {
-  __shared__ float red[kPackThreads / 64];
+template <int THREADS, bool SCAN, int TILES>
+__global__ __launch_bounds__(THREADS) void k_pack_split(const pack_jobs JJ, float* __restrict__ zero, int zero_count) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[rgcn_pack_lds_bytes<TILES>()];
   // (on the side: the heads of `zero_count` amax buffers the coming pass publishes into, as rgcn_absmax clears them)
-  if (blockIdx.y == 0 && (int)threadIdx.x < zero_count)
-    for (int h = (int)blockIdx.x; h < RGCN_AMAX_HEADS; h += (int)gridDim.x)
-      zero[(size_t)threadIdx.x * RGCN_AMAX_FLOATS + h * RGCN_AMAX_HEAD_STRIDE] = 0.f;
-  pack_body(JJ.j[blockIdx.y], red, (int)gridDim.x, (int)blockIdx.x);   // one layer per grid row
+  if (blockIdx.y == 0)
+    for (int z = (int)threadIdx.x; z < zero_count; z += THREADS)
+      for (int h = (int)blockIdx.x; h < RGCN_AMAX_HEADS; h += (int)gridDim.x)
+        zero[(size_t)z * RGCN_AMAX_FLOATS + h * RGCN_AMAX_HEAD_STRIDE] = 0.f;
+  rgcn_pack_body<THREADS, SCAN, TILES>(JJ.j[blockIdx.y], lds, (int)blockIdx.x);   // one layer per grid row
 }
 
 // ---------------------------------------------------------------------------------------
@@ -715,17 +733,17 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
 // the kernels of the coming pass publish into).
 constexpr int kPrepTensors = RGCN_PREP_TENSORS;
 using absmax_multi_job = rgcn_absmax_multi_job;
-template <int THREADS>
+template <int THREADS, bool CLAMPED>
 __device__ inline void absmax_body(const absmax_multi_job& J, float* __restrict__ zero, int zero_count, float* red,
                                    int bid, int nblocks) {
-  rgcn_absmax_body<THREADS>(J, zero, zero_count, red, bid, nblocks);
+  rgcn_absmax_body<THREADS, CLAMPED>(J, zero, zero_count, red, bid, nblocks);
 }
 
 // (1024 threads per workgroup: 4 M floats are then ONE round of four loads per thread instead of four)
-__global__ __launch_bounds__(kPackThreads) void k_absmax_multi(const absmax_multi_job J, float* __restrict__ zero,
+__global__ __launch_bounds__(kScanThreads) void k_absmax_multi(const absmax_multi_job J, float* __restrict__ zero,
                                                                int zero_count) {
-  __shared__ float red[kPackThreads / 64];
-  absmax_body<kPackThreads>(J, zero, zero_count, red, (int)blockIdx.x, (int)gridDim.x);
+  __shared__ float red[kScanThreads / 64];
+  absmax_body<kScanThreads, false>(J, zero, zero_count, red, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // The first launch of a forward pass: grid row 0 takes max |x| of the pass's input table (and clears the amax buffers
@@ -734,12 +752,12 @@ __global__ __launch_bounds__(kPackThreads) void k_absmax_multi(const absmax_mult
 __global__ __launch_bounds__(kPackThreads) void k_absmax_pack(const absmax_multi_job J, float* __restrict__ zero,
                                                               int zero_count, const pack_jobs JJ, int pack_blocks,
                                                               int layers) {
-  __shared__ float red[kPackThreads / 64];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[rgcn_pack_lds_bytes<kPackTiles>()];
   // a flat grid: pack_blocks workgroups per layer first (their chain is the longer one), then the scan's
   const int b = (int)blockIdx.x, npack = pack_blocks * layers;
   RGCN_STAMP(0);
-  if (b < npack) pack_body(JJ.j[b / pack_blocks], red, pack_blocks, b % pack_blocks);
-  else absmax_body<kPackThreads>(J, zero, zero_count, red, b - npack, RGCN_AMAX_HEADS);
+  if (b < npack) rgcn_pack_body<kPackThreads, true, kPackTiles>(JJ.j[b / pack_blocks], lds, b % pack_blocks);
+  else absmax_body<kPackThreads, true>(J, zero, zero_count, reinterpret_cast<float*>(lds), b - npack, RGCN_AMAX_HEADS);
 #ifdef RGCN_STAMPS
   if (b >= npack) { RGCN_STAMP(1); RGCN_STAMP(2); }     // (a scanning workgroup: entry and end only)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1108,13 +1126,34 @@ pack_job make_pack_job(const float* weight, const float* root, int64_t R, int64_
   return j;
 }
 
+// plans the jobs for workgroups of `threads` threads and `tiles` tiles (`cap` of them per layer at most) -> the widest
+// layer's count
+int plan_pack_jobs(pack_jobs* JJ, int count, int threads, int tiles, int cap) {
+  int most = 1;
+  for (int l = 0; l < count; ++l) {
+    rgcn_pack_plan(&JJ->j[l], threads, tiles, cap);
+    most = std::max(most, JJ->j[l].nblocks);
+  }
+  return most;
+}
+// one launch of k_pack_split: small workgroups when no layer scans its weights
+void launch_pack_split(pack_jobs& JJ, int count, float* zero, int zero_count, hipStream_t stream) {
+  bool given = true;
+  for (int l = 0; l < count; ++l) given = given && JJ.j[l].w_amax;
+  if (given) {
+    const dim3 grid((unsigned)plan_pack_jobs(&JJ, count, kSplitThreads, 1, kPackCapGiven), (unsigned)count);
+    k_pack_split<kSplitThreads, false, 1><<<grid, kSplitThreads, 0, stream>>>(JJ, zero, zero_count);
+  } else {
+    const dim3 grid((unsigned)plan_pack_jobs(&JJ, count, kPackThreads, kPackTiles, kPackCapScan), (unsigned)count);
+    k_pack_split<kPackThreads, true, kPackTiles><<<grid, kPackThreads, 0, stream>>>(JJ, zero, zero_count);
+  }
+}
+
 int pack_weights(const float* weight, const float* root, int64_t R, int64_t d_in, int64_t d_out, void* packed,
                  hipStream_t stream) {
   pack_jobs JJ{};
   JJ.j[0] = make_pack_job(weight, root, R, d_in, d_out, packed, nullptr, nullptr);
-  const int64_t total = (R + (root ? 1 : 0)) * d_in * d_out;
-  dim3 grid((unsigned)std::min<int64_t>(64, ceil_div64(total, kPackThreads)), 1);
-  k_pack_split<<<grid, kPackThreads, 0, stream>>>(JJ, nullptr, 0);
+  launch_pack_split(JJ, 1, nullptr, 0, stream);
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
@@ -1277,7 +1316,7 @@ size_t rgcn_split_packed_bytes(int64_t R, int64_t d_in, int64_t d_out) { return 
 int rgcn_prep_fill(const float* x, int64_t numel, float* x_amax, float* zero_buffers, int zero_count, int count,
                    const float* const* weights, const float* const* roots, const int64_t* R, const int64_t* d_in,
                    const int64_t* d_out, void* const* packed, const size_t* packed_bytes_, int threads, rgcn_prep* out) {
-  if (numel < 0 || !x_amax || (numel > 0 && !x) || zero_count < 0 || zero_count > threads ||
+  if (numel < 0 || !x_amax || (numel > 0 && !x) || zero_count < 0 || zero_count > kZeroMax ||
       (zero_count > 0 && !zero_buffers) || !out)
     return RGCN_ERR_ARG;
   if (count < 1 || count > kPackJobs || !weights || !roots || !R || !d_in || !d_out || !packed || !packed_bytes_)
@@ -1287,17 +1326,14 @@ int rgcn_prep_fill(const float* x, int64_t numel, float* x_amax, float* zero_buf
   out->J.p[0] = x; out->J.n[0] = numel; out->J.out[0] = x_amax;
   out->zero = zero_buffers;
   out->zero_count = zero_count;
-  int64_t most = 0;
   for (int l = 0; l < count; ++l) {
     const int rc = rgcn_pack_layer_check(R[l], d_in[l], d_out[l], 4, weights[l], packed[l], packed_bytes_[l],
                                          packed_bytes(R[l], d_in[l], d_out[l]));
     if (rc != RGCN_OK) return rc;
     out->JJ.j[l] = make_pack_job(weights[l], roots[l], R[l], d_in[l], d_out[l], packed[l], nullptr, nullptr);
-    most = std::max<int64_t>(most, (R[l] + (roots[l] ? 1 : 0)) * d_in[l] * d_out[l]);
   }
-  // as many workgroups per layer as the 1,024-thread launch uses (each scans the layer's weights for their maximum
-  // itself: more of them would multiply that redundant scan), whatever their size
-  out->pack_blocks = (int)std::min<int64_t>(64, ceil_div64(most, kPackThreads));
+  // (each workgroup scans its layer's weights for their maximum itself: more of them would multiply that redundant scan)
+  out->pack_blocks = plan_pack_jobs(&out->JJ, count, threads, kPackTiles, kPackCapScan);
   out->layers = count;
   return RGCN_OK;
 }
@@ -1306,7 +1342,7 @@ extern "C" {
 
 int rgcn_absmax_multi(int count, const float* const* tensors, const int64_t* numels, float* const* outs,
                       float* zero_buffers, int zero_count, void* stream_) {
-  if (count < 1 || count > kPrepTensors || !tensors || !numels || !outs || zero_count < 0 || zero_count > kPackThreads ||
+  if (count < 1 || count > kPrepTensors || !tensors || !numels || !outs || zero_count < 0 || zero_count > kZeroMax ||
       (zero_count > 0 && !zero_buffers))
     return RGCN_ERR_ARG;
   absmax_multi_job J{};
@@ -1320,7 +1356,7 @@ int rgcn_absmax_multi(int count, const float* const* tensors, const int64_t* num
     RGCN_ALIGN_TRY(4, outs[t]);
   }
   RGCN_ALIGN_TRY(4, zero_buffers);
-  k_absmax_multi<<<RGCN_AMAX_HEADS, kPackThreads, 0, (hipStream_t)stream_>>>(J, zero_buffers, zero_count);
+  k_absmax_multi<<<RGCN_AMAX_HEADS, kScanThreads, 0, (hipStream_t)stream_>>>(J, zero_buffers, zero_count);
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }
@@ -1364,24 +1400,21 @@ int rgcn_weights_split_pack_multi(int count, const float* const* weights, const 
                                   const size_t* packed_bytes_, float* zero_buffers, int zero_count, void* stream_) {
   if (count < 1 || count > kPackJobs || !weights || !roots || !R || !d_in || !d_out || !packed || !packed_bytes_)
     return RGCN_ERR_ARG;
-  if (zero_count < 0 || zero_count > kPackThreads || (zero_count > 0 && !zero_buffers)) return RGCN_ERR_ARG;
+  if (zero_count < 0 || zero_count > kZeroMax || (zero_count > 0 && !zero_buffers)) return RGCN_ERR_ARG;
   pack_jobs JJ{};
-  int64_t most = 0;
   for (int l = 0; l < count; ++l) {
     const int rc = rgcn_pack_layer_check(R[l], d_in[l], d_out[l], 4, weights[l], packed[l], packed_bytes_[l],
                                          packed_bytes(R[l], d_in[l], d_out[l]));
     if (rc != RGCN_OK) return rc;
     JJ.j[l] = make_pack_job(weights[l], roots[l], R[l], d_in[l], d_out[l], packed[l], w_amax ? w_amax[l] : nullptr,
                             r_amax ? r_amax[l] : nullptr);
-    most = std::max<int64_t>(most, (R[l] + (roots[l] ? 1 : 0)) * d_in[l] * d_out[l]);
   }
   for (int l = 0; l < count; ++l) {
     RGCN_ALIGN_TRY(16, weights[l], roots[l], packed[l]);
     RGCN_ALIGN_TRY(4, w_amax ? w_amax[l] : nullptr, r_amax ? r_amax[l] : nullptr);
   }
   RGCN_ALIGN_TRY(4, zero_buffers);
-  dim3 grid((unsigned)std::min<int64_t>(64, ceil_div64(most, kPackThreads)), (unsigned)count);
-  k_pack_split<<<grid, kPackThreads, 0, (hipStream_t)stream_>>>(JJ, zero_buffers, zero_count);
+  launch_pack_split(JJ, count, zero_buffers, zero_count, (hipStream_t)stream_);
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }

@@ -1,7 +1,9 @@
 // Round 4 probe: where do the ~13 us of the first launch of a forward pass (k_absmax_pack: max |x| + both layers' split
 // weights) go?  Times the launch and its parts on C2's shapes, each as 20 back-to-back launches between events:
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 [-DRGCN_STAMPS] tools/pack_probe.hip -o tools/pack_probe && tools/pack_probe
-// (with -DRGCN_STAMPS: also the in-kernel wall clock of the launch's phases, per workgroup)
+// (with -DRGCN_STAMPS: also the in-kernel wall clock of the launch's phases, per workgroup; with
+// -DRGCN_PACK_THREADS=, -DRGCN_SPLIT_THREADS=, -DRGCN_SCAN_THREADS= 256 | 512 | 1024: the other workgroup sizes of
+// the scanning pack, the pack with given maxima and the maxima-only launch - profiles/first_launch.txt)
 #include "../primekg_rgcn_linkprediction_amd/csrc/rgcn_transform_split.hip"
 
 #include <algorithm>
@@ -44,6 +46,8 @@ int main() {
   const float* tens[5] = {x, w1, r1, w2, r2}; const int64_t nums[5] = {N * 64, R * 64 * 128, 64 * 128, R * 128 * 128, 128 * 128};
   float* outs[5] = {ax, wa[0], ra[0], wa[1], ra[1]};
   int rc = 0;
+  printf("workgroups of %d (scanning pack), %d (pack, maxima given), %d (maxima only) threads\n", kPackThreads, kSplitThreads,
+         kScanThreads);
   auto timed = [&](auto launch, const char* name) {
     for (int i = 0; i < 5; ++i) launch();
     hipEventRecord(beg, stream);
@@ -70,17 +74,22 @@ int main() {
   hipStreamSynchronize(stream);
   std::vector<unsigned long long> st(8192 * 4);
   hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(g_rgcn_stamps), st.size() * sizeof(unsigned long long));
-  const int npack = 128, total = 128 + RGCN_AMAX_HEADS;
+  rgcn_prep pp;
+  rc = rgcn_prep_fill(x, N * 64, ax, zero, 1, 2, ws, rs, Rs, di, dout, pk, pb, kPackThreads, &pp);
+  const int npack = pp.pack_blocks * pp.layers, total = npack + RGCN_AMAX_HEADS;
+  std::vector<char> works(total, 1);             // (a launch is as wide as its widest layer: the others' spare workgroups leave at once)
+  int working = 0;
+  for (int w = 0; w < npack; ++w) working += works[w] = (w % pp.pack_blocks) < pp.JJ.j[w / pp.pack_blocks].nblocks;
   unsigned long long t0 = ~0ull, t3 = 0;
   for (int w = 0; w < total; ++w) { t0 = std::min(t0, st[w * 4]); t3 = std::max(t3, st[w * 4 + 3]); }
   auto med = [&](int lo, int hi, auto f) {
     std::vector<double> v;
-    for (int w = lo; w < hi; ++w) v.push_back(f(w) * 0.01);
+    for (int w = lo; w < hi; ++w) if (works[w]) v.push_back(f(w) * 0.01);
     std::sort(v.begin(), v.end());
     printf(" min %5.2f median %5.2f max %5.2f us\n", v.front(), v[v.size() / 2], v.back());
   };
-  printf("  one launch, first entry -> last exit %.2f us\n", (t3 - t0) * 0.01);
-  printf("  pack workgroups (128): entry after first entry  "); med(0, npack, [&](int w) { return (double)(st[w * 4] - t0); });
+  printf("  one launch of %d workgroups, first entry -> last exit %.2f us\n", total, (t3 - t0) * 0.01);
+  printf("  pack workgroups (%3d): entry after first entry  ", working); med(0, npack, [&](int w) { return (double)(st[w * 4] - t0); });
   printf("                         entry -> maximum known   "); med(0, npack, [&](int w) { return (double)(st[w * 4 + 1] - st[w * 4]); });
   printf("                         -> every store issued    "); med(0, npack, [&](int w) { return (double)(st[w * 4 + 2] - st[w * 4 + 1]); });
   printf("                         -> stores drained        "); med(0, npack, [&](int w) { return (double)(st[w * 4 + 3] - st[w * 4 + 2]); });
