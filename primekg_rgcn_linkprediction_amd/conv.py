@@ -27,9 +27,11 @@ from . import ops
 
 def _glorot(t: Optional[Tensor]) -> None:
     # PyG nn.inits.glorot: U(-a, a), a = sqrt(6 / (size(-2) + size(-1)))
+    # written to the parameter itself, not through ``.data``: the write must move ``_version`` (``ops.amax_hint``)
     if t is not None:
         bound = math.sqrt(6.0 / (t.size(-2) + t.size(-1)))
-        t.data.uniform_(-bound, bound)
+        with torch.no_grad():
+            t.uniform_(-bound, bound)
 
 
 def _table(x: Tensor, gather_dtype) -> Tensor:
@@ -771,7 +773,8 @@ class RGCNConv(nn.Module):
         _glorot(self.comp)
         _glorot(self.root)
         if self.bias is not None:
-            self.bias.data.zero_()
+            with torch.no_grad():
+                self.bias.zero_()
 
     def effective_weight(self) -> Tensor:
         """``weight`` or the basis composition ``comp[R, B] @ weight[B, d_in*d_out]`` (row A5)."""

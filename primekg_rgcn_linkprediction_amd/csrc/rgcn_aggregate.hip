@@ -457,10 +457,10 @@ int aggregate_levels(const rgcn_graph* g, int transposed, int first, int last, c
     RGCN_HIP_TRY(hipGetLastError());
     return RGCN_OK;
   }
-  if (!agg || d <= 0 || (d & 3) || (half_in && (d & 7))) return RGCN_ERR_ARG;
+  if (d <= 0 || (d & 3) || (half_in && (d & 7))) return RGCN_ERR_ARG;
   if (!c->rowptr) return RGCN_ERR_ARG;   // direction not built
-  if (c->n_key == 0) return RGCN_OK;
-  if (!x) return RGCN_ERR_ARG;
+  if (c->n_key == 0) return RGCN_OK;     // no row to write: an empty result has no address
+  if (!agg || !x) return RGCN_ERR_ARG;
   if (d > (1 << 20)) return RGCN_ERR_UNSUPPORTED;
   if (first < 0 || last > c->num_levels || first > last) return RGCN_ERR_ARG;
   if (c->num_partials > 0 &&

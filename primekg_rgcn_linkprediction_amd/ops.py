@@ -153,21 +153,33 @@ def _check_amax(name: str, t: Optional[torch.Tensor], device) -> None:
 _AMAX_HINTS = {}
 
 
+def _drop_amax_hint(key: int, ref) -> None:
+    h = _AMAX_HINTS.get(key)
+    if h is not None and h[0] is ref:                       # (not the hint of a newer tensor that took over the id)
+        del _AMAX_HINTS[key]
+
+
 def set_amax_hint(t: torch.Tensor, buf: Optional[torch.Tensor]) -> None:
+    """``buf`` (an amax buffer) holds ``max |t|`` as of now; ``None`` withdraws the hint.  The hint stands for this
+    tensor object at this ``_version`` and this ``data_ptr()``: an in-place op through torch (under ``no_grad``, on
+    ``t.detach()``) or ``t.data = other`` loses it.  An in-place write THROUGH ``t.data`` (``t.data.mul_(2)``) moves
+    neither and cannot be detected: whoever writes a hinted tensor that way calls ``set_amax_hint(t, None)``."""
     import weakref
     if buf is None:
         _AMAX_HINTS.pop(id(t), None)
         return
     _check_amax("buf", buf, t.device)
     key = id(t)
-    _AMAX_HINTS[key] = (weakref.ref(t, lambda _, k=key: _AMAX_HINTS.pop(k, None)), buf, t._version)
+    ref = weakref.ref(t, lambda r, k=key: _drop_amax_hint(k, r))
+    _AMAX_HINTS[key] = (ref, buf, t._version, t.data_ptr())
 
 
 def amax_hint(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     if t is None:
         return None
     h = _AMAX_HINTS.get(id(t))
-    if h is None or h[0]() is not t or h[2] != t._version or not t.is_contiguous() or t.dtype != torch.float32:
+    if (h is None or h[0]() is not t or h[2] != t._version or h[3] != t.data_ptr() or not t.is_contiguous()
+            or t.dtype != torch.float32):
         return None
     return h[1]
 
@@ -532,6 +544,11 @@ class BucketedGraph:
             raise RuntimeError("BucketedGraph was destroyed")
         return self._handle
 
+    @property
+    def alive(self) -> bool:
+        """may a recorded pass that holds this graph's addresses still be issued? (``Region.run``)"""
+        return self._handle is not None
+
     def tile_mask_ptr(self, transposed: bool) -> Optional[int]:
         """device pointer (as int) of the relation-occupancy mask of 32-row tiles, or None"""
         if self.bipartite and transposed:
@@ -701,6 +718,12 @@ class BucketedGraph:
         return self._merged
 
     def destroy(self) -> None:
+        # recorded passes hold the handle and addresses of its arrays as immediates: they go first, and with them every
+        # address remembered for the life of the handle
+        for memo in ("_regions", "_mask_ptrs", "_row_mask_ptrs"):
+            self.__dict__.pop(memo, None)
+        for key in [k for k, hit in _GRAPH_CACHE.items() if hit[0] is self]:
+            del _GRAPH_CACHE[key]                       # ``bucket`` must not hand this object out again
         merged = getattr(self, "_merged", None)
         if merged is not None:
             merged.destroy()
@@ -761,8 +784,10 @@ def bucket(edge_index: torch.Tensor, edge_type: torch.Tensor, num_nodes: int,
            tuple(edge_index.shape), int(num_nodes), int(num_relations), str(edge_index.device))
     hit = _GRAPH_CACHE.get(key)
     if hit is not None:
-        _GRAPH_CACHE.move_to_end(key)
-        return hit[0]
+        if hit[0].alive:
+            _GRAPH_CACHE.move_to_end(key)
+            return hit[0]
+        del _GRAPH_CACHE[key]                          # destroyed behind the cache's back: build again
     g = None
     if sidecar is not None and os.path.exists(sidecar):
         _need_gpu("edge_index", edge_index, torch.int64)
@@ -815,8 +840,21 @@ class _EdgeDropoutView(BucketedGraph):
     def merged_transposed(self):
         self._stale("merged_transposed() (the transform-first input gradient)")
 
+    @property
+    def handle(self) -> ctypes.c_void_p:
+        if self._handle is None:
+            raise RuntimeError("BucketedGraph was destroyed")
+        if not self.parent.alive:                  # every index array of the view is the parent's
+            raise RuntimeError("the parent BucketedGraph of this edge-dropout view was destroyed")
+        return self._handle
+
+    @property
+    def alive(self) -> bool:
+        return self._handle is not None and self.parent.alive
+
     def destroy(self) -> None:
-        self.__dict__.pop("_regions", None)       # recorded passes hold addresses of the view's arrays
+        for memo in ("_regions", "_mask_ptrs", "_row_mask_ptrs"):
+            self.__dict__.pop(memo, None)          # recorded passes hold addresses of the view's arrays
         self._handle = None                        # owned by the EdgeDropout, not by this object
 
     def __del__(self):  # pragma: no cover
@@ -828,7 +866,8 @@ class EdgeDropout:
     ``from_state``), drawn on the device (``rgcn_edge_dropout_*``).  ``.view`` is a bucketed graph of stable identity
     whose per-edge weights every ``draw`` rewrites in place: ``aggregate(view, x)`` is the mean over the KEPT in-edges
     of every (node, relation) - ``RGCNConv`` on ``edge_index[:, kept]`` - and ``aggregate(view, g, transposed=True)``
-    its adjoint.  ``graph`` must outlive this object; the draw happens outside any recorded pass, before the forward."""
+    its adjoint.  ``graph`` must outlive this object (once it is destroyed ``draw``, ``kept_counts`` and the view's
+    ``handle`` raise); the draw happens outside any recorded pass, before the forward."""
 
     def __init__(self, graph: BucketedGraph):
         self._handle = None
@@ -852,6 +891,8 @@ class EdgeDropout:
     def handle(self) -> ctypes.c_void_p:
         if self._handle is None:
             raise RuntimeError("EdgeDropout was destroyed")
+        if not self.graph.alive:                   # the draw walks the parent's index arrays
+            raise RuntimeError("the parent BucketedGraph of this EdgeDropout was destroyed")
         return self._handle
 
     def draw(self, p: float, rng: torch.Tensor, cursor: Optional[torch.Tensor] = None, batch: int = 0,
@@ -861,6 +902,7 @@ class EdgeDropout:
         epoch's order) the columns at positions ``[cursor, cursor + batch)`` - the batch's own edges - are hidden
         too.  ``rng``: int64[2] = {seed, epoch}; ``cursor``: int64[1] or None (0); ``stats``: int64[2] or None,
         accumulates (kept, hidden).  All on the graph's device."""
+        handle = self.handle                       # raises once this object or its parent graph is destroyed
         if not 0.0 <= float(p) < 1.0:
             raise ValueError(f"edge dropout p must be in [0, 1), got {p}")
         for name, t, n in (("rng", rng, 2), ("cursor", cursor, 1), ("position", position, self.graph.num_edges),
@@ -875,16 +917,17 @@ class EdgeDropout:
         if int(batch) < 0:
             raise ValueError("batch must be >= 0")
         with _on(self.device):
-            rc = _lib.load().rgcn_edge_dropout_draw(self.handle, float(p), _ptr(rng), _ptr(cursor), int(batch),
+            rc = _lib.load().rgcn_edge_dropout_draw(handle, float(p), _ptr(rng), _ptr(cursor), int(batch),
                                                     _ptr(position), _ptr(stats), _stream())
         _lib.check(rc, "rgcn_edge_dropout_draw")
 
     def kept_counts(self) -> torch.Tensor:
         """int32[N * R]: the kept edges of every (destination, relation) segment under the last draw (a copy)"""
+        handle = self.handle                       # raises once this object or its parent graph is destroyed
         nr = self.graph.num_nodes * self.graph.num_relations
         with _on(self.device):
             out = _empty(nr, dtype=torch.int32, device=self.device)
-            rc = _lib.load().rgcn_edge_dropout_kept_export(self.handle, _ptr(out), _stream())
+            rc = _lib.load().rgcn_edge_dropout_kept_export(handle, _ptr(out), _stream())
         _lib.check(rc, "rgcn_edge_dropout_kept_export")
         return out
 
@@ -3653,6 +3696,29 @@ def _signature(t):
     return (t.dtype, tuple(t.shape), t.get_device())           # (-1 on the host)
 
 
+def _overlaps(ptrs, sizes) -> tuple:
+    """which of a pass's inputs share bytes, and how: ``((i, j, ptrs[j] - ptrs[i]), ...)`` over the pairs i < j whose
+    spans ``[ptr, ptr + size)`` overlap - ``()`` for inputs that lie apart (one sort and one walk: this runs on every
+    replay).  An absent or empty input (size 0) holds no byte.  The record names a pointer after the FIRST input whose
+    span holds it, so a recorded list is right exactly for calls whose inputs overlap the way the recorded ones did:
+    tied weights, ``out.backward(x)``, a shard's own rows handed in as their own table."""
+    spans = sorted((p, p + n, k) for k, (p, n) in enumerate(zip(ptrs, sizes)) if n)
+    reach = 0
+    for lo, hi, _ in spans:
+        if lo < reach:
+            break
+        reach = hi
+    else:
+        return ()
+    pairs = []
+    for a, (_, hi, i) in enumerate(spans):
+        for lo, _, j in spans[a + 1:]:
+            if lo >= hi:
+                break
+            pairs.append((i, j, ptrs[j] - ptrs[i]) if i < j else (j, i, ptrs[i] - ptrs[j]))
+    return tuple(sorted(pairs))
+
+
 class _Proxy:
     def __init__(self, rec):
         self._rec, self._real = rec, _lib.load()
@@ -3693,6 +3759,8 @@ class _Recorder:
             self.inputs = [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) if t is not None else None
                            for t in inputs]
             self.input_signature = [_signature(t) for t in inputs]
+            self.input_bytes = [s[1] - s[0] if s is not None else 0 for s in self.inputs]
+            self.input_overlaps = _overlaps([s[0] if s is not None else 0 for s in self.inputs], self.input_bytes)
             self.proxy = _Proxy(self)
 
     def alloc(self, shape, dtype, device):
@@ -3839,10 +3907,12 @@ class _Plan:
         # what the recorded addresses stand for: a later call whose inputs differ in type, shape or place must not be
         # replayed (the wrappers would have refused it; the native list would read the wrong bytes)
         self.signature = rec.input_signature
+        # ... and how the recorded inputs lay to each other: an address inside two of them was noted under the first
+        self.input_bytes, self.overlaps = rec.input_bytes, rec.input_overlaps
 
     def matches(self, inputs) -> bool:
-        """the inputs of this call are what the recorded addresses stand for (a few attribute reads per input: this runs
-        on every replay)"""
+        """the inputs of this call are what the recorded addresses stand for: type, shape, device and density one by
+        one, and the same overlaps among them (a few attribute reads per input: this runs on every replay)"""
         sigs = self.signature
         if len(inputs) != len(sigs):
             return False
@@ -3857,7 +3927,7 @@ class _Plan:
             elif (t.dtype is not sig[0] or t.shape != sig[1] or t.get_device() != sig[2]
                   or not t.is_contiguous()):                 # (a strided input would be read as dense through its data_ptr)
                 return False
-        return True
+        return _overlaps([t.data_ptr() if t is not None else 0 for t in inputs], self.input_bytes) == self.overlaps
 
     def run(self, inputs, want, fill=None):
         """-> list of outputs: tensors for the positions in `want`, Lazy for the rest.  `fill`: a byte value the arena
@@ -3918,6 +3988,8 @@ class Region:
         tensors = list(tensors)
         if not REGIONS or GATHER_EVENTS is not None or GEMM_EVENTS is not None or FUSED_EVENTS is not None or _REC is not None:
             return self._eager(tensors, static)
+        if not getattr(owner, "alive", True):                # a destroyed graph: no plan is kept, looked up or issued for
+            return self._eager(tensors, static)              # it - the wrappers say so by name
         store = owner.__dict__.setdefault("_regions", {})
         full_key = (self.name, key, GEMM_PRECISION)
         state = store.get(full_key)
