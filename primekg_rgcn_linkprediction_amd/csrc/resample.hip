@@ -308,16 +308,6 @@ __global__ __launch_bounds__(kThreads) void k_resample_ranks(
   else if (q - 2 < nk) hits[row * nk + (q - 2)] = a;
 }
 
-// the sticky index-error flag of the current device, looked up once per device (not a stream operation)
-int* index_error_flag() {
-  static int* flags[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  if (dev < 0 || dev >= 64) return rgcn_index_error_flag();
-  if (!flags[dev]) flags[dev] = rgcn_index_error_flag();
-  return flags[dev];
-}
-
 inline int check_sizes(int64_t samples, int64_t num_units, int64_t replicates) {
   if (samples < 0 || num_units <= 0 || replicates < 0) return RGCN_ERR_ARG;
   if (samples > RGCN_RESAMPLE_MAX_SAMPLES || num_units > INT32_MAX || replicates > RGCN_RESAMPLE_MAX_REPLICATES)
@@ -349,7 +339,7 @@ extern "C" int rgcn_resample_curves(const uint8_t* label, const int32_t* unit, c
   RGCN_ALIGN_TRY(16, unit);
   RGCN_ALIGN_TRY(8, wp, wn, auc2, ap, tp, fp);
   RGCN_ALIGN_TRY(4, label, tie_end);
-  int* flag = index_error_flag();
+  int* flag = rgcn_index_error_flag();
   if (!flag) return RGCN_ERR_HIP;
   const uint64_t s = (uint64_t)seed;
   k_resample_curves<<<groups_of(replicates), kThreads, 0, (hipStream_t)stream_>>>(
@@ -368,7 +358,7 @@ extern "C" int rgcn_resample_ranks(const int64_t* rank, const int32_t* unit, int
   if (m > 0 && (!rank || !unit)) return RGCN_ERR_ARG;
   RGCN_ALIGN_TRY(8, rank, w_sum, rank_sum, hits, rr_sum);
   RGCN_ALIGN_TRY(4, unit, k_values);
-  int* flag = index_error_flag();
+  int* flag = rgcn_index_error_flag();
   if (!flag) return RGCN_ERR_HIP;
   const uint64_t s = (uint64_t)seed;
   k_resample_ranks<<<groups_of(replicates), kThreads, 0, (hipStream_t)stream_>>>(

@@ -146,7 +146,9 @@ struct rgcn_graph {
 };
 
 // Device address of the current device's sticky index-error flag (distmult.hip; rgcn_index_error_fetch reads and
-// clears it) for kernels of other translation units that meet an id outside its table.  NULL if HIP fails.
+// clears it) for the kernels that meet an id outside its table: they take it as a parameter.  NULL if HIP fails.
+// The address is looked up on the first call per device and kept.  That lookup is not a stream operation, so a call
+// that is being captured into a HIP graph must not make it: an eager call on the device comes first.
 __attribute__((visibility("hidden"))) int* rgcn_index_error_flag();
 
 // ---------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // The ordered scatter, whole: contribution rows plus int32 keys in, one row per key out, every sum in slot order, so two
-// runs give the same bits.  Users: distmult.hip (the DistMult backward, rgcn_segment_sum), complex.hip (the ComplEx
-// backward) and transe.hip (the TransE step).
+// runs give the same bits.  Users: rgcn_decoder_head.h (the backward of the DistMult and ComplEx heads, for distmult.hip
+// and complex.hip), distmult.hip (rgcn_segment_sum, the loss reduction), complex.hip (the query launch's lane groups) and
+// transe.hip (the TransE step).
 //   - rgcn_pick_group / RGCN_DISPATCH_G: the lane group of d/4 lanes per sample of the contribution launches.
 //   - rgcn_checked_row: an id outside its table is clamped to row 0 and the library's sticky flag raised.
 //   - stage_keys / earlier_slot_has: the prologue of the one-wave-per-slot kernels (k_scatter_rows, k_transe_apply): the
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(64 * kScatterWaves) void k_scatter_rows(const int32
   }
 }
 
-// the scatter launch of a head's backward (distmult.hip, complex.hip): the instance by where the S keys fit
+// the scatter launch of a head's backward (rgcn_decoder_head.h): the instance by where the S keys fit
 inline void rgcn_scatter_rows(const int32_t* keys, int S, const float* rows, int d, float* out, hipStream_t stream) {
   const unsigned grid = (unsigned)((S + kScatterWaves - 1) / kScatterWaves);
   if (S <= kKeysInLds) k_scatter_rows<true><<<grid, 64 * kScatterWaves, 0, stream>>>(keys, S, rows, d, out);

@@ -397,15 +397,6 @@ inline SoftmaxPlan plan_softmax(int64_t batch, int64_t num_entities, int64_t sli
   return p;
 }
 
-int* index_error_flag() {
-  static int* flags[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  if (dev < 0 || dev >= 64) return rgcn_index_error_flag();
-  if (!flags[dev]) flags[dev] = rgcn_index_error_flag();
-  return flags[dev];
-}
-
 // the checks both entry points share, in the header's order
 inline int check_shape(int64_t batch, int64_t num_entities, int64_t d, int64_t slices, int64_t num_classes,
                        const uint32_t* allow, const int32_t* query_class) {
@@ -467,7 +458,7 @@ int rgcn_softmax_lse(const float* q, const float* emb, const int64_t* target, co
   RGCN_ALIGN_TRY(8, target);
   RGCN_ALIGN_TRY(4, allow, query_class, exclude, lse, true_score, row_max, loss, hit);
   hipStream_t stream = (hipStream_t)stream_;
-  int* flag = index_error_flag();
+  int* flag = rgcn_index_error_flag();
   if (!flag) return RGCN_ERR_HIP;
   const SoftmaxPlan p = plan_softmax(batch, num_entities, slices);
   static bool raised[64] = {};
@@ -506,7 +497,7 @@ int rgcn_softmax_grad(const float* g, const float* q, const float* emb, const in
   RGCN_ALIGN_TRY(16, q, emb, dq, dE, workspace);
   RGCN_ALIGN_TRY(8, target);
   RGCN_ALIGN_TRY(4, g, lse, allow, query_class, exclude);
-  int* flag = index_error_flag();
+  int* flag = rgcn_index_error_flag();
   if (!flag) return RGCN_ERR_HIP;
   const int classes = allow ? (int)num_classes : 0;
   const int nb = (int)((d / 32 + 1) / 2);

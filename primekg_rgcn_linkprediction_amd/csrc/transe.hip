@@ -166,17 +166,6 @@ Layout layout(int64_t batch, int64_t d, int64_t R) {
 
 constexpr int64_t kMaxBatch = (int64_t)1 << 28;  // 4 * batch slots are counted in an int
 
-// the sticky index-error flag of the current device, looked up once per device: the lookup is not a stream operation,
-// so a step that is being captured into a HIP graph must not make it (an eager step comes first)
-int* index_error_flag() {
-  static int* flags[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  if (dev < 0 || dev >= 64) return rgcn_index_error_flag();
-  if (!flags[dev]) flags[dev] = rgcn_index_error_flag();
-  return flags[dev];
-}
-
 }  // namespace
 
 extern "C" {
@@ -199,7 +188,7 @@ int rgcn_transe_step(float* emb, int64_t num_nodes, float* rel, int64_t num_rela
   RGCN_ALIGN_TRY(8, heads, tails, rels, loss_sum, active_sum);
   RGCN_ALIGN_TRY(4, loss_mean);
   hipStream_t stream = (hipStream_t)stream_;
-  int* flag = index_error_flag();
+  int* flag = rgcn_index_error_flag();
   if (!flag) return RGCN_ERR_HIP;
   char* ws = (char*)workspace;
   float* dpn = (float*)(ws + l.dpn);

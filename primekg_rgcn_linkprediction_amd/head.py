@@ -24,43 +24,52 @@ from torch import Tensor
 from . import ops
 
 
-class _DistMultFunction(torch.autograd.Function):
-    """scores[b] = sum_d H[hi(b)] * Rm[ri(b)] * T[ti(b)]; an index of None means row b."""
+def _head_op(decoder: str, call: str):
+    """the ``ops`` entry of a decoder of ``DECODERS``: ``ops.distmult_fwd``, ``ops.complex_bce_bwd``, ..."""
+    return getattr(ops, f"{decoder}_{call}")
+
+
+def _operands(h, h_idx, t, t_idx, r, r_idx):
+    """-> the six operands contiguous, the batch, and whether head and tail are gathered from one table"""
+    h, t, r = h.contiguous(), t.contiguous(), r.contiguous()
+    h_idx, t_idx, r_idx = (i.contiguous() if i is not None else None for i in (h_idx, t_idx, r_idx))
+    batch = (h_idx if h_idx is not None else h).size(0)
+    return (h, h_idx, t, t_idx, r, r_idx), batch, h.data_ptr() == t.data_ptr() and h.shape == t.shape
+
+
+def _grad_buffers(same_ht, h, h_idx, t, t_idx, r, need_h, need_t, need_r):
+    """-> (grad_h, grad_t, grad_r, shared) for a head's backward, uninitialised (an indexed table is cleared by the
+    backward's first launch).  ``shared``: head and tail gathered from one table accumulate into one buffer, and since
+    autograd sums the two returned grads of the same leaf, the caller hands back the whole accumulation once and an
+    untouched None for the tail's slot."""
+    gh = torch.empty_like(h) if need_h else None
+    shared = same_ht and need_h and need_t and h_idx is not None and t_idx is not None
+    gt = gh if shared else (torch.empty_like(t) if need_t else None)
+    gr = torch.empty_like(r) if need_r else None
+    return gh, gt, gr, shared
+
+
+class _ScoreFunction(torch.autograd.Function):
+    """The score of ``decoder`` (a name of ``DECODERS``, not a tensor: its gradient slot is None); an index of None
+    means row b.  DistMult: scores[b] = sum_d H[hi(b)] * Rm[ri(b)] * T[ti(b)]; ComplEx:
+    scores[b] = Re <H[hi(b)], Rm[ri(b)], conj(T[ti(b)])>."""
 
     @staticmethod
-    def forward(ctx, h: Tensor, h_idx: Optional[Tensor], t: Tensor, t_idx: Optional[Tensor],
+    def forward(ctx, decoder: str, h: Tensor, h_idx: Optional[Tensor], t: Tensor, t_idx: Optional[Tensor],
                 r: Tensor, r_idx: Optional[Tensor]) -> Tensor:
-        h, t, r = h.contiguous(), t.contiguous(), r.contiguous()
-        h_idx = h_idx.contiguous() if h_idx is not None else None
-        t_idx = t_idx.contiguous() if t_idx is not None else None
-        r_idx = r_idx.contiguous() if r_idx is not None else None
-        batch = (h_idx if h_idx is not None else h).size(0)
-        scores = ops.distmult_fwd(h, h_idx, t, t_idx, r, r_idx, batch)
-        ctx.batch = batch
-        ctx.same_ht = h.data_ptr() == t.data_ptr() and h.shape == t.shape
-        ctx.save_for_backward(h, h_idx, t, t_idx, r, r_idx)
+        operands, batch, same_ht = _operands(h, h_idx, t, t_idx, r, r_idx)
+        scores = _head_op(decoder, "fwd")(*operands, batch)
+        ctx.decoder, ctx.batch, ctx.same_ht = decoder, batch, same_ht
+        ctx.save_for_backward(*operands)
         return scores
 
     @staticmethod
     def backward(ctx, gs: Tensor):
         h, h_idx, t, t_idx, r, r_idx = ctx.saved_tensors
-        gs = gs.contiguous()
-        need_h, _, need_t, _, need_r, _ = ctx.needs_input_grad
-
-        def buf(src, idx, need):                     # (an indexed table is cleared by the backward's first launch)
-            return torch.empty_like(src) if need else None
-
-        gh = buf(h, h_idx, need_h)
-        # head and tail gathered from one table: accumulate both into one buffer
-        shared = ctx.same_ht and need_h and need_t and h_idx is not None and t_idx is not None
-        gt = gh if shared else buf(t, t_idx, need_t)
-        gr = buf(r, r_idx, need_r)
-        ops.distmult_bwd(gs, h, h_idx, t, t_idx, r, r_idx, ctx.batch, gh, gt, gr, zero_tables=True)
-        if shared:
-            # autograd sums the two returned grads of the same leaf: hand back the whole
-            # accumulation once and an untouched None for the second slot
-            return gh, None, None, None, gr, None
-        return gh, None, gt, None, gr, None
+        _, need_h, _, need_t, _, need_r, _ = ctx.needs_input_grad
+        gh, gt, gr, shared = _grad_buffers(ctx.same_ht, h, h_idx, t, t_idx, r, need_h, need_t, need_r)
+        _head_op(ctx.decoder, "bwd")(gs.contiguous(), h, h_idx, t, t_idx, r, r_idx, ctx.batch, gh, gt, gr, zero_tables=True)
+        return None, gh, None, (None if shared else gt), None, gr, None
 
 
 class _RelationRows(torch.autograd.Function):
@@ -81,23 +90,21 @@ class _RelationRows(torch.autograd.Function):
         return ops.segment_sum(g.contiguous(), idx.contiguous(), ctx.rows), None
 
 
-class _DistMultBCEFunction(torch.autograd.Function):
-    """(mean binary_cross_entropy_with_logits(scores, labels), scores): the scoring kernel also
-    emits the per-sample loss, and ONE backward kernel turns the gradient of the mean loss into
-    the head / tail / relation gradients (sigmoid, subtraction, 1/B and the DistMult products
+class _ScoreBCEFunction(torch.autograd.Function):
+    """(mean binary_cross_entropy_with_logits(scores, labels), scores) of ``decoder``: the scoring kernel also
+    emits the per-sample loss, and ONE backward call turns the gradient of the mean loss into
+    the head / tail / relation gradients (sigmoid, subtraction, 1/B and the decoder's products
     fused) - instead of the eight elementwise launches of BCEWithLogitsLoss around the head
-    (``src/train.py:300``).  ``scores`` is returned for the accuracy bookkeeping only."""
+    (``src/train.py:300``).  The mean and the step's bookkeeping are ``distmult_bce_reduce``'s (decoder-independent).
+    ``scores`` is returned for the accuracy bookkeeping only."""
 
     @staticmethod
-    def forward(ctx, h, h_idx, t, t_idx, r, r_idx, labels, stats=None):
-        h, t, r = h.contiguous(), t.contiguous(), r.contiguous()
-        h_idx, t_idx, r_idx = (i.contiguous() if i is not None else None for i in (h_idx, t_idx, r_idx))
+    def forward(ctx, decoder, h, h_idx, t, t_idx, r, r_idx, labels, stats=None):
+        operands, batch, same_ht = _operands(h, h_idx, t, t_idx, r, r_idx)
         labels = labels.contiguous()
-        batch = (h_idx if h_idx is not None else h).size(0)
-        scores, per_sample = ops.distmult_bce_fwd(h, h_idx, t, t_idx, r, r_idx, labels, batch)
-        ctx.batch = batch
-        ctx.same_ht = h.data_ptr() == t.data_ptr() and h.shape == t.shape
-        ctx.save_for_backward(h, h_idx, t, t_idx, r, r_idx, labels, scores)
+        scores, per_sample = _head_op(decoder, "bce_fwd")(*operands, labels, batch)
+        ctx.decoder, ctx.batch, ctx.same_ht = decoder, batch, same_ht
+        ctx.save_for_backward(*operands, labels, scores)
         ctx.mark_non_differentiable(scores)
         ctx.set_materialize_grads(False)             # (no zero-filled stand-in for the gradient of `scores` per step)
         # the mean in a fixed order and, when the caller keeps running sums on the device (``stats`` = (loss_sum,
@@ -109,22 +116,13 @@ class _DistMultBCEFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_scores):
         h, h_idx, t, t_idx, r, r_idx, labels, scores = ctx.saved_tensors
-        need_h, _, need_t, _, need_r, _, _, _ = ctx.needs_input_grad
+        _, need_h, _, need_t, _, need_r, _, _, _ = ctx.needs_input_grad
         if g_loss is None:                           # nothing downstream used the loss
-            return (None,) * 8
-
-        def buf(src, idx, need):                     # (an indexed table is cleared by the backward's first launch)
-            return torch.empty_like(src) if need else None
-
-        gh = buf(h, h_idx, need_h)
-        shared = ctx.same_ht and need_h and need_t and h_idx is not None and t_idx is not None
-        gt = gh if shared else buf(t, t_idx, need_t)
-        gr = buf(r, r_idx, need_r)
-        ops.distmult_bce_bwd(g_loss.reshape(1).contiguous(), scores, labels, h, h_idx, t, t_idx, r, r_idx,
-                             ctx.batch, gh, gt, gr, zero_tables=True)
-        if shared:
-            return gh, None, None, None, gr, None, None, None
-        return gh, None, gt, None, gr, None, None, None
+            return (None,) * 9
+        gh, gt, gr, shared = _grad_buffers(ctx.same_ht, h, h_idx, t, t_idx, r, need_h, need_t, need_r)
+        _head_op(ctx.decoder, "bce_bwd")(g_loss.reshape(1).contiguous(), scores, labels, h, h_idx, t, t_idx, r, r_idx,
+                                         ctx.batch, gh, gt, gr, zero_tables=True)
+        return None, gh, None, (None if shared else gt), None, gr, None, None, None
 
 
 class _ScoreAllTailsFunction(torch.autograd.Function):
@@ -153,70 +151,6 @@ class _ScoreAllTailsFunction(torch.autograd.Function):
         if ctx.needs_input_grad[3]:
             grad_emb = g.t() @ hr
         return grad_head, grad_rel, None, grad_emb
-
-
-class _ComplExFunction(torch.autograd.Function):
-    """scores[b] = Re <H[hi(b)], Rm[ri(b)], conj(T[ti(b)])>; an index of None means row b."""
-
-    @staticmethod
-    def forward(ctx, h: Tensor, h_idx: Optional[Tensor], t: Tensor, t_idx: Optional[Tensor],
-                r: Tensor, r_idx: Optional[Tensor]) -> Tensor:
-        h, t, r = h.contiguous(), t.contiguous(), r.contiguous()
-        h_idx, t_idx, r_idx = (i.contiguous() if i is not None else None for i in (h_idx, t_idx, r_idx))
-        batch = (h_idx if h_idx is not None else h).size(0)
-        scores = ops.complex_fwd(h, h_idx, t, t_idx, r, r_idx, batch)
-        ctx.batch = batch
-        ctx.same_ht = h.data_ptr() == t.data_ptr() and h.shape == t.shape
-        ctx.save_for_backward(h, h_idx, t, t_idx, r, r_idx)
-        return scores
-
-    @staticmethod
-    def backward(ctx, gs: Tensor):
-        h, h_idx, t, t_idx, r, r_idx = ctx.saved_tensors
-        need_h, _, need_t, _, need_r, _ = ctx.needs_input_grad
-        gh = torch.empty_like(h) if need_h else None
-        # head and tail gathered from one table: accumulate both into one buffer
-        shared = ctx.same_ht and need_h and need_t and h_idx is not None and t_idx is not None
-        gt = gh if shared else (torch.empty_like(t) if need_t else None)
-        gr = torch.empty_like(r) if need_r else None
-        ops.complex_bwd(gs.contiguous(), h, h_idx, t, t_idx, r, r_idx, ctx.batch, gh, gt, gr, zero_tables=True)
-        return gh, None, (None if shared else gt), None, gr, None
-
-
-class _ComplExBCEFunction(torch.autograd.Function):
-    """``_DistMultBCEFunction`` with the ComplEx score: the scoring launch emits the per-sample loss, the mean and the
-    step's bookkeeping are ``distmult_bce_reduce``'s (decoder-independent), and one backward call turns the gradient of
-    the mean loss into the head / tail / relation gradients."""
-
-    @staticmethod
-    def forward(ctx, h, h_idx, t, t_idx, r, r_idx, labels, stats=None):
-        h, t, r = h.contiguous(), t.contiguous(), r.contiguous()
-        h_idx, t_idx, r_idx = (i.contiguous() if i is not None else None for i in (h_idx, t_idx, r_idx))
-        labels = labels.contiguous()
-        batch = (h_idx if h_idx is not None else h).size(0)
-        scores, per_sample = ops.complex_bce_fwd(h, h_idx, t, t_idx, r, r_idx, labels, batch)
-        ctx.batch = batch
-        ctx.same_ht = h.data_ptr() == t.data_ptr() and h.shape == t.shape
-        ctx.save_for_backward(h, h_idx, t, t_idx, r, r_idx, labels, scores)
-        ctx.mark_non_differentiable(scores)
-        ctx.set_materialize_grads(False)
-        loss_sum, correct, cursor, cursor_add = stats if stats is not None else (None, None, None, 0)
-        mean = ops.distmult_bce_reduce(per_sample, scores, labels, loss_sum, correct, cursor, cursor_add)
-        return mean.reshape(()), scores
-
-    @staticmethod
-    def backward(ctx, g_loss, _g_scores):
-        h, h_idx, t, t_idx, r, r_idx, labels, scores = ctx.saved_tensors
-        need_h, _, need_t, _, need_r, _, _, _ = ctx.needs_input_grad
-        if g_loss is None:                           # nothing downstream used the loss
-            return (None,) * 8
-        gh = torch.empty_like(h) if need_h else None
-        shared = ctx.same_ht and need_h and need_t and h_idx is not None and t_idx is not None
-        gt = gh if shared else (torch.empty_like(t) if need_t else None)
-        gr = torch.empty_like(r) if need_r else None
-        ops.complex_bce_bwd(g_loss.reshape(1).contiguous(), scores, labels, h, h_idx, t, t_idx, r, r_idx,
-                            ctx.batch, gh, gt, gr, zero_tables=True)
-        return gh, None, (None if shared else gt), None, gr, None, None, None
 
 
 class _SoftmaxLossFunction(torch.autograd.Function):
@@ -298,11 +232,11 @@ DECODERS = ("distmult", "complex")
 
 
 def distmult(h, h_idx, t, t_idx, r, r_idx) -> Tensor:
-    return _DistMultFunction.apply(h, h_idx, t, t_idx, r, r_idx)
+    return _ScoreFunction.apply("distmult", h, h_idx, t, t_idx, r, r_idx)
 
 
 def complex_score(h, h_idx, t, t_idx, r, r_idx) -> Tensor:
-    return _ComplExFunction.apply(h, h_idx, t, t_idx, r, r_idx)
+    return _ScoreFunction.apply("complex", h, h_idx, t, t_idx, r, r_idx)
 
 
 class LinkPredictor(nn.Module):
@@ -356,8 +290,8 @@ class LinkPredictor(nn.Module):
         device-resident running sums and batch cursor ``(loss_sum, correct, cursor, cursor_add)``, updated by the launch
         that forms the mean (``Trainer``: ``src/train.py:321-326`` without nine elementwise launches per step)."""
         r, r_idx = self._relation_operand(relation_types)
-        fn = _ComplExBCEFunction if self.decoder == "complex" else _DistMultBCEFunction
-        return fn.apply(node_embeddings, head_indices, node_embeddings, tail_indices, r, r_idx, labels, stats)
+        return _ScoreBCEFunction.apply(self.decoder, node_embeddings, head_indices, node_embeddings, tail_indices, r, r_idx,
+                                       labels, stats)
 
     def softmax_loss(self, node_embeddings: Tensor, head_indices: Tensor, tail_indices: Tensor,
                      relation_types: Tensor, *, sides=("tail", "head"), known: Optional["ops.KnownTriples"] = None,

@@ -1558,8 +1558,12 @@ def transform_bwd_params(agg, x, g, num_relations: int, want_root: bool = True, 
 
 
 # ----------------------------------------------------------------------------------
-# DistMult head (rows C1 + C2)
+# Decoder heads: DistMult (rows C1 + C2) and ComplEx (further down).  One body per call for both; a decoder is the
+# prefix of its library symbols and the multiple its embedding width must have (csrc/rgcn_decoder_head.h: kWidth).
 # ----------------------------------------------------------------------------------
+_HEAD_WIDTH = {"distmult": 4, "complex": 8}
+
+
 def _check_operand(name, mat, idx, batch):
     _need_gpu(name, mat, torch.float32)
     if mat.dim() != 2:
@@ -1572,21 +1576,85 @@ def _check_operand(name, mat, idx, batch):
         raise ValueError(f"{name} must have {batch} rows when no index is given")
 
 
-def distmult_fwd(h, h_idx, t, t_idx, r, r_idx, batch: int) -> torch.Tensor:
+def _check_width(d: int, width: int) -> None:
+    if d % width:
+        raise ValueError(f"embedding dim must be a multiple of {width}")
+
+
+def _check_head_operands(h, h_idx, t, t_idx, r, r_idx, batch: int, width: int) -> int:
     d = h.size(1)
     for name, m, i in (("head", h, h_idx), ("tail", t, t_idx), ("rel", r, r_idx)):
         _check_operand(name, m, i, batch)
         if m.size(1) != d:
             raise ValueError("head / tail / relation embedding dims differ")
-    if d % 4:
-        raise ValueError("embedding dim must be a multiple of 4")
+    _check_width(d, width)
+    return d
+
+
+def _head_fwd(decoder: str, h, h_idx, t, t_idx, r, r_idx, batch: int) -> torch.Tensor:
+    d = _check_head_operands(h, h_idx, t, t_idx, r, r_idx, batch, _HEAD_WIDTH[decoder])
     lib = _L()
     with _on(h.device):
         scores = _empty(batch, dtype=torch.float32, device=h.device)
-        rc = lib.distmult_fwd(_ptr(h), _ptr(h_idx), h.size(0), _ptr(t), _ptr(t_idx), t.size(0), _ptr(r), _ptr(r_idx),
-                              r.size(0), batch, d, _ptr(scores), _stream())
-    _lib.check(rc, "distmult_fwd")
+        rc = getattr(lib, decoder + "_fwd")(_ptr(h), _ptr(h_idx), h.size(0), _ptr(t), _ptr(t_idx), t.size(0), _ptr(r),
+                                            _ptr(r_idx), r.size(0), batch, d, _ptr(scores), _stream())
+    _lib.check(rc, decoder + "_fwd")
     return scores
+
+
+def _head_bce_fwd(decoder: str, h, h_idx, t, t_idx, r, r_idx, labels, batch: int):
+    d = _check_head_operands(h, h_idx, t, t_idx, r, r_idx, batch, _HEAD_WIDTH[decoder])
+    _need_gpu("labels", labels, torch.float32)
+    if labels.shape != (batch,):
+        raise ValueError(f"labels must be [{batch}], got {tuple(labels.shape)}")
+    lib = _L()
+    with _on(h.device):
+        scores = _empty(batch, dtype=torch.float32, device=h.device)
+        loss = _empty(batch, dtype=torch.float32, device=h.device)
+        rc = getattr(lib, decoder + "_bce_fwd")(_ptr(h), _ptr(h_idx), h.size(0), _ptr(t), _ptr(t_idx), t.size(0), _ptr(r),
+                                                _ptr(r_idx), r.size(0), _ptr(labels), batch, d, _ptr(scores), _ptr(loss),
+                                                _stream())
+    _lib.check(rc, decoder + "_bce_fwd")
+    return scores, loss
+
+
+def _head_bwd_workspace(decoder: str, lib, batch: int, d: int, r, r_idx, device):
+    nbytes = getattr(lib, decoder + "_bwd_workspace_bytes")(batch, d, r.size(0) if r_idx is not None else 0)
+    return _workspace(nbytes, device), nbytes
+
+
+def _head_bwd(decoder: str, gs, h, h_idx, t, t_idx, r, r_idx, batch: int, grad_h, grad_t, grad_r, zero_tables) -> None:
+    _need_gpu("grad_scores", gs, torch.float32)
+    d = h.size(1)
+    _check_width(d, _HEAD_WIDTH[decoder])
+    lib = _L()
+    with _on(h.device):
+        ws, nbytes = _head_bwd_workspace(decoder, lib, batch, d, r, r_idx, h.device)
+        rc = getattr(lib, decoder + "_bwd")(_ptr(gs), _ptr(h), _ptr(h_idx), h.size(0), _ptr(t), _ptr(t_idx), t.size(0),
+                                            _ptr(r), _ptr(r_idx), r.size(0), batch, d, _ptr(grad_h), _ptr(grad_t),
+                                            _ptr(grad_r), _ptr(ws), nbytes, int(bool(zero_tables)), _stream())
+    _lib.check(rc, decoder + "_bwd")
+
+
+def _head_bce_bwd(decoder: str, grad_mean_loss, scores, labels, h, h_idx, t, t_idx, r, r_idx, batch: int,
+                  grad_h, grad_t, grad_r, zero_tables) -> None:
+    _need_gpu("grad_mean_loss", grad_mean_loss, torch.float32)
+    if grad_mean_loss.numel() != 1:
+        raise ValueError("grad_mean_loss must hold one float")
+    d = h.size(1)
+    _check_width(d, _HEAD_WIDTH[decoder])
+    lib = _L()
+    with _on(h.device):
+        ws, nbytes = _head_bwd_workspace(decoder, lib, batch, d, r, r_idx, h.device)
+        rc = getattr(lib, decoder + "_bce_bwd")(_ptr(grad_mean_loss), _ptr(scores), _ptr(labels), _ptr(h), _ptr(h_idx),
+                                                h.size(0), _ptr(t), _ptr(t_idx), t.size(0), _ptr(r), _ptr(r_idx), r.size(0),
+                                                batch, d, _ptr(grad_h), _ptr(grad_t), _ptr(grad_r), _ptr(ws), nbytes,
+                                                int(bool(zero_tables)), _stream())
+    _lib.check(rc, decoder + "_bce_bwd")
+
+
+def distmult_fwd(h, h_idx, t, t_idx, r, r_idx, batch: int) -> torch.Tensor:
+    return _head_fwd("distmult", h, h_idx, t, t_idx, r, r_idx, batch)
 
 
 def check_indices(device=None) -> None:
@@ -1716,24 +1784,7 @@ def sample_batch(edge_index: torch.Tensor, edge_type: torch.Tensor, order: Optio
 
 def distmult_bce_fwd(h, h_idx, t, t_idx, r, r_idx, labels, batch: int):
     """-> (scores [B], per-sample binary_cross_entropy_with_logits(scores, labels) [B]) in one launch."""
-    d = h.size(1)
-    for name, m, i in (("head", h, h_idx), ("tail", t, t_idx), ("rel", r, r_idx)):
-        _check_operand(name, m, i, batch)
-        if m.size(1) != d:
-            raise ValueError("head / tail / relation embedding dims differ")
-    if d % 4:
-        raise ValueError("embedding dim must be a multiple of 4")
-    _need_gpu("labels", labels, torch.float32)
-    if labels.shape != (batch,):
-        raise ValueError(f"labels must be [{batch}], got {tuple(labels.shape)}")
-    lib = _L()
-    with _on(h.device):
-        scores = _empty(batch, dtype=torch.float32, device=h.device)
-        loss = _empty(batch, dtype=torch.float32, device=h.device)
-        rc = lib.distmult_bce_fwd(_ptr(h), _ptr(h_idx), h.size(0), _ptr(t), _ptr(t_idx), t.size(0), _ptr(r), _ptr(r_idx),
-                                  r.size(0), _ptr(labels), batch, d, _ptr(scores), _ptr(loss), _stream())
-    _lib.check(rc, "distmult_bce_fwd")
-    return scores, loss
+    return _head_bce_fwd("distmult", h, h_idx, t, t_idx, r, r_idx, labels, batch)
 
 
 def basis_compose(comp: torch.Tensor, basis: torch.Tensor) -> torch.Tensor:
@@ -1806,27 +1857,12 @@ def distmult_bce_reduce(loss: torch.Tensor, scores: torch.Tensor, labels: torch.
     return mean
 
 
-def _bwd_workspace(lib, batch: int, d: int, r, r_idx, device):
-    nbytes = lib.distmult_bwd_workspace_bytes(batch, d, r.size(0) if r_idx is not None else 0)
-    return _workspace(nbytes, device), nbytes
-
-
 def distmult_bce_bwd(grad_mean_loss, scores, labels, h, h_idx, t, t_idx, r, r_idx, batch: int,
                      grad_h, grad_t, grad_r, zero_tables: bool = False) -> None:
     """Backward of ``mean(bce_with_logits(distmult(...), labels))``; ``grad_mean_loss`` is a
     one-element device tensor.  Writes like ``distmult_bwd`` (``zero_tables`` as there)."""
-    _need_gpu("grad_mean_loss", grad_mean_loss, torch.float32)
-    if grad_mean_loss.numel() != 1:
-        raise ValueError("grad_mean_loss must hold one float")
-    d = h.size(1)
-    lib = _L()
-    with _on(h.device):
-        ws, nbytes = _bwd_workspace(lib, batch, d, r, r_idx, h.device)
-        rc = lib.distmult_bce_bwd(_ptr(grad_mean_loss), _ptr(scores), _ptr(labels), _ptr(h), _ptr(h_idx), h.size(0),
-                                  _ptr(t), _ptr(t_idx), t.size(0), _ptr(r), _ptr(r_idx), r.size(0), batch, d,
-                                  _ptr(grad_h), _ptr(grad_t), _ptr(grad_r), _ptr(ws), nbytes, int(bool(zero_tables)),
-                                  _stream())
-    _lib.check(rc, "distmult_bce_bwd")
+    _head_bce_bwd("distmult", grad_mean_loss, scores, labels, h, h_idx, t, t_idx, r, r_idx, batch, grad_h, grad_t, grad_r,
+                  zero_tables)
 
 
 def distmult_bwd(gs, h, h_idx, t, t_idx, r, r_idx, batch: int, grad_h, grad_t, grad_r, zero_tables: bool = False) -> None:
@@ -1834,101 +1870,37 @@ def distmult_bwd(gs, h, h_idx, t, t_idx, r, r_idx, batch: int, grad_h, grad_t, g
     index vector are WRITTEN with the ordered sum of their samples' contributions; the rows nobody touches are
     cleared by the first launch itself (``zero_tables``: the buffers may then be ``torch.empty``) or must come
     zeroed from the caller; ``grad_h is grad_t`` (one table) is one key space."""
-    _need_gpu("grad_scores", gs, torch.float32)
-    d = h.size(1)
-    lib = _L()
-    with _on(h.device):
-        ws, nbytes = _bwd_workspace(lib, batch, d, r, r_idx, h.device)
-        rc = lib.distmult_bwd(_ptr(gs), _ptr(h), _ptr(h_idx), h.size(0), _ptr(t), _ptr(t_idx), t.size(0), _ptr(r),
-                              _ptr(r_idx), r.size(0), batch, d, _ptr(grad_h), _ptr(grad_t), _ptr(grad_r), _ptr(ws),
-                              nbytes, int(bool(zero_tables)), _stream())
-    _lib.check(rc, "distmult_bwd")
+    _head_bwd("distmult", gs, h, h_idx, t, t_idx, r, r_idx, batch, grad_h, grad_t, grad_r, zero_tables)
 
 
 # ----------------------------------------------------------------------------------
 # ComplEx head (include/rgcn_complex.h, csrc/complex.hip): score(h, r, t) = Re <h, r, conj(t)>, asymmetric in h and t.
 # A row of width d is d / 2 complex numbers, real parts in columns [0, d / 2), imaginary parts in [d / 2, d).
 # ----------------------------------------------------------------------------------
-def _check_complex_operands(h, h_idx, t, t_idx, r, r_idx, batch: int) -> int:
-    d = h.size(1)
-    for name, m, i in (("head", h, h_idx), ("tail", t, t_idx), ("rel", r, r_idx)):
-        _check_operand(name, m, i, batch)
-        if m.size(1) != d:
-            raise ValueError("head / tail / relation embedding dims differ")
-    if d % 8:
-        raise ValueError("embedding dim must be a multiple of 8")
-    return d
-
-
 def complex_fwd(h, h_idx, t, t_idx, r, r_idx, batch: int) -> torch.Tensor:
     """``scores[b] = Re <H[hi(b)], R[ri(b)], conj(T[ti(b)])>`` (``complex_fwd``); an index of None means row b."""
-    d = _check_complex_operands(h, h_idx, t, t_idx, r, r_idx, batch)
-    lib = _L()
-    with _on(h.device):
-        scores = _empty(batch, dtype=torch.float32, device=h.device)
-        rc = lib.complex_fwd(_ptr(h), _ptr(h_idx), h.size(0), _ptr(t), _ptr(t_idx), t.size(0), _ptr(r), _ptr(r_idx),
-                             r.size(0), batch, d, _ptr(scores), _stream())
-    _lib.check(rc, "complex_fwd")
-    return scores
+    return _head_fwd("complex", h, h_idx, t, t_idx, r, r_idx, batch)
 
 
 def complex_bce_fwd(h, h_idx, t, t_idx, r, r_idx, labels, batch: int):
     """-> (scores [B], per-sample binary_cross_entropy_with_logits(scores, labels) [B]) in one launch; the mean is
     ``distmult_bce_reduce``'s (decoder-independent)."""
-    d = _check_complex_operands(h, h_idx, t, t_idx, r, r_idx, batch)
-    _need_gpu("labels", labels, torch.float32)
-    if labels.shape != (batch,):
-        raise ValueError(f"labels must be [{batch}], got {tuple(labels.shape)}")
-    lib = _L()
-    with _on(h.device):
-        scores = _empty(batch, dtype=torch.float32, device=h.device)
-        loss = _empty(batch, dtype=torch.float32, device=h.device)
-        rc = lib.complex_bce_fwd(_ptr(h), _ptr(h_idx), h.size(0), _ptr(t), _ptr(t_idx), t.size(0), _ptr(r), _ptr(r_idx),
-                                 r.size(0), _ptr(labels), batch, d, _ptr(scores), _ptr(loss), _stream())
-    _lib.check(rc, "complex_bce_fwd")
-    return scores, loss
-
-
-def _complex_bwd_workspace(lib, batch: int, d: int, r, r_idx, device):
-    nbytes = lib.complex_bwd_workspace_bytes(batch, d, r.size(0) if r_idx is not None else 0)
-    return _workspace(nbytes, device), nbytes
+    return _head_bce_fwd("complex", h, h_idx, t, t_idx, r, r_idx, labels, batch)
 
 
 def complex_bce_bwd(grad_mean_loss, scores, labels, h, h_idx, t, t_idx, r, r_idx, batch: int,
                     grad_h, grad_t, grad_r, zero_tables: bool = False) -> None:
     """Backward of ``mean(bce_with_logits(complex(...), labels))``; ``grad_mean_loss`` is a one-element device tensor.
     Writes like ``complex_bwd`` (``zero_tables`` as there)."""
-    _need_gpu("grad_mean_loss", grad_mean_loss, torch.float32)
-    if grad_mean_loss.numel() != 1:
-        raise ValueError("grad_mean_loss must hold one float")
-    d = h.size(1)
-    if d % 8:
-        raise ValueError("embedding dim must be a multiple of 8")
-    lib = _L()
-    with _on(h.device):
-        ws, nbytes = _complex_bwd_workspace(lib, batch, d, r, r_idx, h.device)
-        rc = lib.complex_bce_bwd(_ptr(grad_mean_loss), _ptr(scores), _ptr(labels), _ptr(h), _ptr(h_idx), h.size(0),
-                                 _ptr(t), _ptr(t_idx), t.size(0), _ptr(r), _ptr(r_idx), r.size(0), batch, d,
-                                 _ptr(grad_h), _ptr(grad_t), _ptr(grad_r), _ptr(ws), nbytes, int(bool(zero_tables)),
-                                 _stream())
-    _lib.check(rc, "complex_bce_bwd")
+    _head_bce_bwd("complex", grad_mean_loss, scores, labels, h, h_idx, t, t_idx, r, r_idx, batch, grad_h, grad_t, grad_r,
+                  zero_tables)
 
 
 def complex_bwd(gs, h, h_idx, t, t_idx, r, r_idx, batch: int, grad_h, grad_t, grad_r, zero_tables: bool = False) -> None:
     """Deterministic backward of ``complex_fwd``, with the write rules of ``distmult_bwd``: rows reached through an index
     vector are WRITTEN with the ordered sum of their samples' contributions, the rows nobody touches are cleared by the
     first launch (``zero_tables``) or must come zeroed, ``grad_h is grad_t`` (one table) is one key space."""
-    _need_gpu("grad_scores", gs, torch.float32)
-    d = h.size(1)
-    if d % 8:
-        raise ValueError("embedding dim must be a multiple of 8")
-    lib = _L()
-    with _on(h.device):
-        ws, nbytes = _complex_bwd_workspace(lib, batch, d, r, r_idx, h.device)
-        rc = lib.complex_bwd(_ptr(gs), _ptr(h), _ptr(h_idx), h.size(0), _ptr(t), _ptr(t_idx), t.size(0), _ptr(r),
-                             _ptr(r_idx), r.size(0), batch, d, _ptr(grad_h), _ptr(grad_t), _ptr(grad_r), _ptr(ws),
-                             nbytes, int(bool(zero_tables)), _stream())
-    _lib.check(rc, "complex_bwd")
+    _head_bwd("complex", gs, h, h_idx, t, t_idx, r, r_idx, batch, grad_h, grad_t, grad_r, zero_tables)
 
 
 def complex_query(x, x_idx, rel, rel_idx, side: str = "tail") -> torch.Tensor:
