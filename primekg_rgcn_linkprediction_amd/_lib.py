@@ -268,6 +268,22 @@ SPARSE_PROTOTYPES = {
 }
 MODE_SPARSE_ROWS = 2
 
+
+# include/rgcn_row_order.h, one to one: the occupancy order of a structure's rows, built with the graph behind its
+# occupancy words (csrc/rgcn_graph.hip; queries, never forwarded by rgcn_sequence_run).  MODE_ROW_ORDER:
+# RGCN_MODE_ROW_ORDER of that header, one more bit of the option word that carries MODE_SPARSE_ROWS - the split NT
+# transforms then take their 64-row tiles in that order.
+class RowOrderLayout(ctypes.Structure):
+    _fields_ = [(name, c_int64) for name in ("padded_rows", "perm", "row_words", "tile_words", "fin_ptr", "items",
+                                              "num_items", "total_words")]
+
+
+ROW_ORDER_PROTOTYPES = {
+    "rgcn_graph_row_order": (c_void_p, [c_void_p, c_int, POINTER(c_int64)]),
+    "rgcn_row_order_host": (_I64, [_P, _I64, _I64, _P, POINTER(RowOrderLayout)]),
+}
+MODE_ROW_ORDER = 4
+
 _lib = None
 
 
@@ -289,7 +305,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise RGCNLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + list(COMPLEX_PROTOTYPES.items()) + list(SPARSE_PROTOTYPES.items()) + list(SOFTMAX_PROTOTYPES.items()) + list(EDGE_DROPOUT_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + list(COMPLEX_PROTOTYPES.items()) + list(SPARSE_PROTOTYPES.items()) + list(ROW_ORDER_PROTOTYPES.items()) + list(SOFTMAX_PROTOTYPES.items()) + list(EDGE_DROPOUT_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -135,6 +135,11 @@ def _transform_first(graph: "ops.BucketedGraph", weight: Tensor, root: Optional[
 # profiles/sparse_aggregate.txt.  A module attribute (tests patch it); part of _policy_key().
 _SPARSE_AGG = True
 
+# Row tiles of the split NT transforms in occupancy order (include/rgcn_row_order.h; ops._order_bit has the conditions):
+# same bytes, a quarter fewer live k-tiles at C2 - profiles/nt_row_order.txt.  RGCN_NT_ROW_ORDER=0 gives the launches in
+# node order, for A/B.  A module attribute (tests patch it); part of _policy_key().
+_NT_ROW_ORDER = _os.environ.get("RGCN_NT_ROW_ORDER", "1") != "0"
+
 
 def _sparse_agg(graph: "ops.BucketedGraph", transposed: bool, half: bool, packed, amax, d: int, precision=None) -> bool:
     """is the d-wide aggregate of this layer a sparse one (see above)?  The consumers' own conditions: split precision
@@ -216,11 +221,12 @@ def _input_grad(graph: "ops.BucketedGraph", g: Tensor, weight: Tensor, root: Opt
                     and ops.chain_supported(weight, lower[0])):
                 gx, t = ops.transform_bwd_input_chain(gagg, g, weight, root, relu_mask, packed, lower[2], graph=graph,
                                                       amax=amax, amax_mul=mul, amax_out=amax_out, out_scale=out_scale,
-                                                      sparse=sparse)
+                                                      sparse=sparse, row_order=_NT_ROW_ORDER)
             else:
                 gx = ops.transform_bwd_input(gagg, g, weight, root, relu_mask=relu_mask, graph=graph, amax=amax,
                                              amax_mul=mul, amax_out=amax_out, packed=packed, precision=precision,
-                                             out_scale=out_scale, sparse=sparse)    # autograd of A6 wrt x
+                                             out_scale=out_scale, sparse=sparse,
+                                             row_order=_NT_ROW_ORDER)               # autograd of A6 wrt x
     return (gx, t) if lower is not None else gx
 
 
@@ -297,7 +303,8 @@ def _layer_train_forward(graph: "ops.BucketedGraph", x: Tensor, gather_dtype, we
     else:
         agg, hubs = ops.aggregate(graph, _table(x, gather_dtype)), None
     out = ops.transform_fwd(agg, x, weight, root, bias, relu=relu, graph=graph, half=half, amax=(x_amax, x_amax),
-                            amax_out=amax_out, packed=packed, hubs=hubs, sparse=sparse, amax_mul=_agg_bound(graph))
+                            amax_out=amax_out, packed=packed, hubs=hubs, sparse=sparse, amax_mul=_agg_bound(graph),
+                            row_order=_NT_ROW_ORDER)
     return agg, out
 
 
@@ -440,7 +447,8 @@ _R_BACKWARD = ops.Region("encoder2.backward", _enc2_backward)
 
 
 def _policy_key():
-    return (_TRAIN_FUSED, _DEFER_HUBS, _TRANSFORM_FIRST_RATIO, _EVAL_INLINE_LIMIT, _TRAIN_FUSED_MIN_BYTES, _SPARSE_AGG)
+    return (_TRAIN_FUSED, _DEFER_HUBS, _TRANSFORM_FIRST_RATIO, _EVAL_INLINE_LIMIT, _TRAIN_FUSED_MIN_BYTES, _SPARSE_AGG,
+            _NT_ROW_ORDER)
 
 
 def _enc2_train_forward(graph, params, gather_dtype, half_backward: bool, hints, p: float = 0.0):

@@ -14,6 +14,7 @@
 
 #include "rgcn_common.h"
 #include "../../include/rgcn_sparse.h"
+#include "../../include/rgcn_row_order.h"
 
 namespace {
 
@@ -84,7 +85,8 @@ __global__ void k_permute_weights(const float* __restrict__ w_in, const int64_t*
 inline unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, ceil_div64(n, kThreads)); }
 
 // Host-side plan: rgcn_build_plan (rgcn_plan.h) turns rowptr into levels of items; here they go to the device.
-int build_plan(const std::vector<int32_t>& rowptr, int64_t NR, int64_t R, rgcn_csr* csr) {
+// `fin_items` <- the items of a single reduce level as uploaded (by destination tile), for the row order's regrouping
+int build_plan(const std::vector<int32_t>& rowptr, int64_t NR, int64_t R, rgcn_csr* csr, std::vector<rgcn_item>* fin_items) {
   rgcn_plan plan;
   const int rc = rgcn_build_plan(rowptr, NR, R, csr->n_key, &plan);
   if (rc != RGCN_OK) return rc;
@@ -112,6 +114,7 @@ int build_plan(const std::vector<int32_t>& rowptr, int64_t NR, int64_t R, rgcn_c
     RGCN_HIP_TRY(hipMalloc((void**)&csr->fin_ptr, fin_ptr.size() * sizeof(int32_t)));
     RGCN_HIP_TRY(hipMemcpy(csr->fin_ptr, fin_ptr.data(), fin_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     csr->num_fin_tiles = (int64_t)fin_ptr.size() - 1;
+    *fin_items = levels[1];
   }
   return RGCN_OK;
 }
@@ -214,14 +217,16 @@ int plan_structure(rgcn_csr* c, int64_t R, hipStream_t stream) {
   std::vector<int32_t> rp((size_t)NR + 1);
   RGCN_HIP_TRY(hipMemcpyAsync(rp.data(), c->rowptr, (NR + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   RGCN_HIP_TRY(hipStreamSynchronize(stream));
-  if (R <= 32 && c->n_key > 0) {          // relation occupancy per 32-row tile and, behind it, per row
+  std::vector<rgcn_item> fin_items;
+  TRY_PLAN(build_plan(rp, NR, R, c, &fin_items));
+  if (R <= 32 && c->n_key > 0) {          // relation occupancy per 32-row tile and, behind it, per row; then the row order
     c->num_row_tiles = ceil_div64(c->n_key, 32);
     std::vector<uint32_t> mask((size_t)rgcn_occupancy_words(c->n_key));
     rgcn_fill_occupancy(rp.data(), c->n_key, R, mask.data());
+    rgcn_fill_row_order(c->n_key, R, fin_items.data(), (int64_t)fin_items.size(), mask);
     RGCN_HIP_TRY(hipMalloc((void**)&c->tile_mask, mask.size() * sizeof(uint32_t)));
     RGCN_HIP_TRY(hipMemcpy(c->tile_mask, mask.data(), mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
-  TRY_PLAN(build_plan(rp, NR, R, c));
   c->weight_bound = 1.f;
   if (c->weighted && NR > 0 && rp[(size_t)NR] > 0) {      // one-time, on the host: max over segments of sum |w|
     std::vector<float> w((size_t)rp[(size_t)NR]);
@@ -495,6 +500,38 @@ int64_t rgcn_occupancy_host(const int32_t* rowptr, int64_t num_rows, int64_t num
     rgcn_fill_occupancy(rowptr, num_rows, num_relations, words);
   }
   return rgcn_occupancy_words(num_rows);
+}
+
+const int32_t* rgcn_graph_row_order(const rgcn_graph* g, int transposed, int64_t* padded_rows) {
+  if (padded_rows) *padded_rows = 0;
+  if (!g) return nullptr;
+  const rgcn_csr* c = &g->dir[transposed ? 1 : 0];
+  if (!c->tile_mask) return nullptr;             // (every builder leaves the order behind the occupancy words: plan_structure)
+  const rgcn_order_offsets o = rgcn_order_offsets_of(c->n_key);
+  if (padded_rows) *padded_rows = o.P;
+  return reinterpret_cast<const int32_t*>(c->tile_mask + o.perm);
+}
+
+int64_t rgcn_row_order_host(const int32_t* rowptr, int64_t num_rows, int64_t num_relations, uint32_t* words,
+                            rgcn_row_order_layout* layout) {
+  if (layout) *layout = rgcn_row_order_layout{};
+  if (num_rows < 0 || num_relations <= 0 || !rowptr) return -1;
+  if (num_relations > 32 || num_rows == 0) return 0;
+  if (num_rows > INT32_MAX / num_relations) return -1;
+  const int64_t NR = num_rows * num_relations;
+  std::vector<int32_t> rp(rowptr, rowptr + NR + 1);
+  rgcn_plan plan;                                // exactly what plan_structure does with a structure's rowptr
+  if (rgcn_build_plan(rp, NR, num_relations, num_rows, &plan) != RGCN_OK) return -1;
+  std::vector<rgcn_item> none;
+  const std::vector<rgcn_item>& level1 = plan.fin_ptr.empty() ? none : plan.levels[1];
+  std::vector<uint32_t> image((size_t)rgcn_occupancy_words(num_rows));
+  rgcn_fill_occupancy(rowptr, num_rows, num_relations, image.data());
+  rgcn_fill_row_order(num_rows, num_relations, level1.data(), (int64_t)level1.size(), image);
+  const rgcn_order_offsets o = rgcn_order_offsets_of(num_rows);
+  if (layout)
+    *layout = rgcn_row_order_layout{o.P, o.perm, o.rows, o.tiles, o.fin, o.items, (int64_t)level1.size(), (int64_t)image.size()};
+  if (words) std::copy(image.begin(), image.end(), words);
+  return (int64_t)image.size();
 }
 
 int rgcn_graph_arrays(const rgcn_graph* g, int transposed, const int32_t** rowptr, const int32_t** col,

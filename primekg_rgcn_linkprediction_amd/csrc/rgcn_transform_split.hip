@@ -45,14 +45,22 @@
 #include "rgcn_hub_finish.h"
 #include "rgcn_split.h"
 #include "rgcn_transform_host.h"
+#include "../../include/rgcn_row_order.h"
 
 // tools/gemm_stamps.hip includes this file with RGCN_STAMPS defined: thread 0 of every workgroup then leaves the 100 MHz
-// wall clock at four points of the kernel (entry, main loop reached, main loop left, end) - where a launch's time goes.
+// wall clock at four points of the kernel (entry, main loop reached, main loop left, end) - where a launch's time goes -
+// and, at entry, where it runs: HW_REG_XCC_ID << 16 | HW_REG_HW_ID[15:0] (which workgroups the dispatcher puts on one CU).
 #ifdef RGCN_STAMPS
 __device__ unsigned long long g_rgcn_stamps[8192 * 4];
+__device__ unsigned g_rgcn_stamp_cu[8192];
 #define RGCN_STAMP(i)                                                                                               \
   do {                                                                                                              \
-    if (threadIdx.x == 0) g_rgcn_stamps[((blockIdx.y * gridDim.x + blockIdx.x) & 8191) * 4 + (i)] = __builtin_amdgcn_s_memrealtime(); \
+    if (threadIdx.x == 0) {                                                                                         \
+      const unsigned wg_ = (blockIdx.y * gridDim.x + blockIdx.x) & 8191;                                            \
+      g_rgcn_stamps[wg_ * 4 + (i)] = __builtin_amdgcn_s_memrealtime();                                              \
+      if ((i) == 0) /* hwreg(id, 0, 32) = id | 31 << 11: HW_REG_HW_ID = 4, HW_REG_XCC_ID = 20 */                    \
+        g_rgcn_stamp_cu[wg_] = (__builtin_amdgcn_s_getreg(20 | 31 << 11) << 16) | (__builtin_amdgcn_s_getreg(4 | 31 << 11) & 0xffffu); \
+    }                                                                                                               \
   } while (0)
 #else
 #define RGCN_STAMP(i)
@@ -241,7 +249,13 @@ struct nt_chain {
 // nothing there and the buffer may hold anything - the kernels below never issue a load from it.
 __device__ __attribute__((aligned(16))) float g_zero_row[128];
 
-template <int WM, int WN, int TN, int EPI, bool LO, bool CHAIN = false>
+// ORDER (RGCN_MODE_ROW_ORDER, include/rgcn_row_order.h): the workgroup owns POSITIONS [64 b, 64 b + 64) of the rows'
+// occupancy order - rows of (nearly always) one occupancy word, so `tile_mask` skips every relation they lack.
+// `row_perm` [tiles * 64] names the row at each position; `tile_mask`, `row_mask` and `fin` arrive in position order
+// (the host's doing), so only the source rows of the A DMAs and the rows of C, `mask` and T go through the
+// permutation: lane l of every wave holds the row of position m0 + l, read with the prologue's other words.  A row's
+// k loop is what it was - the same bits at the same addresses.  Without ORDER nothing of this is compiled.
+template <int WM, int WN, int TN, int EPI, bool LO, bool CHAIN = false, bool ORDER = false>
 __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __restrict__ A1, int K1,
                                                             const float* __restrict__ A2, int K2,
                                                             const __half* __restrict__ Bh,
@@ -253,8 +267,10 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
                                                             int M, int N, const uint32_t* __restrict__ tile_mask,
                                                             int kseg, unsigned* __restrict__ amax_out,
                                                             const hub_fin fin, float out_scale, const nt_chain chain,
-                                                            const uint32_t* __restrict__ row_mask) {
+                                                            const uint32_t* __restrict__ row_mask,
+                                                            const int* __restrict__ row_perm) {
   static_assert(!CHAIN || (WM == 2 && WN == 2 && TN == 2 && LO), "the chained product is built for the 64 x 128 tile");
+  static_assert(!ORDER || WM == 2, "a wave holds the rows of one 64-position tile, one per lane");
   constexpr int WAVES = WM * WN;                 // WM wave rows (32 output rows each) x WN wave columns (32 TN columns each)
   constexpr int BM = 32 * WM, BN = 32 * TN * WN, NBUF = WM == 2 ? 3 : 4, D = NBUF - 1;   // D k-tiles in flight
   constexpr int PARTS = LO ? 2 : 1;              // B images staged: hi (and lo)
@@ -288,14 +304,27 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
       if ((t32 + q) * 32 < M) rel_mask |= tile_mask[t32 + q];
     rel_mask = __builtin_amdgcn_readfirstlane(rel_mask);
   }
-  int a_m[A_PW], a_c4[A_PW];                                     // source row and (swizzled) column of this lane
+  int pv = 0;                                                    // ORDER: the row at position m0 + lane (padded to whole tiles)
+  if constexpr (ORDER) pv = row_perm[m0 + lane];
+  auto row_at = [&](int m) {                                     // the row an output / operand position m of this tile stands for
+    if constexpr (ORDER) return __shfl(pv, m - m0);
+    else return m;
+  };
+  // (the epilogues fetch their rows once, while every lane is active, into `rows`; without ORDER the row is the position)
+  auto row_of = [&](const int* rows, int q, int m) {
+    if constexpr (ORDER) return rows[q];
+    else return m;
+  };
+  int a_m[A_PW], a_c4[A_PW];                                    // source row and (swizzled) column of this lane
   unsigned a_rm[A_PW];                                           // relations the row has in a sparse A1 (row_mask; else all)
 #pragma unroll
   for (int j = 0; j < A_PW; ++j) {
     const int row = (wave * A_PW + j) * 8 + (lane >> 3);
-    a_m[j] = min(m0 + row, M - 1);                               // rows past M read a valid row; never stored
+    if constexpr (ORDER) a_m[j] = row_at(m0 + row);              // positions past M hold a valid row; never stored
+    else a_m[j] = min(m0 + row, M - 1);                          // rows past M read a valid row; never stored
     a_c4[j] = ((lane & 7) ^ ((row >> 1) & 7)) * 4;
-    a_rm[j] = row_mask ? row_mask[a_m[j]] : 0xffffffffu;         // the lane's rows are fixed for the whole k loop
+    // the lane's rows are fixed for the whole k loop (ORDER: words in position order - requested beside `pv`, not behind it)
+    a_rm[j] = row_mask ? row_mask[ORDER ? m0 + row : a_m[j]] : 0xffffffffu;
   }
   const float* a_zero = g_zero_row + (lane & 7) * 4;
   int fin_b = 0, fin_e = 0;                      // this row tile's range of deferred hub items (below): the same round trip
@@ -512,11 +541,16 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
     const int trow = lane >> 4, tc4 = (lane & 15) * 4;
     const int nq = wn * W + tc4;                                      // n0 == 0: the workgroup owns whole rows
     float4 mk4[NV];
+    [[maybe_unused]] int mrow[ORDER ? NV : 1];     // ORDER: the rows of this lane's positions
+    if constexpr (ORDER) {
+#pragma unroll
+      for (int q = 0; q < NV; ++q) mrow[q] = row_at(m0 + wm * 32 + q * RPR + trow);
+    }
     if (EPI == EPI_MASK) {
 #pragma unroll
       for (int q = 0; q < NV; ++q) {
         const int m = m0 + wm * 32 + q * RPR + trow;
-        mk4[q] = m < M ? *reinterpret_cast<const float4*>(mask + (size_t)m * N + nq) : make_float4(0.f, 0.f, 0.f, 0.f);
+        mk4[q] = m < M ? *reinterpret_cast<const float4*>(mask + (size_t)row_of(mrow, q, m) * N + nq) : make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
 #pragma unroll
@@ -529,7 +563,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
         v.x = mk4[q].x > 0.f ? v.x : 0.f; v.y = mk4[q].y > 0.f ? v.y : 0.f;
         v.z = mk4[q].z > 0.f ? v.z : 0.f; v.w = mk4[q].w > 0.f ? v.w : 0.f;
       }
-      if (m < M) *reinterpret_cast<float4*>(C + (size_t)m * N + nq) = v;
+      if (m < M) *reinterpret_cast<float4*>(C + (size_t)row_of(mrow, q, m) * N + nq) = v;
       else v = make_float4(0.f, 0.f, 0.f, 0.f);
       cmax = fmaxf(cmax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
       *reinterpret_cast<float4*>(tr + (q * RPR + trow) * W + tc4) = v;   // (the same lane reads it back below)
@@ -651,13 +685,18 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
       }
       if (kq == KT2 - 1) {                         // the column block is complete: out, straight from the MFMA layout
         const int cb = cb2;
+        [[maybe_unused]] int trows[ORDER ? 16 : 1];   // ORDER: the rows of this lane's 16 positions (all lanes are here)
+        if constexpr (ORDER) {
+#pragma unroll
+          for (int q = 0; q < 16; ++q) trows[q] = row_at(m0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh);
+        }
 #pragma unroll
         for (int b = 0; b < TN; ++b) {
           const int n = cb * BN + (wn * TN + b) * 32 + li;
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
             const int m = m0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh;
-            if (m < M && n < N2) chain.T[(size_t)m * N2 + n] = acc2[b][q] * i2 * ic;
+            if (m < M && n < N2) chain.T[(size_t)row_of(trows, q, m) * N2 + n] = acc2[b][q] * i2 * ic;
             acc2[b][q] = 0.f;
           }
         }
@@ -683,10 +722,15 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
     float4 bv4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (bias) bv4 = *reinterpret_cast<const float4*>(bias + nq);
     float4 mk4[NV];
+    [[maybe_unused]] int mrow[ORDER ? NV : 1];     // ORDER: the rows of this lane's positions
+    if constexpr (ORDER) {
+#pragma unroll
+      for (int q = 0; q < NV; ++q) mrow[q] = row_at(m0 + wm * 32 + q * RPR + trow);
+    }
     if (EPI == EPI_MASK) {
 #pragma unroll
       for (int q = 0; q < NV; ++q)
-        mk4[q] = *reinterpret_cast<const float4*>(mask + (size_t)(m0 + wm * 32 + q * RPR + trow) * N + nq);
+        mk4[q] = *reinterpret_cast<const float4*>(mask + (size_t)row_of(mrow, q, m0 + wm * 32 + q * RPR + trow) * N + nq);
     }
 #pragma unroll
     for (int q = 0; q < NV; ++q) {
@@ -699,9 +743,14 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
         v.z = mk4[q].z > 0.f ? v.z : 0.f; v.w = mk4[q].w > 0.f ? v.w : 0.f;
       }
       cmax = fmaxf(cmax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-      *reinterpret_cast<float4*>(C + (size_t)(m0 + wm * 32 + q * RPR + trow) * N + nq) = v;
+      *reinterpret_cast<float4*>(C + (size_t)row_of(mrow, q, m0 + wm * 32 + q * RPR + trow) * N + nq) = v;
     }
   } else {
+    [[maybe_unused]] int erows[ORDER ? 16 : 1];    // ORDER: the rows of this lane's 16 positions, while all lanes are here
+    if constexpr (ORDER) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) erows[r] = row_at(m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh);
+    }
 #pragma unroll
     for (int b = 0; b < TN; ++b) {
       const int n = n0 + (wn * TN + b) * 32 + li;
@@ -713,9 +762,9 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_nt_split(const float* __r
         if (m < M) {
           float v = acc[b][r] * ia * ib + bv;
           if (EPI == EPI_RELU) v = rgcn_relu(v);
-          if (EPI == EPI_MASK) v = mask[(size_t)m * N + n] > 0.f ? v : 0.f;
+          if (EPI == EPI_MASK) v = mask[(size_t)row_of(erows, r, m) * N + n] > 0.f ? v : 0.f;
           cmax = fmaxf(cmax, fabsf(v));
-          C[(size_t)m * N + n] = v;
+          C[(size_t)row_of(erows, r, m) * N + n] = v;
         }
       }
     }
@@ -1178,6 +1227,7 @@ struct nt_call {
   const uint32_t* tile_mask = nullptr;         // relation occupancy of A1's row tiles, `kseg` columns per relation
   int kseg = 0;
   const uint32_t* row_mask = nullptr;          // A1 is a sparse aggregate: its rows' relation occupancy (behind tile_mask)
+  const int* row_perm = nullptr;               // row tiles in occupancy order (nt_row_order: masks and hub index follow it)
   const float *a1_amax = nullptr, *a2_amax = nullptr;   // amax buffers of the A operands; NULL: scanned into scan_slots
   float a1_mul = 1.f, out_scale = 1.f;
   float* c_amax = nullptr;                     // amax buffer that receives max |C|
@@ -1191,12 +1241,34 @@ struct nt_call {
 };
 
 // two wave columns (WM x WN = 2 x 2): see the notes in launch_nt_split
-template <int TN, int EPI, bool LO, bool CHAIN>
+template <int TN, int EPI, bool LO, bool CHAIN, bool ORDER = false>
 void nt_launch(const nt_call& c) {
   const dim3 grid((unsigned)ceil_div64(c.M, 64), CHAIN ? 1u : (unsigned)ceil_div64(c.N, 64 * TN));
-  k_gemm_nt_split<2, 2, TN, EPI, LO, CHAIN><<<grid, 256, 0, c.stream>>>(
+  k_gemm_nt_split<2, 2, TN, EPI, LO, CHAIN, ORDER><<<grid, 256, 0, c.stream>>>(
       c.A1, c.K1, c.A2, c.K2, c.Bh, c.Bl, c.b_inv, c.r1, c.a1_mul, c.r2, c.bias, c.mask, c.C, c.M, c.N, c.tile_mask, c.kseg,
-      reinterpret_cast<unsigned*>(c.c_amax), c.fin, c.out_scale, CHAIN ? c.chain : nt_chain{}, c.row_mask);
+      reinterpret_cast<unsigned*>(c.c_amax), c.fin, c.out_scale, CHAIN ? c.chain : nt_chain{}, c.row_mask, c.row_perm);
+}
+
+// RGCN_MODE_ROW_ORDER: the call's row tiles in the occupancy order that lies behind the structure's occupancy words
+// (`occupancy` = its tile_mask, rgcn_common.h) - the tile words, the row words of a sparse A1 and the index of the hub
+// tails all in position order, so that the kernel indexes them as it always did.
+int nt_row_order(nt_call* c, const uint32_t* occupancy, int64_t N, const rgcn_graph* hub_graph, int hub_transposed) {
+  // the regrouped hub items are those of the structure whose occupancy allocation this is
+  if (c->fin.ptr && hub_graph->dir[hub_transposed ? 1 : 0].tile_mask != occupancy) return RGCN_ERR_ARG;
+  const rgcn_order_offsets o = rgcn_order_offsets_of(N);
+  c->row_perm = reinterpret_cast<const int*>(occupancy + o.perm);
+  c->tile_mask = occupancy + o.tiles;
+  if (c->row_mask) c->row_mask = occupancy + o.rows;
+  if (c->fin.ptr) {
+    c->fin.ptr = reinterpret_cast<const int32_t*>(occupancy + o.fin);
+    c->fin.items = reinterpret_cast<const rgcn_item*>(occupancy + o.items);
+    c->fin.tiles = (int)(o.P / 32);
+  }
+  return RGCN_OK;
+}
+// what an entry point refuses of that bit before anything is launched: no occupancy allocation, or a structure without one
+inline bool nt_row_order_bad(int mode, const uint32_t* tile_mask, int64_t R) {
+  return (mode & RGCN_MODE_ROW_ORDER) && (!tile_mask || R > 32);
 }
 
 int launch_nt_split(nt_call c) {
@@ -1208,6 +1280,7 @@ int launch_nt_split(nt_call c) {
   if (fin.ptr && fin.d != 64 && fin.d != 128 && fin.d != 256) return RGCN_ERR_UNSUPPORTED;
   if (fin.ptr && (!c.a1_amax || fin.d != c.kseg)) return RGCN_ERR_ARG;   // an unfinished A1 cannot be scanned for its maximum
   if (c.row_mask && (!c.a1_amax || c.kseg <= 0 || c.kseg % BK != 0)) return RGCN_ERR_ARG;   // nor can a sparse one
+  if (c.row_perm && c.half) return RGCN_ERR_UNSUPPORTED;       // the occupancy order is built for the two-pass kernels
   const int K1 = c.K1, K2 = c.K2;
   if (K1 % BK || K2 % BK || K1 + K2 <= 0) return RGCN_ERR_UNSUPPORTED;
   // maxima of the A operands: from their producers, or scanned here (one launch over what is missing)
@@ -1232,6 +1305,7 @@ int launch_nt_split(nt_call c) {
   auto plain = [&](auto tn) {
     with_epi([&](auto epi) {
       if (c.half) nt_launch<decltype(tn)::value, decltype(epi)::value, false, false>(c);
+      else if (c.row_perm) nt_launch<decltype(tn)::value, decltype(epi)::value, true, false, true>(c);
       else nt_launch<decltype(tn)::value, decltype(epi)::value, true, false>(c);
     });
   };
@@ -1245,7 +1319,10 @@ int launch_nt_split(nt_call c) {
   // phase of four waves alone takes ~0.6 us, longer than the 0.25 us of MFMAs it was meant to hide behind.)
   if (c.chained)                 // the second product rides behind the first one (64 x 128 tiles, whole rows; no RELU: above)
     with_epi([&](auto epi) {
-      if constexpr (decltype(epi)::value != EPI_RELU) nt_launch<2, decltype(epi)::value, true, true>(c);
+      if constexpr (decltype(epi)::value != EPI_RELU) {
+        if (c.row_perm) nt_launch<2, decltype(epi)::value, true, true, true>(c);
+        else nt_launch<2, decltype(epi)::value, true, true>(c);
+      }
     });
   else if (c.N <= 64) plain(std::integral_constant<int, 1>{});
   else plain(std::integral_constant<int, 2>{});   // (a 128-row tile, WM = 4, was measured no faster at C2: 15.8 against 15.2 us of main loop)
@@ -1433,6 +1510,7 @@ int rgcn_transform_fwd_split(const float* agg, const float* x, const float* weig
   if (rgcn_layer_bad_dims(N, R, d_in, d_out) || !out) return RGCN_ERR_ARG;
   if (N == 0) return RGCN_OK;
   if (!agg || !x || !weight || ((half & RGCN_MODE_SPARSE_ROWS) && !tile_mask)) return RGCN_ERR_ARG;
+  if (nt_row_order_bad(half, tile_mask, R)) return RGCN_ERR_ARG;
   if (d_in % BK) return RGCN_ERR_UNSUPPORTED;
   if (rgcn_gemm_out_of_range(N, (R + 1) * d_in, d_out)) return RGCN_ERR_UNSUPPORTED;
   nt_call c;
@@ -1448,6 +1526,10 @@ int rgcn_transform_fwd_split(const float* agg, const float* x, const float* weig
   c.bias = bias; c.epi = relu ? EPI_RELU : EPI_NONE;
   c.C = out; c.N = (int)d_out; c.c_amax = out_amax;
   c.half = (half & 1) != 0;
+  if (half & RGCN_MODE_ROW_ORDER) {
+    const int orc = nt_row_order(&c, tile_mask, N, hub_graph, hub_transposed);
+    if (orc != RGCN_OK) return orc;
+  }
   return launch_nt_split(c);
 }
 
@@ -1461,6 +1543,7 @@ int rgcn_transform_bwd_input_split(const float* gagg, const float* g, const floa
   if (rgcn_layer_bad_dims(N, R, d_in, d_out) || !grad_x || !(out_scale > 0.f)) return RGCN_ERR_ARG;
   if (N == 0) return RGCN_OK;
   if (!gagg || !g || !weight || ((half & RGCN_MODE_SPARSE_ROWS) && !tile_mask)) return RGCN_ERR_ARG;
+  if (nt_row_order_bad(half, tile_mask, R)) return RGCN_ERR_ARG;
   if (d_out % BK) return RGCN_ERR_UNSUPPORTED;
   if (rgcn_gemm_out_of_range(N, (R + 1) * d_out, d_in)) return RGCN_ERR_UNSUPPORTED;
   nt_call c;
@@ -1476,6 +1559,10 @@ int rgcn_transform_bwd_input_split(const float* gagg, const float* g, const floa
   c.mask = relu_mask; c.epi = relu_mask ? EPI_MASK : EPI_NONE;
   c.C = grad_x; c.N = (int)d_in; c.c_amax = grad_x_amax; c.out_scale = out_scale;
   c.half = (half & 1) != 0;
+  if (half & RGCN_MODE_ROW_ORDER) {
+    const int orc = nt_row_order(&c, tile_mask, N, hub_graph, hub_transposed);
+    if (orc != RGCN_OK) return orc;
+  }
   return launch_nt_split(c);
 }
 
@@ -1499,6 +1586,8 @@ int rgcn_transform_bwd_input_chain_split(const float* gagg, const float* g, cons
   if (N == 0) return RGCN_OK;
   if (!gagg || !g || !weight || !gagg_amax || !g_amax) return RGCN_ERR_ARG;
   const bool sparse = (has_root1 & RGCN_MODE_SPARSE_ROWS) != 0;
+  const bool ordered = (has_root1 & RGCN_MODE_ROW_ORDER) != 0;
+  if (nt_row_order_bad(has_root1, tile_mask, R)) return RGCN_ERR_ARG;
   has_root1 &= 1;
   if (sparse && !tile_mask) return RGCN_ERR_ARG;
   if (rgcn_gemm_out_of_range(N, (R + 1) * d_out, (R1 + 1) * d_in1)) return RGCN_ERR_UNSUPPORTED;
@@ -1518,6 +1607,10 @@ int rgcn_transform_bwd_input_chain_split(const float* gagg, const float* g, cons
   c.C = grad_x; c.N = (int)d_in; c.c_amax = grad_x_amax; c.out_scale = out_scale;
   c.chained = true;
   c.chain = nt_chain{v1.Bh_n, v1.Bl_n, v1.inv_scale, t_out, (int)((R1 + (has_root1 ? 1 : 0)) * d_in1)};
+  if (ordered) {
+    const int orc = nt_row_order(&c, tile_mask, N, hub_graph, hub_transposed);
+    if (orc != RGCN_OK) return orc;
+  }
   return launch_nt_split(c);
 }
 

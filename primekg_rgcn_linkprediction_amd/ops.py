@@ -570,6 +570,17 @@ class BucketedGraph:
             cache[transposed] = _L().rgcn_graph_row_mask(handle, int(transposed), None) or None
         return cache[transposed]
 
+    def row_order_ptr(self, transposed: bool) -> Optional[int]:
+        """device pointer (as int) of the rows' occupancy order (``include/rgcn_row_order.h``), or None - what lets a
+        split NT transform take its row tiles in that order (``MODE_ROW_ORDER``)"""
+        if self.bipartite and transposed:
+            raise ValueError("a shard structure has one direction only (transposed=False)")
+        handle = self.handle                                         # raises once the graph is destroyed
+        cache = self.__dict__.setdefault("_row_order_ptrs", {})     # fixed for the life of the handle
+        if transposed not in cache:
+            cache[transposed] = _L().rgcn_graph_row_order(handle, int(transposed), None) or None
+        return cache[transposed]
+
     def workspace_bytes(self, transposed: bool, d: int) -> int:
         """bytes of partial-sum workspace ``aggregate`` needs for rows of width d (memoised)"""
         handle = self.handle
@@ -720,7 +731,7 @@ class BucketedGraph:
     def destroy(self) -> None:
         # recorded passes hold the handle and addresses of its arrays as immediates: they go first, and with them every
         # address remembered for the life of the handle
-        for memo in ("_regions", "_mask_ptrs", "_row_mask_ptrs"):
+        for memo in ("_regions", "_mask_ptrs", "_row_mask_ptrs", "_row_order_ptrs"):
             self.__dict__.pop(memo, None)
         for key in [k for k, hit in _GRAPH_CACHE.items() if hit[0] is self]:
             del _GRAPH_CACHE[key]                       # ``bucket`` must not hand this object out again
@@ -853,7 +864,7 @@ class _EdgeDropoutView(BucketedGraph):
         return self._handle is not None and self.parent.alive
 
     def destroy(self) -> None:
-        for memo in ("_regions", "_mask_ptrs", "_row_mask_ptrs"):
+        for memo in ("_regions", "_mask_ptrs", "_row_mask_ptrs", "_row_order_ptrs"):
             self.__dict__.pop(memo, None)          # recorded passes hold addresses of the view's arrays
         self._handle = None                        # owned by the EdgeDropout, not by this object
 
@@ -1302,12 +1313,22 @@ def _sparse_bit(sparse: bool, graph: Optional[BucketedGraph], transposed: bool, 
     return _lib.MODE_SPARSE_ROWS
 
 
+def _order_bit(row_order: bool, graph: Optional[BucketedGraph], transposed: bool, split) -> int:
+    """the option bit of a split NT transform that takes its row tiles in the occupancy order of ``graph``
+    (``include/rgcn_row_order.h``): two-pass split precision over a square structure of at most 32 relations that
+    carries an order; anything else runs in node order, as it always did (same bits either way)"""
+    if (not row_order or split != 1 or graph is None or graph.bipartite or graph.num_relations > 32
+            or graph.tile_mask_ptr(transposed) is None or graph.row_order_ptr(transposed) is None):
+        return 0
+    return _lib.MODE_ROW_ORDER
+
+
 def transform_fwd(agg, x, weight, root=None, bias=None, relu: bool = False,
                   graph: Optional[BucketedGraph] = None, half: bool = False, amax=None,
                   amax_out: Optional[torch.Tensor] = None, precision: Optional[str] = None,
                   packed: Optional[SplitWeights] = None, amax_mul: float = 1.0,
                   out: Optional[torch.Tensor] = None, hubs: Optional[DeferredHubs] = None,
-                  sparse: bool = False) -> torch.Tensor:
+                  sparse: bool = False, row_order: bool = False) -> torch.Tensor:
     """``sum_r agg[:, r] @ weight[r] + x @ root + bias`` as one fp32-MFMA GEMM; ``relu``
     fuses the activation that follows conv1 (``rgcn.py:124``) into the epilogue.  ``graph``
     (the structure ``agg`` was aggregated over) lets the kernel skip the k-tiles of relations
@@ -1343,6 +1364,7 @@ def transform_fwd(agg, x, weight, root=None, bias=None, relu: bool = False,
     elif hubs is not None:
         raise ValueError("deferred hub tails need the split-precision transform (finish them with aggregate instead)")
     mode = _sparse_bit(sparse, graph, False, split, _pair(amax, 2)[0] if split else None)
+    mode |= _order_bit(row_order, graph, False, split)
     k = (r + (root is not None)) * d_in
     with _on(x.device):
         if out is None:
@@ -1380,7 +1402,7 @@ def transform_bwd_input(gagg, g, weight, root=None, relu_mask=None,
                         graph: Optional[BucketedGraph] = None, amax=None, amax_out: Optional[torch.Tensor] = None,
                         precision: Optional[str] = None, packed: Optional[SplitWeights] = None,
                         amax_mul: float = 1.0, hubs: Optional[DeferredHubs] = None,
-                        out_scale: float = 1.0, sparse: bool = False) -> torch.Tensor:
+                        out_scale: float = 1.0, sparse: bool = False, row_order: bool = False) -> torch.Tensor:
     """``grad_x = out_scale * (sum_r gagg[:, r] @ weight[r]^T + g @ root^T)``; with ``relu_mask`` (the
     layer's input, when that input is the output of a fused-ReLU layer) the result is
     additionally multiplied by ``relu_mask > 0``.  ``out_scale`` (the ``1 / (1 - p)`` of a dropout whose
@@ -1393,6 +1415,7 @@ def transform_bwd_input(gagg, g, weight, root=None, relu_mask=None,
         raise ValueError("in/out channels must be multiples of 4")
     split = _use_split(precision, d_out, 32)
     mode = _sparse_bit(sparse, graph, True, split and n > 0, _pair(amax, 2)[0])
+    mode |= _order_bit(row_order, graph, True, split)
     if split and n > 0:
         a1, a2 = _pair(amax, 2)
         _check_amax("gagg_amax", a1, g.device)
@@ -1440,7 +1463,7 @@ def chain_supported(weight: torch.Tensor, weight1: torch.Tensor) -> bool:
 def transform_bwd_input_chain(gagg, g, weight, root, relu_mask, packed: SplitWeights, packed1: SplitWeights,
                               graph: Optional[BucketedGraph] = None, amax=None, amax_out: Optional[torch.Tensor] = None,
                               amax_mul: float = 1.0, hubs: Optional[DeferredHubs] = None, out_scale: float = 1.0,
-                              sparse: bool = False):
+                              sparse: bool = False, row_order: bool = False):
     """``(gz, T)``: ``gz = transform_bwd_input(gagg, g, weight, root, relu_mask, ...)`` - the same bits - and
     ``T = transform_first(gz, packed1)``, conv1's transform-first product (``[N, (R1 + 1) * d_in1]``), computed by the
     SAME launch: every workgroup keeps its 64-row tile of ``gz`` as fp16 hi / lo fragments and multiplies it by conv1's
@@ -1455,7 +1478,7 @@ def transform_bwd_input_chain(gagg, g, weight, root, relu_mask, packed: SplitWei
     _check_amax("amax_out", amax_out, g.device)
     if a1 is None or a2 is None:
         raise ValueError("the chained transform needs the operand maxima (amax=)")
-    mode = _sparse_bit(sparse, graph, True, True, a1)
+    mode = _sparse_bit(sparse, graph, True, True, a1) | _order_bit(row_order, graph, True, 1)
     lib = _L()
     cols = (r1 + (1 if packed1.has_root else 0)) * d_in1
     with _on(g.device):
@@ -3608,7 +3631,7 @@ class _NotRecordable(Exception):
 
 
 _SEQ_INDEX = {name: i for i, name in enumerate(_lib.SEQ_FUNCTIONS)}
-_SEQ_PURE = ("rgcn_graph_tile_mask", "rgcn_graph_row_mask", "rgcn_graph_num_levels", "rgcn_graph_weight_bound", "rgcn_aggregate_deferrable",
+_SEQ_PURE = ("rgcn_graph_tile_mask", "rgcn_graph_row_mask", "rgcn_graph_row_order", "rgcn_graph_num_levels", "rgcn_graph_weight_bound", "rgcn_aggregate_deferrable",
              "rgcn_graph_num_edges", "rgcn_graph_num_nodes", "rgcn_graph_num_relations", "rgcn_abi_version", "rgcn_strerror")
 REGIONS = True      # False: always through the wrappers (tests, tools/host_profile.py)
 
