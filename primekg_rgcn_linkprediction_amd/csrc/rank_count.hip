@@ -17,8 +17,7 @@
 // discipline there has to be made here too.  On the walk itself the kernel was measured 28 % slower (the raw launch
 // at B = 15,372, N = 30,926, d = 128: 1.645 -> 2.109 ms, profiles/tile_walk_shared.txt): there the epilogue sits
 // inside the loop, and the kernel came out at 186 VGPRs and 2,669 instructions against 150 and 2,399 here.
-#include "rgcn_common.h"
-#include "rgcn_mma_f32_dma.h"
+#include "rgcn_candidate_filter.h"    // and with it rgcn_common.h and rgcn_mma_f32_dma.h
 
 namespace {
 
@@ -166,7 +165,7 @@ int distmult_rank_tails(const float* hr, const float* emb, const float* true_sco
   if (batch < 0 || num_entities <= 0 || d <= 0 || (d % BK)) return (d > 0 && (d % BK)) ? RGCN_ERR_UNSUPPORTED : RGCN_ERR_ARG;
   if (batch == 0) return RGCN_OK;
   if (!hr || !emb || !true_score || !tail || !beaten_by) return RGCN_ERR_ARG;
-  if (batch > INT32_MAX / 2 || num_entities > INT32_MAX / 2) return RGCN_ERR_UNSUPPORTED;
+  if (!candidate_range_ok(batch, num_entities)) return RGCN_ERR_UNSUPPORTED;
   return launch_rank_count(hr, emb, true_score, tail, nullptr, nullptr, 0, nullptr, batch, num_entities, d, beaten_by,
                            stream_);
 }
@@ -175,10 +174,10 @@ int distmult_rank_masked(const float* q, const float* emb, const float* true_sco
                          const uint32_t* allow, const int32_t* query_class, int64_t num_classes, const uint32_t* exclude,
                          int64_t batch, int64_t num_entities, int64_t d, int32_t* beaten_by, void* stream_) {
   if (batch < 0 || num_entities <= 0 || d <= 0 || (d % BK)) return (d > 0 && (d % BK)) ? RGCN_ERR_UNSUPPORTED : RGCN_ERR_ARG;
-  if (num_classes < 0 || (allow && (num_classes == 0 || !query_class))) return RGCN_ERR_ARG;
+  if (!filter_args_ok(allow, query_class, num_classes)) return RGCN_ERR_ARG;
   if (batch == 0) return RGCN_OK;
   if (!q || !emb || !true_score || !target || !beaten_by) return RGCN_ERR_ARG;
-  if (batch > INT32_MAX / 2 || num_entities > INT32_MAX / 2) return RGCN_ERR_UNSUPPORTED;
+  if (!candidate_range_ok(batch, num_entities)) return RGCN_ERR_UNSUPPORTED;
   const int64_t words = ceil_div64(num_entities, 32);
   if (allow && num_classes * words > INT32_MAX) return RGCN_ERR_UNSUPPORTED;   // 32-bit word offsets in the epilogue
   return launch_rank_count(q, emb, true_score, target, allow, query_class, num_classes, exclude, batch, num_entities, d,

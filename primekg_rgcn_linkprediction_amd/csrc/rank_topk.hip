@@ -22,8 +22,7 @@
 // Merge pass, one workgroup per row: a k-round S-way merge of the row's slice lists by the total order.
 #include <math.h>
 
-#include "rgcn_common.h"
-#include "rgcn_mma_f32_dma.h"
+#include "rgcn_candidate_filter.h"    // and with it rgcn_common.h and rgcn_mma_f32_dma.h
 
 namespace {
 
@@ -104,18 +103,8 @@ __global__ __launch_bounds__(kThreads) void k_topk_select(const float* __restric
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // landed before the first barrier of the walk, which every epilogue follows
 
-  // this lane's mask row: lanes 0-31 carry the first 32-column group of the wave, lanes 32-63 the second.  The words
-  // are loaded at the first k-tile of a column tile from addresses that are always valid and looked at only in the
-  // epilogue (a load whose value is needed at once would drain the DMA ring behind it).
-  const int mrow = m0 + wm * 32 + li;
-  bool allowed_row = true;                                     // false: this query's class allows nothing
-  const uint32_t* arow_p = allow;
-  if (allow) {
-    const int c = qcls[min(mrow, M - 1)];
-    allowed_row = c >= 0 && c < num_classes;
-    arow_p = allow + (size_t)(allowed_row ? c : 0) * words;
-  }
-  const uint32_t* erow_p = excl ? excl + (size_t)min(mrow, M - 1) * words : nullptr;
+  // this lane's mask row: lanes 0-31 carry the first 32-column group of the wave, lanes 32-63 the second
+  lane_filter filt(allow, qcls, num_classes, excl, m0 + wm * 32 + li, M, words);
 
   Tile tile(wm, wn, li, lh);
 
@@ -178,13 +167,8 @@ __global__ __launch_bounds__(kThreads) void k_topk_select(const float* __restric
     }
   };
 
-  unsigned aw_raw = 0xffffffffu, ew_raw = 0u;
-  auto pre = [&](int ct) {
-    // the column tile's mask words, one (row, 32-column group) per lane, a column tile ahead of their use
-    const int w = min((ct * BN + (wn * 2 + lh) * 32) >> 5, words - 1);
-    if (allow) aw_raw = arow_p[w];
-    if (excl) ew_raw = erow_p[w];
-  };
+  // the column tile's mask words, one (row, 32-column group) per lane, a column tile ahead of their use
+  auto pre = [&](int ct) { filt.load(ct * BN + (wn * 2 + lh) * 32); };
   auto epi = [&](int ct, floatx16 (&acc)[2]) {
     // wave column 0 selects, then wave column 1: one stream of ascending ids per row.  Every wave passes exactly
     // one barrier here; the list writes of the first are complete (lgkmcnt(0)) before it, and those of the second
@@ -193,8 +177,7 @@ __global__ __launch_bounds__(kThreads) void k_topk_select(const float* __restric
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
     }
-    // (a 32-column group wholly past N has no word of its own: its lanes fail the n < N test)
-    select(ct, acc, (allowed_row ? aw_raw : 0u) & ~ew_raw);
+    select(ct, acc, filt.word());
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (wn == 0) __builtin_amdgcn_s_barrier();
   };
@@ -280,30 +263,13 @@ __global__ __launch_bounds__(kThreads) void k_topk_merge(const float* __restrict
   }
 }
 
-struct TopkPlan {
-  int num_tiles, tiles_per_slice, slices;
-};
-
-// Slices of the entity range: enough workgroups to fill the machine when the batch is small (one row tile: up to one
-// slice per column tile), one slice when the row tiles alone fill it (the workspace is batch x slices x k pairs).
-inline TopkPlan plan_topk(int64_t batch, int64_t num_entities, int64_t slices) {
-  TopkPlan p;
-  p.num_tiles = (int)ceil_div64(num_entities, BN);
-  const int64_t row_tiles = ceil_div64(batch, BM);
-  const int64_t want = slices > 0 ? slices : (row_tiles >= kCUs / 2 ? 1 : ceil_div64(kCUs, row_tiles));
-  const rgcn_slicing cut = rgcn_slice_tiles(p.num_tiles, want, kMaxSlices);
-  p.tiles_per_slice = cut.tiles_per_slice;
-  p.slices = cut.slices;
-  return p;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t distmult_topk_workspace_bytes(int64_t batch, int64_t num_entities, int64_t k, int64_t slices) {
   if (batch <= 0 || num_entities <= 0 || k <= 0 || slices < 0) return 0;
-  const TopkPlan p = plan_topk(batch, num_entities, slices);
+  const entity_slices p = plan_entity_slices(batch, num_entities, slices, kMaxSlices);
   return (size_t)batch * p.slices * k * (sizeof(float) + sizeof(int32_t));
 }
 
@@ -313,11 +279,11 @@ int distmult_topk_masked(const float* q, const float* emb, const uint32_t* allow
                          void* workspace, size_t workspace_bytes, void* stream_) {
   if (batch < 0 || num_entities <= 0 || d <= 0 || (d % BK)) return (d > 0 && (d % BK)) ? RGCN_ERR_UNSUPPORTED : RGCN_ERR_ARG;
   if (k <= 0 || slices < 0 || min_score != min_score) return RGCN_ERR_ARG;
-  if (num_classes < 0 || (allow && (num_classes == 0 || !query_class))) return RGCN_ERR_ARG;
+  if (!filter_args_ok(allow, query_class, num_classes)) return RGCN_ERR_ARG;
   if (batch == 0) return RGCN_OK;
   if (!q || !emb || !top_ids || !top_scores) return RGCN_ERR_ARG;
   if (k > kMaxK) return RGCN_ERR_UNSUPPORTED;
-  if (batch > INT32_MAX / 2 || num_entities > INT32_MAX / 2 || d > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
+  if (!candidate_range_ok(batch, num_entities) || d > (1 << 24)) return RGCN_ERR_UNSUPPORTED;
   const int64_t words = ceil_div64(num_entities, 32);
   if (allow && num_classes * words > INT32_MAX) return RGCN_ERR_UNSUPPORTED;   // 32-bit word offsets in the epilogue
   if (!workspace || workspace_bytes < distmult_topk_workspace_bytes(batch, num_entities, k, slices)) return RGCN_ERR_ARG;
@@ -325,7 +291,7 @@ int distmult_topk_masked(const float* q, const float* emb, const uint32_t* allow
   RGCN_ALIGN_TRY(8, top_ids);
   RGCN_ALIGN_TRY(4, allow, query_class, exclude, top_scores);
   hipStream_t stream = (hipStream_t)stream_;
-  const TopkPlan p = plan_topk(batch, num_entities, slices);
+  const entity_slices p = plan_entity_slices(batch, num_entities, slices, kMaxSlices);
   const size_t lds_bytes = select_lds_bytes((int)k);
   static bool raised[64] = {};
   const int rc = raise_lds(k_topk_select, (int)select_lds_bytes(kMaxK), raised);

@@ -17,8 +17,7 @@
 // score pass has just filled) into an output tile of 64 x d that lives in accumulators for the whole walk.
 #include <math.h>
 
-#include "rgcn_common.h"
-#include "rgcn_mma_f32_dma.h"
+#include "rgcn_candidate_filter.h"    // and with it rgcn_common.h and rgcn_mma_f32_dma.h
 #include "../../include/rgcn_softmax.h"
 
 namespace {
@@ -81,17 +80,8 @@ __global__ __launch_bounds__(kThreads) void k_softmax_fwd(const float* __restric
   const int li = lane & 31, lh = lane >> 5;
   const int words = (N + 31) >> 5;
 
-  // this lane's mask row, as in k_topk_select: lanes 0-31 carry the first 32-column group of the wave, lanes 32-63 the
-  // second; loaded at the first k-tile of a column tile, looked at only in the epilogue
-  const int mrow = m0 + wm * 32 + li;
-  bool allowed_row = true;
-  const uint32_t* arow_p = allow;
-  if (allow) {
-    const int c = qcls[min(mrow, M - 1)];
-    allowed_row = c >= 0 && c < num_classes;
-    arow_p = allow + (size_t)(allowed_row ? c : 0) * words;
-  }
-  const uint32_t* erow_p = excl ? excl + (size_t)min(mrow, M - 1) * words : nullptr;
+  // this lane's mask row: lanes 0-31 carry the first 32-column group of the wave, lanes 32-63 the second
+  lane_filter filt(allow, qcls, num_classes, excl, m0 + wm * 32 + li, M, words);
 
   int tg[16];                                                    // the targets of this lane's 16 rows
   float rm[16], rl[16];                                          // their running (max, sum relative to it)
@@ -103,14 +93,9 @@ __global__ __launch_bounds__(kThreads) void k_softmax_fwd(const float* __restric
   }
 
   Tile tile(wm, wn, li, lh);
-  unsigned aw_raw = 0xffffffffu, ew_raw = 0u;
-  auto pre = [&](int ct) {
-    const int w = min((ct * BN + (wn * 2 + lh) * 32) >> 5, words - 1);
-    if (allow) aw_raw = arow_p[w];
-    if (excl) ew_raw = erow_p[w];
-  };
+  auto pre = [&](int ct) { filt.load(ct * BN + (wn * 2 + lh) * 32); };
   auto epi = [&](int ct, floatx16 (&acc)[2]) {
-    const unsigned okw = (allowed_row ? aw_raw : 0u) & ~ew_raw;
+    const unsigned okw = filt.word();
     const int c0 = ct * BN + wn * 64 + li, c1 = c0 + 32;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -229,18 +214,9 @@ __global__ __launch_bounds__(kThreads) void k_softmax_bwd(const float* __restric
   int tg[DE ? 2 : 16];
   float gl[DE ? 2 : 16], ls[DE ? 2 : 16];
   unsigned okc[2] = {0u, 0u};
-  const int mrow = m0 + wm * 32 + li;
-  bool allowed_row = true;
-  const uint32_t* arow_p = allow;
-  const uint32_t* erow_p = nullptr;
-  unsigned aw_raw = 0xffffffffu, ew_raw = 0u;
+  lane_filter filt;
   if constexpr (!DE) {
-    if (allow) {
-      const int c = qcls[min(mrow, Bq - 1)];
-      allowed_row = c >= 0 && c < num_classes;
-      arow_p = allow + (size_t)(allowed_row ? c : 0) * words;
-    }
-    erow_p = excl ? excl + (size_t)min(mrow, Bq - 1) * words : nullptr;
+    filt = lane_filter(allow, qcls, num_classes, excl, m0 + wm * 32 + li, Bq, words);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = min(m0 + wm * 32 + acc_row(r, lh), Bq - 1);
@@ -254,9 +230,7 @@ __global__ __launch_bounds__(kThreads) void k_softmax_bwd(const float* __restric
   Tile tile(wm, wn, li, lh);
   auto pre = [&](int ct) {
     if constexpr (!DE) {
-      const int w = min((ct * BN + (wn * 2 + lh) * 32) >> 5, words - 1);
-      if (allow) aw_raw = arow_p[w];
-      if (excl) ew_raw = erow_p[w];
+      filt.load(ct * BN + (wn * 2 + lh) * 32);
     } else {
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
@@ -278,7 +252,7 @@ __global__ __launch_bounds__(kThreads) void k_softmax_bwd(const float* __restric
   };
   auto epi = [&](int ct, floatx16 (&acc)[2]) {
     // the coefficient tile -> LDS.  An ineligible entry is an exact 0 (selected), a streamed column past the end too.
-    const unsigned okw = (allowed_row ? aw_raw : 0u) & ~ew_raw;   // (dq)
+    const unsigned okw = filt.word();                             // (dq)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int rowl = acc_row(r, lh);
@@ -380,29 +354,12 @@ __global__ __launch_bounds__(kThreads) void k_softmax_slab_sum(const float* __re
   *reinterpret_cast<f32x4*>(dq + i) = v;
 }
 
-struct SoftmaxPlan {
-  int num_tiles, tiles_per_slice, slices;
-};
-
-// Slices of the entity range, the rule of the top-k pass: enough workgroups to fill the machine when the batch is small,
-// one slice when the row tiles alone fill it.  From batch and num_entities alone.
-inline SoftmaxPlan plan_softmax(int64_t batch, int64_t num_entities, int64_t slices) {
-  SoftmaxPlan p;
-  p.num_tiles = (int)ceil_div64(num_entities, BN);
-  const int64_t row_tiles = ceil_div64(batch, BM);
-  const int64_t want = slices > 0 ? slices : (row_tiles >= kCUs / 2 ? 1 : ceil_div64(kCUs, row_tiles));
-  const rgcn_slicing cut = rgcn_slice_tiles(p.num_tiles, want, kMaxSlices);
-  p.tiles_per_slice = cut.tiles_per_slice;
-  p.slices = cut.slices;
-  return p;
-}
-
 // the checks both entry points share, in the header's order
 inline int check_shape(int64_t batch, int64_t num_entities, int64_t d, int64_t slices, int64_t num_classes,
                        const uint32_t* allow, const int32_t* query_class) {
   if (batch < 0 || num_entities <= 0 || d <= 0 || slices < 0) return RGCN_ERR_ARG;
   if ((d % BK) || d > kMaxD) return RGCN_ERR_UNSUPPORTED;
-  if (num_classes < 0 || (allow && (num_classes == 0 || !query_class))) return RGCN_ERR_ARG;
+  if (!filter_args_ok(allow, query_class, num_classes)) return RGCN_ERR_ARG;
   return RGCN_OK;
 }
 
@@ -438,7 +395,7 @@ extern "C" {
 
 size_t rgcn_softmax_workspace_bytes(int64_t batch, int64_t num_entities, int64_t d, int64_t slices) {
   if (batch <= 0 || num_entities <= 0 || d <= 0 || slices < 0) return 0;
-  const SoftmaxPlan p = plan_softmax(batch, num_entities, slices);
+  const entity_slices p = plan_entity_slices(batch, num_entities, slices, kMaxSlices);
   const size_t fwd = (size_t)2 * p.slices * batch * sizeof(float);                       // (m, sum) per slice and row
   const size_t bwd = p.slices > 1 ? (size_t)p.slices * batch * d * sizeof(float) : 0;    // the partial dq slabs
   return align256(fwd > bwd ? fwd : bwd);
@@ -452,7 +409,7 @@ int rgcn_softmax_lse(const float* q, const float* emb, const int64_t* target, co
   if (bad) return bad;
   if (batch == 0) return RGCN_OK;
   if (!q || !emb || !target || !lse || !true_score || !row_max) return RGCN_ERR_ARG;
-  if (batch > INT32_MAX / 2 || num_entities > INT32_MAX / 2) return RGCN_ERR_UNSUPPORTED;
+  if (!candidate_range_ok(batch, num_entities)) return RGCN_ERR_UNSUPPORTED;
   if (!workspace || workspace_bytes < rgcn_softmax_workspace_bytes(batch, num_entities, d, slices)) return RGCN_ERR_WORKSPACE;
   RGCN_ALIGN_TRY(16, q, emb, workspace);
   RGCN_ALIGN_TRY(8, target);
@@ -460,7 +417,7 @@ int rgcn_softmax_lse(const float* q, const float* emb, const int64_t* target, co
   hipStream_t stream = (hipStream_t)stream_;
   int* flag = rgcn_index_error_flag();
   if (!flag) return RGCN_ERR_HIP;
-  const SoftmaxPlan p = plan_softmax(batch, num_entities, slices);
+  const entity_slices p = plan_entity_slices(batch, num_entities, slices, kMaxSlices);
   static bool raised[64] = {};
   const int rc = raise_lds(k_softmax_fwd, (int)kFwdLds, raised);
   if (rc) return rc;
@@ -489,8 +446,8 @@ int rgcn_softmax_grad(const float* g, const float* q, const float* emb, const in
     return RGCN_OK;
   }
   if (!g || !q || !emb || !target || !lse) return RGCN_ERR_ARG;
-  if (batch > INT32_MAX / 2 || num_entities > INT32_MAX / 2) return RGCN_ERR_UNSUPPORTED;
-  const SoftmaxPlan p = plan_softmax(batch, num_entities, slices);
+  if (!candidate_range_ok(batch, num_entities)) return RGCN_ERR_UNSUPPORTED;
+  const entity_slices p = plan_entity_slices(batch, num_entities, slices, kMaxSlices);
   const bool slabs = dq && p.slices > 1;
   if (slabs && (!workspace || workspace_bytes < rgcn_softmax_workspace_bytes(batch, num_entities, d, slices)))
     return RGCN_ERR_WORKSPACE;

@@ -1951,6 +1951,95 @@ def complex_query(x, x_idx, rel, rel_idx, side: str = "tail") -> torch.Tensor:
     return q
 
 
+# ----------------------------------------------------------------------------------
+# The frame of the passes that score every entity for every query - ranking, top-k, the 1-vs-all softmax (device side:
+# csrc/rgcn_candidate_filter.h): one check of the score operands, one of the candidate filter, one chunk rule and one
+# walk over the chunks of a known-triple mask.  Shapes are checked before devices: a wrong shape is a ``ValueError``
+# wherever the tensors live, right shapes on CPU tensors the "no CPU fallback" ``RuntimeError`` of ``_need_gpu``.
+# ----------------------------------------------------------------------------------
+def _score_shapes(kernels: str, q_name: str, q, emb, **vectors):
+    """``q [B, d]`` against ``emb [N, d]``, N > 0, d a multiple of 32, and the per-query ``vectors`` ``[B]``
+    -> ``(B, N, d)``"""
+    for name, t in ((q_name, q), ("emb", emb), *vectors.items()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    if (q.dim() != 2 or emb.dim() != 2 or emb.size(1) != q.size(1) or emb.size(0) == 0
+            or any(v.shape != (q.size(0),) for v in vectors.values())):
+        raise ValueError(f"{q_name} [B, d], emb [N, d] (N > 0)" + "".join(f", {name} [B]" for name in vectors) + " expected")
+    b, d = q.shape
+    if d % 32:
+        raise ValueError(f"embedding dim must be a multiple of 32 for the fused {kernels}, got {d}")
+    return b, emb.size(0), d
+
+
+def _filter_shapes(allow, query_class, exclude, b: int, w: int):
+    """``allow [C, W]`` with ``query_class [B]``, ``exclude [B, W]``, each optional -> ``(C, [(name, tensor, dtype)])``:
+    the number of classes (0 without ``allow``) and what ``_need_gpu`` has to see once every shape is right"""
+    classes, need = 0, []
+    if (allow is None) != (query_class is None):
+        raise ValueError("allow and query_class go together")
+    if allow is not None:
+        classes = allow.size(0) if allow.dim() == 2 else 0
+        if allow.dim() != 2 or allow.size(1) != w or classes == 0 or query_class.shape != (b,):
+            raise ValueError(f"allow [C, {w}] and query_class [B] expected")
+        need += [("allow", allow, torch.int32), ("query_class", query_class, torch.int32)]
+    if exclude is not None:
+        if exclude.shape != (b, w):
+            raise ValueError(f"exclude [{b}, {w}] expected")
+        need.append(("exclude", exclude, torch.int32))
+    return classes, need
+
+
+def _mask_chunk_rows(b: int, w: int, tile: int, max_mask_bytes: int) -> int:
+    """how many of ``b`` queries a chunk takes when a mask row costs ``4 w`` bytes: what fits into ``max_mask_bytes``
+    (one row at least), in whole row tiles of the pass (``tile``: 64 for ranking and top-k, 128 for the softmax, whose
+    backward streams queries in tiles of 128) once a tile fits"""
+    rows = max(1, int(max_mask_bytes) // (4 * w))
+    if rows >= tile:
+        rows -= rows % tile
+    return min(rows, b)
+
+
+def _exclude_chunks(needs: str, q, emb, known, side, anchor_idx, rel_idx, tile: int, max_mask_bytes: int):
+    """The queries in chunks whose exclude mask of ``known`` stays under ``max_mask_bytes`` (a mask row costs ``W * 4``
+    bytes, 62 KB per query at 500k nodes): yields ``(lo, hi, exclude rows of queries lo..hi)``.  One chunk: the mask is
+    built directly; more: every chunk's mask is built in ONE buffer, so a chunk's rows are gone at the next.  Nothing to
+    exclude (``known is None``) or no query: yields nothing."""
+    b = q.size(0)
+    if known is None or b == 0:
+        return
+    if anchor_idx is None or rel_idx is None:
+        raise ValueError(f"{needs} the anchor node ids and relation ids of the queries")
+    if known.num_nodes != emb.size(0):
+        raise ValueError(f"known triples are over {known.num_nodes} nodes, the candidates are {emb.size(0)}")
+    w = mask_words(emb.size(0))
+    rows = _mask_chunk_rows(b, w, tile, max_mask_bytes)
+    if rows >= b:
+        yield 0, b, known.exclude_bits(side, anchor_idx, rel_idx)
+        return
+    buf = _empty((rows, w), dtype=torch.int32, device=q.device)
+    for lo in range(0, b, rows):
+        hi = min(lo + rows, b)
+        yield lo, hi, known.exclude_bits(side, anchor_idx[lo:hi], rel_idx[lo:hi], out=buf)
+
+
+def _rows(t: Optional[torch.Tensor], lo: int, hi: int) -> Optional[torch.Tensor]:
+    return None if t is None else t[lo:hi]
+
+
+def _gather_chunk(outs, b: int, lo: int, hi: int, parts):
+    """the results ``parts`` of queries lo..hi into the whole-batch outputs ``outs`` (None before the first chunk: they
+    are allocated here); the one chunk that covers the batch is the output itself.  -> ``outs``"""
+    if hi - lo == b:
+        return tuple(parts)
+    if outs is None:
+        outs = tuple(None if p is None else _empty((b,) + tuple(p.shape[1:]), dtype=p.dtype, device=p.device) for p in parts)
+    for o, p in zip(outs, parts):
+        if p is not None:
+            o[lo:hi] = p
+    return outs
+
+
 def distmult_rank_tails(hr: torch.Tensor, emb: torch.Tensor, true_score: torch.Tensor,
                         tail: torch.Tensor) -> torch.Tensor:
     """``rank[b] = 1 + #{n != tail[b] : not (<hr[b], emb[n]> <= true_score[b])}`` (int64 [B]): the
@@ -1958,15 +2047,10 @@ def distmult_rank_tails(hr: torch.Tensor, emb: torch.Tensor, true_score: torch.T
     (``evaluate.py:260-276``).  Without NaN "not <=" is ">", infinities included, and equal scores do not count.  A NaN
     candidate counts against every true score (torch's descending argsort puts it there too); a NaN true score is beaten
     by every candidate: rank ``N`` - a missing value never ranks well (the rule of ``distmult_rank_masked``)."""
-    _need_gpu("hr", hr, torch.float32)
-    _need_gpu("emb", emb, torch.float32)
-    _need_gpu("true_score", true_score, torch.float32)
-    _need_gpu("tail", tail, torch.int64)
-    b, d = hr.shape
-    if emb.dim() != 2 or emb.size(1) != d or true_score.shape != (b,) or tail.shape != (b,):
-        raise ValueError("hr [B, d], emb [N, d], true_score [B], tail [B] expected")
-    if d % 32:
-        raise ValueError("embedding dim must be a multiple of 32 for the fused ranking kernel")
+    b, _, d = _score_shapes("ranking kernel", "hr", hr, emb, true_score=true_score, tail=tail)
+    for need in (("hr", hr, torch.float32), ("emb", emb, torch.float32), ("true_score", true_score, torch.float32),
+                 ("tail", tail, torch.int64)):
+        _need_gpu(*need)
     lib = _L()
     with _on(hr.device):
         beaten = _empty(b, dtype=torch.int32, device=hr.device).zero_()
@@ -2188,28 +2272,11 @@ def distmult_rank_masked(q: torch.Tensor, emb: torch.Tensor, true_score: torch.T
     reference protocol's argsort order).  A NaN true score is beaten by every eligible candidate: ``rank = 1 +
     #eligible`` (no mask: ``N``), on purpose unlike the reference, whose argsort would rank the missing value first.
     ``distmult_topk_masked`` differs: it never lists a NaN score - a list shows answers, a rank counts threats."""
-    _need_gpu("q", q, torch.float32)
-    _need_gpu("emb", emb, torch.float32)
-    _need_gpu("true_score", true_score, torch.float32)
-    _need_gpu("target", target, torch.int64)
-    b, d = q.shape
-    if emb.dim() != 2 or emb.size(1) != d or true_score.shape != (b,) or target.shape != (b,):
-        raise ValueError("q [B, d], emb [N, d], true_score [B], target [B] expected")
-    if d % 32:
-        raise ValueError("embedding dim must be a multiple of 32 for the fused ranking kernel")
-    w, classes = mask_words(emb.size(0)), 0
-    if (allow is None) != (query_class is None):
-        raise ValueError("allow and query_class go together")
-    if allow is not None:
-        _need_gpu("allow", allow, torch.int32)
-        _need_gpu("query_class", query_class, torch.int32)
-        classes = allow.size(0)
-        if allow.dim() != 2 or allow.size(1) != w or classes == 0 or query_class.shape != (b,):
-            raise ValueError(f"allow [C, {w}] and query_class [B] expected")
-    if exclude is not None:
-        _need_gpu("exclude", exclude, torch.int32)
-        if exclude.shape != (b, w):
-            raise ValueError(f"exclude [{b}, {w}] expected")
+    b, n, d = _score_shapes("ranking kernel", "q", q, emb, true_score=true_score, target=target)
+    classes, filters = _filter_shapes(allow, query_class, exclude, b, mask_words(n))
+    for need in (("q", q, torch.float32), ("emb", emb, torch.float32), ("true_score", true_score, torch.float32),
+                 ("target", target, torch.int64), *filters):
+        _need_gpu(*need)
     lib = _L()
     with _on(q.device):
         beaten = _empty(b, dtype=torch.int32, device=q.device).zero_()
@@ -2229,26 +2296,11 @@ def distmult_rank_filtered(q: torch.Tensor, emb: torch.Tensor, true_score: torch
     ``max_mask_bytes``, all through one buffer.  The count is ``distmult_rank_masked``'s - an eligible candidate counts
     unless ``score <= true_score`` - so a NaN candidate counts against every query that does not know it, and a NaN true
     score gives ``1 +`` the number of eligible (allowed, unknown, not the target) candidates."""
-    b = q.size(0)
-    if known is None or b == 0:
-        return distmult_rank_masked(q, emb, true_score, target, allow, query_class)
-    if anchor_idx is None or rel_idx is None:
-        raise ValueError("filtered ranking needs the anchor node ids and relation ids of the queries")
-    if known.num_nodes != emb.size(0):
-        raise ValueError(f"known triples are over {known.num_nodes} nodes, the candidates are {emb.size(0)}")
-    w = mask_words(emb.size(0))
-    rows = max(1, int(max_mask_bytes) // (4 * w))
-    if rows >= 64:
-        rows -= rows % 64                                        # whole row tiles of the ranking pass
-    rows = min(rows, b)
-    ranks = _empty(b, dtype=torch.int64, device=q.device)
-    buf = _empty((rows, w), dtype=torch.int32, device=q.device)
-    for lo in range(0, b, rows):
-        hi = min(lo + rows, b)
-        excl = known.exclude_bits(side, anchor_idx[lo:hi], rel_idx[lo:hi], out=buf)
-        ranks[lo:hi] = distmult_rank_masked(q[lo:hi], emb, true_score[lo:hi], target[lo:hi], allow,
-                                            None if query_class is None else query_class[lo:hi], excl)
-    return ranks
+    out = None
+    for lo, hi, excl in _exclude_chunks("filtered ranking needs", q, emb, known, side, anchor_idx, rel_idx, 64, max_mask_bytes):
+        part = distmult_rank_masked(q[lo:hi], emb, true_score[lo:hi], target[lo:hi], allow, _rows(query_class, lo, hi), excl)
+        out = _gather_chunk(out, q.size(0), lo, hi, (part,))
+    return out[0] if out else distmult_rank_masked(q, emb, true_score, target, allow, query_class)
 
 
 TOPK_MAX_K = 128          # list length the select kernel is built for (csrc/rank_topk.hip)
@@ -2268,29 +2320,13 @@ def distmult_topk_masked(q: torch.Tensor, emb: torch.Tensor, k: int, allow: Opti
         raise ValueError(f"k must be in [1, {TOPK_MAX_K}] (the top-k kernel keeps at most {TOPK_MAX_K} candidates per query), got {k}")
     if slices < 0:
         raise ValueError("slices must be >= 0 (0: chosen from the batch)")
-    _need_gpu("q", q, torch.float32)
-    _need_gpu("emb", emb, torch.float32)
-    if q.dim() != 2 or emb.dim() != 2 or emb.size(1) != q.size(1) or emb.size(0) == 0:
-        raise ValueError("q [B, d], emb [N, d] (N > 0) expected")
-    b, d = q.shape
-    if d % 32:
-        raise ValueError("embedding dim must be a multiple of 32 for the fused ranking kernel")
+    b, n, d = _score_shapes("ranking kernel", "q", q, emb)
     floor = float("-inf") if min_score is None else float(min_score)
     if floor != floor:
         raise ValueError("min_score must not be NaN")
-    w, classes = mask_words(emb.size(0)), 0
-    if (allow is None) != (query_class is None):
-        raise ValueError("allow and query_class go together")
-    if allow is not None:
-        _need_gpu("allow", allow, torch.int32)
-        _need_gpu("query_class", query_class, torch.int32)
-        classes = allow.size(0)
-        if allow.dim() != 2 or allow.size(1) != w or classes == 0 or query_class.shape != (b,):
-            raise ValueError(f"allow [C, {w}] and query_class [B] expected")
-    if exclude is not None:
-        _need_gpu("exclude", exclude, torch.int32)
-        if exclude.shape != (b, w):
-            raise ValueError(f"exclude [{b}, {w}] expected")
+    classes, filters = _filter_shapes(allow, query_class, exclude, b, mask_words(n))
+    for need in (("q", q, torch.float32), ("emb", emb, torch.float32), *filters):
+        _need_gpu(*need)
     lib = _L()
     with _on(q.device):
         ids = _empty((b, k), dtype=torch.int64, device=q.device)
@@ -2313,31 +2349,11 @@ def distmult_topk_filtered(q: torch.Tensor, emb: torch.Tensor, k: int, known: Op
     """``distmult_topk_masked`` over all queries with the exclude mask of ``known`` built chunk by chunk through one
     buffer, exactly as ``distmult_rank_filtered`` does: the novel candidates - no returned id completes a known
     triple with its query."""
-    b = q.size(0)
-    if known is None or b == 0:
-        return distmult_topk_masked(q, emb, k, allow, query_class, None, min_score, slices)
-    if anchor_idx is None or rel_idx is None:
-        raise ValueError("novel candidates need the anchor node ids and relation ids of the queries")
-    if known.num_nodes != emb.size(0):
-        raise ValueError(f"known triples are over {known.num_nodes} nodes, the candidates are {emb.size(0)}")
-    w = mask_words(emb.size(0))
-    rows = max(1, int(max_mask_bytes) // (4 * w))
-    if rows >= 64:
-        rows -= rows % 64                                        # whole row tiles of the select pass
-    rows = min(rows, b)
-    if rows >= b:
-        excl = known.exclude_bits(side, anchor_idx, rel_idx)
-        return distmult_topk_masked(q, emb, k, allow, query_class, excl, min_score, slices)
-    ids = _empty((b, int(k)), dtype=torch.int64, device=q.device)
-    scores = _empty((b, int(k)), dtype=torch.float32, device=q.device)
-    buf = _empty((rows, w), dtype=torch.int32, device=q.device)
-    for lo in range(0, b, rows):
-        hi = min(lo + rows, b)
-        excl = known.exclude_bits(side, anchor_idx[lo:hi], rel_idx[lo:hi], out=buf)
-        ids[lo:hi], scores[lo:hi] = distmult_topk_masked(q[lo:hi], emb, k, allow,
-                                                         None if query_class is None else query_class[lo:hi], excl,
-                                                         min_score, slices)
-    return ids, scores
+    out = None
+    for lo, hi, excl in _exclude_chunks("novel candidates need", q, emb, known, side, anchor_idx, rel_idx, 64, max_mask_bytes):
+        part = distmult_topk_masked(q[lo:hi], emb, k, allow, _rows(query_class, lo, hi), excl, min_score, slices)
+        out = _gather_chunk(out, q.size(0), lo, hi, part)
+    return out or distmult_topk_masked(q, emb, k, allow, query_class, None, min_score, slices)
 
 
 # ----------------------------------------------------------------------------------
@@ -2350,42 +2366,20 @@ SOFTMAX_MAX_D = _lib.SOFTMAX_MAX_D
 def _softmax_check(q, emb, target, allow, query_class, exclude, slices: int, g=None, lse=None):
     """the argument checks of ``softmax_lse`` / ``softmax_grad``, shapes before devices (a wrong shape is a ``ValueError``
     wherever the tensors live) -> (B, N, d, classes)"""
-    if not all(isinstance(t, torch.Tensor) for t in (q, emb, target)):
-        raise TypeError("q, emb and target must be torch.Tensors")
-    if q.dim() != 2 or emb.dim() != 2 or emb.size(1) != q.size(1) or emb.size(0) == 0 or target.shape != (q.size(0),):
-        raise ValueError("q [B, d], emb [N, d] (N > 0), target [B] expected")
-    b, d = q.shape
-    if d % 32:
-        raise ValueError(f"embedding dim must be a multiple of 32 for the fused softmax kernels, got {d}")
+    b, n, d = _score_shapes("softmax kernels", "q", q, emb, target=target)
     if d > SOFTMAX_MAX_D:
         raise ValueError(f"embedding dim must be at most {SOFTMAX_MAX_D} (the backward keeps a 64 x d output tile in "
                          f"accumulators), got {d}")
     if int(slices) < 0:
         raise ValueError("slices must be >= 0 (0: chosen from the batch and the number of entities)")
-    w, classes = mask_words(emb.size(0)), 0
-    if (allow is None) != (query_class is None):
-        raise ValueError("allow and query_class go together")
-    if allow is not None:
-        classes = allow.size(0) if allow.dim() == 2 else 0
-        if allow.dim() != 2 or allow.size(1) != w or classes == 0 or query_class.shape != (b,):
-            raise ValueError(f"allow [C, {w}] and query_class [B] expected")
-    if exclude is not None and exclude.shape != (b, w):
-        raise ValueError(f"exclude [{b}, {w}] expected")
-    for name, t in (("g", g), ("lse", lse)):
-        if t is not None and t.shape != (b,):
+    classes, filters = _filter_shapes(allow, query_class, exclude, b, mask_words(n))
+    grads = [(name, t, torch.float32) for name, t in (("g", g), ("lse", lse)) if t is not None]
+    for name, t, _ in grads:
+        if t.shape != (b,):
             raise ValueError(f"{name} [{b}] expected")
-    _need_gpu("q", q, torch.float32)
-    _need_gpu("emb", emb, torch.float32)
-    _need_gpu("target", target, torch.int64)
-    if allow is not None:
-        _need_gpu("allow", allow, torch.int32)
-        _need_gpu("query_class", query_class, torch.int32)
-    if exclude is not None:
-        _need_gpu("exclude", exclude, torch.int32)
-    for name, t in (("g", g), ("lse", lse)):
-        if t is not None:
-            _need_gpu(name, t, torch.float32)
-    return b, emb.size(0), d, classes
+    for need in (("q", q, torch.float32), ("emb", emb, torch.float32), ("target", target, torch.int64), *filters, *grads):
+        _need_gpu(*need)
+    return b, n, d, classes
 
 
 def softmax_lse(q: torch.Tensor, emb: torch.Tensor, target: torch.Tensor, allow: Optional[torch.Tensor] = None,
@@ -2449,13 +2443,6 @@ def softmax_grad(g: torch.Tensor, q: torch.Tensor, emb: torch.Tensor, target: to
     return dq, demb
 
 
-def _softmax_chunk_rows(b: int, w: int, max_mask_bytes: int) -> int:
-    rows = max(1, int(max_mask_bytes) // (4 * w))
-    if rows >= 128:
-        rows -= rows % 128                                       # whole query tiles of both passes
-    return min(rows, b)
-
-
 def softmax_lse_filtered(q, emb, target, known: Optional[KnownTriples] = None, side: str = "tail",
                          anchor_idx: Optional[torch.Tensor] = None, rel_idx: Optional[torch.Tensor] = None,
                          allow: Optional[torch.Tensor] = None, query_class: Optional[torch.Tensor] = None,
@@ -2463,28 +2450,11 @@ def softmax_lse_filtered(q, emb, target, known: Optional[KnownTriples] = None, s
     """``softmax_lse(..., with_loss=True)`` with the exclude mask of ``known`` built chunk by chunk through one buffer,
     as ``distmult_rank_filtered`` does (a mask row costs ``W * 4`` bytes): the forward is chunkable by rows, a row's
     result does not depend on the chunking.  -> ``(lse, true_score, row_max, loss, hit)``."""
-    b = q.size(0)
-    if known is None or b == 0:
-        return softmax_lse(q, emb, target, allow, query_class, None, slices, with_loss=True)
-    if anchor_idx is None or rel_idx is None:
-        raise ValueError("a filtered softmax needs the anchor node ids and relation ids of the queries")
-    if known.num_nodes != emb.size(0):
-        raise ValueError(f"known triples are over {known.num_nodes} nodes, the candidates are {emb.size(0)}")
-    w = mask_words(emb.size(0))
-    rows = _softmax_chunk_rows(b, w, max_mask_bytes)
-    if rows >= b:
-        return softmax_lse(q, emb, target, allow, query_class, known.exclude_bits(side, anchor_idx, rel_idx), slices,
-                           with_loss=True)
-    outs = [_empty(b, dtype=dt, device=q.device) for dt in (torch.float32,) * 4 + (torch.int32,)]
-    buf = _empty((rows, w), dtype=torch.int32, device=q.device)
-    for lo in range(0, b, rows):
-        hi = min(lo + rows, b)
-        excl = known.exclude_bits(side, anchor_idx[lo:hi], rel_idx[lo:hi], out=buf)
-        part = softmax_lse(q[lo:hi], emb, target[lo:hi], allow, None if query_class is None else query_class[lo:hi],
-                           excl, slices, with_loss=True)
-        for o, p in zip(outs, part):
-            o[lo:hi] = p
-    return tuple(outs)
+    out = None
+    for lo, hi, excl in _exclude_chunks("a filtered softmax needs", q, emb, known, side, anchor_idx, rel_idx, 128, max_mask_bytes):
+        part = softmax_lse(q[lo:hi], emb, target[lo:hi], allow, _rows(query_class, lo, hi), excl, slices, with_loss=True)
+        out = _gather_chunk(out, q.size(0), lo, hi, part)
+    return out or softmax_lse(q, emb, target, allow, query_class, None, slices, with_loss=True)
 
 
 def softmax_grad_filtered(g, q, emb, target, lse, known: Optional[KnownTriples] = None, side: str = "tail",
@@ -2496,31 +2466,16 @@ def softmax_grad_filtered(g, q, emb, target, lse, known: Optional[KnownTriples] 
     ``softmax_lse_filtered``.  ``dq`` is chunkable by rows.  ``demb`` accumulates over the chunks in chunk order - chunk
     0 writes it (or adds to it: ``accumulate``), every later chunk adds - so the same chunking (the same
     ``max_mask_bytes``) gives the same bits, and another chunking the same values to rounding."""
-    b = q.size(0)
-    if known is None or b == 0:
+    b, out = q.size(0), None
+    for lo, hi, excl in _exclude_chunks("a filtered softmax needs", q, emb, known, side, anchor_idx, rel_idx, 128, max_mask_bytes):
+        if hi - lo < b:                              # (the one chunk that covers the batch: the arguments as they came)
+            demb, accumulate = (demb, accumulate or lo > 0) if need_demb else (None, False)
+        part, demb = softmax_grad(g[lo:hi], q[lo:hi], emb, target[lo:hi], lse[lo:hi], allow, _rows(query_class, lo, hi),
+                                  excl, slices, need_dq, need_demb, demb, accumulate)
+        out = _gather_chunk(out, b, lo, hi, (part,))
+    if out is None:
         return softmax_grad(g, q, emb, target, lse, allow, query_class, None, slices, need_dq, need_demb, demb, accumulate)
-    if anchor_idx is None or rel_idx is None:
-        raise ValueError("a filtered softmax needs the anchor node ids and relation ids of the queries")
-    if known.num_nodes != emb.size(0):
-        raise ValueError(f"known triples are over {known.num_nodes} nodes, the candidates are {emb.size(0)}")
-    w = mask_words(emb.size(0))
-    rows = _softmax_chunk_rows(b, w, max_mask_bytes)
-    if rows >= b:
-        return softmax_grad(g, q, emb, target, lse, allow, query_class, known.exclude_bits(side, anchor_idx, rel_idx),
-                            slices, need_dq, need_demb, demb, accumulate)
-    dq = _empty((b, q.size(1)), dtype=torch.float32, device=q.device) if need_dq else None
-    if need_demb and demb is None:
-        demb = _empty(tuple(emb.shape), dtype=torch.float32, device=q.device)
-    buf = _empty((rows, w), dtype=torch.int32, device=q.device)
-    for lo in range(0, b, rows):
-        hi = min(lo + rows, b)
-        excl = known.exclude_bits(side, anchor_idx[lo:hi], rel_idx[lo:hi], out=buf)
-        part, _ = softmax_grad(g[lo:hi], q[lo:hi], emb, target[lo:hi], lse[lo:hi], allow,
-                               None if query_class is None else query_class[lo:hi], excl, slices, need_dq, need_demb,
-                               demb if need_demb else None, need_demb and (accumulate or lo > 0))
-        if need_dq:
-            dq[lo:hi] = part
-    return dq, (demb if need_demb else None)
+    return out[0], demb
 
 
 PATHS_MAX_K = 64          # one list entry per lane of the inserting wave (csrc/paths.hip)
