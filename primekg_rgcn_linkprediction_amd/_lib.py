@@ -64,7 +64,11 @@ SEQ_HOST_ARRAYS = {
 }
 
 
-# name -> (restype, argtypes); mirrors include/rgcn_hip.h one to one
+# The C boundary: one table per header of include/, name -> (restype, argtypes), each mirroring its header one to one;
+# HEADERS below is the registry that load() and the tests enumerate.  rgcn_hip.h is the training path: error codes, ABI
+# version, graph handles, and the only entry points rgcn_sequence_run may forward (SEQ_FUNCTIONS above).  Every other
+# header includes it for those conventions, declares entry points rgcn_hip.h does not know, and is never forwarded:
+# its calls (sampling, analysis, baselines, other heads, queries) happen outside any recorded Region.
 PROTOTYPES = {
     "rgcn_abi_version": (c_int, []),
     "rgcn_strerror": (c_char_p, [c_int]),
@@ -147,8 +151,7 @@ PROTOTYPES = {
                                  c_size_t, c_int, _P]),
 }
 
-# include/rgcn_sampling.h, one to one: the same library's protocol-aware sampler (not part of rgcn_hip.h, never forwarded by
-# rgcn_sequence_run - the trainer samples outside any recorded Region)
+# rgcn_sampling.h: the protocol-aware batch sampler (csrc/sampler_constrained.hip)
 SAMPLING_PROTOTYPES = {
     "rgcn_sample_batch_constrained": (c_int, [_P, _P, _I64, _P, _P, _I64, _I64, _I64, _P,          # slice, cursor, rng
                                               _P, _P, _P, _I64,                                    # classes
@@ -157,8 +160,7 @@ SAMPLING_PROTOTYPES = {
                                               _P, _P, _P, _P, _P]),
 }
 
-# include/rgcn_paths.h, one to one: score-ranked connecting paths between node pairs (csrc/paths.hip; not part of
-# rgcn_hip.h, never forwarded by rgcn_sequence_run - an analysis call, outside any recorded Region)
+# rgcn_paths.h: score-ranked connecting paths between node pairs (csrc/paths.hip)
 PATHS_PROTOTYPES = {
     "rgcn_edge_cosine": (c_int, [_P, _I64, c_int, _P, _P, _I64, _P, _P]),
     "rgcn_paths_workspace_bytes": (c_size_t, [_I64, c_int, c_int]),
@@ -167,8 +169,7 @@ PATHS_PROTOTYPES = {
                                 _P, _P, _P, _P, _P, c_size_t, _P]),            # outputs, workspace, stream
 }
 
-# include/rgcn_cluster.h, one to one: k-means and silhouette analysis of embedding rows (csrc/cluster.hip; not part of
-# rgcn_hip.h, never forwarded by rgcn_sequence_run - an analysis call, outside any recorded Region)
+# rgcn_cluster.h: k-means and silhouette analysis of embedding rows (csrc/cluster.hip)
 CLUSTER_PROTOTYPES = {
     "rgcn_kmeans_workspace_bytes": (c_size_t, [_I64, _I64, _I64, _I64]),
     "rgcn_kmeans_assign": (c_int, [_P, _I64, _I64, _P, _I64, _I64,                # rows, centroids
@@ -180,8 +181,7 @@ CLUSTER_PROTOTYPES = {
     "rgcn_silhouette_samples": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, c_size_t, _P]),
 }
 
-# include/rgcn_tsne.h, one to one: t-SNE projection of embedding rows to the plane (csrc/tsne.hip; not part of
-# rgcn_hip.h, never forwarded by rgcn_sequence_run - an analysis call, outside any recorded Region)
+# rgcn_tsne.h: t-SNE projection of embedding rows to the plane (csrc/tsne.hip)
 TSNE_PROTOTYPES = {
     "rgcn_knn_refine": (c_int, [_P, _I64, _I64, _P, _I64, _P, _P, _P]),
     "rgcn_tsne_affinities": (c_int, [_P, _I64, _I64, c_double, _P, _P, _P]),
@@ -191,8 +191,7 @@ TSNE_PROTOTYPES = {
     "rgcn_tsne_update": (c_int, [_P, _I64, c_float, c_float, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
-# include/rgcn_neighborhood.h, one to one: local-neighbourhood statistics of node pairs (csrc/neighborhood.hip; not part
-# of rgcn_hip.h, never forwarded by rgcn_sequence_run - an analysis call, outside any recorded Region)
+# rgcn_neighborhood.h: local-neighbourhood statistics of node pairs (csrc/neighborhood.hip)
 NEIGHBORHOOD_PROTOTYPES = {
     "rgcn_neighborhood_max_nodes": (_I64, []),
     "rgcn_pair_neighborhood": (c_int, [_P, _P, _P, _P, _I64, _I64,                 # structure
@@ -201,8 +200,7 @@ NEIGHBORHOOD_PROTOTYPES = {
                                        _P, _P, _P, _P, _P, _P, _P, _P]),           # outputs, stream
 }
 
-# include/rgcn_transe.h, one to one: one batch-synchronous TransE training step (csrc/transe.hip; not part of
-# rgcn_hip.h, never forwarded by rgcn_sequence_run - the baseline trains outside any recorded Region)
+# rgcn_transe.h: one batch-synchronous TransE training step (csrc/transe.hip)
 TRANSE_PROTOTYPES = {
     "rgcn_transe_step_workspace_bytes": (c_size_t, [_I64, _I64, _I64]),
     "rgcn_transe_step": (c_int, [_P, _I64, _P, _I64, _I64,                         # tables
@@ -210,8 +208,7 @@ TRANSE_PROTOTYPES = {
                                  _P, _P, _P, _P, c_size_t, _P]),                   # loss outputs, workspace, stream
 }
 
-# include/rgcn_resample.h, one to one: bootstrap resampling of the evaluation metrics (csrc/resample.hip; not part of
-# rgcn_hip.h, never forwarded by rgcn_sequence_run - an analysis call, outside any recorded Region)
+# rgcn_resample.h: bootstrap resampling of the evaluation metrics (csrc/resample.hip)
 RESAMPLE_PROTOTYPES = {
     "rgcn_resample_weights": (c_int, [_I64, _I64, _I64, _P, _P]),
     "rgcn_resample_curves": (c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64,     # sorted samples, cut, units, replicates, seed
@@ -224,8 +221,7 @@ RESAMPLE_MAX_SAMPLES = 1 << 28   # RGCN_RESAMPLE_MAX_SAMPLES
 RESAMPLE_MAX_REPLICATES = 65535  # RGCN_RESAMPLE_MAX_REPLICATES
 RESAMPLE_MAX_K = 8               # RGCN_RESAMPLE_MAX_K
 
-# include/rgcn_complex.h, one to one: the ComplEx scoring head (csrc/complex.hip; not part of rgcn_hip.h, never forwarded
-# by rgcn_sequence_run - the head runs outside any recorded Region).  Parameter for parameter the DistMult head's rows.
+# rgcn_complex.h: the ComplEx scoring head (csrc/complex.hip); parameter for parameter the DistMult head's rows
 COMPLEX_PROTOTYPES = {
     "complex_fwd": (c_int, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P]),
     "complex_bce_fwd": (c_int, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _P, _P]),
@@ -236,8 +232,7 @@ COMPLEX_PROTOTYPES = {
     "rgcn_complex_query": (c_int, [c_int, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P]),
 }
 
-# include/rgcn_softmax.h, one to one: the 1-vs-all softmax loss over every candidate (csrc/softmax_loss.hip; not part of
-# rgcn_hip.h, never forwarded by rgcn_sequence_run - the softmax step runs eagerly, outside any recorded Region)
+# rgcn_softmax.h: the 1-vs-all softmax loss over every candidate (csrc/softmax_loss.hip)
 SOFTMAX_PROTOTYPES = {
     "rgcn_softmax_workspace_bytes": (c_size_t, [_I64, _I64, _I64, _I64]),
     "rgcn_softmax_lse": (c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, _I64,     # operands, masks, sizes, slices
@@ -247,8 +242,7 @@ SOFTMAX_PROTOTYPES = {
 }
 SOFTMAX_MAX_D = 256              # widest row the backward keeps in accumulators (csrc/softmax_loss.hip)
 
-# include/rgcn_edge_dropout.h, one to one: edge dropout and hidden batch edges (csrc/edge_dropout.hip; not part of
-# rgcn_hip.h, never forwarded by rgcn_sequence_run - the draw happens outside any recorded Region, before the forward)
+# rgcn_edge_dropout.h: edge dropout and hidden batch edges, drawn before the forward (csrc/edge_dropout.hip)
 EDGE_DROPOUT_PROTOTYPES = {
     "rgcn_edge_dropout_create": (c_int, [c_void_p, _P, POINTER(c_void_p)]),
     "rgcn_edge_dropout_destroy": (None, [c_void_p]),
@@ -259,9 +253,9 @@ EDGE_DROPOUT_PROTOTYPES = {
 }
 EDGE_DROPOUT_STREAM = 0x45444F50   # RGCN_EDGE_DROPOUT_STREAM
 
-# include/rgcn_sparse.h, one to one: the row-granular occupancy behind sparse aggregates (csrc/rgcn_graph.hip; queries,
-# never forwarded by rgcn_sequence_run).  MODE_SPARSE_ROWS: RGCN_MODE_SPARSE_ROWS of rgcn_hip.h, the bit a training pass
-# sets in the `int` option word of its gathers and of the split transforms that read their aggregates.
+# rgcn_sparse.h: the row-granular occupancy behind sparse aggregates (csrc/rgcn_graph.hip).  MODE_SPARSE_ROWS:
+# RGCN_MODE_SPARSE_ROWS of rgcn_hip.h, the bit a training pass sets in the `int` option word of its gathers and of the
+# split transforms that read their aggregates.
 SPARSE_PROTOTYPES = {
     "rgcn_graph_row_mask": (c_void_p, [c_void_p, c_int, POINTER(c_int64)]),
     "rgcn_occupancy_host": (_I64, [_P, _I64, _I64, _P, POINTER(c_int64)]),
@@ -269,10 +263,9 @@ SPARSE_PROTOTYPES = {
 MODE_SPARSE_ROWS = 2
 
 
-# include/rgcn_row_order.h, one to one: the occupancy order of a structure's rows, built with the graph behind its
-# occupancy words (csrc/rgcn_graph.hip; queries, never forwarded by rgcn_sequence_run).  MODE_ROW_ORDER:
-# RGCN_MODE_ROW_ORDER of that header, one more bit of the option word that carries MODE_SPARSE_ROWS - the split NT
-# transforms then take their 64-row tiles in that order.
+# rgcn_row_order.h: the occupancy order of a structure's rows, built with the graph behind its occupancy words
+# (csrc/rgcn_graph.hip).  MODE_ROW_ORDER: RGCN_MODE_ROW_ORDER of that header, one more bit of the option word that
+# carries MODE_SPARSE_ROWS - the split NT transforms then take their 64-row tiles in that order.
 class RowOrderLayout(ctypes.Structure):
     _fields_ = [(name, c_int64) for name in ("padded_rows", "perm", "row_words", "tile_words", "fin_ptr", "items",
                                               "num_items", "total_words")]
@@ -284,6 +277,23 @@ ROW_ORDER_PROTOTYPES = {
 }
 MODE_ROW_ORDER = 4
 
+# header of include/ -> its table, in the order the headers arrived: what load() types and every test enumerates
+HEADERS = {
+    "rgcn_hip.h": PROTOTYPES,
+    "rgcn_sampling.h": SAMPLING_PROTOTYPES,
+    "rgcn_paths.h": PATHS_PROTOTYPES,
+    "rgcn_cluster.h": CLUSTER_PROTOTYPES,
+    "rgcn_tsne.h": TSNE_PROTOTYPES,
+    "rgcn_neighborhood.h": NEIGHBORHOOD_PROTOTYPES,
+    "rgcn_transe.h": TRANSE_PROTOTYPES,
+    "rgcn_resample.h": RESAMPLE_PROTOTYPES,
+    "rgcn_complex.h": COMPLEX_PROTOTYPES,
+    "rgcn_softmax.h": SOFTMAX_PROTOTYPES,
+    "rgcn_edge_dropout.h": EDGE_DROPOUT_PROTOTYPES,
+    "rgcn_sparse.h": SPARSE_PROTOTYPES,
+    "rgcn_row_order.h": ROW_ORDER_PROTOTYPES,
+}
+
 _lib = None
 
 
@@ -291,11 +301,23 @@ class RGCNLibraryError(RuntimeError):
     """The HIP library is missing / unloadable / of the wrong ABI."""
 
 
+def all_prototypes() -> dict:
+    """name -> (restype, argtypes) over every header; a name that two headers' tables hold is refused"""
+    merged, owner = {}, {}
+    for header, table in HEADERS.items():
+        for name, prototype in table.items():
+            if name in owner:
+                raise RGCNLibraryError(f"{name} is in the tables of both {owner[name]} and {header}")
+            merged[name], owner[name] = prototype, header
+    return merged
+
+
 def load() -> ctypes.CDLL:
     """dlopen the library once and type every entry point.  Raises loudly."""
     global _lib
     if _lib is not None:
         return _lib
+    prototypes = all_prototypes()
     if not os.path.exists(LIB_PATH):
         raise RGCNLibraryError(
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; "
@@ -305,7 +327,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:  # pragma: no cover - depends on the host
         raise RGCNLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SAMPLING_PROTOTYPES.items()) + list(PATHS_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()) + list(NEIGHBORHOOD_PROTOTYPES.items()) + list(TRANSE_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + list(COMPLEX_PROTOTYPES.items()) + list(SPARSE_PROTOTYPES.items()) + list(ROW_ORDER_PROTOTYPES.items()) + list(SOFTMAX_PROTOTYPES.items()) + list(EDGE_DROPOUT_PROTOTYPES.items()):
+    for name, (restype, argtypes) in prototypes.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -2,78 +2,26 @@
 check that runs before a launch, the Python wrappers' checks by name, the float64 restatement (``cluster_reference.py``)
 the GPU tier holds the device to against scikit-learn, and the CLI's parser and JSON shape on a stubbed evaluator."""
 import argparse
-import ctypes
 import json
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import c_surface as S
 import cluster_reference as R
-from conftest import ROOT
 from primekg_rgcn_linkprediction_amd import _lib, consumers, evaluate, ops
 from primekg_rgcn_linkprediction_amd import cluster as C
 
-NAMES = ["rgcn_kmeans_assign", "rgcn_kmeans_inertia", "rgcn_kmeans_update", "rgcn_kmeans_workspace_bytes",
-         "rgcn_silhouette_samples", "rgcn_silhouette_workspace_bytes"]
-
 
 # ---------------------------------------------------------------------------------- C surface
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    found = re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", text)
-    return {name: [" ".join(p.split()) for p in params.split(",")] for name, params in found}
-
-
-def _kind_in_header(param):
-    if "*" in param:
-        return "pointer"
-    return next(k for k in ("float", "double", "size_t", "int64_t", "int") if re.search(rf"\b{k}\b", param))
-
-
-def _kind_in_ctypes(ty):
-    kinds = {ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_size_t: "size_t", ctypes.c_int64: "int64_t",
-             ctypes.c_int: "int"}
-    if ty in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ty, ctypes._Pointer):
-        return "pointer"
-    return kinds[ty]
-
-
 def test_cluster_header_table_and_library_agree():
-    declared = _declared("rgcn_cluster.h")
-    assert sorted(declared) == sorted(_lib.CLUSTER_PROTOTYPES) == NAMES
-    lib = _lib.load()
-    for name, params in declared.items():
-        restype, argtypes = _lib.CLUSTER_PROTOTYPES[name]
-        assert restype is (ctypes.c_size_t if name.endswith("_bytes") else ctypes.c_int) and len(argtypes) == len(params), name
-        for i, (param, ty) in enumerate(zip(params, argtypes)):
-            assert _kind_in_ctypes(ty) == _kind_in_header(param), f"{name}: parameter {i} ({param})"
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == argtypes
-        assert name not in _lib.PROTOTYPES and name not in _lib.SAMPLING_PROTOTYPES and name not in _lib.PATHS_PROTOTYPES
-        assert name not in _lib.SEQ_FUNCTIONS
-    main_header = open(os.path.join(ROOT, "include", "rgcn_hip.h")).read()
-    assert "rgcn_kmeans" not in main_header and "rgcn_silhouette" not in main_header
-    assert f"#define RGCN_ABI_VERSION {_lib.ABI_VERSION}\n" in main_header and lib.rgcn_abi_version() == _lib.ABI_VERSION >= 32
-    for other in ("rgcn_sampling.h", "rgcn_paths.h"):
-        assert not set(declared) & set(_declared(other))
-    text = open(os.path.join(ROOT, "include", "rgcn_cluster.h")).read()
-    assert '#include "rgcn_hip.h"' in text
+    """names, parameters, return types and exports: test_c_surface.py, for every header.  Here: the limits the header
+    states and the wrappers mirror"""
+    text = S.header_text("rgcn_cluster.h")
     assert f"#define RGCN_CLUSTER_MAX_K {ops.CLUSTER_MAX_K}\n" in text and ops.CLUSTER_MAX_K >= 33
     assert f"#define RGCN_CLUSTER_MAX_RESTARTS {ops.CLUSTER_MAX_RESTARTS}\n" in text
     assert "relocate" in text                                  # the empty-cluster rule and how scikit-learn differs
-
-
-def test_cluster_header_is_plain_c(tmp_path):
-    import shutil
-    import subprocess
-    if shutil.which("gcc") is None:
-        pytest.skip("no gcc")
-    src = tmp_path / "c.c"
-    src.write_text('#include "include/rgcn_cluster.h"\nint main(void) { return RGCN_CLUSTER_MAX_K > 32 ? RGCN_OK : 1; }\n')
-    for cc, std, lang in (("gcc", "-std=c99", "c"), ("g++", "-std=c++17", "c++")):
-        subprocess.run([cc, std, "-Wall", "-Wextra", "-pedantic", "-fsyntax-only", "-x", lang, "-I", ROOT, str(src)], check=True)
 
 
 def test_cluster_entry_points_reject_bad_arguments_without_a_gpu():

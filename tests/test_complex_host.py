@@ -1,30 +1,26 @@
 """CPU tier of the ComplEx head (``csrc/complex.hip``, ``include/rgcn_complex.h``, ``head.py``): the C surface, every
-argument check that runs before a launch (sizes, NULLs, alignment with the fake addresses of ``test_alignment_host.py``),
+argument check that runs before a launch (sizes, NULLs, alignment with the fake addresses of ``c_surface.py``),
 and the float64 restatement the GPU tier judges the kernels by (``complex_reference.py``) against itself: the two query
 operands on integer data, exactly, and the six gradient products against torch autograd of the score."""
-import ctypes
 import os
-import re
 
 import pytest
 import torch
 
+import c_surface as S
 import complex_reference as R
-import test_alignment_host as TA
+from c_surface import STREAM, T4, T8, T16
 from conftest import ROOT
 from primekg_rgcn_linkprediction_amd import _lib, head, ops
 
-OK, ARG, ALIGN = _lib.RGCN_OK, _lib.RGCN_ERR_ARG, _lib.RGCN_ERR_ALIGN
-NAMES = ["complex_bce_bwd", "complex_bce_fwd", "complex_bwd", "complex_bwd_workspace_bytes", "complex_fwd",
-         "rgcn_complex_query"]
-T16, T8, T4, STREAM = TA.T16, TA.T8, TA.T4, TA.STREAM
+OK, ARG = _lib.RGCN_OK, _lib.RGCN_ERR_ARG
 
 
 def _ws(batch=1, d=8, r=1):
     return lambda: _lib.load().complex_bwd_workspace_bytes(batch, d, r)
 
 
-# argument sets at the smallest legal sizes, parameter by parameter, in the notation of test_alignment_host.CASES
+# argument sets at the smallest legal sizes, parameter by parameter, in the notation of c_surface.py
 CASES = {
     "complex_fwd": [T16, T8, 1, T16, T8, 1, T16, T8, 1, 1, 8, T4, STREAM],
     "complex_bce_fwd": [T16, T8, 1, T16, T8, 1, T16, T8, 1, T4, 1, 8, T4, T4, STREAM],
@@ -32,76 +28,26 @@ CASES = {
     "complex_bce_bwd": [T4, T4, T4, T16, T8, 1, T16, T8, 1, T16, T8, 1, 1, 8, T16, T16, T16, T16, _ws(), 1, STREAM],
     "rgcn_complex_query": [0, T16, T8, 1, T16, T8, 1, 1, 8, T16, STREAM],
 }
+ALIGNMENT_CASES = {name: [args] for name, args in CASES.items()}
 BATCH_AT = {"complex_fwd": 9, "complex_bce_fwd": 10, "complex_bwd": 10, "complex_bce_bwd": 12, "rgcn_complex_query": 7}
 
 
 # ---------------------------------------------------------------------------------- C surface
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    found = re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", text)
-    return {name: [" ".join(p.split()) for p in params.split(",")] for name, params in found}
-
-
-def _kind_in_header(param):
-    if "*" in param:
-        return "pointer"
-    return next(k for k in ("float", "double", "size_t", "int64_t", "int") if re.search(rf"\b{k}\b", param))
-
-
-def _kind_in_ctypes(ty):
-    kinds = {ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_size_t: "size_t", ctypes.c_int64: "int64_t",
-             ctypes.c_int: "int"}
-    if ty in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ty, ctypes._Pointer):
-        return "pointer"
-    return kinds[ty]
-
-
 def test_header_table_and_library_agree():
-    lib = _lib.load()
-    declared = _declared("rgcn_complex.h")
-    assert sorted(declared) == sorted(_lib.COMPLEX_PROTOTYPES) == NAMES
-    for name in NAMES:
-        restype, argtypes = _lib.COMPLEX_PROTOTYPES[name]
-        params = declared[name]
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == argtypes
-        assert len(argtypes) == len(params), name
-        for i, (param, ty) in enumerate(zip(params, argtypes)):
-            assert _kind_in_ctypes(ty) == _kind_in_header(param), f"{name}: parameter {i} ({param})"
-        assert restype is (ctypes.c_size_t if name.endswith("_bytes") else ctypes.c_int)
-        assert all(name not in table for table in (_lib.PROTOTYPES, _lib.SEQ_FUNCTIONS))
-    # the DistMult head's operand convention, parameter for parameter
+    """names, parameters, return types and exports: test_c_surface.py, for every header.  Here: the DistMult head's
+    operand convention, parameter for parameter"""
     for ours, theirs in (("complex_fwd", "distmult_fwd"), ("complex_bce_fwd", "distmult_bce_fwd"), ("complex_bwd", "distmult_bwd"),
                          ("complex_bce_bwd", "distmult_bce_bwd"), ("complex_bwd_workspace_bytes", "distmult_bwd_workspace_bytes")):
         assert _lib.COMPLEX_PROTOTYPES[ours] == _lib.PROTOTYPES[theirs]
-    header = open(os.path.join(ROOT, "include", "rgcn_complex.h")).read()
-    main_header = open(os.path.join(ROOT, "include", "rgcn_hip.h")).read()
-    assert '#include "rgcn_hip.h"' in header and not any(name in main_header for name in NAMES)
     makefile = open(os.path.join(ROOT, "primekg_rgcn_linkprediction_amd", "csrc", "Makefile")).read()
     assert " complex.hip" in makefile
-
-
-def test_abi_38_in_both_places():
-    main_header = open(os.path.join(ROOT, "include", "rgcn_hip.h")).read()
-    assert "#define RGCN_ABI_VERSION 38\n" in main_header
-    assert _lib.ABI_VERSION == 38 == _lib.load().rgcn_abi_version()
-
-
-def test_header_is_plain_c(tmp_path):
-    import shutil
-    import subprocess
-    if shutil.which("gcc") is None:
-        pytest.skip("no gcc")
-    src = tmp_path / "t.c"
-    src.write_text('#include "include/rgcn_complex.h"\nint main(void) { return RGCN_OK; }\n')
-    for cc, std, lang in (("gcc", "-std=c99", "c"), ("g++", "-std=c++17", "c++")):
-        subprocess.run([cc, std, "-Wall", "-Wextra", "-pedantic", "-fsyntax-only", "-x", lang, "-I", ROOT, str(src)], check=True)
 
 
 def _values(name, **changes):
     args = list(CASES[name])
     for pos, v in changes.items():
         args[int(pos)] = v
-    values, keep = TA._build(args)
+    values, keep = S.build(args)
     return values, keep
 
 
@@ -118,21 +64,21 @@ def test_sizes_and_nulls_are_refused_without_a_gpu(name):
     values, keep = _values(name, **{str(BATCH_AT[name]): -1})
     assert fn(*values) == ARG
     # batch = 0: RGCN_OK before any pointer is looked at - every pointer NULL (the backward with nothing to clear)
-    empty = [None if isinstance(a, TA.Dev) else a for a in args]
+    empty = [None if isinstance(a, S.Dev) else a for a in args]
     empty[BATCH_AT[name]] = 0
     if name.endswith("bwd"):
         empty[-2] = 0                                                    # zero_tables off: nothing to clear, no HIP call
-    values, keep = TA._build(empty)
+    values, keep = S.build(empty)
     assert fn(*values) == OK, name
     bad = list(empty)
     bad[d_at] = 12
-    values, keep = TA._build(bad)
+    values, keep = S.build(bad)
     assert fn(*values) == ARG                                            # the size check comes first
     # a needed pointer NULL with batch > 0.  Index vectors and gradients are optional: with one of those NULL the set
     # would pass every check and launch on fake addresses, so they are never called here
     for pos, a in enumerate(args):
         optional = name.endswith("bwd") and pos in (len(args) - 7, len(args) - 6, len(args) - 5)
-        if isinstance(a, TA.Dev) and a.align != 8 and not optional:
+        if isinstance(a, S.Dev) and a.align != 8 and not optional:
             values, keep = _values(name, **{str(pos): None})
             code = fn(*values)
             if name.endswith("bwd") and pos == len(args) - 4:
@@ -161,18 +107,11 @@ def test_workspace_query():
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_a_pointer_below_its_alignment_is_refused(name):
-    fn = getattr(_lib.load(), name)
     args = CASES[name]
-    failed = []
-    targets = TA._targets(name, args)
-    assert len(targets) == sum(_kind_in_ctypes(ty) == "pointer" for ty in _lib.COMPLEX_PROTOTYPES[name][1]) - 1   # all but the stream
-    for pos, sub, dev in targets:
-        for shift in dev.shifts():
-            values, keep = TA._build(args, (pos, sub), shift)
-            code = fn(*values)
-            if code != ALIGN:
-                failed.append(f"parameter {pos} (alignment {dev.align}) moved by {shift}: code {code} ({_lib.strerror(code)})")
-    assert not failed, f"{name}: " + "; ".join(failed)
+    pointers = sum(S.is_pointer(ty) for ty in _lib.COMPLEX_PROTOTYPES[name][1])
+    assert len(S.targets(name, args)) == pointers - 1                      # all but the stream
+    failed = S.misaligned_refusals(getattr(_lib.load(), name), name, args)
+    assert not failed, "; ".join(failed)
 
 
 # ---------------------------------------------------------------------------------- wrappers and the module

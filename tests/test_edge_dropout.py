@@ -9,10 +9,10 @@ import pytest
 import torch
 
 import edge_dropout_reference as R
+from c_surface import _Graph
 from conftest import need_gpu
 from oracle import rgcn_oracle as O
 from primekg_rgcn_linkprediction_amd import RGCNConv, _lib, conv as C, ops, rgcn_encoder2, train as T
-from test_alignment_host import _Graph
 from test_gpu_parity import assert_fwd, assert_grad
 
 pytestmark = pytest.mark.gpu

@@ -11,41 +11,21 @@ import numpy as np
 import pytest
 import torch
 
+import c_surface as S
 import edge_dropout_reference as R
 import resample_reference as RR
 from conftest import ROOT
 from oracle import rgcn_oracle as O
 from primekg_rgcn_linkprediction_amd import _lib, train
 
-NAMES = ["rgcn_edge_dropout_create", "rgcn_edge_dropout_destroy", "rgcn_edge_dropout_draw", "rgcn_edge_dropout_graph",
-         "rgcn_edge_dropout_kept", "rgcn_edge_dropout_kept_export"]
-FAKE = 0x7F0000000000            # fake addresses, never dereferenced
+FAKE = S.FAKE_BASE               # a fake address, never dereferenced
 
 
 # ---------------------------------------------------------------------------------- C surface
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    found = re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", text)
-    return {name: [" ".join(p.split()) for p in params.split(",")] for name, params in found}
-
-
 def test_header_table_and_library_agree():
-    lib = _lib.load()
-    declared = _declared("rgcn_edge_dropout.h")
-    assert sorted(declared) == sorted(_lib.EDGE_DROPOUT_PROTOTYPES) == NAMES
-    for name in NAMES:
-        restype, argtypes = _lib.EDGE_DROPOUT_PROTOTYPES[name]
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == argtypes
-        assert len(argtypes) == len(declared[name]), name
-        for param, ty in zip(declared[name], argtypes):
-            kind = "pointer" if "*" in param else next(k for k in ("double", "int64_t", "int") if re.search(rf"\b{k}\b", param))
-            want = {ctypes.c_double: "double", ctypes.c_int64: "int64_t", ctypes.c_int: "int"}.get(ty, "pointer")
-            assert kind == want, f"{name}: {param}"
-        # never forwarded by rgcn_sequence_run: the draw happens outside any recorded pass
-        assert name not in _lib.PROTOTYPES and name not in _lib.SEQ_FUNCTIONS
-    header = open(os.path.join(ROOT, "include", "rgcn_edge_dropout.h")).read()
-    main_header = open(os.path.join(ROOT, "include", "rgcn_hip.h")).read()
-    assert '#include "rgcn_hip.h"' in header and "edge_dropout" not in main_header
+    """names, parameters, return types and exports: test_c_surface.py, for every header.  Here: the Philox stream of the
+    draw, in the header, the restatement and the binding, and the build list"""
+    header = S.header_text("rgcn_edge_dropout.h")
     stream = int(re.search(r"#define RGCN_EDGE_DROPOUT_STREAM (0x[0-9A-Fa-f]+)u", header).group(1), 16)
     assert stream == R.STREAM == _lib.EDGE_DROPOUT_STREAM != RR.STREAM
     makefile = open(os.path.join(ROOT, "primekg_rgcn_linkprediction_amd", "csrc", "Makefile")).read()
@@ -61,8 +41,7 @@ def test_argument_checks_run_before_any_launch():
     assert lib.rgcn_edge_dropout_kept_export(None, FAKE, None) == _lib.RGCN_ERR_ARG
     lib.rgcn_edge_dropout_destroy(None)
     # a handle that is not a square graph with a mean forward and a weighted transposed direction: refused, untouched
-    from test_alignment_host import GRAPH
-    assert lib.rgcn_edge_dropout_create(GRAPH, None, ctypes.byref(out)) == _lib.RGCN_ERR_UNSUPPORTED and out.value is None
+    assert lib.rgcn_edge_dropout_create(S.GRAPH, None, ctypes.byref(out)) == _lib.RGCN_ERR_UNSUPPORTED and out.value is None
     # draw: NULL handle / rng first; the other checks need a handle and run on the GPU tier
     assert lib.rgcn_edge_dropout_draw(None, 0.5, FAKE, None, 0, None, None, None) == _lib.RGCN_ERR_ARG
 

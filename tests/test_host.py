@@ -6,38 +6,13 @@ import re
 import pytest
 import torch
 
+import c_surface as S
 from conftest import ROOT, load_golden
 from primekg_rgcn_linkprediction_amd import (DrugDiseaseModel, DrugDiseaseRGCN, LinkPredictor, RGCNConv, _lib,
                                              ops, synth)
 
 
-# ------------------------------------------------------------------ C ABI surface
-def _header_text():
-    text = open(os.path.join(ROOT, "include", "rgcn_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
-def _declared_prototypes():
-    """name -> list of parameter declarations, for every function include/rgcn_hip.h declares"""
-    found = re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", _header_text())
-    return {name: [] if params.strip() == "void" else [" ".join(p.split()) for p in params.split(",")]
-            for name, params in found if name.startswith(("rgcn_", "distmult_"))}
-
-
-def _declared_functions():
-    return sorted(_declared_prototypes())
-
-
-def test_library_loads_and_exports_every_declared_symbol():
-    lib = _lib.load()
-    declared = _declared_functions()
-    assert len(declared) >= 19
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/rgcn_hip.h but not exported"
-    assert sorted(_lib.PROTOTYPES) == declared, "ctypes prototypes and header disagree"
-    assert lib.rgcn_abi_version() == _lib.ABI_VERSION
-
-
+# ------------------------------------------------------------------ C ABI surface (the tables against the headers: test_c_surface.py)
 def test_error_strings():
     for code in (0, -1, -2, -3, -4, -5):
         assert _lib.strerror(code) and "unknown" not in _lib.strerror(code)
@@ -90,38 +65,17 @@ def test_null_handle_and_bad_args_return_codes_without_a_gpu():
     assert lib.rgcn_sample_batch(None, None, 10, None, None, 0, 1, 100, None, None, None, None, None, None) == _lib.RGCN_OK
 
 
-def _kind_in_header(param):
-    if "*" in param:
-        return "pointer"
-    return next(k for k in ("float", "double", "size_t", "int64_t", "int") if re.search(rf"\b{k}\b", param))
-
-
-def _kind_in_ctypes(ty):
-    import ctypes
-    kinds = {ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_size_t: "size_t", ctypes.c_int64: "int64_t",
-             ctypes.c_int: "int"}
-    if ty in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ty, ctypes._Pointer):
-        return "pointer"
-    return kinds[ty]
-
-
 def test_ctypes_prototypes_match_the_header_parameter_by_parameter():
-    """count and, position by position, kind (pointer / float / double / size_t / int64_t / int) of EVERY declared
-    function: a ctypes prototype that drifts from the header passes a wrong pointer or size without any error"""
-    declared = _declared_prototypes()
-    assert len(declared) == 67 and sorted(declared) == sorted(_lib.PROTOTYPES)
-    for name, params in declared.items():
-        argtypes = _lib.PROTOTYPES[name][1]
-        assert len(argtypes) == len(params), name
-        for i, (param, ty) in enumerate(zip(params, argtypes)):
-            assert _kind_in_ctypes(ty) == _kind_in_header(param), f"{name}: parameter {i} ({param})"
+    """parameter by parameter: test_c_surface.py, for every header; here the size of the main surface"""
+    assert len(S.declared("rgcn_hip.h")) == 67 == len(_lib.PROTOTYPES)
 
 
 def test_sequence_tables_match_the_header():
     """what rgcn_sequence_run's host side still writes down by hand, held to include/rgcn_hip.h: the forwarded
     functions in RGCN_FN_* order, each one's `void* stream` position, which HOST arrays hold device pointers, and
     the job limit"""
-    text, declared = _header_text(), _declared_prototypes()
+    text = S.header_code("rgcn_hip.h")
+    declared = {name: params for name, (_, params) in S.declared("rgcn_hip.h").items()}
     fns = re.search(r"enum\s*\{\s*(RGCN_FN_ABSMAX\b[^}]*)\}", text).group(1)
     fns = [f.split("=")[0].strip() for f in fns.split(",")]
     assert fns[-1] == "RGCN_FN_COUNT" and len(fns) == 15
@@ -133,7 +87,7 @@ def test_sequence_tables_match_the_header():
         params = declared[name]
         for pos, (is_ptr, cnt_pos) in arrays.items():
             assert "*" in params[pos] and is_ptr == (params[pos].count("*") == 2), f"{name}: parameter {pos} ({params[pos]})"
-            assert _kind_in_header(params[cnt_pos]) == "int", f"{name}: parameter {cnt_pos} ({params[cnt_pos]})"
+            assert S.kind_in_header(params[cnt_pos]) == "int", f"{name}: parameter {cnt_pos} ({params[cnt_pos]})"
     assert int(re.search(r"RGCN_SEQ_MAX_JOBS\s*=\s*(\d+)", text).group(1)) == _lib.SEQ_MAX_JOBS
 
 
@@ -148,7 +102,7 @@ def test_sequence_run_forwards_every_entry_point_with_its_own_argument_count():
     for fn, (name, stream_pos) in enumerate(_lib.SEQ_FUNCTIONS.items()):
         proto = _lib.PROTOTYPES[name][1]
         direct = getattr(lib, name)(*[ctypes.byref(_lib.SlabJob()) if ty is job_ptr else
-                                      None if _kind_in_ctypes(ty) == "pointer" else 0 for ty in proto])
+                                      None if S.is_pointer(ty) else 0 for ty in proto])
         direct_codes[name] = direct
         args = (_lib.SeqArg * (len(proto) + 1))()
         for i, ty in enumerate(proto):
@@ -297,22 +251,12 @@ def test_bucket_input_validation_on_host():
 def test_header_is_plain_c_and_links_against_the_library(tmp_path):
     """include/rgcn_hip.h compiles as C99 and as C++ (-pedantic), and a C program linked against
     librgcn_hip.so sees the ABI version the header declares - the boundary is a real C ABI."""
-    import os
-    import shutil
     import subprocess
-    if shutil.which("gcc") is None:
-        pytest.skip("no gcc")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = tmp_path / "abi.c"
-    src.write_text('#include "include/rgcn_hip.h"\n#include <stdio.h>\n'
-                   'int main(void) { printf("%d %d %s\\n", rgcn_abi_version(), RGCN_ABI_VERSION, rgcn_strerror(-2));\n'
-                   '  return rgcn_graph_num_edges(0) == -1 ? 0 : 1; }\n')
-    for cc, std in (("gcc", "-std=c99"), ("g++", "-std=c++17")):
-        subprocess.run([cc, std, "-Wall", "-Wextra", "-pedantic", "-fsyntax-only", "-x", "c" if cc == "gcc" else "c++",
-                        "-I", root, str(src)], check=True)
+    src = S.plain_c("rgcn_hip.h", tmp_path, 'printf("%d %d %s\\n", rgcn_abi_version(), RGCN_ABI_VERSION, rgcn_strerror(-2));\n'
+                    '  return rgcn_graph_num_edges(0) == -1 ? 0 : 1;', before_main="#include <stdio.h>\n")
     lib_dir = os.path.dirname(_lib.LIB_PATH)
     exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-std=c99", "-I", root, str(src), "-o", str(exe), "-L", lib_dir, "-l:librgcn_hip.so",
+    subprocess.run(["gcc", "-std=c99", "-I", ROOT, str(src), "-o", str(exe), "-L", lib_dir, "-l:librgcn_hip.so",
                     f"-Wl,-rpath,{lib_dir}", "-Wl,--allow-shlib-undefined"], check=True)
     import torch as _torch                                     # its bundled HIP runtime satisfies the .so at run time
     hip_dir = os.path.join(os.path.dirname(_torch.__file__), "lib")

@@ -2,7 +2,6 @@
 surface and every argument check that runs before a launch, the host restatement (``neighborhood_reference.py``) the GPU
 tier holds the device to against a literal transcription of the reference's networkx code, the failure analysis' typing
 and summary against the reference's formulas, and the command line's flags and JSON keys on a stubbed evaluator."""
-import ctypes
 import json
 import os
 import re
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import c_surface as S
 import neighborhood_reference as R
 from conftest import ROOT
 from primekg_rgcn_linkprediction_amd import _lib, consumers, evaluate, ops
@@ -37,12 +37,6 @@ def _call(lib, n=10, nnz=5, q=3, radius=2, num_classes=0, common_cap=0, given=()
 
 def test_entry_points_reject_bad_arguments_without_a_gpu():
     lib = _lib.load()
-    for name in ("rgcn_neighborhood_max_nodes", "rgcn_pair_neighborhood"):
-        assert name in _lib.NEIGHBORHOOD_PROTOTYPES and hasattr(lib, name)
-        assert all(name not in table for table in (_lib.PROTOTYPES, _lib.SAMPLING_PROTOTYPES, _lib.PATHS_PROTOTYPES,
-                                                   _lib.CLUSTER_PROTOTYPES, _lib.TSNE_PROTOTYPES, _lib.SEQ_FUNCTIONS))
-        assert getattr(lib, name).argtypes == _lib.NEIGHBORHOOD_PROTOTYPES[name][1]
-    assert lib.rgcn_abi_version() == _lib.ABI_VERSION >= 34
     A, U, OK = _lib.RGCN_ERR_ARG, _lib.RGCN_ERR_UNSUPPORTED, _lib.RGCN_OK
     most = lib.rgcn_neighborhood_max_nodes()
     assert most >= 262144 and most == ops.neighborhood_max_nodes()
@@ -74,57 +68,16 @@ def test_entry_points_reject_bad_arguments_without_a_gpu():
     assert (ops.NEIGHBORHOOD_MAX_RADIUS, ops.NEIGHBORHOOD_MAX_CLASSES, ops.NEIGHBORHOOD_MAX_COMMON) == (4, 32, 1024)
 
 
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    found = re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", text)
-    return {name: [" ".join(p.split()) for p in params.split(",")] for name, params in found}
-
-
-def _kind_in_header(param):
-    if "*" in param:
-        return "pointer"
-    return next(k for k in ("float", "double", "size_t", "int64_t", "int") if re.search(rf"\b{k}\b", param))
-
-
-def _kind_in_ctypes(ty):
-    kinds = {ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_size_t: "size_t", ctypes.c_int64: "int64_t",
-             ctypes.c_int: "int"}
-    if ty in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ty, ctypes._Pointer):
-        return "pointer"
-    return kinds[ty]
-
-
 def test_header_and_table_agree():
-    declared = _declared("rgcn_neighborhood.h")
-    assert sorted(declared) == sorted(_lib.NEIGHBORHOOD_PROTOTYPES) == ["rgcn_neighborhood_max_nodes", "rgcn_pair_neighborhood"]
-    assert declared.pop("rgcn_neighborhood_max_nodes") == ["void"]
-    assert _lib.NEIGHBORHOOD_PROTOTYPES["rgcn_neighborhood_max_nodes"] == (ctypes.c_int64, [])
-    restype, argtypes = _lib.NEIGHBORHOOD_PROTOTYPES["rgcn_pair_neighborhood"]
-    params = declared["rgcn_pair_neighborhood"]
-    assert restype is ctypes.c_int and len(argtypes) == len(params) == 21
-    for i, (param, ty) in enumerate(zip(params, argtypes)):
-        assert _kind_in_ctypes(ty) == _kind_in_header(param), f"parameter {i} ({param})"
-    header = open(os.path.join(ROOT, "include", "rgcn_neighborhood.h")).read()
-    main_header = open(os.path.join(ROOT, "include", "rgcn_hip.h")).read()
-    assert "rgcn_pair_neighborhood" not in main_header and '#include "rgcn_hip.h"' in header
-    assert f"#define RGCN_ABI_VERSION {_lib.ABI_VERSION}\n" in main_header
+    """names, parameters, return types and exports: test_c_surface.py, for every header.  Here: the limits the header
+    states and the wrappers mirror, and the build list"""
+    header = S.header_text("rgcn_neighborhood.h")
     for macro, value in (("HUB_DEGREE", ops.NEIGHBORHOOD_HUB_DEGREE), ("MAX_RADIUS", ops.NEIGHBORHOOD_MAX_RADIUS),
                          ("MAX_CLASSES", ops.NEIGHBORHOOD_MAX_CLASSES), ("MAX_COMMON", ops.NEIGHBORHOOD_MAX_COMMON)):
         assert re.search(rf"#define RGCN_NEIGHBORHOOD_{macro} {value}\n", header), macro
     assert ops.NEIGHBORHOOD_HUB_DEGREE >= 64                                        # a hub row fills a wave at least once
     makefile = open(os.path.join(ROOT, "primekg_rgcn_linkprediction_amd", "csrc", "Makefile")).read()
     assert " neighborhood.hip" in makefile
-
-
-def test_header_is_plain_c(tmp_path):
-    import shutil
-    import subprocess
-    if shutil.which("gcc") is None:
-        pytest.skip("no gcc")
-    src = tmp_path / "n.c"
-    src.write_text('#include "include/rgcn_neighborhood.h"\nint main(void) { return RGCN_OK; }\n')
-    for cc, std, lang in (("gcc", "-std=c99", "c"), ("g++", "-std=c++17", "c++")):
-        subprocess.run([cc, std, "-Wall", "-Wextra", "-pedantic", "-fsyntax-only", "-x", lang, "-I", ROOT, str(src)], check=True)
 
 
 def test_python_wrapper_checks_the_ranges_first_and_has_no_cpu_path():

@@ -14,9 +14,6 @@ from primekg_rgcn_linkprediction_amd import evaluate as E
 
 def test_new_entry_points_reject_bad_arguments_without_a_gpu():
     lib = _lib.load()
-    for name in ("distmult_rank_masked", "rgcn_rank_exclude_bits", "rgcn_rank_allow_bits"):
-        assert name in _lib.PROTOTYPES and hasattr(lib, name)
-    assert lib.rgcn_abi_version() == _lib.ABI_VERSION >= 26
     A, U, OK = _lib.RGCN_ERR_ARG, _lib.RGCN_ERR_UNSUPPORTED, _lib.RGCN_OK
     # distmult_rank_masked(q, emb, true, target, allow, query_class, classes, exclude, B, N, d, beaten, stream)
     assert lib.distmult_rank_masked(None, None, None, None, None, None, 0, None, 4, 100, 48, None, None) == U    # d % 32

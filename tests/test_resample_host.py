@@ -2,7 +2,6 @@
 restatement of the contract (``resample_reference.py``) against scikit-learn and against the definition of its own
 constants, the interval and p-value arithmetic on hand-made arrays, the C surface (prototypes, every refusal that comes
 before a launch) and the command lines' new flags."""
-import ctypes
 import decimal
 import os
 import re
@@ -11,12 +10,12 @@ import numpy as np
 import pytest
 import torch
 
+import c_surface as S
 import resample_reference as R
+from c_surface import STREAM, T4, T8, T16
 from conftest import ROOT
 from primekg_rgcn_linkprediction_amd import _lib, bootstrap, compare, evaluate, ops
 
-FAKE_BASE, FAKE_STEP = 0x7F0000000000, 0x100000        # fake device addresses: multiples of 1 MiB, never dereferenced
-NAMES = ["rgcn_resample_curves", "rgcn_resample_ranks", "rgcn_resample_weights"]
 
 
 # ---------------------------------------------------------------------------------- the rule
@@ -139,93 +138,31 @@ def test_units_follow_the_sampler_layout():
 
 
 # ---------------------------------------------------------------------------------- C surface
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    found = re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", text)
-    return {name: [" ".join(p.split()) for p in params.split(",")] for name, params in found}
-
-
-def _kind_in_header(param):
-    if "*" in param:
-        return "pointer"
-    return next(k for k in ("float", "double", "size_t", "int64_t", "int") if re.search(rf"\b{k}\b", param))
-
-
-def _kind_in_ctypes(ty):
-    kinds = {ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_size_t: "size_t", ctypes.c_int64: "int64_t",
-             ctypes.c_int: "int"}
-    if ty in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ty, ctypes._Pointer):
-        return "pointer"
-    return kinds[ty]
-
-
 def test_header_table_and_library_agree():
-    lib = _lib.load()
-    declared = _declared("rgcn_resample.h")
-    assert sorted(declared) == sorted(_lib.RESAMPLE_PROTOTYPES) == NAMES
-    for name, count in (("rgcn_resample_weights", 5), ("rgcn_resample_curves", 15), ("rgcn_resample_ranks", 13)):
-        restype, argtypes = _lib.RESAMPLE_PROTOTYPES[name]
-        params = declared[name]
-        assert restype is ctypes.c_int and len(argtypes) == len(params) == count
-        for i, (param, ty) in enumerate(zip(params, argtypes)):
-            assert _kind_in_ctypes(ty) == _kind_in_header(param), f"{name}: parameter {i} ({param})"
-        assert getattr(lib, name).argtypes == argtypes
-        assert all(name not in table for table in (_lib.PROTOTYPES, _lib.SAMPLING_PROTOTYPES, _lib.PATHS_PROTOTYPES,
-                                                   _lib.CLUSTER_PROTOTYPES, _lib.TSNE_PROTOTYPES,
-                                                   _lib.NEIGHBORHOOD_PROTOTYPES, _lib.TRANSE_PROTOTYPES, _lib.SEQ_FUNCTIONS))
-    header = open(os.path.join(ROOT, "include", "rgcn_resample.h")).read()
-    main_header = open(os.path.join(ROOT, "include", "rgcn_hip.h")).read()
-    assert "rgcn_resample" not in main_header and '#include "rgcn_hip.h"' in header
-    assert f"#define RGCN_ABI_VERSION {_lib.ABI_VERSION}\n" in main_header and lib.rgcn_abi_version() == _lib.ABI_VERSION >= 37
+    """names, parameters, return types and exports: test_c_surface.py, for every header"""
     makefile = open(os.path.join(ROOT, "primekg_rgcn_linkprediction_amd", "csrc", "Makefile")).read()
     assert " resample.hip" in makefile
 
 
-def test_header_is_plain_c(tmp_path):
-    import shutil
-    import subprocess
-    if shutil.which("gcc") is None:
-        pytest.skip("no gcc")
-    src = tmp_path / "t.c"
-    src.write_text('#include "include/rgcn_resample.h"\n'
-                   'static const unsigned t[RGCN_RESAMPLE_LEVELS] = RGCN_RESAMPLE_THRESHOLDS;\n'
-                   'int main(void) { return t[0] == 1580030168u ? RGCN_OK : 1; }\n')
-    for cc, std, lang in (("gcc", "-std=c99", "c"), ("g++", "-std=c++17", "c++")):
-        subprocess.run([cc, std, "-Wall", "-Wextra", "-pedantic", "-fsyntax-only", "-x", lang, "-I", ROOT, str(src)], check=True)
-
-
-# name -> (arguments with ("dev", alignment) for a device pointer, smallest legal sizes; positions of the sizes)
-CURVES = [("dev", 4), ("dev", 16), ("dev", 4), 1, 1, 1, 1, 0, ("dev", 8), ("dev", 8), ("dev", 8), ("dev", 8), ("dev", 8),
-          ("dev", 8), None]
-RANKS = [("dev", 8), ("dev", 4), 1, ("dev", 4), 1, 1, 1, 0, ("dev", 8), ("dev", 8), ("dev", 8), ("dev", 8), None]
-SHIFTS = {16: (4, 8, 12), 8: (4,), 4: (2,)}             # 4 bytes off an 8- or 16-byte rule; 2 off a 4-byte one
+# argument sets at the smallest legal sizes, in the notation of c_surface.py
+CURVES = [T4, T16, T4, 1, 1, 1, 1, 0, T8, T8, T8, T8, T8, T8, STREAM]
+RANKS = [T8, T4, 1, T4, 1, 1, 1, 0, T8, T8, T8, T8, STREAM]
+ALIGNMENT_CASES = {"rgcn_resample_curves": [CURVES], "rgcn_resample_ranks": [RANKS]}
 
 
 def _values(args, shift_at=None, shift=0, **sizes):
-    out = []
-    for pos, a in enumerate(args):
-        if isinstance(a, tuple):
-            out.append(FAKE_BASE + (pos + 1) * FAKE_STEP + (shift if pos == shift_at else 0))
-        else:
-            out.append(a)
+    args = list(args)
     for pos, v in sizes.items():
-        out[int(pos[1:])] = v
-    return out
+        args[int(pos[1:])] = v
+    return S.build(args, (shift_at, None), shift)[0]
 
 
 @pytest.mark.parametrize("name,args", [("rgcn_resample_curves", CURVES), ("rgcn_resample_ranks", RANKS)])
 def test_a_pointer_below_its_alignment_is_refused(name, args):
     """after every other check and before the first HIP call: the set passes everything else, so exactly
     RGCN_ERR_ALIGN comes back; the fully aligned set is never called - that would be a launch"""
-    fn = getattr(_lib.load(), name)
-    failed = []
-    for pos, a in enumerate(args):
-        if isinstance(a, tuple):
-            for shift in SHIFTS[a[1]]:
-                code = fn(*_values(args, pos, shift))
-                if code != _lib.RGCN_ERR_ALIGN:
-                    failed.append(f"parameter {pos} (alignment {a[1]}) moved by {shift}: code {code}")
-    assert not failed, f"{name}: " + "; ".join(failed)
+    failed = S.misaligned_refusals(getattr(_lib.load(), name), name, args)
+    assert not failed, "; ".join(failed)
 
 
 def test_sizes_are_refused_before_any_launch():
@@ -238,7 +175,7 @@ def test_sizes_are_refused_before_any_launch():
     assert curves(*_values(CURVES, p5=2 ** 31)) == RANGE
     assert ranks(*_values(RANKS, p2=big)) == RANGE and ranks(*_values(RANKS, p6=65536)) == RANGE
     assert ranks(*_values(RANKS, p4=9)) == RANGE and ranks(*_values(RANKS, p5=2 ** 31)) == RANGE
-    out = FAKE_BASE + FAKE_STEP
+    out = S.FAKE_BASE + S.FAKE_STEP
     assert weights(1, 65536, 0, out, None) == RANGE and weights(2 ** 31, 1, 0, out, None) == RANGE
     for bad in (dict(p3=-1), dict(p4=-1), dict(p4=2), dict(p5=0), dict(p6=-1), dict(p0=None), dict(p1=None), dict(p2=None),
                 dict(p8=None), dict(p9=None), dict(p10=None), dict(p11=None), dict(p12=None), dict(p13=None)):

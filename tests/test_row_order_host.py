@@ -10,9 +10,9 @@ import re
 import numpy as np
 import pytest
 
+import c_surface as S
 from primekg_rgcn_linkprediction_amd import _lib, conv
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PACK_SPAN = 256                                        # RGCN_CHUNK * RGCN_PACK: longer segments leave partial rows
 
 
@@ -154,19 +154,12 @@ def test_structures_without_an_order_and_bad_arguments():
 
 
 def test_the_header_the_binding_and_the_policy_agree():
-    with open(os.path.join(ROOT, "include", "rgcn_row_order.h")) as f:
-        text = f.read()
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert set(re.findall(r"\b(rgcn_\w+)\s*\(", code)) == set(_lib.ROW_ORDER_PROTOTYPES)
+    """(the header's functions against the binding and the library: test_c_surface.py, for every header)"""
+    text, code = S.header_text("rgcn_row_order.h"), S.header_code("rgcn_row_order.h")
     assert f"#define RGCN_MODE_ROW_ORDER {_lib.MODE_ROW_ORDER}\n" in text
     assert _lib.MODE_ROW_ORDER == 4 and not _lib.MODE_ROW_ORDER & (1 | _lib.MODE_SPARSE_ROWS)
     fields = re.search(r"typedef struct rgcn_row_order_layout \{(.*?)\}", code, flags=re.S).group(1)
     assert re.findall(r"\b(\w+)\s*[,;]", fields) == [f for f, _ in _lib.RowOrderLayout._fields_]
-    lib = _lib.load()
-    for name, (restype, argtypes) in _lib.ROW_ORDER_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype == restype and fn.argtypes == argtypes
-        assert all(name not in table for table in (_lib.PROTOTYPES, _lib.SEQ_FUNCTIONS))
     # the switch is a module attribute that recorded passes are keyed by, like _SPARSE_AGG; on unless the environment says 0
     assert conv._NT_ROW_ORDER is (os.environ.get("RGCN_NT_ROW_ORDER", "1") != "0")
     before = conv._policy_key()

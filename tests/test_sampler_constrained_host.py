@@ -20,9 +20,7 @@ The contract, from its words:
 
 The host Philox is pinned to the published Random123 known-answer vectors first.
 """
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -197,58 +195,6 @@ def test_restatement_meets_the_conditions_the_gpu_tier_rests_on():
 
 
 # ---------------------------------------------------------------------------------- C surface
-def _sampling_prototypes():
-    text = open(os.path.join(ROOT, "include", "rgcn_sampling.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    found = re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", text)
-    return {name: [" ".join(p.split()) for p in params.split(",")] for name, params in found}
-
-
-def _kind_in_header(param):
-    if "*" in param:
-        return "pointer"
-    return next(k for k in ("float", "double", "size_t", "int64_t", "int") if re.search(rf"\b{k}\b", param))
-
-
-def _kind_in_ctypes(ty):
-    kinds = {ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_size_t: "size_t", ctypes.c_int64: "int64_t",
-             ctypes.c_int: "int"}
-    if ty in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ty, ctypes._Pointer):
-        return "pointer"
-    return kinds[ty]
-
-
-def test_sampling_header_and_table_agree():
-    """include/rgcn_sampling.h and _lib.SAMPLING_PROTOTYPES: the same functions, the same parameter count and, position
-    by position, kind; the symbol is exported and typed by load(); the 67-function header and table do not know it"""
-    declared = _sampling_prototypes()
-    assert sorted(declared) == sorted(_lib.SAMPLING_PROTOTYPES) == ["rgcn_sample_batch_constrained"]
-    lib = _lib.load()
-    for name, params in declared.items():
-        restype, argtypes = _lib.SAMPLING_PROTOTYPES[name]
-        assert restype is ctypes.c_int and len(argtypes) == len(params), name
-        for i, (param, ty) in enumerate(zip(params, argtypes)):
-            assert _kind_in_ctypes(ty) == _kind_in_header(param), f"{name}: parameter {i} ({param})"
-        fn = getattr(lib, name)
-        assert fn.argtypes == argtypes and name not in _lib.PROTOTYPES and name not in _lib.SEQ_FUNCTIONS
-    main_header = open(os.path.join(ROOT, "include", "rgcn_hip.h")).read()
-    assert "rgcn_sample_batch_constrained" not in main_header
-    assert f"#define RGCN_ABI_VERSION {_lib.ABI_VERSION}\n" in main_header and _lib.ABI_VERSION >= 30
-    text = open(os.path.join(ROOT, "include", "rgcn_sampling.h")).read()
-    assert '#include "rgcn_hip.h"' in text
-
-
-def test_sampling_header_is_plain_c(tmp_path):
-    import shutil
-    import subprocess
-    if shutil.which("gcc") is None:
-        pytest.skip("no gcc")
-    src = tmp_path / "s.c"
-    src.write_text('#include "include/rgcn_sampling.h"\nint main(void) { return RGCN_OK; }\n')
-    for cc, std, lang in (("gcc", "-std=c99", "c"), ("g++", "-std=c++17", "c++")):
-        subprocess.run([cc, std, "-Wall", "-Wextra", "-pedantic", "-fsyntax-only", "-x", lang, "-I", ROOT, str(src)], check=True)
-
-
 def _call(lib, batch=0, num_neg=1, num_nodes=100, tries=8, classes=(None, None, None, 0),
           known=(None, None, None, 0, 0, None, None, None, 0, 0, 0)):
     """the entry point with NULL graph arrays and outputs, so that no case can reach a launch: with a batch it is

@@ -2,79 +2,31 @@
 ``softmax_grad``, ``LinkPredictor.softmax_loss``, ``train.py --loss softmax``): the C surface, every argument check that
 runs before a launch, the float64 restatement (``softmax_reference.py``) against torch autograd of the CPU fallback,
 the fallback in float32 against the bounds the device is held to, and the trainer on the CPU."""
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 
+import c_surface as S
 import softmax_reference as R
+from c_surface import STREAM, T4, T8, T16
 from conftest import ROOT
 from primekg_rgcn_linkprediction_amd import _lib, head, ops, train
 
-OK, ARG, UNSUPPORTED, WORKSPACE, ALIGN = (_lib.RGCN_OK, _lib.RGCN_ERR_ARG, _lib.RGCN_ERR_UNSUPPORTED,
-                                          _lib.RGCN_ERR_WORKSPACE, _lib.RGCN_ERR_ALIGN)
-NAMES = ["rgcn_softmax_grad", "rgcn_softmax_lse", "rgcn_softmax_workspace_bytes"]
-FAKE = 0x7F0000000000            # fake device addresses, multiples of 1 MiB apart, never dereferenced
+OK, ARG, UNSUPPORTED, WORKSPACE = _lib.RGCN_OK, _lib.RGCN_ERR_ARG, _lib.RGCN_ERR_UNSUPPORTED, _lib.RGCN_ERR_WORKSPACE
 
 
 def _fake(i):
-    return FAKE + i * 0x100000
+    return S.FAKE_BASE + i * S.FAKE_STEP
 
 
 # ---------------------------------------------------------------------------------- C surface
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    found = re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", text)
-    return {name: [" ".join(p.split()) for p in params.split(",")] for name, params in found}
-
-
-def _kind_in_header(param):
-    if "*" in param:
-        return "pointer"
-    return next(k for k in ("float", "double", "size_t", "int64_t", "int") if re.search(rf"\b{k}\b", param))
-
-
-def _kind_in_ctypes(ty):
-    kinds = {ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_size_t: "size_t", ctypes.c_int64: "int64_t",
-             ctypes.c_int: "int"}
-    if ty in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ty, ctypes._Pointer):
-        return "pointer"
-    return kinds[ty]
-
-
 def test_header_table_and_library_agree():
-    lib = _lib.load()
-    declared = _declared("rgcn_softmax.h")
-    assert sorted(declared) == sorted(_lib.SOFTMAX_PROTOTYPES) == NAMES
-    for name in NAMES:
-        restype, argtypes = _lib.SOFTMAX_PROTOTYPES[name]
-        params = declared[name]
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == argtypes
-        assert len(argtypes) == len(params), name
-        for i, (param, ty) in enumerate(zip(params, argtypes)):
-            assert _kind_in_ctypes(ty) == _kind_in_header(param), f"{name}: parameter {i} ({param})"
-        assert restype is (ctypes.c_size_t if name.endswith("_bytes") else ctypes.c_int)
-        assert all(name not in table for table in (_lib.PROTOTYPES, _lib.SEQ_FUNCTIONS, _lib.COMPLEX_PROTOTYPES))
-    header = open(os.path.join(ROOT, "include", "rgcn_softmax.h")).read()
-    main_header = open(os.path.join(ROOT, "include", "rgcn_hip.h")).read()
-    assert '#include "rgcn_hip.h"' in header and not any(name in main_header for name in NAMES)
+    """names, parameters, return types and exports: test_c_surface.py, for every header"""
     makefile = open(os.path.join(ROOT, "primekg_rgcn_linkprediction_amd", "csrc", "Makefile")).read()
     assert " softmax_loss.hip" in makefile
-
-
-def test_header_is_plain_c(tmp_path):
-    import shutil
-    import subprocess
-    if shutil.which("gcc") is None:
-        pytest.skip("no gcc")
-    src = tmp_path / "t.c"
-    src.write_text('#include "include/rgcn_softmax.h"\nint main(void) { return RGCN_OK; }\n')
-    for cc, std, lang in (("gcc", "-std=c99", "c"), ("g++", "-std=c++17", "c++")):
-        subprocess.run([cc, std, "-Wall", "-Wextra", "-pedantic", "-fsyntax-only", "-x", lang, "-I", ROOT, str(src)], check=True)
 
 
 def _lse_args(batch=1, n=1, d=32, slices=0, **ptr):
@@ -97,6 +49,17 @@ def _grad_args(batch=1, n=1, d=32, slices=0, **ptr):
             slices, p["dq"], p["dE"], p["acc"], p["ws"], p["bytes"], None]
 
 
+# the smallest legal call in the notation of c_surface.py: tables, the query rows, the workspace and the gradients by
+# 16 bytes, the int64 targets by 8, every per-sample vector and mask word by 4; the masks absent, then all three given
+_WS = S._q("rgcn_softmax_workspace_bytes", 1, 1, 32, 0)
+ALIGNMENT_CASES = {
+    "rgcn_softmax_lse": [[T16, T16, T8, None, None, 0, None, 1, 1, 32, 0, T4, T4, T4, None, None, T16, _WS, STREAM],
+                         [T16, T16, T8, T4, T4, 2, T4, 1, 1, 32, 0, T4, T4, T4, None, None, T16, _WS, STREAM]],
+    "rgcn_softmax_grad": [[T4, T16, T16, T8, None, None, 0, None, T4, 1, 1, 32, 0, T16, T16, 0, T16, _WS, STREAM],
+                          [T4, T16, T16, T8, T4, T4, 2, T4, T4, 1, 1, 32, 0, T16, T16, 0, T16, _WS, STREAM]],
+}
+
+
 @pytest.mark.parametrize("fn, args", [("rgcn_softmax_lse", _lse_args), ("rgcn_softmax_grad", _grad_args)])
 def test_sizes_nulls_and_alignment_are_refused_without_a_gpu(fn, args):
     call = getattr(_lib.load(), fn)
@@ -115,23 +78,15 @@ def test_sizes_nulls_and_alignment_are_refused_without_a_gpu(fn, args):
         for name in ("q", "emb", "target", "lse", "ts", "rmax"):
             assert call(*args(**{name: None})) == ARG, name
         assert call(*args(ws=None)) == WORKSPACE and call(*args(bytes=8)) == WORKSPACE
-        aligned16, aligned8, aligned4 = ("q", "emb", "ws"), ("target",), ("lse", "ts", "rmax")
     else:
         assert call(*args(batch=0, g=None, dq=None, dE=None, **none)) == OK
         for name in ("g", "q", "emb", "target", "lse"):
             assert call(*args(**{name: None})) == ARG, name
         # two slices of a two-tile range: the partial dq slabs need the workspace; without dq they do not
         assert call(*args(n=200, slices=2, ws=None)) == WORKSPACE and call(*args(n=200, slices=2, bytes=8)) == WORKSPACE
-        aligned16, aligned8, aligned4 = ("q", "emb", "ws", "dq", "dE"), ("target",), ("g", "lse")
-    base = dict(zip(("q", "emb", "target", "lse", "ws", "g", "dq", "dE", "ts", "rmax"),
-                    (_fake(1), _fake(2), _fake(3), _fake(4), _fake(7), _fake(8), _fake(9), _fake(10), _fake(5), _fake(6))))
-    for names, shifts in ((aligned16, (4, 8, 12)), (aligned8, (4,)), (aligned4, (2,))):
-        for name in names:
-            for shift in shifts:
-                assert call(*args(**{name: base[name] + shift})) == ALIGN, (name, shift)
-    masks = dict(allow=_fake(11), qcls=_fake(12), classes=2, excl=_fake(13))
-    for name in ("allow", "qcls", "excl"):
-        assert call(*args(**{**masks, name: masks[name] + 2})) == ALIGN, name
+    # a pointer below its alignment, after every other check: the sets of ALIGNMENT_CASES, without and with the masks
+    failed = [f for case in ALIGNMENT_CASES[fn] for f in S.misaligned_refusals(call, fn, case)]
+    assert not failed, "; ".join(failed)
 
 
 def test_workspace_bytes_follow_the_slice_rule():

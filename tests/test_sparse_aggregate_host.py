@@ -2,16 +2,14 @@
 the graph builders upload, computed by the library's own host routine and held to a NumPy restatement from ``rowptr`` -
 and the places the mode's one option bit and its policy switch are written down."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
+import c_surface as S
 import sparse_graphs as SG
 from primekg_rgcn_linkprediction_amd import _lib, conv
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PAD = 96                                                # RGCN_ROW_MASK_PAD
 
 
@@ -81,17 +79,8 @@ def test_more_than_32_relations_have_no_occupancy_words():
 
 
 def test_the_header_the_binding_and_the_policy_agree():
-    with open(os.path.join(ROOT, "include", "rgcn_sparse.h")) as f:
-        text = f.read()
-    declared = set(re.findall(r"\b(rgcn_\w+)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S)))
-    assert declared == set(_lib.SPARSE_PROTOTYPES)
-    lib = _lib.load()
-    for name, (restype, argtypes) in _lib.SPARSE_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype == restype and fn.argtypes == argtypes
-        assert all(name not in table for table in (_lib.PROTOTYPES, _lib.SEQ_FUNCTIONS))
-    with open(os.path.join(ROOT, "include", "rgcn_hip.h")) as f:
-        main = f.read()
+    """(the header against the binding and the library: test_c_surface.py, for every header)"""
+    main = S.header_text("rgcn_hip.h")
     assert f"#define RGCN_MODE_SPARSE_ROWS {_lib.MODE_SPARSE_ROWS}\n" in main and _lib.MODE_SPARSE_ROWS == 2
     # the switch is a module attribute that recorded passes are keyed by, like _DEFER_HUBS
     assert conv._SPARSE_AGG is True and conv._SPARSE_AGG in conv._policy_key()

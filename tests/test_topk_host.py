@@ -17,9 +17,6 @@ NINF = -math.inf
 
 def test_topk_entry_points_reject_bad_arguments_without_a_gpu():
     lib = _lib.load()
-    for name in ("distmult_topk_masked", "distmult_topk_workspace_bytes"):
-        assert name in _lib.PROTOTYPES and hasattr(lib, name)
-    assert lib.rgcn_abi_version() == _lib.ABI_VERSION >= 27
     A, U, OK = _lib.RGCN_ERR_ARG, _lib.RGCN_ERR_UNSUPPORTED, _lib.RGCN_OK
 
     # distmult_topk_masked(q, emb, allow, query_class, classes, exclude, min_score, B, N, d, k, slices, ids, scores, ws, ws_bytes, stream)

@@ -3,78 +3,30 @@ that runs before a launch, the Python wrappers' checks by name, the float64 rest
 tier holds the device to against scikit-learn's private helpers, the CLI's parser and JSON shape on a stubbed evaluator,
 ``reduce_dimensions``' sampling, and the recorded whole-run fixture (``golden/tsne_blobs300.json``)."""
 import argparse
-import ctypes
 import functools
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import c_surface as S
 import tsne_reference as R
 from conftest import ROOT
 from primekg_rgcn_linkprediction_amd import _lib, consumers, evaluate, ops
 from primekg_rgcn_linkprediction_amd import project as P
 
-NAMES = ["rgcn_knn_refine", "rgcn_tsne_affinities", "rgcn_tsne_gradient", "rgcn_tsne_update", "rgcn_tsne_workspace_bytes"]
 GOLDEN = os.path.join(ROOT, "tests", "golden", "tsne_blobs300.json")
 
 
 # ---------------------------------------------------------------------------------- C surface
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    found = re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", text)
-    return {name: [" ".join(p.split()) for p in params.split(",")] for name, params in found}
-
-
-def _kind_in_header(param):
-    if "*" in param:
-        return "pointer"
-    return next(k for k in ("float", "double", "size_t", "int64_t", "int") if re.search(rf"\b{k}\b", param))
-
-
-def _kind_in_ctypes(ty):
-    kinds = {ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_size_t: "size_t", ctypes.c_int64: "int64_t",
-             ctypes.c_int: "int"}
-    if ty in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ty, ctypes._Pointer):
-        return "pointer"
-    return kinds[ty]
-
-
 def test_tsne_header_table_and_library_agree():
-    declared = _declared("rgcn_tsne.h")
-    assert sorted(declared) == sorted(_lib.TSNE_PROTOTYPES) == NAMES
-    lib = _lib.load()
-    others = (_lib.PROTOTYPES, _lib.SAMPLING_PROTOTYPES, _lib.PATHS_PROTOTYPES, _lib.CLUSTER_PROTOTYPES, _lib.SEQ_FUNCTIONS)
-    for name, params in declared.items():
-        restype, argtypes = _lib.TSNE_PROTOTYPES[name]
-        assert restype is (ctypes.c_size_t if name.endswith("_bytes") else ctypes.c_int) and len(argtypes) == len(params), name
-        for i, (param, ty) in enumerate(zip(params, argtypes)):
-            assert _kind_in_ctypes(ty) == _kind_in_header(param), f"{name}: parameter {i} ({param})"
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == argtypes
-        assert not any(name in table for table in others)
-    main_header = open(os.path.join(ROOT, "include", "rgcn_hip.h")).read()
-    assert "rgcn_tsne" not in main_header and "rgcn_knn" not in main_header
-    assert f"#define RGCN_ABI_VERSION {_lib.ABI_VERSION}\n" in main_header and lib.rgcn_abi_version() == _lib.ABI_VERSION >= 33
-    for other in ("rgcn_sampling.h", "rgcn_paths.h", "rgcn_cluster.h"):
-        assert not set(declared) & set(_declared(other))
-    text = open(os.path.join(ROOT, "include", "rgcn_tsne.h")).read()
-    assert '#include "rgcn_hip.h"' in text
+    """names, parameters, return types and exports: test_c_surface.py, for every header.  Here: the limit the header
+    states and what it says about the method"""
+    text = S.header_text("rgcn_tsne.h")
     assert f"#define RGCN_KNN_MAX_K {ops.KNN_MAX_K}\n" in text and ops.KNN_MAX_K + 1 == ops.TOPK_MAX_K
     assert "angle = 0" in text and "O(M^2)" in text               # what differs from scikit-learn's default, and the cost
-
-
-def test_tsne_header_is_plain_c(tmp_path):
-    import shutil
-    import subprocess
-    if shutil.which("gcc") is None:
-        pytest.skip("no gcc")
-    src = tmp_path / "c.c"
-    src.write_text('#include "include/rgcn_tsne.h"\nint main(void) { return RGCN_KNN_MAX_K == 127 ? RGCN_OK : 1; }\n')
-    for cc, std, lang in (("gcc", "-std=c99", "c"), ("g++", "-std=c++17", "c++")):
-        subprocess.run([cc, std, "-Wall", "-Wextra", "-pedantic", "-fsyntax-only", "-x", lang, "-I", ROOT, str(src)], check=True)
 
 
 def test_tsne_entry_points_reject_bad_arguments_without_a_gpu():
