@@ -18,9 +18,21 @@
  * ids and the occupancy masks with the parent - it does not own them, and the parent must outlive the view.  The
  * view OWNS, per direction, val (float[E]) and head_w (float[level-0 items * 8]), one int32[N * R] array of kept
  * counts (and the int32[N * R] counters a draw adds into), and two int32[E] index arrays (the forward segment of
- * every forward position and of every transposed position), which make the draw a flat walk of the edges.  Ownership lives in the wrapper, not in the structure:
+ * every forward position and of every transposed position), which make the draw a flat walk of the edges, and twin
+ * (int32[E], below).  Ownership lives in the wrapper, not in the structure:
  * rgcn_edge_dropout_destroy frees only what the view owns.  After create the view holds the draw p = 0,
- * position = NULL, so it is usable at once.  create may allocate and synchronise.
+ * position = NULL, so it is usable at once.  create may allocate and synchronise; what it allocates besides the view's
+ * own arrays (the sorts that pair the twins) is freed before it returns.
+ *
+ * TWINS - the contract; tests restate it on the host (tests/edge_dropout_twins_reference.py).  Data that stores a pair as
+ * two columns, (h, r, t) and (t, r, h), has to hide and drop them together.  twin is indexed by ORIGINAL column.  For a
+ * triple (a, r, b) with a != b let F be the columns holding (src, rel, dst) = (a, r, b) in ascending order and B the
+ * columns holding (b, r, a) in ascending order: twin[F[j]] = B[j] and twin[B[j]] = F[j] for j < min(|F|, |B|).  Every
+ * other column has twin = -1: a column whose reversed triple is not stored, a self loop, and the SURPLUS copies of the
+ * longer side (the last |F| - |B| of F or |B| - |F| of B) - as a duplicate column of a batch triple that is not itself
+ * in the window is not hidden either.  The relation must be equal: (a, 0, b) and (b, 1, a) are not twins.  twin is an
+ * involution on the columns that have one.  Built on the device (two stable radix sorts and one pairing kernel) for
+ * every graph create accepts; 4 bytes per edge stay resident.
  *
  * Every entry point that takes an rgcn_graph takes rgcn_edge_dropout_graph(ed):
  *   rgcn_aggregate(view, 0, x)   agg[i * R + r] = sum over the in-edges of (i, r) of w_fwd * x[src], in the weighted
@@ -48,6 +60,14 @@
  * p = 0 without a position reproduces the parent's transposed weights bit for bit.  The word depends on (seed, epoch,
  * cursor, column) only: the same step draws the same mask whatever ran before it, and a replayed HIP graph whose device
  * cursor has moved draws that cursor's mask.
+ * The two option bits of `batch` (below) change two lines of the above and nothing else; `batch` above is the window's
+ * LENGTH, batch with both bits cleared.  With in_window(x) = c0 <= position[x] < c0 + length:
+ *   RGCN_EDGE_DROPOUT_HIDE_TWINS  hidden(e) = position != NULL and (in_window(e) or (twin[e] >= 0 and in_window(twin[e])))
+ *   RGCN_EDGE_DROPOUT_PAIRED      counter word 0 of the Philox call is low32(twin[e] >= 0 ? min(e, twin[e]) : e): a pair
+ *                                 shares one word and is dropped or kept together
+ * stats[1] counts every hidden edge once, twins included.  k, both val, both head_w, the three launches without a memset
+ * node, capture and the absence of any allocation are as above.  A draw with an option reads twin[e] and, for
+ * HIDE_TWINS, position[twin[e]] on top of what the plain draw reads; the plain draw reads neither.
  *
  * Non-finite values - a deliberate deviation.  A dropped or hidden edge contributes 0 * x: it is MULTIPLIED by a zero
  * weight, not skipped, so a non-finite source row still reaches the aggregate of a segment it was dropped from
@@ -63,6 +83,11 @@ extern "C" {
 #endif
 
 #define RGCN_EDGE_DROPOUT_STREAM 0x45444F50u   /* counter word 3 of every edge-dropout draw ("EDOP"; not RGCN_RESAMPLE_STREAM) */
+
+/* Option bits of rgcn_edge_dropout_draw's `batch` (as RGCN_MODE_SPARSE_ROWS rides in a mode word): the window's length
+ * is `batch` with both cleared, and a draw with neither set writes the bytes it always wrote. */
+#define RGCN_EDGE_DROPOUT_HIDE_TWINS (1LL << 62)   /* a column whose twin stands in the window is hidden too */
+#define RGCN_EDGE_DROPOUT_PAIRED     (1LL << 61)   /* a column and its twin share one Philox word: dropped or kept together */
 
 typedef struct rgcn_edge_dropout rgcn_edge_dropout;
 
@@ -80,7 +105,8 @@ int rgcn_edge_dropout_kept_export(const rgcn_edge_dropout* ed, int32_t* out, voi
 
 /* One draw: asynchronous on `stream`, no allocation, no host synchronisation, capturable into a HIP graph (three
  * kernels, no memset node: the draw's last launch clears the counters the next one adds into).  rng: DEVICE int64[2] =
- * {seed, epoch}; cursor: DEVICE int64[1] or NULL (= 0); batch >= 0;
+ * {seed, epoch}; cursor: DEVICE int64[1] or NULL (= 0); batch >= 0: the window's length, below 2^61, ORed with any of
+ * RGCN_EDGE_DROPOUT_HIDE_TWINS and RGCN_EDGE_DROPOUT_PAIRED;
  * position: DEVICE int64[E] or NULL, position[e] = where column e stands in the epoch's order; stats: DEVICE int64[2]
  * or NULL.  RGCN_ERR_ARG: ed or rng NULL, batch < 0, p outside [0, 1) (NaN included).  RGCN_ERR_ALIGN: rng, cursor,
  * position, stats need 8. */

@@ -252,6 +252,7 @@ EDGE_DROPOUT_PROTOTYPES = {
     "rgcn_edge_dropout_draw": (c_int, [c_void_p, c_double, _P, _P, _I64, _P, _P, _P]),   # p, rng, cursor, batch, position, stats
 }
 EDGE_DROPOUT_STREAM = 0x45444F50   # RGCN_EDGE_DROPOUT_STREAM
+EDGE_DROPOUT_HIDE_TWINS, EDGE_DROPOUT_PAIRED = 1 << 62, 1 << 61   # option bits of the draw's `batch`
 
 # rgcn_sparse.h: the row-granular occupancy behind sparse aggregates (csrc/rgcn_graph.hip).  MODE_SPARSE_ROWS:
 # RGCN_MODE_SPARSE_ROWS of rgcn_hip.h, the bit a training pass sets in the `int` option word of its gathers and of the

@@ -14,6 +14,15 @@
 // The counts are added into counters that are zero between two draws: k_ed_weights copies them out (what
 // rgcn_edge_dropout_kept shows) and k_ed_heads, the last launch, clears them - no memset node in a captured step.
 // Integer sums are order-free, so two draws with the same (seed, epoch, cursor) leave the same bits.
+//
+// Twins (RGCN_EDGE_DROPOUT_HIDE_TWINS / RGCN_EDGE_DROPOUT_PAIRED).  Data that stores (h, r, t) and (t, r, h) as two
+// columns leaks half of a hidden edge back and drops half of a dropped pair.  create pairs the columns once, on the
+// device: two stable radix sorts (direction and the canonical (min, max) node pair, then the relation) put the copies
+// of a triple and of its reverse next to each other, forward copies first, each side in column order; k_tw_pair gives
+// the j-th forward copy the j-th backward one.  A draw with an option reads twin[e] (and position[twin[e]]) on top of
+// what the plain draw reads; the plain draw is the instantiation without either and reads what it always did.
+#include <hipcub/hipcub.hpp>
+
 #include <algorithm>
 #include <new>
 #include <vector>
@@ -34,6 +43,7 @@ struct rgcn_edge_dropout {
   int32_t* count = nullptr;     // [N * R] the counters a draw adds into: all zero between two draws (k_ed_heads clears them)
   int32_t* seg_f = nullptr;     // [E] forward segment of every forward position
   int32_t* seg_t = nullptr;     // [E] forward segment (dst * R + rel) of every transposed position
+  int32_t* twin = nullptr;      // [E] by ORIGINAL column: the column holding the reversed triple, -1 without one
 };
 
 namespace {
@@ -46,8 +56,9 @@ struct draw_params {
   const int64_t* position;
   const int64_t* cursor;
   const int64_t* rng;
-  int64_t batch;
+  int64_t batch;                // the window's length: the option bits are template arguments by now
   uint32_t threshold;
+  const int32_t* twin;          // read by the instantiations with an option only
 };
 
 // (c0, key, epoch) of a draw, read once per thread
@@ -64,12 +75,26 @@ __device__ inline draw_state draw_begin(const draw_params& p) {
   s.epoch = (uint32_t)(uint64_t)p.rng[1];
   return s;
 }
-__device__ inline bool edge_hidden(const draw_params& p, const draw_state& s, int64_t e) {
+// twin[e] where an option looks at it (-1: none); the plain draw has no such load
+template <bool kHideTwins, bool kPaired>
+__device__ inline int64_t edge_twin(const draw_params& p, int64_t e) {
+  if constexpr (kHideTwins || kPaired) return p.twin[e];
+  return -1;
+}
+template <bool kHideTwins>
+__device__ inline bool edge_hidden(const draw_params& p, const draw_state& s, int64_t e, int64_t t) {
   if (!p.position) return false;
   const int64_t at = p.position[e];
-  return at >= s.c0 && at < s.c0 + p.batch;
+  bool hidden = at >= s.c0 && at < s.c0 + p.batch;
+  if constexpr (kHideTwins) {                    // the index clamped and the result selected: no branch around the load
+    const int64_t at_t = p.position[t < 0 ? 0 : t];
+    hidden |= (t >= 0) & (at_t >= s.c0) & (at_t < s.c0 + p.batch);
+  }
+  return hidden;
 }
-__device__ inline bool edge_dropped(const draw_params& p, const draw_state& s, int64_t e) {
+template <bool kPaired>
+__device__ inline bool edge_dropped(const draw_params& p, const draw_state& s, int64_t e, int64_t t) {
+  if constexpr (kPaired) e = t >= 0 && t < e ? t : e;   // a pair shares the word of its lower column
   uint32_t c[4] = {(uint32_t)(uint64_t)e, (uint32_t)(uint64_t)s.c0, s.epoch, RGCN_EDGE_DROPOUT_STREAM};
   philox4x32_10(c, s.k0, s.k1);
   return c[0] < p.threshold;
@@ -89,6 +114,7 @@ __global__ void k_ed_segments(const int32_t* __restrict__ rowptr, int64_t NR, in
   seg[pos] = col ? (int32_t)((int64_t)col[pos] * R + lo % R) : (int32_t)lo;
 }
 
+template <bool kHideTwins, bool kPaired>
 __global__ __launch_bounds__(kMarkThreads) void k_ed_mark(const int64_t* __restrict__ perm,
                                                           const int32_t* __restrict__ seg_f, int64_t E, draw_params p,
                                                           float* __restrict__ w_fwd, int32_t* __restrict__ kept,
@@ -104,8 +130,9 @@ __global__ __launch_bounds__(kMarkThreads) void k_ed_mark(const int64_t* __restr
   if (valid) {
     const int64_t e = perm[pos];
     seg = seg_f[pos];
-    hide = edge_hidden(p, st, e);
-    keep = !hide && !edge_dropped(p, st, e);
+    const int64_t t = edge_twin<kHideTwins, kPaired>(p, e);
+    hide = edge_hidden<kHideTwins>(p, st, e, t);
+    keep = !hide && !edge_dropped<kPaired>(p, st, e, t);
     w_fwd[pos] = keep ? 1.f : 0.f;               // the mark; k_ed_weights turns it into the weight
   }
   s_seg[tid] = seg;
@@ -141,6 +168,7 @@ __global__ __launch_bounds__(kMarkThreads) void k_ed_mark(const int64_t* __restr
   if (stats && tid < 2 && s_stat[tid] > 0) atomicAdd(&stats[tid], (unsigned long long)s_stat[tid]);
 }
 
+template <bool kHideTwins, bool kPaired>
 __global__ __launch_bounds__(kThreads) void k_ed_weights(const int64_t* __restrict__ perm_t,
                                                          const int32_t* __restrict__ seg_f,
                                                          const int32_t* __restrict__ seg_t, int64_t E, draw_params p,
@@ -154,7 +182,8 @@ __global__ __launch_bounds__(kThreads) void k_ed_weights(const int64_t* __restri
   } else if (i < 2 * E) {
     const int64_t pos = i - E, e = perm_t[pos];
     const draw_state st = draw_begin(p);
-    const bool keep = !edge_hidden(p, st, e) && !edge_dropped(p, st, e);
+    const int64_t t = edge_twin<kHideTwins, kPaired>(p, e);
+    const bool keep = !edge_hidden<kHideTwins>(p, st, e, t) && !edge_dropped<kPaired>(p, st, e, t);
     w_t[pos] = keep ? 1.0f / (float)kept[seg_t[pos]] : 0.f;   // a kept edge is counted in its own segment: k >= 1
   }
 }
@@ -180,19 +209,131 @@ __global__ __launch_bounds__(kThreads) void k_ed_heads(const rgcn_item* __restri
   head[i] = e < it.end ? w[e] : 0.f;
 }
 
-int draw_impl(rgcn_edge_dropout* ed, const draw_params& p, int64_t* stats, hipStream_t stream) {
+// the two launches that form the mark, instantiated on the options
+template <bool kHideTwins, bool kPaired>
+void launch_mark(rgcn_edge_dropout* ed, const draw_params& p, int64_t* stats, hipStream_t stream) {
+  const rgcn_graph& v = ed->view;
+  const int64_t E = v.E, NR = v.N * v.R;
+  k_ed_mark<kHideTwins, kPaired><<<grid_for(E, kMarkThreads), kMarkThreads, 0, stream>>>(
+      v.dir[0].perm, ed->seg_f, E, p, ed->val[0], ed->count, reinterpret_cast<unsigned long long*>(stats));
+  k_ed_weights<kHideTwins, kPaired><<<grid_for(std::max(2 * E, NR), kThreads), kThreads, 0, stream>>>(
+      v.dir[1].perm, ed->seg_f, ed->seg_t, E, p, ed->count, ed->val[0], ed->val[1], NR, ed->kept);
+}
+
+int draw_impl(rgcn_edge_dropout* ed, const draw_params& p, bool hide_twins, bool paired, int64_t* stats, hipStream_t stream) {
   const rgcn_graph& v = ed->view;
   const int64_t E = v.E, NR = v.N * v.R;
   if (E <= 0) return RGCN_OK;                    // no edge: kept holds the zeros rgcn_edge_dropout_create left
+  hide_twins = hide_twins && p.position;         // (without a position nothing is hidden, a twin's column neither)
   // kernels only, no memset node: the counters are zero on entry (create, then every draw's last launch clears them)
-  k_ed_mark<<<grid_for(E, kMarkThreads), kMarkThreads, 0, stream>>>(v.dir[0].perm, ed->seg_f, E, p, ed->val[0], ed->count,
-                                                                   reinterpret_cast<unsigned long long*>(stats));
-  k_ed_weights<<<grid_for(std::max(2 * E, NR), kThreads), kThreads, 0, stream>>>(v.dir[1].perm, ed->seg_f, ed->seg_t, E, p,
-                                                                                ed->count, ed->val[0], ed->val[1], NR, ed->kept);
+  if (hide_twins && paired) launch_mark<true, true>(ed, p, stats, stream);
+  else if (hide_twins) launch_mark<true, false>(ed, p, stats, stream);
+  else if (paired) launch_mark<false, true>(ed, p, stats, stream);
+  else launch_mark<false, false>(ed, p, stats, stream);
   const int64_t n0 = v.dir[0].num_items[0], n1 = v.dir[1].num_items[0];
   k_ed_heads<<<grid_for(std::max((n0 + n1) * RGCN_HEAD, NR), kThreads), kThreads, 0, stream>>>(
       v.dir[0].items[0], n0, ed->val[0], ed->head_w[0], v.dir[1].items[0], n1, ed->val[1], ed->head_w[1], NR, ed->count);
   RGCN_HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- twins
+// key of a column: (min, max) of its endpoints above the direction bit (1: source > destination); node ids are < 2^31,
+// so bit 63 stays clear and key + 1 cannot wrap.  A self loop is a forward copy without a backward side.
+__global__ __launch_bounds__(kThreads) void k_tw_keys(const int64_t* __restrict__ perm, const int32_t* __restrict__ col,
+                                                      const int32_t* __restrict__ seg_f, int64_t E, int64_t R,
+                                                      unsigned long long* __restrict__ key, int32_t* __restrict__ rel,
+                                                      int32_t* __restrict__ ids) {
+  const int64_t pos = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (pos >= E) return;
+  ids[pos] = (int32_t)pos;                       // the columns in ascending order: what the stable sorts keep inside a run
+  const int64_t e = clamp64(perm[pos], 0, E - 1);
+  const int64_t seg = seg_f[pos], dst = seg / R, src = col[pos];
+  const unsigned long long lo = (unsigned long long)(uint32_t)(src < dst ? src : dst);
+  const unsigned long long hi = (unsigned long long)(uint32_t)(src < dst ? dst : src);
+  key[e] = (lo << 32) | (hi << 1) | (src > dst ? 1ull : 0ull);
+  rel[e] = (int32_t)(seg % R);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void k_tw_gather(const T* __restrict__ by_col, const int32_t* __restrict__ ids,
+                                                        int64_t E, T* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i < E) out[i] = by_col[ids[i]];
+}
+
+// first i in [0, E) with (rel[i], key[i]) >= (r, k) in the sorted order, E if none
+__device__ inline int64_t tw_lower_bound(const int32_t* __restrict__ rel, const unsigned long long* __restrict__ key,
+                                         int64_t E, int32_t r, unsigned long long k) {
+  int64_t lo = 0, hi = E;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    const int32_t rm = rel[mid];
+    if (rm < r || (rm == r && key[mid] < k)) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// ids: the columns sorted by (relation, min, max, direction, column), rel / key: their keys in that order.  The copies
+// of (a, r, b) and of (b, r, a) form one run, forward copies first; a search finds the run's three borders whatever its
+// length (a walk to the borders would be linear in the duplicates of one triple).
+__global__ __launch_bounds__(kThreads) void k_tw_pair(const int32_t* __restrict__ ids, const int32_t* __restrict__ rel,
+                                                      const unsigned long long* __restrict__ key, int64_t E,
+                                                      int32_t* __restrict__ twin) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= E) return;
+  const int32_t r = rel[i];
+  const unsigned long long k = key[i], fwd = k & ~1ull;
+  const int64_t f0 = tw_lower_bound(rel, key, E, r, fwd), b0 = tw_lower_bound(rel, key, E, r, fwd | 1ull),
+                b1 = tw_lower_bound(rel, key, E, r, (fwd | 1ull) + 1ull);
+  const bool backward = (k & 1ull) != 0;
+  const int64_t j = i - (backward ? b0 : f0), others = backward ? b0 - f0 : b1 - b0;
+  const int64_t at = clamp64((backward ? f0 : b0) + j, 0, E - 1);
+  twin[clamp64(ids[i], 0, E - 1)] = j < others ? ids[at] : -1;   // surplus copies of the longer side stay alone
+}
+
+struct twin_scratch {
+  unsigned long long *key = nullptr, *skey = nullptr;
+  int32_t *rel = nullptr, *srel_in = nullptr, *srel = nullptr, *ids[3] = {nullptr, nullptr, nullptr};
+  void* tmp = nullptr;
+  ~twin_scratch() {
+    for (void* p : {(void*)key, (void*)skey, (void*)rel, (void*)srel_in, (void*)srel, (void*)ids[0], (void*)ids[1], (void*)ids[2], tmp})
+      (void)hipFree(p);
+  }
+};
+
+// twin[] of rgcn_edge_dropout.h from the parent's forward structure (seg_f is built).  Everything allocated here is
+// freed before it returns; it synchronises `stream`.
+int build_twins(const rgcn_graph* g, const int32_t* seg_f, hipStream_t stream, int32_t* twin) {
+  const int64_t E = g->E;
+  const size_t n = (size_t)E;
+  twin_scratch sc;
+  RGCN_HIP_TRY(hipMalloc((void**)&sc.key, n * sizeof(unsigned long long)));
+  RGCN_HIP_TRY(hipMalloc((void**)&sc.skey, n * sizeof(unsigned long long)));
+  for (int32_t** p : {&sc.rel, &sc.srel_in, &sc.srel, &sc.ids[0], &sc.ids[1], &sc.ids[2]})
+    RGCN_HIP_TRY(hipMalloc((void**)p, n * sizeof(int32_t)));
+  RGCN_HIP_TRY(hipMemsetAsync(sc.key, 0, n * sizeof(unsigned long long), stream));   // (a perm that skips a column leaves
+  RGCN_HIP_TRY(hipMemsetAsync(sc.rel, 0, n * sizeof(int32_t), stream));              //  its keys defined)
+  int rel_bits = 1;                              // bits that hold R - 1 (R < 2^31)
+  while (rel_bits < 31 && ((g->R - 1) >> rel_bits) != 0) ++rel_bits;
+  size_t bytes_key = 0, bytes_rel = 0;
+  RGCN_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes_key, sc.key, sc.skey, sc.ids[0], sc.ids[1], (int)E, 0, 63, stream));
+  RGCN_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes_rel, sc.srel_in, sc.srel, sc.ids[1], sc.ids[2], (int)E, 0,
+                                                   rel_bits, stream));
+  size_t bytes = std::max(bytes_key, bytes_rel);
+  RGCN_HIP_TRY(hipMalloc(&sc.tmp, bytes + 256));
+  const unsigned grid = grid_for(E, kThreads);
+  k_tw_keys<<<grid, kThreads, 0, stream>>>(g->dir[0].perm, g->dir[0].col, seg_f, E, g->R, sc.key, sc.rel, sc.ids[0]);
+  // least significant first: direction and node pair, then the relation; both passes stable, so a run keeps column order
+  size_t b = bytes;
+  RGCN_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(sc.tmp, b, sc.key, sc.skey, sc.ids[0], sc.ids[1], (int)E, 0, 63, stream));
+  k_tw_gather<int32_t><<<grid, kThreads, 0, stream>>>(sc.rel, sc.ids[1], E, sc.srel_in);
+  b = bytes;
+  RGCN_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(sc.tmp, b, sc.srel_in, sc.srel, sc.ids[1], sc.ids[2], (int)E, 0, rel_bits, stream));
+  k_tw_gather<unsigned long long><<<grid, kThreads, 0, stream>>>(sc.key, sc.ids[2], E, sc.skey);
+  k_tw_pair<<<grid, kThreads, 0, stream>>>(sc.ids[2], sc.srel, sc.skey, E, twin);
+  RGCN_HIP_TRY(hipGetLastError());
+  RGCN_HIP_TRY(hipStreamSynchronize(stream));    // the scratch is freed on return
   return RGCN_OK;
 }
 
@@ -230,12 +371,15 @@ int create_impl(const rgcn_graph* g, hipStream_t stream, rgcn_edge_dropout* ed) 
     k_ed_segments<<<grid_for(E, kThreads), kThreads, 0, stream>>>(g->dir[0].rowptr, NR, E, g->R, nullptr, ed->seg_f);
     k_ed_segments<<<grid_for(E, kThreads), kThreads, 0, stream>>>(g->dir[1].rowptr, NR, E, g->R, g->dir[1].col, ed->seg_t);
     RGCN_HIP_TRY(hipGetLastError());
+    RGCN_HIP_TRY(hipMalloc((void**)&ed->twin, (size_t)E * sizeof(int32_t)));
+    const int rc = build_twins(g, ed->seg_f, stream, ed->twin);
+    if (rc != RGCN_OK) return rc;
   }
   // the draw p = 0 without a window: usable at once (threshold 0 drops nothing, whatever the key)
   int64_t* rng = nullptr;
   RGCN_HIP_TRY(hipMalloc((void**)&rng, 2 * sizeof(int64_t)));
   int rc = hipMemsetAsync(rng, 0, 2 * sizeof(int64_t), stream) == hipSuccess ? RGCN_OK : RGCN_ERR_HIP;
-  if (rc == RGCN_OK) rc = draw_impl(ed, draw_params{nullptr, nullptr, rng, 0, 0u}, nullptr, stream);
+  if (rc == RGCN_OK) rc = draw_impl(ed, draw_params{nullptr, nullptr, rng, 0, 0u, ed->twin}, false, false, nullptr, stream);
   if (rc == RGCN_OK && hipStreamSynchronize(stream) != hipSuccess) rc = RGCN_ERR_HIP;
   (void)hipFree(rng);
   return rc;
@@ -274,6 +418,7 @@ void rgcn_edge_dropout_destroy(rgcn_edge_dropout* ed) {
   (void)hipFree(ed->count);
   (void)hipFree(ed->seg_f);
   (void)hipFree(ed->seg_t);
+  (void)hipFree(ed->twin);
   delete ed;                                     // the shared arrays stay the parent's
 }
 
@@ -292,11 +437,14 @@ int rgcn_edge_dropout_kept_export(const rgcn_edge_dropout* ed, int32_t* out, voi
 
 int rgcn_edge_dropout_draw(rgcn_edge_dropout* ed, double p, const int64_t* rng, const int64_t* cursor, int64_t batch,
                            const int64_t* position, int64_t* stats, void* stream) {
-  if (!ed || !rng || batch < 0) return RGCN_ERR_ARG;
+  if (!ed || !rng || batch < 0) return RGCN_ERR_ARG;            // (bit 63 is no option: a negative batch)
+  const bool hide_twins = (batch & RGCN_EDGE_DROPOUT_HIDE_TWINS) != 0, paired = (batch & RGCN_EDGE_DROPOUT_PAIRED) != 0;
+  batch &= ~(RGCN_EDGE_DROPOUT_HIDE_TWINS | RGCN_EDGE_DROPOUT_PAIRED);   // what is left is the window's length
   if (!(p >= 0.0 && p < 1.0)) return RGCN_ERR_ARG;            // NaN fails both compares
   RGCN_ALIGN_TRY(8, rng, cursor, position, stats);
   const uint32_t threshold = (uint32_t)(uint64_t)(p * 4294967296.0);   // floor(p * 2^32) <= 2^32 - 1 for p < 1
-  return draw_impl(ed, draw_params{position, cursor, rng, batch, threshold}, stats, (hipStream_t)stream);
+  return draw_impl(ed, draw_params{position, cursor, rng, batch, threshold, ed->twin}, hide_twins, paired, stats,
+                   (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -907,15 +907,25 @@ class EdgeDropout:
         return self._handle
 
     def draw(self, p: float, rng: torch.Tensor, cursor: Optional[torch.Tensor] = None, batch: int = 0,
-             position: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None) -> None:
+             position: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None, hide_twins: bool = False,
+             paired: bool = False) -> None:
         """One draw into the view (asynchronous, capturable): every edge is dropped with probability ``p`` by the Philox
         word of (its original column, ``cursor``, epoch); with ``position`` (int64[E]: where each column stands in the
         epoch's order) the columns at positions ``[cursor, cursor + batch)`` - the batch's own edges - are hidden
         too.  ``rng``: int64[2] = {seed, epoch}; ``cursor``: int64[1] or None (0); ``stats``: int64[2] or None,
-        accumulates (kept, hidden).  All on the graph's device."""
+        accumulates (kept, hidden).  All on the graph's device.
+
+        A column's TWIN is the column that holds its reversed triple with the same relation (``rgcn_edge_dropout.h``:
+        the j-th copy of ``(a, r, b)`` pairs with the j-th copy of ``(b, r, a)``; paired at create).  ``hide_twins``
+        hides the twin of every column in the window as well (needs ``position``); ``paired`` draws ONE word per pair, so
+        both directions of an edge are dropped or kept together.  Both ride as option bits in ``batch``."""
         handle = self.handle                       # raises once this object or its parent graph is destroyed
         if not 0.0 <= float(p) < 1.0:
             raise ValueError(f"edge dropout p must be in [0, 1), got {p}")
+        if not 0 <= int(batch) < _lib.EDGE_DROPOUT_PAIRED:
+            raise ValueError("batch must be >= 0 and below 2**61 (the bits above carry the draw's options)")
+        if hide_twins and position is None:
+            raise ValueError("hide_twins hides the twins of the window's columns: it needs position")
         for name, t, n in (("rng", rng, 2), ("cursor", cursor, 1), ("position", position, self.graph.num_edges),
                            ("stats", stats, 2)):
             if t is None:
@@ -925,10 +935,9 @@ class EdgeDropout:
             _need_gpu(name, t, torch.int64)
             if t.numel() != n or t.device != self.device:
                 raise ValueError(f"{name} must be int64[{n}] on the graph's device")
-        if int(batch) < 0:
-            raise ValueError("batch must be >= 0")
+        word = int(batch) | (_lib.EDGE_DROPOUT_HIDE_TWINS if hide_twins else 0) | (_lib.EDGE_DROPOUT_PAIRED if paired else 0)
         with _on(self.device):
-            rc = _lib.load().rgcn_edge_dropout_draw(handle, float(p), _ptr(rng), _ptr(cursor), int(batch),
+            rc = _lib.load().rgcn_edge_dropout_draw(handle, float(p), _ptr(rng), _ptr(cursor), word,
                                                     _ptr(position), _ptr(stats), _stream())
         _lib.check(rc, "rgcn_edge_dropout_draw")
 

@@ -110,6 +110,14 @@ class Trainer:
         # that a positive is not an edge the encoder has just averaged into both of its endpoints (ops.EdgeDropout)
         self.edge_dropout_p = float(getattr(args, "edge_dropout", 0.0) or 0.0)
         self.hide_batch_edges = bool(getattr(args, "hide_batch_edges", False))
+        # --hide_reverse_edges / --paired_edge_dropout: data that stores a pair as two columns, (h, r, t) and (t, r, h),
+        # hides and drops the two together (the twin map of rgcn_edge_dropout.h)
+        self.hide_reverse_edges = bool(getattr(args, "hide_reverse_edges", False))
+        self.paired_edge_dropout = bool(getattr(args, "paired_edge_dropout", False))
+        if self.hide_reverse_edges and not self.hide_batch_edges:
+            raise ValueError("--hide_reverse_edges hides the reverse columns of the batch's own: it needs --hide_batch_edges")
+        if self.paired_edge_dropout and not self.edge_dropout_p > 0.0:
+            raise ValueError("--paired_edge_dropout draws one word per pair of columns: it needs --edge_dropout P with P > 0")
         self._edge_dropout = self._ed_stats = self._ed_position = None
         self.edge_dropout_stats = (0, 0)       # (kept edges, hidden edges) summed over the steps of the last training epoch
         self._ed_steps = 0                     # steps of that epoch: kept fraction = kept / (steps * train columns)
@@ -277,7 +285,8 @@ class Trainer:
         if self._edge_dropout is None:
             return {}
         self._edge_dropout.draw(self.edge_dropout_p, self._rng, cursor=self._cursor, batch=size if self.hide_batch_edges else 0,
-                                position=self._ed_position if self.hide_batch_edges else None, stats=self._ed_stats)
+                                position=self._ed_position if self.hide_batch_edges else None, stats=self._ed_stats,
+                                hide_twins=self.hide_reverse_edges, paired=self.paired_edge_dropout)
         return {"graph": self._edge_dropout.view}
 
     def _softmax_step(self, lo: int, size: int, accum: int = 1, update: bool = True):
@@ -413,6 +422,15 @@ class Trainer:
             ops.check_indices(self.device)   # an id outside the embedding table anywhere in the epoch: IndexError, here
         return result
 
+    def reverse_edges_found(self):
+        """After a training epoch with ``--hide_reverse_edges``: False if the epoch hid exactly as many edges as it has
+        columns - every step hid its own columns and not one reverse column, the data stores one direction; True if it
+        hid more; None without the flag or when the last epoch was cut short."""
+        e, bsz = self.train_edge_index.size(1), self.args.batch_size
+        if not self.hide_reverse_edges or self._ed_steps != -(-e // bsz):
+            return None
+        return self.edge_dropout_stats[1] != e
+
     @torch.no_grad()
     def validate(self):
         """Validation triples scored with messages passed over the FULL graph."""
@@ -498,6 +516,9 @@ class Trainer:
                 kept, hidden = self.edge_dropout_stats
                 drawn = max(1, self._ed_steps * self.train_edge_index.size(1))
                 negatives += " | Edges Kept: %.4f | Edges Hidden: %d" % (kept / drawn, hidden)
+                if epoch == 1 and self.reverse_edges_found() is False:
+                    logger.warning("--hide_reverse_edges hid %d edges in an epoch of %d columns: no column of this data has "
+                                   "a reverse column with the same relation, so the flag did nothing", hidden, hidden)
             logger.info("Epoch %d/%d | Time: %.2fs | Train Loss: %.4f | Train Acc: %.4f | Val Loss: %.4f | "
                         "Val Acc: %.4f%s", epoch, self.args.epochs, time.time() - t0, tr_loss, tr_acc, va_loss, va_acc,
                         negatives)
@@ -632,7 +653,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "the device; Schlichtkrull et al. 2018); validation and evaluation use the whole graph")
     p.add_argument("--hide_batch_edges", action="store_true",
                    help="hide the batch's own columns from the message-passing graph of its step, so that a positive is "
-                        "not an edge the encoder can see (the reverse column of a pair stays)")
+                        "not an edge the encoder can see (the reverse column of a pair stays: --hide_reverse_edges)")
+    p.add_argument("--hide_reverse_edges", action="store_true",
+                   help="with --hide_batch_edges: hide the column that holds a batch triple reversed, (t, r, h) for (h, r, t), "
+                        "as well - data that stores both directions leaks the positive through it otherwise")
+    p.add_argument("--paired_edge_dropout", action="store_true",
+                   help="with --edge_dropout P: a column and its reverse column are dropped or kept together")
     p.add_argument("--no_hip_graph", action="store_true",
                    help="launch every training step eagerly instead of replaying one captured HIP graph")
     p.add_argument("--synthetic", action="store_true",

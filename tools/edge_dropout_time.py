@@ -3,18 +3,21 @@ row 13) on the PrimeKG-shaped synthetic graph of the true train-graph size (C2: 
 
     python tools/edge_dropout_time.py [--out FILE.txt]
 
-Three things, on one GPU in one run: the draw itself (three launches: p = 0.4 with the batch window, p = 0.4
-alone, the window alone); the forward gather over the view (weighted sums, 4 more bytes per edge) against the parent's
+Four things, on one GPU in one run: rgcn_edge_dropout_create (it sorts the columns to pair the twins; wall time around
+a synchronised call); the draw itself (three launches: p = 0.4 with the batch window, p = 0.4 alone, the window alone,
+and the windowed draw with RGCN_EDGE_DROPOUT_HIDE_TWINS, with RGCN_EDGE_DROPOUT_PAIRED and with both); the forward gather over the view (weighted sums, 4 more bytes per edge) against the parent's
 mean gather at the two widths of the encoder; the transposed gather over the view against the parent's (the same
 kernel: the difference is the zeros among the weights).  Times are event times around back-to-back calls on one stream
 after a warm-up, as many calls as fill ``--window_ms`` (at least ``--reps``); the figure is the median of ``--runs`` such
 windows, the spread their minimum and maximum; the things compared alternate window by window.  The training step as a
-whole is tools/epoch_time.py with and without ``--edge_dropout 0.4 --hide_batch_edges``.
+whole is tools/epoch_time.py with and without ``--edge_dropout 0.4 --hide_batch_edges`` (and ``--hide_reverse_edges
+--paired_edge_dropout`` on top).  ``--skip_gathers`` stops after the draws.
 """
 import argparse
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -28,6 +31,7 @@ ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--window_ms", type=float, default=50.0)
 ap.add_argument("--edges", type=int, default=1_708_556)      # 2 x 854,278 kg rows; ~1.68M train columns
+ap.add_argument("--skip_gathers", action="store_true")
 args = ap.parse_args()
 
 if not torch.cuda.is_available():
@@ -64,7 +68,15 @@ n, r = tr["num_nodes"], tr["num_relations"]
 ei, et = tr["edge_index"].to(dev), tr["edge_type"].to(dev)
 e = ei.size(1)
 graph = ops.BucketedGraph(ei, et, n, r)
-ed = ops.EdgeDropout(graph)
+create_ms = []
+for _ in range(4):                                          # the first one warms the sorts up and is not reported
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ed = ops.EdgeDropout(graph)
+    torch.cuda.synchronize()
+    create_ms.append((time.perf_counter() - t0) * 1e3)
+    if len(create_ms) < 4:
+        ed.destroy()
 view = ed.view
 gen = torch.Generator().manual_seed(0)
 order = torch.randperm(e, generator=gen).to(dev)
@@ -78,9 +90,15 @@ lines = [f"edge dropout on the train graph of C2's size: {n:,} nodes, {r} relati
          f"{int((graph.arrays(True)[0][1:] - graph.arrays(True)[0][:-1]).max()):,} (transposed) edges",
          f"event time per call over windows of >= {args.window_ms:.0f} ms of back-to-back calls, median (min, max) of {args.runs} "
          f"windows, the paths alternating"]
-res = compare({"draw p = 0.4 + window of 1,024": lambda: ed.draw(0.4, rng, cursor=cursor, batch=batch, position=position, stats=stats),
+lines.append(f"  rgcn_edge_dropout_create (wall, synchronised) {statistics.median(create_ms[1:]):8.2f} ms  "
+             f"({min(create_ms[1:]):.2f}, {max(create_ms[1:]):.2f}; 3 calls after a first of {create_ms[0]:.2f} ms)")
+windowed = lambda **kw: ed.draw(0.4, rng, cursor=cursor, batch=batch, position=position, stats=stats, **kw)   # noqa: E731
+res = compare({"draw p = 0.4 + window of 1,024": windowed,
                "draw p = 0.4": lambda: ed.draw(0.4, rng, cursor=cursor, stats=stats),
-               "draw window of 1,024 alone": lambda: ed.draw(0.0, rng, cursor=cursor, batch=batch, position=position, stats=stats)})
+               "draw window of 1,024 alone": lambda: ed.draw(0.0, rng, cursor=cursor, batch=batch, position=position, stats=stats),
+               "  the same + HIDE_TWINS": lambda: windowed(hide_twins=True),
+               "  the same + PAIRED": lambda: windowed(paired=True),
+               "  the same + HIDE_TWINS + PAIRED": lambda: windowed(hide_twins=True, paired=True)})
 # bytes the draw moves at least: perm (8) + segment id (4) + mark (4) per forward position; perm_t (8) + position (8, random)
 # + segment id (4) + both weights written and the mark re-read (12) per edge in the second launch
 need = e * (16 + 32)
@@ -89,7 +107,10 @@ for name, (med, lo, hi, reps) in res.items():
 ed.draw(0.4, rng, cursor=cursor, batch=batch, position=position, stats=stats)
 kept = int(ed.kept_counts().sum())
 lines.append(f"  the view then keeps {kept:,} of {e:,} edges ({kept / e:.4f})")
-for d in (64, 128):
+stats.zero_()
+windowed(hide_twins=True, paired=True)
+lines.append(f"  with both options it keeps {int(ed.kept_counts().sum()):,} and hides {int(stats[1]):,} (the window's {batch:,} and their twins)")
+for d in () if args.skip_gathers else (64, 128):
     x = torch.randn(n, d, generator=gen).to(dev)
     res = compare({"forward, parent (mean)": lambda: ops.aggregate(graph, x), "forward, view (p = 0.4)": lambda: ops.aggregate(view, x),
                    "transposed, parent": lambda: ops.aggregate(graph, x, transposed=True),
