@@ -250,6 +250,49 @@ typedef struct rgcn_slab_job {
  * segment has no edge is never loaded - the lane's LDS-DMA reads a zero row kept by the library instead.  x / g and
  * the other operands are read as ever; results are bit-identical to the dense call. */
 #define RGCN_MODE_SPARSE_ROWS 2
+/* The gather's adjoint in its EDGE WEIGHTS (x_f16 of rgcn_aggregate_ex only; 4 is RGCN_MODE_ROW_ORDER in the sibling
+ * option words).  For agg[s] = sum_p w[p] * x[col[p]] and an upstream gradient gagg = dL/dagg,
+ *
+ *     dL/dw[p] = < gagg[s(p), :], x[col[p], :] >          one fp32 dot product per edge, over the same CSR walk.
+ *
+ * With RGCN_MODE_WEIGHT_GRAD set the call is not a gather and its parameters take these roles:
+ *   x          float[n_other, d], the table the gather of that direction reads.  Not written.
+ *   agg        READ, never written: float[n_key * R, d], the upstream gradient of the aggregate, one row per segment.
+ *   workspace  THE OUTPUT: float[E] in the direction's bucketed order - the order of col[] and w_t[]; perm of
+ *              rgcn_graph_arrays / rgcn_graph_export maps a position back to its original column.
+ *              workspace_bytes >= 4 * E (RGCN_ERR_WORKSPACE otherwise).  Every position is written and nothing else
+ *              is; the value a position holds when the call has run never depends on what it held before.  No
+ *              allocation, no host synchronisation: the call is capturable.
+ *   plain      out[p] = sum_k agg[s(p), k] * x[col[p], k] in fp32, for either direction of any structure - mean,
+ *              weighted, a shard, the view of an edge dropout: the CSR is what matters, the weights are not read.  A dot
+ *              is a fixed tree (four fused multiply-adds per lane from +0.0f, then a fixed exchange pattern over the
+ *              d / 4 lanes of a row), so the bits are the same on every call; a dot is never -0.0f.
+ *   | RGCN_MODE_MEAN_GRAD   (a mean structure only, i.e. not weighted: RGCN_ERR_UNSUPPORTED otherwise)
+ *              out[p] = (dot[p] - S[s] * w[s]) * w[s], each operation rounded by itself, with w[s] = 1.0f / cnt[s] (one
+ *              IEEE division) and S[s] the sum of the dots of segment s in this FIXED order, b the segment's first
+ *              position and every partial sum starting from +0.0f:
+ *                <= 64 edges  eight partial sums P_j = dot[b + j] + dot[b + j + 8] + dot[b + j + 16] + ... (in that
+ *                             order), S = ((P_0 + P_4) + (P_2 + P_6)) + ((P_1 + P_5) + (P_3 + P_7));
+ *                 > 64 edges  256 partial sums T_t = dot[b + t] + dot[b + t + 256] + ... (in that order); each 64
+ *                             consecutive ones (t = 64 v ... 64 v + 63) are combined by an xor butterfly with the
+ *                             offsets 32, 16, 8, 4, 2, 1 (entry l becomes entry l + entry (l ^ offset) at every step)
+ *                             into W_v, and S = ((W_0 + W_1) + W_2) + W_3.  A hub segment of any length takes this rule.
+ *              No floating-point atomics.  This is dL/dm[p] at m = 1 for w = m / sum_s m: the first-order effect of
+ *              deleting the edge from the mean.  A segment of one edge gives exactly +0.0f (finite operands).  The dots
+ *              are stored first and rewritten in place by the same call (the longer segments by a second launch).
+ *   refusals   in this order, nothing launched on any of them: RGCN_MODE_MEAN_GRAD without RGCN_MODE_WEIGHT_GRAD
+ *              RGCN_ERR_ARG; with bit 0 (fp16 table) or RGCN_MODE_SPARSE_ROWS RGCN_ERR_UNSUPPORTED; d <= 0 or d % 4
+ *              RGCN_ERR_ARG; d > 256 RGCN_ERR_UNSUPPORTED (the dot would span column blocks); amax != NULL
+ *              RGCN_ERR_UNSUPPORTED; a job with a non-NULL slab RGCN_ERR_UNSUPPORTED (a pending reduction is never lost
+ *              silently); a direction that was not built RGCN_ERR_ARG; first_level != 0, or last_level neither < 0 nor
+ *              rgcn_graph_num_levels, RGCN_ERR_ARG; the mean mode on a weighted structure RGCN_ERR_UNSUPPORTED.  Then
+ *              E == 0 or no key rows: RGCN_OK, nothing written.  Then x or agg NULL RGCN_ERR_ARG, the workspace
+ *              RGCN_ERR_WORKSPACE, and last x, agg or workspace below 16 bytes RGCN_ERR_ALIGN.
+ *   non-finite values   a NaN or infinity in a row of x reaches the output of every edge that reads that row (an
+ *              infinity may arrive as NaN), one in a row of agg every edge of that segment; in the mean mode it reaches
+ *              every edge of those segments, through S.  No other position is affected. */
+#define RGCN_MODE_WEIGHT_GRAD 8
+#define RGCN_MODE_MEAN_GRAD 16     /* only together with RGCN_MODE_WEIGHT_GRAD */
 size_t rgcn_aggregate_workspace_bytes(const rgcn_graph* g, int transposed, int64_t d);
 int rgcn_aggregate_deferrable(const rgcn_graph* g, int transposed, int64_t d);
 int rgcn_aggregate(const rgcn_graph* g, int transposed, const float* x, int64_t d, float* agg,

@@ -277,6 +277,10 @@ ROW_ORDER_PROTOTYPES = {
     "rgcn_row_order_host": (_I64, [_P, _I64, _I64, _P, POINTER(RowOrderLayout)]),
 }
 MODE_ROW_ORDER = 4
+# rgcn_hip.h: RGCN_MODE_WEIGHT_GRAD / RGCN_MODE_MEAN_GRAD, bits of rgcn_aggregate_ex's option word only - the call
+# then computes the gather's adjoint in its edge weights (csrc/edge_grad.hip) instead of gathering.
+MODE_WEIGHT_GRAD = 8
+MODE_MEAN_GRAD = 16
 
 # header of include/ -> its table, in the order the headers arrived: what load() types and every test enumerates
 HEADERS = {

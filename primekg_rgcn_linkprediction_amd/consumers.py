@@ -178,6 +178,33 @@ def connecting_paths(embeddings: Tensor, graph: "ops.PathGraph", pairs, k: int =
     return (paths, count.cpu().tolist()) if return_counts else paths
 
 
+@torch.no_grad()
+def attributed_edges(attr: Mapping[str, Tensor], edge_index: Tensor, edge_type: Tensor, k: int) -> List[Tuple]:
+    """the ``k`` columns a score depends on most: ``[(column, src, rel, dst, value)]`` by ``|value|`` descending, ``value``
+    the column's ``attr["total"]`` (``attribution.edge_attribution``); equal magnitudes in column order (a stable sort)"""
+    total = attr["total"]
+    if total.dim() != 1 or total.numel() != edge_index.size(1) or edge_type.numel() != total.numel():
+        raise ValueError("attr['total'] must hold one value per column of edge_index / edge_type")
+    order = torch.sort(total.abs(), descending=True, stable=True).indices[:max(int(k), 0)]
+    cols = order.cpu()
+    ei, et = edge_index.cpu(), edge_type.cpu()
+    return list(zip(cols.tolist(), ei[0][cols].tolist(), et[cols].tolist(), ei[1][cols].tolist(), total[order].cpu().tolist()))
+
+
+@torch.no_grad()
+def attribution_edge_score(attr: Mapping[str, Tensor], path_graph: "ops.PathGraph", edge_index: Tensor) -> Tensor:
+    """float32 ``[nnz]``, an ``edge_score`` for ``ops.paths_topk``: per unique ``(src, dst)`` pair of ``path_graph`` the
+    LARGEST ``|attr["total"]|`` over the columns that name the pair (a maximum does not depend on the order the columns
+    arrive in, so the result is deterministic; a sum by atomics would not be)"""
+    total = attr["total"]
+    graph = path_graph.to(total.device)
+    entries = graph.column_entries(edge_index)
+    if entries.numel() != total.numel():
+        raise ValueError("attr['total'] must hold one value per column of edge_index")
+    out = torch.zeros(graph.nnz, dtype=torch.float32, device=total.device)
+    return out.scatter_reduce_(0, entries, total.abs().to(torch.float32), "amax", include_self=True)
+
+
 def _class_names(class_names, num_classes: int) -> List[str]:
     """name of every class id in ``[0, num_classes)``: from ``{name: class id}`` or a sequence indexed by class id; an
     id without a name is called by its number"""

@@ -524,6 +524,10 @@ int rgcn_aggregate_ex(const rgcn_graph* g, int transposed, const void* x, int x_
                       void* workspace, size_t workspace_bytes, int first_level, int last_level, const rgcn_slab_job* job,
                       float* amax, void* stream) {
   if (!g) return RGCN_ERR_ARG;
+  if ((x_f16 & RGCN_MODE_MEAN_GRAD) && !(x_f16 & RGCN_MODE_WEIGHT_GRAD)) return RGCN_ERR_ARG;
+  if (x_f16 & RGCN_MODE_WEIGHT_GRAD)            // not a gather: the adjoint in the edge weights (edge_grad.hip)
+    return rgcn_edge_grad(g, transposed, x, x_f16, d, agg, workspace, workspace_bytes, first_level, last_level, job, amax,
+                          stream);
   return aggregate_levels(g, transposed, first_level, last_level < 0 ? g->dir[transposed ? 1 : 0].num_levels : last_level,
                           reinterpret_cast<const float*>(x), d, agg, workspace, workspace_bytes, stream, (x_f16 & 1) != 0, job,
                           amax, (x_f16 & RGCN_MODE_SPARSE_ROWS) != 0);

@@ -209,6 +209,13 @@ struct rgcn_graph {
 // that is being captured into a HIP graph must not make it: an eager call on the device comes first.
 __attribute__((visibility("hidden"))) int* rgcn_index_error_flag();
 
+// rgcn_aggregate_ex with RGCN_MODE_WEIGHT_GRAD in its option word (edge_grad.hip): the same parameters in the roles
+// include/rgcn_hip.h gives them there - `gagg` is the call's agg, `out` / `out_bytes` its workspace.  g is not NULL.
+__attribute__((visibility("hidden"))) int rgcn_edge_grad(const rgcn_graph* g, int transposed, const void* x, int mode,
+                                                         int64_t d, const float* gagg, void* out, size_t out_bytes,
+                                                         int first_level, int last_level, const rgcn_slab_job* job,
+                                                         const float* amax, void* stream);
+
 // ---------------------------------------------------------------------------------------------
 // "amax" buffers: max |tensor| as the split-precision transforms need it (rgcn_transform_split.hip).
 // A buffer is RGCN_AMAX_FLOATS floats, zeroed by the caller; its VALUE is the maximum over all entries.

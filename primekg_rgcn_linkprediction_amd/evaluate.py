@@ -179,12 +179,25 @@ class ModelEvaluator:
         return self.model.decoder.top_heads(emb[anchors], relations, emb, k, tail_indices=anchors, **kwargs)
 
     @torch.no_grad()
-    def explain(self, pairs, k: int = 5, max_len: int = 4):
+    def explain(self, pairs, k: int = 5, max_len: int = 4, by: str = "cosine", relations=None, top_edges: int = 0):
         """why a pair is predicted: for every ``(source, target)`` of ``pairs`` the ``k`` best-scoring simple paths of at
         most ``max_len`` edges through the full graph (``consumers.connecting_paths`` on the cached embeddings) and the
         exact number of such paths of length 1..4 -> ``(paths, counts)``.  The full graph's ``PathGraph`` and the cosine
-        of every edge are built on first use and kept."""
+        of every edge are built on first use and kept.
+
+        ``by="gradient"`` asks the model instead of the embeddings' geometry -> ``(paths, counts, edges)``: every pair is
+        the triple ``(source, relations[q], target)`` (``relations`` is required: one id per pair, or one for all), its
+        score is attributed to the edges of the full graph (``attribution.edge_attribution``, one pair at a time), a
+        hop scores the largest ``|attribution|`` of the columns that name it (``consumers.attribution_edge_score``)
+        and the paths are ranked as before; ``edges[q]``: the ``top_edges`` columns the score depends on most
+        (``consumers.attributed_edges``)."""
         from . import consumers, ops
+        if by not in ("cosine", "gradient"):
+            raise ValueError(f"by must be 'cosine' or 'gradient', got {by!r}")
+        if by == "gradient":
+            if relations is None:
+                raise ValueError("explain(by='gradient') attributes the score of a triple: relations (one per pair) is required")
+            return self._explain_by_gradient(pairs, k, max_len, relations, int(top_edges))
         if self._path_graph is None:
             self._path_graph = ops.PathGraph(self.full_edge_index, self.full_edge_type, self.num_nodes)
         emb = self.embeddings()
@@ -192,6 +205,25 @@ class ModelEvaluator:
             self._edge_cosine = ops.edge_cosine(emb.contiguous(), self._path_graph)
         return consumers.connecting_paths(emb, self._path_graph, pairs, k, max_len, return_counts=True,
                                           edge_score=self._edge_cosine)
+
+    def _explain_by_gradient(self, pairs, k: int, max_len: int, relations, top_edges: int):
+        from . import attribution, consumers
+        pairs = torch.as_tensor(pairs, dtype=torch.int64).reshape(-1, 2)
+        relations = torch.as_tensor(relations, dtype=torch.int64).view(-1)
+        if relations.numel() == 1 and pairs.size(0) != 1:
+            relations = relations.expand(pairs.size(0))
+        if relations.numel() != pairs.size(0):
+            raise ValueError("one relation per pair (or a single relation for all) expected")
+        graph, emb = self._structure(), self.embeddings()
+        paths, counts, edges = [], [], []
+        for (h, t), r in zip(pairs.tolist(), relations.tolist()):
+            attr = attribution.edge_attribution(self.model, self.full_edge_index, self.full_edge_type, [h], [r], [t])
+            hop_score = consumers.attribution_edge_score(attr, graph, self.full_edge_index)
+            p, c = consumers.connecting_paths(emb, graph, [(h, t)], k, max_len, return_counts=True, edge_score=hop_score)
+            paths.extend(p)
+            counts.extend(c)
+            edges.append(consumers.attributed_edges(attr, self.full_edge_index, self.full_edge_type, top_edges))
+        return paths, counts, edges
 
     def _structure(self):
         """the full graph's ``PathGraph``, built on first use and kept (``explain`` shares it)"""

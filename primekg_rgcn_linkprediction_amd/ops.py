@@ -1110,6 +1110,56 @@ def aggregate_sparse(graph: BucketedGraph, x: torch.Tensor, transposed: bool = F
     return _gather(graph, x, transposed, tail, amax_out, out, sparse=True)[0], None
 
 
+def aggregate_weight_grad(graph: BucketedGraph, x: torch.Tensor, gagg: torch.Tensor, transposed: bool = False,
+                          through_mean: bool = False, original_order: bool = False) -> torch.Tensor:
+    """float32 ``[E]``: the adjoint of ``aggregate(graph, x, transposed)`` in its per-edge weights - for every edge p
+    of that direction the dot product of ``gagg``'s row of p's segment (``gagg``: ``[N, R * d]``, the gradient of the
+    aggregate) and the row of ``x`` the edge reads (``RGCN_MODE_WEIGHT_GRAD`` of ``rgcn_aggregate_ex``,
+    ``include/rgcn_hip.h``).  The weights themselves are not read, so any structure qualifies.  ``through_mean`` (a mean
+    structure only: the forward direction of a graph or an unweighted shard): the gradient in the edge's MASK ``m`` at
+    ``m = 1`` for ``w = m / sum(m)`` instead - what deleting the edge does to the mean, to first order.  The result is in
+    the direction's bucketed order (``graph.arrays(transposed)``: the order of ``col``), or with ``original_order`` in
+    the order of the columns the graph was built from.  An analysis call: it cannot be part of a recorded pass."""
+    guard_torch_op("aggregate_weight_grad is an analysis call, not part of a pass")
+    if not isinstance(graph, BucketedGraph):
+        raise TypeError("graph must be an ops.BucketedGraph")
+    if isinstance(x, torch.Tensor) and x.dtype == torch.float16:
+        raise NotImplementedError("the weight gradient reads an fp32 table (no fp16 path)")
+    _need_gpu("x", x, torch.float32)
+    _need_gpu("gagg", gagg, torch.float32)
+    if graph.bipartite and transposed:
+        raise ValueError("a shard structure has one direction only (transposed=False)")
+    if x.dim() != 2 or x.size(0) != graph.num_other_nodes:
+        raise ValueError(f"x must be [{graph.num_other_nodes}, d], got {tuple(x.shape)}")
+    d = x.size(1)
+    if d == 0 or d % 4:
+        raise ValueError(f"feature dim {d} must be a positive multiple of 4")
+    if d > 256:
+        raise NotImplementedError(f"the weight gradient takes rows up to 256 wide, got {d}")
+    if tuple(gagg.shape) != (graph.num_nodes, graph.num_relations * d):
+        raise ValueError(f"gagg must be [{graph.num_nodes}, {graph.num_relations * d}], got {tuple(gagg.shape)}")
+    if x.device != graph.device or gagg.device != graph.device:
+        raise RuntimeError("x, gagg and the bucketed graph must be on one device")
+    if through_mean and (transposed or graph.weighted_shard):
+        raise NotImplementedError("through_mean differentiates the mean's mask: a weighted structure (a transposed "
+                                  "direction, a weighted shard, an edge-dropout view) has none")
+    mode = _lib.MODE_WEIGHT_GRAD | (_lib.MODE_MEAN_GRAD if through_mean else 0)
+    e = graph.num_edges
+    with _on(x.device):
+        out = _empty(e, dtype=torch.float32, device=x.device)
+        rc = _lib.load().rgcn_aggregate_ex(graph.handle, int(transposed), _ptr(x), mode, d, _ptr(gagg), _ptr(out), 4 * e,
+                                           0, -1, None, None, _stream())
+        _lib.check(rc, "rgcn_aggregate_ex (weight gradient)")
+        if not original_order or e == 0:
+            return out
+        perms = graph.__dict__.setdefault("_perms", {})              # fixed for the life of the handle
+        if bool(transposed) not in perms:
+            perms[bool(transposed)] = graph.arrays(transposed)[2]
+        by_column = _empty(e, dtype=torch.float32, device=x.device)
+        by_column[perms[bool(transposed)]] = out                     # perm is a permutation: a plain indexed store
+    return by_column
+
+
 def fused_bwd_supported(num_relations: int, d_in: int, d_out: int) -> bool:
     """does the one-kernel input gradient cover this layer shape (in split precision)?"""
     return GEMM_PRECISION != "fp32" and bool(_query("rgcn_layer_bwd_input_fused_supported", int(num_relations), int(d_in), int(d_out)))
@@ -2535,6 +2585,19 @@ class PathGraph:
         other.__dict__.update({k: v.to(device) if isinstance(v, torch.Tensor) else v for k, v in self.__dict__.items()})
         other.device = other.out_ptr.device
         return other
+
+    def column_entries(self, edge_index: torch.Tensor) -> torch.Tensor:
+        """int64 ``[E]``: for every column of ``edge_index`` (the columns this structure was built from, or any pairs
+        it holds) the position of its ``(src, dst)`` pair in the out arrays - the out keys ``src * N + dst`` ascend"""
+        if edge_index.dim() != 2 or edge_index.size(0) != 2:
+            raise ValueError("edge_index must be [2, E]")
+        ei = edge_index.to(device=self.device, dtype=torch.int64)
+        keys = self.out_src * self.num_nodes + self.out_dst.to(torch.int64)
+        want = ei[0] * self.num_nodes + ei[1]
+        pos = torch.searchsorted(keys, want).clamp_(max=max(self.nnz - 1, 0))
+        if want.numel() and (self.nnz == 0 or not bool((keys[pos] == want).all())):
+            raise IndexError("a column names a (src, dst) pair the path graph does not hold")
+        return pos
 
     def _arrays(self):
         return (("out_ptr", self.out_ptr, torch.int64), ("out_dst", self.out_dst, torch.int32),

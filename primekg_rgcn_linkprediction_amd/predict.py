@@ -53,6 +53,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--explain", type=int, default=0, metavar="K",
                    help="also list the K best-scoring connecting paths of every (anchor, candidate) (0: off)")
     p.add_argument("--max_path_length", type=int, default=4, help="edges of the longest connecting path, 1..4")
+    p.add_argument("--explain_by", choices=("cosine", "gradient"), default="cosine",
+                   help="what scores a hop of a connecting path: the cosine of its two embedding rows, or the gradient of "
+                        "the candidate's score in the edge (what the model itself rests on)")
+    p.add_argument("--explain_edges", type=int, default=0, metavar="M",
+                   help="with --explain_by gradient: also list the M edges every candidate's score depends on most (0: off)")
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--trust_checkpoint", action="store_true",
                    help="allow the unrestricted pickle loader for --model_path (only for files you wrote yourself)")
@@ -71,6 +76,12 @@ def parse_args(argv=None) -> argparse.Namespace:
         parser.error("--explain must be >= 0")
     if not 1 <= args.max_path_length <= 4:
         parser.error("--max_path_length must be in 1..4")
+    if args.explain_edges < 0:
+        parser.error("--explain_edges must be >= 0")
+    if args.explain_edges > 0 and args.explain_by != "gradient":
+        parser.error("--explain_edges lists attributed edges: it needs --explain_by gradient")
+    if args.explain_by == "gradient" and args.explain < 1:
+        parser.error("--explain_by gradient ranks connecting paths: it needs --explain K with K >= 1")
     return args
 
 
@@ -114,11 +125,19 @@ def predict(evaluator, args: argparse.Namespace, names: Optional[Dict[int, str]]
         # the triple reads (anchor, relation, candidate) for tails and (candidate, relation, anchor) for heads
         pairs = [(q["anchor"], c) if args.side == "tail" else (c, q["anchor"]) for q in queries for c, _ in q["candidates"]]
         max_len = int(getattr(args, "max_path_length", 4))
-        paths, counts = evaluator.explain(pairs, explain, max_len) if pairs else ([], [])
+        by, top_edges = getattr(args, "explain_by", "cosine"), int(getattr(args, "explain_edges", 0) or 0)
+        edges = None
+        if by == "gradient":
+            paths, counts, edges = (evaluator.explain(pairs, explain, max_len, by="gradient", relations=[args.relation],
+                                                      top_edges=top_edges) if pairs else ([], [], []))
+        else:
+            paths, counts = evaluator.explain(pairs, explain, max_len) if pairs else ([], [])
         at = 0
         for q in queries:
             n = len(q["candidates"])
             q["paths"], q["path_counts"] = paths[at:at + n], counts[at:at + n]
+            if edges is not None and top_edges > 0:
+                q["edges"] = [[list(e) for e in per_candidate] for per_candidate in edges[at:at + n]]
             at += n
             if names is not None:
                 for per_candidate in q["paths"]:
@@ -129,6 +148,12 @@ def predict(evaluator, args: argparse.Namespace, names: Optional[Dict[int, str]]
                              "score": "mean cosine of consecutive nodes * 1 / (1 + 0.2 * (edges - 1)), float32",
                              "order": "score descending, then fewer edges, then interior nodes ascending",
                              "path_counts": "simple paths of 1, 2, 3, 4 edges, all of them"}
+        if by == "gradient":
+            protocol["paths"]["score"] = ("mean over the hops of the largest |d score / d edge mask| of the columns naming "
+                                          "the hop * 1 / (1 + 0.2 * (edges - 1)), float32")
+            if top_edges > 0:
+                protocol["edges"] = {"per_candidate": top_edges, "entry": "[column, source, relation, target, d score / d edge mask]",
+                                     "order": "|value| descending, equal magnitudes by column ascending"}
     return {"protocol": protocol, "queries": queries}
 
 
