@@ -42,7 +42,17 @@
  *   rgcn_aggregate(view, 1, g)   its adjoint.
  *   rgcn_graph_weight_bound      a true bound for EVERY draw: forward 1 + 1e-6 (a segment's weights sum to
  *                                k * fl(1 / k) <= 1 + 2^-23), transposed the edge count of the longest (source,
- *                                relation) segment (every weight is <= 1).
+ *                                relation) segment (every weight is <= 1).  A mask draw (below) with values in
+ *                                [0, inf) keeps both: transposed because every weight is still <= 1 (a rounded sum
+ *                                of non-negative terms is never below one of them - rounding is monotone - so
+ *                                M >= m and fl(m / M) <= 1), forward because M is a sum of non-negative terms through at most h rounded
+ *                                additions on any path of its fixed order - h = ceil(L / 8) + 3 for a segment of
+ *                                L <= 64 edges, ceil(L / 256) + 6 + 3 past that - so M >= (sum m) (1 - u)^h, u = 2^-24,
+ *                                each quotient is <= (m / M) (1 + u), and the weights of a segment sum to at most
+ *                                (1 + u) / (1 - u)^h.  Up to L = 1,280 that is below the float 1 + 1e-6 rounds to
+ *                                (1 + 16 u) and the value is what it always was; a view whose longest forward segment
+ *                                is longer returns (1 + u) / (1 - u)^h rounded up, e.g. 1 + 7.9e-6 at 31,017 edges.
+ *                                Negative or non-finite mask values void the bound.
  *   tile / row occupancy masks   the parent's: supersets under every draw (a tile they skip is zero under every draw).
  *
  * THE DRAW - the contract; tests restate it on the host (tests/edge_dropout_reference.py).  With e the ORIGINAL
@@ -69,6 +79,36 @@
  * node, capture and the absence of any allocation are as above.  A draw with an option reads twin[e] and, for
  * HIDE_TWINS, position[twin[e]] on top of what the plain draw reads; the plain draw reads neither.
  *
+ * THE MASK DRAW - RGCN_EDGE_DROPOUT_MASK, a third option bit of `batch`; tests restate it on the host
+ * (tests/edge_mask_reference.py).  With the bit set the call draws nothing and its parameters take these roles:
+ *   p          must be 0 (RGCN_ERR_ARG otherwise); RGCN_EDGE_DROPOUT_PAIRED has no word to share: RGCN_ERR_ARG.
+ *   rng        NOT {seed, epoch}: DEVICE const float mask[E], indexed by ORIGINAL column, read and never written.  It
+ *              still needs 8 bytes (RGCN_ERR_ALIGN) and must not be NULL.
+ *   cursor, position, batch's length, RGCN_EDGE_DROPOUT_HIDE_TWINS, stats      as in the plain draw: hard hiding
+ *              composes with the soft mask.
+ * With e the original column of a position and s = (dst, r) its forward segment:
+ *   m(e)      = hidden(e) ? 0.0f : mask[e]          a select: a hidden column's value is never looked at.  Nothing is
+ *               clamped - plain fp32 arithmetic: a NEGATIVE value enters M as it is and gives a negative weight where
+ *               M > 0; a NaN makes M NaN, and M > 0 is then false: every weight of that segment is 0.  Neither is
+ *               counted in k.  Denormal values are summed and divided as the denormals they are.
+ *   M[s]      = the sum of m over the positions of s in this FIXED order - the one rgcn_hip.h states for S[s] under
+ *               RGCN_MODE_MEAN_GRAD - b the segment's first position, every partial sum starting from +0.0f:
+ *                 <= 64 edges  eight partial sums P_j = m[b + j] + m[b + j + 8] + m[b + j + 16] + ... (in that order),
+ *                              M = ((P_0 + P_4) + (P_2 + P_6)) + ((P_1 + P_5) + (P_3 + P_7));
+ *                  > 64 edges  256 partial sums T_t = m[b + t] + m[b + t + 256] + ... (in that order); each 64
+ *                              consecutive ones are combined by an xor butterfly with the offsets 32, 16, 8, 4, 2, 1
+ *                              (entry l becomes entry l + entry (l ^ offset) at every step) into W_v, and
+ *                              M = ((W_0 + W_1) + W_2) + W_3.  A hub segment of any length takes this rule.
+ *               No floating-point atomics: two calls with the same arguments leave the same bits.
+ *   w_fwd[pos] = w_t[pos'] = M[s] > 0 ? m(e) / M[s] : 0.0f          one IEEE division; the same value in both directions
+ *   head_w     refreshed for both directions, as the plain draw does
+ *   k[s]       = the number of positions of s with m(e) > 0 (int32)  - rgcn_edge_dropout_kept
+ *   stats[0]  += edges with m(e) > 0,  stats[1] += hidden edges
+ * mask = 1 everywhere is the draw p = 0 bit for bit (a sum of n < 2^24 ones is exact in every order), and a mask of
+ * zeros and ones is the plain draw p = 0 with exactly the zero columns hidden through `position`.  Three kernels, no
+ * memset node, no allocation (M lives in a float[N * R] create allocated), no host synchronisation: capturable.  The
+ * plain draw's launches are not the mask draw's and run the instructions they always ran.
+ *
  * Non-finite values - a deliberate deviation.  A dropped or hidden edge contributes 0 * x: it is MULTIPLIED by a zero
  * weight, not skipped, so a non-finite source row still reaches the aggregate of a segment it was dropped from
  * (0 * NaN = NaN), where RGCNConv on the kept subgraph would not see it.  The hot gather is not changed for it.
@@ -85,9 +125,10 @@ extern "C" {
 #define RGCN_EDGE_DROPOUT_STREAM 0x45444F50u   /* counter word 3 of every edge-dropout draw ("EDOP"; not RGCN_RESAMPLE_STREAM) */
 
 /* Option bits of rgcn_edge_dropout_draw's `batch` (as RGCN_MODE_SPARSE_ROWS rides in a mode word): the window's length
- * is `batch` with both cleared, and a draw with neither set writes the bytes it always wrote. */
+ * is `batch` with all of them cleared, and a draw with none set writes the bytes it always wrote. */
 #define RGCN_EDGE_DROPOUT_HIDE_TWINS (1LL << 62)   /* a column whose twin stands in the window is hidden too */
 #define RGCN_EDGE_DROPOUT_PAIRED     (1LL << 61)   /* a column and its twin share one Philox word: dropped or kept together */
+#define RGCN_EDGE_DROPOUT_MASK       ((int64_t)1 << 60)   /* = 1LL << 60.  THE MASK DRAW above: rng is const float mask[E], p must be 0 */
 
 typedef struct rgcn_edge_dropout rgcn_edge_dropout;
 
@@ -105,11 +146,12 @@ int rgcn_edge_dropout_kept_export(const rgcn_edge_dropout* ed, int32_t* out, voi
 
 /* One draw: asynchronous on `stream`, no allocation, no host synchronisation, capturable into a HIP graph (three
  * kernels, no memset node: the draw's last launch clears the counters the next one adds into).  rng: DEVICE int64[2] =
- * {seed, epoch}; cursor: DEVICE int64[1] or NULL (= 0); batch >= 0: the window's length, below 2^61, ORed with any of
- * RGCN_EDGE_DROPOUT_HIDE_TWINS and RGCN_EDGE_DROPOUT_PAIRED;
+ * {seed, epoch}; cursor: DEVICE int64[1] or NULL (= 0); batch >= 0: the window's length, below 2^60, ORed with any of
+ * RGCN_EDGE_DROPOUT_HIDE_TWINS and RGCN_EDGE_DROPOUT_PAIRED, or with RGCN_EDGE_DROPOUT_MASK (rng is the mask then);
  * position: DEVICE int64[E] or NULL, position[e] = where column e stands in the epoch's order; stats: DEVICE int64[2]
  * or NULL.  RGCN_ERR_ARG: ed or rng NULL, batch < 0, p outside [0, 1) (NaN included).  RGCN_ERR_ALIGN: rng, cursor,
- * position, stats need 8. */
+ * position, stats need 8.  With RGCN_EDGE_DROPOUT_MASK: p != 0 or RGCN_EDGE_DROPOUT_PAIRED RGCN_ERR_ARG (after the range
+ * of p, before the alignment). */
 int rgcn_edge_dropout_draw(rgcn_edge_dropout* ed, double p, const int64_t* rng, const int64_t* cursor, int64_t batch,
                            const int64_t* position, int64_t* stats, void* stream);
 

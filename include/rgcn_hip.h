@@ -280,19 +280,36 @@ typedef struct rgcn_slab_job {
  *              No floating-point atomics.  This is dL/dm[p] at m = 1 for w = m / sum_s m: the first-order effect of
  *              deleting the edge from the mean.  A segment of one edge gives exactly +0.0f (finite operands).  The dots
  *              are stored first and rewritten in place by the same call (the longer segments by a second launch).
+ *   | RGCN_MODE_LOG_WEIGHT_GRAD   (a weighted structure only: RGCN_ERR_UNSUPPORTED otherwise, use the mean mode)
+ *              for weights that are a per-segment normalisation w[p] = m[p] / sum over p's segment of m - the forward
+ *              direction of the view of an edge dropout under any draw, a mask draw included - the gradient in the
+ *              LOGARITHM of the unnormalised weights:
+ *                  out[p] = w[p] == 0 ? +0.0f : w[p] * (dot[p] - S[s]),     S[s] = sum over q in s of fl(w[q] * dot[q])
+ *              every product and the difference rounded by itself (no fused multiply-add), S[s] summed in the FIXED
+ *              order stated above for the mean mode with fl(w[q] * dot[q]) in the place of dot[q] (<= 64 edges: eight
+ *              strided partial sums and the tree; > 64 edges: 256 strided partial sums, the butterfly per 64 and three
+ *              adds).  Only the structure's own weights are read: the mode needs no state of the draw that wrote them.
+ *              This is dL/dlogit[p] of a segment softmax, m = exp(logit); for m = sigmoid(theta) the caller forms
+ *              dL/dtheta = out * (1 - sigmoid(theta)) elementwise.  An edge of weight 0 gets exactly +0.0f.
  *   refusals   in this order, nothing launched on any of them: RGCN_MODE_MEAN_GRAD without RGCN_MODE_WEIGHT_GRAD
- *              RGCN_ERR_ARG; with bit 0 (fp16 table) or RGCN_MODE_SPARSE_ROWS RGCN_ERR_UNSUPPORTED; d <= 0 or d % 4
- *              RGCN_ERR_ARG; d > 256 RGCN_ERR_UNSUPPORTED (the dot would span column blocks); amax != NULL
+ *              RGCN_ERR_ARG; RGCN_MODE_LOG_WEIGHT_GRAD without RGCN_MODE_WEIGHT_GRAD RGCN_ERR_ARG; both of them
+ *              together RGCN_ERR_ARG; with bit 0 (fp16 table) or RGCN_MODE_SPARSE_ROWS RGCN_ERR_UNSUPPORTED; d <= 0 or
+ *              d % 4 RGCN_ERR_ARG; d > 256 RGCN_ERR_UNSUPPORTED (the dot would span column blocks); amax != NULL
  *              RGCN_ERR_UNSUPPORTED; a job with a non-NULL slab RGCN_ERR_UNSUPPORTED (a pending reduction is never lost
  *              silently); a direction that was not built RGCN_ERR_ARG; first_level != 0, or last_level neither < 0 nor
- *              rgcn_graph_num_levels, RGCN_ERR_ARG; the mean mode on a weighted structure RGCN_ERR_UNSUPPORTED.  Then
+ *              rgcn_graph_num_levels, RGCN_ERR_ARG; the mean mode on a weighted structure RGCN_ERR_UNSUPPORTED; the
+ *              log-weight mode on a structure that is not weighted RGCN_ERR_UNSUPPORTED.  Then
  *              E == 0 or no key rows: RGCN_OK, nothing written.  Then x or agg NULL RGCN_ERR_ARG, the workspace
  *              RGCN_ERR_WORKSPACE, and last x, agg or workspace below 16 bytes RGCN_ERR_ALIGN.
  *   non-finite values   a NaN or infinity in a row of x reaches the output of every edge that reads that row (an
  *              infinity may arrive as NaN), one in a row of agg every edge of that segment; in the mean mode it reaches
- *              every edge of those segments, through S.  No other position is affected. */
+ *              every edge of those segments, through S.  No other position is affected.  In the log-weight mode the
+ *              same holds for the positions whose weight is not 0 (a product 0 * NaN inside S is NaN, so an edge of
+ *              weight 0 still carries a non-finite row into S); a position of weight 0 itself holds +0.0f whatever
+ *              its dot or S is, and a non-finite weight makes its own position and, through S, its segment non-finite. */
 #define RGCN_MODE_WEIGHT_GRAD 8
 #define RGCN_MODE_MEAN_GRAD 16     /* only together with RGCN_MODE_WEIGHT_GRAD */
+#define RGCN_MODE_LOG_WEIGHT_GRAD 32   /* only together with RGCN_MODE_WEIGHT_GRAD, never with RGCN_MODE_MEAN_GRAD */
 size_t rgcn_aggregate_workspace_bytes(const rgcn_graph* g, int transposed, int64_t d);
 int rgcn_aggregate_deferrable(const rgcn_graph* g, int transposed, int64_t d);
 int rgcn_aggregate(const rgcn_graph* g, int transposed, const float* x, int64_t d, float* agg,

@@ -253,6 +253,7 @@ EDGE_DROPOUT_PROTOTYPES = {
 }
 EDGE_DROPOUT_STREAM = 0x45444F50   # RGCN_EDGE_DROPOUT_STREAM
 EDGE_DROPOUT_HIDE_TWINS, EDGE_DROPOUT_PAIRED = 1 << 62, 1 << 61   # option bits of the draw's `batch`
+EDGE_DROPOUT_MASK = 1 << 60        # RGCN_EDGE_DROPOUT_MASK: the mask draw - `rng` is float mask[E], nothing is drawn
 
 # rgcn_sparse.h: the row-granular occupancy behind sparse aggregates (csrc/rgcn_graph.hip).  MODE_SPARSE_ROWS:
 # RGCN_MODE_SPARSE_ROWS of rgcn_hip.h, the bit a training pass sets in the `int` option word of its gathers and of the
@@ -281,6 +282,7 @@ MODE_ROW_ORDER = 4
 # then computes the gather's adjoint in its edge weights (csrc/edge_grad.hip) instead of gathering.
 MODE_WEIGHT_GRAD = 8
 MODE_MEAN_GRAD = 16
+MODE_LOG_WEIGHT_GRAD = 32          # RGCN_MODE_LOG_WEIGHT_GRAD: through a weighted structure's per-segment normalisation
 
 # header of include/ -> its table, in the order the headers arrived: what load() types and every test enumerates
 HEADERS = {

@@ -205,6 +205,102 @@ def attribution_edge_score(attr: Mapping[str, Tensor], path_graph: "ops.PathGrap
     return out.scatter_reduce_(0, entries, total.abs().to(torch.float32), "amax", include_self=True)
 
 
+def masked_edges(result: Mapping[str, Tensor], edge_index: Tensor, edge_type: Tensor, k: int) -> List[Tuple]:
+    """the ``k`` columns a learned mask keeps most: ``[(column, src, rel, dst, value)]`` by mask value descending among
+    the columns of the pair's receptive field (``attribution.learn_edge_mask``'s ``mask`` / ``field``; a column outside
+    the field holds 1 because it cannot matter, and is never listed); equal values in column order (a stable sort)"""
+    mask, field = result["mask"], result["field"]
+    if mask.dim() != 1 or mask.numel() != edge_index.size(1) or edge_type.numel() != mask.numel() or field.shape != mask.shape:
+        raise ValueError("result['mask'] / ['field'] must hold one value per column of edge_index / edge_type")
+    cols = torch.nonzero(field).view(-1)
+    order = cols[torch.sort(mask[cols], descending=True, stable=True).indices[:max(int(k), 0)]]
+    at = order.cpu()
+    ei, et = edge_index.cpu(), edge_type.cpu()
+    return list(zip(at.tolist(), ei[0][at].tolist(), et[at].tolist(), ei[1][at].tolist(), mask[order].cpu().tolist()))
+
+
+@torch.no_grad()
+def mask_edge_score(result: Mapping[str, Tensor], path_graph: "ops.PathGraph", edge_index: Tensor) -> Tensor:
+    """float32 ``[nnz]``, an ``edge_score`` for ``ops.paths_topk``: per unique ``(src, dst)`` pair of ``path_graph`` the
+    LARGEST learned mask value over the field's columns that name the pair, 0 for a pair no such column names"""
+    mask, field = result["mask"], result["field"]
+    graph = path_graph.to(mask.device)
+    entries = graph.column_entries(edge_index)
+    if entries.numel() != mask.numel():
+        raise ValueError("result['mask'] must hold one value per column of edge_index")
+    out = torch.zeros(graph.nnz, dtype=torch.float32, device=mask.device)
+    return out.scatter_reduce_(0, entries, torch.where(field, mask, torch.zeros_like(mask)), "amax", include_self=True)
+
+
+def explanation_fidelity(model, edge_index: Tensor, edge_type: Tensor, pairs, relations, edge_sets, *,
+                         dropout: Optional["ops.EdgeDropout"] = None) -> List[Dict[str, Dict[str, float]]]:
+    """What the score does when the edges an explainer names are actually DELETED, and when only they are kept: for
+    every ``(head, tail)`` of ``pairs`` with its relation and every named set of columns in ``edge_sets[q]`` (a mapping
+    ``name -> columns``: the top-M of any explainer) -> ``{name: {"full", "without", "only"}}`` per pair -
+
+        full     the score on the whole graph
+        without  the score with the set hidden (fidelity-: a faithful set moves it)
+        only     the score with every column of the pair's receptive field EXCEPT the set hidden (fidelity+: a
+                 sufficient set preserves it)
+
+    Deletion is exact, not a first-order estimate: the columns are hidden through ``position`` in a draw with ``p = 0``
+    over one reused edge-dropout view (``ops.EdgeDropout.draw``: window = the hidden columns), which makes both layers
+    the mean over the remaining in-edges - ``RGCNConv`` on ``edge_index[:, keep]``.  ``dropout``: an ``ops.EdgeDropout``
+    over ``ops.bucket(edge_index, ...)`` to reuse (its view's weights are overwritten)."""
+    from . import attribution
+    x, _ = attribution._check_explained(model, edge_index, None, "explanation_fidelity")
+    enc = model.encoder
+    dev, n, r, e = x.device, x.size(0), enc.num_relations, edge_index.size(1)
+    pairs = torch.as_tensor(pairs, dtype=torch.int64).reshape(-1, 2).tolist()
+    relations = torch.as_tensor(relations, dtype=torch.int64).view(-1).tolist()
+    if len(relations) == 1 and len(pairs) != 1:
+        relations = relations * len(pairs)
+    if len(relations) != len(pairs) or len(edge_sets) != len(pairs):
+        raise ValueError("one relation and one mapping of edge sets per pair expected")
+    own = dropout is None
+    if own:
+        dropout = ops.EdgeDropout(ops.bucket(edge_index, edge_type, n, r))
+    elif not isinstance(dropout, ops.EdgeDropout) or dropout.graph.num_edges != e:
+        raise ValueError("dropout must be an ops.EdgeDropout over the bucketing of these columns")
+    try:
+        conv1, conv2 = enc.conv1, enc.conv2
+        weights = tuple(None if p is None else p.detach().contiguous() for p in (
+            conv1.effective_weight(), conv1.root, conv1.bias, conv2.effective_weight(), conv2.root, conv2.bias))
+        xg = x.clone().requires_grad_(True)                    # a view counts only where something is differentiated
+        rng = torch.zeros(2, dtype=torch.int64, device=dev)
+        everything = torch.arange(e, device=dev)
+
+        def score(hidden: Tensor, h, rel, t) -> float:
+            """the triple's score with the bool ``[E]`` columns ``hidden`` deleted"""
+            order = torch.cat([everything[hidden], everything[~hidden]])       # the hidden columns stand first
+            position = torch.empty(e, dtype=torch.int64, device=dev)
+            position[order] = everything
+            dropout.draw(0.0, rng, batch=int(hidden.sum()), position=position)
+            ids = [torch.tensor([v], dtype=torch.int64, device=dev) for v in (h, rel, t)]
+            with torch.enable_grad():
+                s = attribution._view_scores(model, dropout.view, xg, edge_index, edge_type, weights, ids[0], ids[1], ids[2])[2]
+            return float(s.detach()[0])
+
+        out = []
+        nothing = torch.zeros(e, dtype=torch.bool, device=dev)
+        for (h, t), rel, sets in zip(pairs, relations, edge_sets):
+            full = score(nothing, h, rel, t)
+            field = attribution.receptive_field(edge_index, h, t, n)
+            row = {}
+            for name, columns in sets.items():
+                named = torch.zeros(e, dtype=torch.bool, device=dev)
+                columns = torch.as_tensor(columns, dtype=torch.int64, device=dev).view(-1)
+                if columns.numel() and (int(columns.min()) < 0 or int(columns.max()) >= e):
+                    raise IndexError(f"edge set {name!r} names a column outside [0, {e})")
+                named[columns] = True
+                row[name] = {"full": full, "without": score(named, h, rel, t), "only": score(field & ~named, h, rel, t)}
+            out.append(row)
+        return out
+    finally:
+        if own:
+            dropout.destroy()
+
+
 def _class_names(class_names, num_classes: int) -> List[str]:
     """name of every class id in ``[0, num_classes)``: from ``{name: class id}`` or a sequence indexed by class id; an
     id without a name is called by its number"""

@@ -21,9 +21,21 @@
 // of a triple and of its reverse next to each other, forward copies first, each side in column order; k_tw_pair gives
 // the j-th forward copy the j-th backward one.  A draw with an option reads twin[e] (and position[twin[e]]) on top of
 // what the plain draw reads; the plain draw is the instantiation without either and reads what it always did.
+//
+// The mask draw (RGCN_EDGE_DROPOUT_MASK).  Nothing is drawn: every edge carries a float of the caller's and a segment's
+// weights are m / M with M the segment's sum in the FIXED order the header states - no counter, no atomic on a float.
+// A segment has one owner, so the launches of the plain draw are not used (and not touched):
+//   k_ed_mask_fwd  a workgroup looks at 256 forward segments.  A thread sums its own if it has at most 64 edges - a
+//                  round of eight positions IS the eight strided partial sums, the ids, positions and mask values of a
+//                  round loaded in three batches - leaves m in w_fwd, and divides its own stores.  The longer ones are
+//                  then taken one at a time by all 256 threads (the strided partial sums, the butterfly, three adds),
+//                  as k_edge_long of edge_grad.hip takes them.  M[s] and k[s] are written by the owner.
+//   k_ed_mask_t    one thread per transposed position: m of its column again, divided by M of its forward segment.
+//   k_ed_heads     as in the plain draw (the counters it clears were never raised).
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cmath>
 #include <new>
 #include <vector>
 
@@ -44,6 +56,7 @@ struct rgcn_edge_dropout {
   int32_t* seg_f = nullptr;     // [E] forward segment of every forward position
   int32_t* seg_t = nullptr;     // [E] forward segment (dst * R + rel) of every transposed position
   int32_t* twin = nullptr;      // [E] by ORIGINAL column: the column holding the reversed triple, -1 without one
+  float* msum = nullptr;        // [N * R] M of the last mask draw (the transposed half of that draw divides by it)
 };
 
 namespace {
@@ -73,6 +86,13 @@ __device__ inline draw_state draw_begin(const draw_params& p) {
   s.k0 = (uint32_t)seed;
   s.k1 = (uint32_t)(seed >> 32);
   s.epoch = (uint32_t)(uint64_t)p.rng[1];
+  return s;
+}
+// the mask draw's: rng holds no seed there, only the cursor is read
+__device__ inline draw_state draw_begin_cursor(const draw_params& p) {
+  draw_state s;
+  s.c0 = p.cursor ? p.cursor[0] : 0;
+  s.k0 = s.k1 = s.epoch = 0u;
   return s;
 }
 // twin[e] where an option looks at it (-1: none); the plain draw has no such load
@@ -207,6 +227,168 @@ __global__ __launch_bounds__(kThreads) void k_ed_heads(const rgcn_item* __restri
   const rgcn_item it = items[i / RGCN_HEAD];
   const int e = it.begin + (int)(i % RGCN_HEAD);
   head[i] = e < it.end ? w[e] : 0.f;
+}
+
+// ----------------------------------------------------------------------------------------------------------- mask draw
+// m(e) of the header: the mask value of a column that is not hidden (a select: a hidden NaN is 0)
+template <bool kHideTwins>
+__device__ inline bool mask_hidden(const draw_params& p, const draw_state& s, int64_t e) {
+  int64_t t = -1;
+  if constexpr (kHideTwins) t = p.twin[e];
+  return edge_hidden<kHideTwins>(p, s, e, t);
+}
+__device__ inline float mask_weight(float m, float M) { return M > 0.f ? __fdiv_rn(m, M) : 0.f; }   // NaN > 0 is false
+
+template <bool kHideTwins>
+__global__ __launch_bounds__(kThreads) void k_ed_mask_fwd(const int32_t* __restrict__ rowptr,
+                                                          const int64_t* __restrict__ perm, int64_t NR, int64_t E,
+                                                          draw_params p, const float* __restrict__ mask, float* w_fwd,
+                                                          float* __restrict__ msum, int32_t* __restrict__ kept,
+                                                          unsigned long long* __restrict__ stats) {
+  constexpr int kBatch = 8;
+  __shared__ int list[kThreads];
+  __shared__ int nlist, s_stat[2], s_kept[kThreads / 64];
+  __shared__ float wsum[kThreads / 64];
+  const int tid = (int)threadIdx.x;
+  const int64_t base = (int64_t)blockIdx.x * kThreads, s_own = base + tid;
+  const draw_state st = draw_begin_cursor(p);
+  if (tid == 0) nlist = 0;
+  if (tid < 2) s_stat[tid] = 0;
+  __syncthreads();
+  int64_t begin = 0, end = 0;
+  if (s_own < NR) { begin = rowptr[s_own]; end = rowptr[s_own + 1]; }
+  const bool is_long = end - begin > RGCN_CHUNK;
+  if (is_long) list[atomicAdd(&nlist, 1)] = tid;
+  int nk = 0, nh = 0;                              // edges with m > 0, hidden edges: this thread's
+  if (!is_long) {                                  // (a segment without an edge: M = 0, k = 0)
+    float part[kBatch];
+#pragma unroll
+    for (int j = 0; j < kBatch; ++j) part[j] = 0.f;
+    const int64_t last = end > begin ? end - 1 : 0;
+    for (int64_t q = begin; q < end; q += kBatch) {
+      int64_t e[kBatch];
+      float m[kBatch];
+      bool hid[kBatch];
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) e[j] = clamp64(perm[min(q + j, last)], 0, E - 1);   // clamped: never under a branch
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) hid[j] = mask_hidden<kHideTwins>(p, st, e[j]);
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) m[j] = mask[e[j]];
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) {
+        const bool in = q + j < end;
+        const float v = hid[j] ? 0.f : m[j];
+        part[j] += in ? v : 0.f;
+        nk += in && v > 0.f;
+        nh += in && hid[j];
+        if (in) w_fwd[q + j] = v;
+      }
+    }
+    const float M = ((part[0] + part[4]) + (part[2] + part[6])) + ((part[1] + part[5]) + (part[3] + part[7]));
+    if (s_own < NR) { msum[s_own] = M; kept[s_own] = nk; }
+    for (int64_t q = begin; q < end; q += kBatch) {         // this thread's own stores
+      float m[kBatch];
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) m[j] = w_fwd[min(q + j, last)];
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j)
+        if (q + j < end) w_fwd[q + j] = mask_weight(m[j], M);
+    }
+  }
+  __syncthreads();
+  const int n = nlist;
+  for (int i = 0; i < n; ++i) {
+    const int64_t s = base + list[i];
+    const int64_t b = rowptr[s], en = rowptr[s + 1];
+    float sum = 0.f;
+    int cnt = 0;
+    for (int64_t q = b + tid; q < en; q += (int64_t)kBatch * kThreads) {   // ascending j: thread t adds b + t + 256 j
+      int64_t e[kBatch];
+      float m[kBatch];
+      bool hid[kBatch];
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) e[j] = clamp64(perm[min(q + (int64_t)j * kThreads, en - 1)], 0, E - 1);
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) hid[j] = mask_hidden<kHideTwins>(p, st, e[j]);
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) m[j] = mask[e[j]];
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) {
+        const int64_t at = q + (int64_t)j * kThreads;
+        const bool in = at < en;
+        const float v = hid[j] ? 0.f : m[j];
+        sum += in ? v : 0.f;
+        cnt += in && v > 0.f;
+        nh += in && hid[j];
+        if (in) w_fwd[at] = v;
+      }
+    }
+    nk += cnt;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      sum += __shfl_xor(sum, off);
+      cnt += __shfl_xor(cnt, off);
+    }
+    if ((tid & 63) == 0) { wsum[tid >> 6] = sum; s_kept[tid >> 6] = cnt; }
+    __syncthreads();
+    const float M = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    if (tid == 0) { msum[s] = M; kept[s] = s_kept[0] + s_kept[1] + s_kept[2] + s_kept[3]; }
+    for (int64_t q = b + tid; q < en; q += (int64_t)kBatch * kThreads) {
+      float m[kBatch];
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) m[j] = w_fwd[min(q + (int64_t)j * kThreads, en - 1)];
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j)
+        if (q + (int64_t)j * kThreads < en) w_fwd[q + (int64_t)j * kThreads] = mask_weight(m[j], M);
+    }
+    __syncthreads();                               // wsum and s_kept are free again
+  }
+  if (stats) {                                     // integers: order-free
+    if (nk) atomicAdd(&s_stat[0], nk);
+    if (nh) atomicAdd(&s_stat[1], nh);
+    __syncthreads();
+    if (tid < 2 && s_stat[tid] > 0) atomicAdd(&stats[tid], (unsigned long long)s_stat[tid]);
+  }
+}
+
+template <bool kHideTwins>
+__global__ __launch_bounds__(kThreads) void k_ed_mask_t(const int64_t* __restrict__ perm_t,
+                                                        const int32_t* __restrict__ seg_t, int64_t E, draw_params p,
+                                                        const float* __restrict__ mask, const float* __restrict__ msum,
+                                                        float* __restrict__ w_t) {
+  const int64_t pos = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (pos >= E) return;
+  const draw_state st = draw_begin_cursor(p);
+  const int64_t e = clamp64(perm_t[pos], 0, E - 1);
+  const float M = msum[seg_t[pos]], m = mask[e];
+  const bool hid = mask_hidden<kHideTwins>(p, st, e);
+  w_t[pos] = mask_weight(hid ? 0.f : m, M);
+}
+
+template <bool kHideTwins>
+void launch_mask(rgcn_edge_dropout* ed, const draw_params& p, const float* mask, int64_t* stats, hipStream_t stream) {
+  const rgcn_graph& v = ed->view;
+  const int64_t E = v.E, NR = v.N * v.R;
+  k_ed_mask_fwd<kHideTwins><<<grid_for(NR, kThreads), kThreads, 0, stream>>>(
+      v.dir[0].rowptr, v.dir[0].perm, NR, E, p, mask, ed->val[0], ed->msum, ed->kept,
+      reinterpret_cast<unsigned long long*>(stats));
+  k_ed_mask_t<kHideTwins><<<grid_for(E, kThreads), kThreads, 0, stream>>>(v.dir[1].perm, ed->seg_t, E, p, mask, ed->msum,
+                                                                          ed->val[1]);
+}
+
+int mask_impl(rgcn_edge_dropout* ed, const draw_params& p, const float* mask, bool hide_twins, int64_t* stats,
+              hipStream_t stream) {
+  const rgcn_graph& v = ed->view;
+  const int64_t NR = v.N * v.R;
+  if (v.E <= 0) return RGCN_OK;
+  if (hide_twins && p.position) launch_mask<true>(ed, p, mask, stats, stream);
+  else launch_mask<false>(ed, p, mask, stats, stream);
+  const int64_t n0 = v.dir[0].num_items[0], n1 = v.dir[1].num_items[0];
+  k_ed_heads<<<grid_for(std::max((n0 + n1) * RGCN_HEAD, NR), kThreads), kThreads, 0, stream>>>(
+      v.dir[0].items[0], n0, ed->val[0], ed->head_w[0], v.dir[1].items[0], n1, ed->val[1], ed->head_w[1], NR, ed->count);
+  RGCN_HIP_TRY(hipGetLastError());
+  return RGCN_OK;
 }
 
 // the two launches that form the mark, instantiated on the options
@@ -345,6 +527,8 @@ int create_impl(const rgcn_graph* g, hipStream_t stream, rgcn_edge_dropout* ed) 
   RGCN_HIP_TRY(hipMalloc((void**)&ed->count, (size_t)std::max<int64_t>(NR, 1) * sizeof(int32_t)));
   RGCN_HIP_TRY(hipMemsetAsync(ed->kept, 0, (size_t)std::max<int64_t>(NR, 1) * sizeof(int32_t), stream));
   RGCN_HIP_TRY(hipMemsetAsync(ed->count, 0, (size_t)std::max<int64_t>(NR, 1) * sizeof(int32_t), stream));
+  RGCN_HIP_TRY(hipMalloc((void**)&ed->msum, (size_t)std::max<int64_t>(NR, 1) * sizeof(float)));
+  RGCN_HIP_TRY(hipMemsetAsync(ed->msum, 0, (size_t)std::max<int64_t>(NR, 1) * sizeof(float), stream));
   for (int d = 0; d < 2; ++d) {                  // ... but the weights and their item-head copies
     rgcn_csr& c = ed->view.dir[d];
     c.weighted = true;
@@ -360,6 +544,25 @@ int create_impl(const rgcn_graph* g, hipStream_t stream, rgcn_edge_dropout* ed) 
   // plan_structure gives a weighted structure); a transposed weight is <= 1, so a segment's sum is at most its length
   ed->view.dir[0].weight_bound = (float)(1.0 + 1e-6);
   std::vector<int32_t> rp((size_t)NR + 1);
+  // ... and for every mask draw with values in [0, inf): M is a sum of non-negative terms through at most h rounded
+  // additions on any path of the fixed order (h = ceil(L / 8) + 3 up to 64 edges, ceil(L / 256) + 6 + 3 past that),
+  // so M >= sum m * (1 - u)^h, every quotient is <= m / M * (1 + u), and a segment's weights sum to at most
+  // (1 + u) / (1 - u)^h, u = 2^-24.  That stays below 1 + 1e-6 up to L = 1,280; a longer forward segment raises the bound.
+  RGCN_HIP_TRY(hipMemcpyAsync(rp.data(), g->dir[0].rowptr, (size_t)(NR + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  RGCN_HIP_TRY(hipStreamSynchronize(stream));
+  int64_t longest_f = 0;
+  for (int64_t s = 0; s < NR; ++s) longest_f = std::max<int64_t>(longest_f, rp[(size_t)s + 1] - rp[(size_t)s]);
+  {
+    const int64_t h = longest_f <= RGCN_CHUNK ? (longest_f + 7) / 8 + 3 : (longest_f + 255) / 256 + 9;
+    const double u = 1.0 / 16777216.0;
+    double b = 1.0 + u;
+    for (int64_t i = 0; i < h; ++i) b /= 1.0 - u;
+    if (b > (double)ed->view.dir[0].weight_bound) {   // (the float that stands there is 1 + 16 u)
+      float fb = (float)b;
+      if ((double)fb < b) fb = nextafterf(fb, 2.f);   // the conversion may have rounded down
+      ed->view.dir[0].weight_bound = fb;
+    }
+  }
   RGCN_HIP_TRY(hipMemcpyAsync(rp.data(), g->dir[1].rowptr, (size_t)(NR + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   RGCN_HIP_TRY(hipStreamSynchronize(stream));
   int32_t longest = 1;
@@ -419,6 +622,7 @@ void rgcn_edge_dropout_destroy(rgcn_edge_dropout* ed) {
   (void)hipFree(ed->seg_f);
   (void)hipFree(ed->seg_t);
   (void)hipFree(ed->twin);
+  (void)hipFree(ed->msum);
   delete ed;                                     // the shared arrays stay the parent's
 }
 
@@ -439,9 +643,14 @@ int rgcn_edge_dropout_draw(rgcn_edge_dropout* ed, double p, const int64_t* rng, 
                            const int64_t* position, int64_t* stats, void* stream) {
   if (!ed || !rng || batch < 0) return RGCN_ERR_ARG;            // (bit 63 is no option: a negative batch)
   const bool hide_twins = (batch & RGCN_EDGE_DROPOUT_HIDE_TWINS) != 0, paired = (batch & RGCN_EDGE_DROPOUT_PAIRED) != 0;
-  batch &= ~(RGCN_EDGE_DROPOUT_HIDE_TWINS | RGCN_EDGE_DROPOUT_PAIRED);   // what is left is the window's length
+  const bool masked = (batch & RGCN_EDGE_DROPOUT_MASK) != 0;
+  batch &= ~(RGCN_EDGE_DROPOUT_HIDE_TWINS | RGCN_EDGE_DROPOUT_PAIRED | RGCN_EDGE_DROPOUT_MASK);   // what is left is the window's length
   if (!(p >= 0.0 && p < 1.0)) return RGCN_ERR_ARG;            // NaN fails both compares
+  if (masked && (p != 0.0 || paired)) return RGCN_ERR_ARG;    // a mask draw draws nothing: no p, no shared word
   RGCN_ALIGN_TRY(8, rng, cursor, position, stats);
+  if (masked)
+    return mask_impl(ed, draw_params{position, cursor, nullptr, batch, 0u, ed->twin}, reinterpret_cast<const float*>(rng),
+                     hide_twins, stats, (hipStream_t)stream);
   const uint32_t threshold = (uint32_t)(uint64_t)(p * 4294967296.0);   // floor(p * 2^32) <= 2^32 - 1 for p < 1
   return draw_impl(ed, draw_params{position, cursor, rng, batch, threshold, ed->twin}, hide_twins, paired, stats,
                    (hipStream_t)stream);

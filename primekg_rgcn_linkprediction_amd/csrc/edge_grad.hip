@@ -17,6 +17,12 @@
 // the dots rewrite their own positions (the first round's from registers, later rounds re-read: a lane's own stores).
 // Longer segments - packs of the plan, a handful per graph - are finished by a second short launch: a workgroup looks
 // at 256 segments, and all of its threads take the long ones among them one by one, in place.
+//
+// RGCN_MODE_LOG_WEIGHT_GRAD, out[p] = w[p] * (dot[p] - S) with S the segment's sum of fl(w[q] * dot[q]) in the SAME
+// fixed order, on a weighted structure whose weights are normalised per segment (the forward direction of an edge
+// dropout's view): the same frame with one more operand per edge.  The weight of the position a lane stores is loaded
+// from a clamped index before the round's row loads - independent of them, never under a branch - and the rewrite of
+// the later rounds re-reads the weights beside the dots in one batch.
 #include "rgcn_common.h"
 
 namespace {
@@ -56,11 +62,32 @@ __device__ inline float mean_value(float dot, float sw, float w) {
   return (dot - sw) * w;
 }
 
-template <int G, bool MEAN>
+// The log-weight mode's arithmetic: the product inside S, and the value (+0.0f at a zero weight, whatever the rest is).
+__device__ inline float logw_term(float w, float dot) {
+#pragma clang fp contract(off)
+  return w * dot;
+}
+__device__ inline float logw_value(float dot, float sum, float w) {
+#pragma clang fp contract(off)
+  const float v = w * (dot - sum);
+  return w == 0.f ? 0.f : v;
+}
+
+enum : int { kPlain = 0, kMean = 1, kLogW = 2 };   // what a launch does with the dots
+// what is subtracted from every dot of a segment, and the value of a position, by mode (w: w[s], or the position's own)
+template <int MODE>
+__device__ inline float seg_total(float sum, float w) { return MODE == kLogW ? sum : mean_scaled_sum(sum, w); }
+template <int MODE>
+__device__ inline float seg_value(float dot, float total, float w) {
+  return MODE == kLogW ? logw_value(dot, total, w) : mean_value(dot, total, w);
+}
+
+template <int G, int MODE>
 __global__ __launch_bounds__(kThreads) void k_edge_dot(
     const float* __restrict__ x, const float* __restrict__ gagg, const rgcn_item* __restrict__ items, int64_t nitems,
     const int32_t* __restrict__ rowptr, int64_t NR, const int32_t* __restrict__ col,
     const int32_t* __restrict__ head_col, const float* __restrict__ cnt, float* out, int d) {
+  constexpr bool MEAN = MODE == kMean, LOGW = MODE == kLogW, SUMS = MODE != kPlain;   // cnt: cnt[s] (mean), w[p] (log weight)
   const int64_t item_id = ((int64_t)blockIdx.x * kThreads + threadIdx.x) / G;
   if (item_id >= nitems) return;                  // whole lane groups only
   const int gl = (int)threadIdx.x % G;
@@ -73,9 +100,11 @@ __global__ __launch_bounds__(kThreads) void k_edge_dot(
   if (!live) g = make_float4(0.f, 0.f, 0.f, 0.f);
   const int last = it.end - 1;
   // mean mode: an item that is no pack is a whole segment (<= 64 edges) and is finished here
-  const bool finish = MEAN && !(it.flags & RGCN_ITEM_PACK);
+  const bool finish = SUMS && !(it.flags & RGCN_ITEM_PACK);
   float w = 0.f;
-  if (finish) w = mean_weight(cnt[seg]);
+  if constexpr (MEAN) {
+    if (finish) w = mean_weight(cnt[seg]);
+  }
 
   if constexpr (G >= kRound) {
     // ids: lane u < 8 of the group holds the id of edge e + u; the first round's come with the item (padded with -1),
@@ -84,8 +113,10 @@ __global__ __launch_bounds__(kThreads) void k_edge_dot(
     const int slot = gl / (G / kRound);           // the top three lane bits, read as a number: the edge of a round
     const bool stores = gl % (G / kRound) == 0;
     float part = 0.f, first = 0.f;                // mean: this slot's partial sum; the first round's dot
+    float wp = 0.f, first_w = 0.f;                // log weight: the weight of this round's / the first round's position
     for (int64_t e = it.begin; e < it.end; e += kRound) {       // int64: a run may end within a round of 2^31
       const int nxt = col[min(e + kRound + (gl & (kRound - 1)), (int64_t)last)];
+      if constexpr (LOGW) wp = cnt[min(e + slot, (int64_t)last)];
       float p[kRound];
       float4 v[kRound];
 #pragma unroll
@@ -110,9 +141,14 @@ __global__ __launch_bounds__(kThreads) void k_edge_dot(
       for (int off = G / 16; off >= 1; off >>= 1) p[0] += __shfl_xor(p[0], off, G);
       const int64_t mine = e + slot;
       if (stores && mine < it.end) out[mine] = p[0];
-      if (MEAN) {
-        part += mine < it.end ? p[0] : 0.f;
+      if (SUMS) {
+        float term = p[0];
+        if constexpr (LOGW) term = logw_term(wp, p[0]);
+        part += mine < it.end ? term : 0.f;
         if (e == it.begin) first = p[0];
+        if constexpr (LOGW) {
+          if (e == it.begin) first_w = wp;
+        }
       }
     }
     if (finish) {
@@ -120,31 +156,39 @@ __global__ __launch_bounds__(kThreads) void k_edge_dot(
       float sum = part;
 #pragma unroll
       for (int off = G / 2; off >= G / kRound; off >>= 1) sum += __shfl_xor(sum, off, G);
-      const float sw = mean_scaled_sum(sum, w);
+      const float sw = seg_total<MODE>(sum, w);
       const int64_t mine = (int64_t)it.begin + slot;
-      if (stores && mine < it.end) out[mine] = mean_value(first, sw, w);
+      if (stores && mine < it.end) out[mine] = seg_value<MODE>(first, sw, LOGW ? first_w : w);
       if (stores && it.end - it.begin > kRound) {             // later rounds: this lane's own stores, re-read in one batch
-        float later[kRound - 1];
+        float later[kRound - 1], later_w[kRound - 1];         // (log weight: their weights beside them)
 #pragma unroll
-        for (int r = 1; r < kRound; ++r) later[r - 1] = out[min(mine + r * kRound, (int64_t)last)];
+        for (int r = 1; r < kRound; ++r) {
+          later[r - 1] = out[min(mine + r * kRound, (int64_t)last)];
+          later_w[r - 1] = LOGW ? cnt[min(mine + r * kRound, (int64_t)last)] : w;
+        }
 #pragma unroll
         for (int r = 1; r < kRound; ++r)
-          if (mine + r * kRound < it.end) out[mine + r * kRound] = mean_value(later[r - 1], sw, w);
+          if (mine + r * kRound < it.end) out[mine + r * kRound] = seg_value<MODE>(later[r - 1], sw, later_w[r - 1]);
       }
     }
   } else {
     int idx_n[kRound];                                      // fewer than 8 lanes per row: every lane loads the ids
-    float part[kRound], first[kRound];
+    float part[kRound], first[kRound], wp[kRound], first_w[kRound];   // wp, first_w: the log weight mode's operands
 #pragma unroll
     for (int u = 0; u < kRound; ++u) {
       idx_n[u] = col[min((int64_t)it.begin + u, (int64_t)last)];
       part[u] = first[u] = 0.f;
+      wp[u] = first_w[u] = w;
     }
     for (int64_t e = it.begin; e < it.end; e += kRound) {
       float p[kRound];
       float4 v[kRound];
 #pragma unroll
       for (int u = 0; u < kRound; ++u) v[u] = *reinterpret_cast<const float4*>(x + (size_t)idx_n[u] * d + c4);
+      if constexpr (LOGW) {
+#pragma unroll
+        for (int u = 0; u < kRound; ++u) wp[u] = cnt[min(e + u, (int64_t)last)];
+      }
 #pragma unroll
       for (int u = 0; u < kRound; ++u) idx_n[u] = col[min(e + kRound + u, (int64_t)last)];
 #pragma unroll
@@ -158,39 +202,45 @@ __global__ __launch_bounds__(kThreads) void k_edge_dot(
         for (int u = 0; u < kRound; ++u)
           if (e + u < it.end) out[e + u] = p[u];
       }
-      if (MEAN) {
+      if (SUMS) {
 #pragma unroll
         for (int u = 0; u < kRound; ++u) {
-          part[u] += e + u < it.end ? p[u] : 0.f;
+          part[u] += e + u < it.end ? (LOGW ? logw_term(wp[u], p[u]) : p[u]) : 0.f;
           if (e == it.begin) first[u] = p[u];
+          if (LOGW && e == it.begin) first_w[u] = wp[u];
         }
       }
     }
     if (finish && gl == 0) {                                // every lane holds every dot: lane 0 stored them all
       const float sum = ((part[0] + part[4]) + (part[2] + part[6])) + ((part[1] + part[5]) + (part[3] + part[7]));
-      const float sw = mean_scaled_sum(sum, w);
+      const float sw = seg_total<MODE>(sum, w);
 #pragma unroll
       for (int u = 0; u < kRound; ++u)
-        if ((int64_t)it.begin + u < it.end) out[it.begin + u] = mean_value(first[u], sw, w);
+        if ((int64_t)it.begin + u < it.end) out[it.begin + u] = seg_value<MODE>(first[u], sw, first_w[u]);
       for (int64_t e = (int64_t)it.begin + kRound; e < it.end; e += kRound) {
-        float later[kRound];
+        float later[kRound], later_w[kRound];
 #pragma unroll
-        for (int u = 0; u < kRound; ++u) later[u] = out[min(e + u, (int64_t)last)];
+        for (int u = 0; u < kRound; ++u) {
+          later[u] = out[min(e + u, (int64_t)last)];
+          later_w[u] = LOGW ? cnt[min(e + u, (int64_t)last)] : w;
+        }
 #pragma unroll
         for (int u = 0; u < kRound; ++u)
-          if (e + u < it.end) out[e + u] = mean_value(later[u], sw, w);
+          if (e + u < it.end) out[e + u] = seg_value<MODE>(later[u], sw, later_w[u]);
       }
     }
   }
 }
 
-// The segments of more than 64 edges of a mean structure, in place over the dots k_edge_dot<., true> stored (it has
-// finished the shorter ones).  A workgroup looks at 256 segments, one per thread, and then takes the long ones among
-// them one at a time with all its threads: thread t adds dot[begin + t + 256 j] for j = 0, 1, ... in ascending j onto
-// +0.0f; the 64 sums of a wavefront meet in an xor butterfly (32, 16, 8, 4, 2, 1); S = ((W0 + W1) + W2) + W3 over the
+// The segments of more than 64 edges of a mean structure (kMean, cnt = cnt[N * R]) or of a weighted one (kLogW, cnt =
+// w[E]), in place over the dots k_edge_dot stored in that mode (it has finished the shorter ones).  A workgroup looks at
+// 256 segments, one per thread, and then takes the long ones among them one at a time with all its threads: thread t
+// adds dot[begin + t + 256 j] (kLogW: fl(w * dot) of that position) for j = 0, 1, ... in ascending j onto +0.0f; the 64 sums of a wavefront meet in an xor butterfly (32, 16, 8, 4, 2, 1); S = ((W0 + W1) + W2) + W3 over the
 // four wavefronts.  Each position is then re-read and rewritten by the thread that summed it.
-__global__ __launch_bounds__(kThreads) void k_edge_mean_long(const int32_t* __restrict__ rowptr,
-                                                             const float* __restrict__ cnt, int64_t NR, float* out) {
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void k_edge_long(const int32_t* __restrict__ rowptr,
+                                                        const float* __restrict__ cnt, int64_t NR, float* out) {
+  constexpr bool LOGW = MODE == kLogW;
   constexpr int kBatch = 8;                       // loads in flight per thread
   __shared__ int list[kThreads];
   __shared__ int nlist;
@@ -205,47 +255,57 @@ __global__ __launch_bounds__(kThreads) void k_edge_mean_long(const int32_t* __re
   for (int i = 0; i < n; ++i) {
     const int64_t s = base + list[i];
     const int64_t begin = rowptr[s], end = rowptr[s + 1];
-    const float w = mean_weight(cnt[s]);
+    float w = 0.f;
+    if constexpr (!LOGW) w = mean_weight(cnt[s]);
     float sum = 0.f;
     int64_t p = begin + tid;
     for (; p + (kBatch - 1) * kThreads < end; p += kBatch * kThreads) {
-      float v[kBatch];
+      float v[kBatch], wv[kBatch];
 #pragma unroll
-      for (int j = 0; j < kBatch; ++j) v[j] = out[p + j * kThreads];
+      for (int j = 0; j < kBatch; ++j) {
+        v[j] = out[p + j * kThreads];
+        if constexpr (LOGW) wv[j] = cnt[p + j * kThreads];
+      }
 #pragma unroll
-      for (int j = 0; j < kBatch; ++j) sum += v[j];
+      for (int j = 0; j < kBatch; ++j) sum += LOGW ? logw_term(wv[j], v[j]) : v[j];
     }
-    for (; p < end; p += kThreads) sum += out[p];
+    for (; p < end; p += kThreads) sum += LOGW ? logw_term(cnt[p], out[p]) : out[p];
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
     if ((tid & 63) == 0) wsum[tid >> 6] = sum;
     __syncthreads();
-    const float sw = mean_scaled_sum(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3], w);
+    const float sw = seg_total<MODE>(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3], w);
     p = begin + tid;
     for (; p + (kBatch - 1) * kThreads < end; p += kBatch * kThreads) {
-      float v[kBatch];
+      float v[kBatch], wv[kBatch];
 #pragma unroll
-      for (int j = 0; j < kBatch; ++j) v[j] = out[p + j * kThreads];
+      for (int j = 0; j < kBatch; ++j) {
+        v[j] = out[p + j * kThreads];
+        wv[j] = LOGW ? cnt[p + j * kThreads] : w;
+      }
 #pragma unroll
-      for (int j = 0; j < kBatch; ++j) out[p + j * kThreads] = mean_value(v[j], sw, w);
+      for (int j = 0; j < kBatch; ++j) out[p + j * kThreads] = seg_value<MODE>(v[j], sw, wv[j]);
     }
-    for (; p < end; p += kThreads) out[p] = mean_value(out[p], sw, w);
+    for (; p < end; p += kThreads) out[p] = seg_value<MODE>(out[p], sw, LOGW ? cnt[p] : w);
     __syncthreads();                              // wsum is free again
   }
 }
 
 template <int G>
-void launch_dot(const rgcn_csr* c, int64_t NR, bool mean, const float* x, const float* gagg, float* out, int d,
+void launch_dot(const rgcn_csr* c, int64_t NR, int what, const float* x, const float* gagg, float* out, int d,
                 hipStream_t stream) {
   const int64_t nitems = c->num_items[0] - c->empty_items0;       // the segments without an edge are the suffix
   if (nitems <= 0) return;
   const unsigned grid = (unsigned)ceil_div64(nitems, kThreads / G);
-  if (mean)
-    k_edge_dot<G, true><<<grid, kThreads, 0, stream>>>(x, gagg, c->items[0], nitems, c->rowptr, NR, c->col, c->head_col,
-                                                       c->val, out, d);
+  if (what == kMean)
+    k_edge_dot<G, kMean><<<grid, kThreads, 0, stream>>>(x, gagg, c->items[0], nitems, c->rowptr, NR, c->col, c->head_col,
+                                                        c->val, out, d);
+  else if (what == kLogW)
+    k_edge_dot<G, kLogW><<<grid, kThreads, 0, stream>>>(x, gagg, c->items[0], nitems, c->rowptr, NR, c->col, c->head_col,
+                                                        c->val, out, d);
   else
-    k_edge_dot<G, false><<<grid, kThreads, 0, stream>>>(x, gagg, c->items[0], nitems, c->rowptr, NR, c->col, c->head_col,
-                                                        nullptr, out, d);
+    k_edge_dot<G, kPlain><<<grid, kThreads, 0, stream>>>(x, gagg, c->items[0], nitems, c->rowptr, NR, c->col, c->head_col,
+                                                         nullptr, out, d);
 }
 
 }  // namespace
@@ -261,8 +321,10 @@ int rgcn_edge_grad(const rgcn_graph* g, int transposed, const void* x, int mode,
   if (job && job->slab) return RGCN_ERR_UNSUPPORTED;   // a pending reduction must not be lost silently
   if (!c->rowptr) return RGCN_ERR_ARG;            // direction not built
   if (first_level != 0 || (last_level >= 0 && last_level != c->num_levels)) return RGCN_ERR_ARG;
-  const bool mean = (mode & RGCN_MODE_MEAN_GRAD) != 0;
+  const bool mean = (mode & RGCN_MODE_MEAN_GRAD) != 0, logw = (mode & RGCN_MODE_LOG_WEIGHT_GRAD) != 0;
   if (mean && c->weighted) return RGCN_ERR_UNSUPPORTED;
+  if (logw && !c->weighted) return RGCN_ERR_UNSUPPORTED;   // a mean structure has no per-edge weights: the mean mode
+  const int what = mean ? kMean : logw ? kLogW : kPlain;
   if (g->E == 0 || c->n_key == 0) return RGCN_OK; // nothing to write
   if (!x || !gagg) return RGCN_ERR_ARG;
   if (!out || out_bytes < (size_t)g->E * sizeof(float)) return RGCN_ERR_WORKSPACE;
@@ -272,15 +334,17 @@ int rgcn_edge_grad(const rgcn_graph* g, int transposed, const void* x, int mode,
   const float* xf = reinterpret_cast<const float*>(x);
   float* o = reinterpret_cast<float*>(out);
   const int q = (int)(d / 4);
-  if (q <= 1) launch_dot<1>(c, NR, mean, xf, gagg, o, (int)d, stream);
-  else if (q <= 2) launch_dot<2>(c, NR, mean, xf, gagg, o, (int)d, stream);
-  else if (q <= 4) launch_dot<4>(c, NR, mean, xf, gagg, o, (int)d, stream);
-  else if (q <= 8) launch_dot<8>(c, NR, mean, xf, gagg, o, (int)d, stream);
-  else if (q <= 16) launch_dot<16>(c, NR, mean, xf, gagg, o, (int)d, stream);
-  else if (q <= 32) launch_dot<32>(c, NR, mean, xf, gagg, o, (int)d, stream);
-  else launch_dot<64>(c, NR, mean, xf, gagg, o, (int)d, stream);
+  if (q <= 1) launch_dot<1>(c, NR, what, xf, gagg, o, (int)d, stream);
+  else if (q <= 2) launch_dot<2>(c, NR, what, xf, gagg, o, (int)d, stream);
+  else if (q <= 4) launch_dot<4>(c, NR, what, xf, gagg, o, (int)d, stream);
+  else if (q <= 8) launch_dot<8>(c, NR, what, xf, gagg, o, (int)d, stream);
+  else if (q <= 16) launch_dot<16>(c, NR, what, xf, gagg, o, (int)d, stream);
+  else if (q <= 32) launch_dot<32>(c, NR, what, xf, gagg, o, (int)d, stream);
+  else launch_dot<64>(c, NR, what, xf, gagg, o, (int)d, stream);
   if (mean)                                       // the segments of more than 64 edges, if there are any
-    k_edge_mean_long<<<(unsigned)ceil_div64(NR, kThreads), kThreads, 0, stream>>>(c->rowptr, c->val, NR, o);
+    k_edge_long<kMean><<<(unsigned)ceil_div64(NR, kThreads), kThreads, 0, stream>>>(c->rowptr, c->val, NR, o);
+  else if (logw)
+    k_edge_long<kLogW><<<(unsigned)ceil_div64(NR, kThreads), kThreads, 0, stream>>>(c->rowptr, c->val, NR, o);
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }

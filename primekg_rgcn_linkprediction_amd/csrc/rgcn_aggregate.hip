@@ -525,6 +525,8 @@ int rgcn_aggregate_ex(const rgcn_graph* g, int transposed, const void* x, int x_
                       float* amax, void* stream) {
   if (!g) return RGCN_ERR_ARG;
   if ((x_f16 & RGCN_MODE_MEAN_GRAD) && !(x_f16 & RGCN_MODE_WEIGHT_GRAD)) return RGCN_ERR_ARG;
+  if ((x_f16 & RGCN_MODE_LOG_WEIGHT_GRAD) && !(x_f16 & RGCN_MODE_WEIGHT_GRAD)) return RGCN_ERR_ARG;
+  if ((x_f16 & RGCN_MODE_LOG_WEIGHT_GRAD) && (x_f16 & RGCN_MODE_MEAN_GRAD)) return RGCN_ERR_ARG;   // one or the other
   if (x_f16 & RGCN_MODE_WEIGHT_GRAD)            // not a gather: the adjoint in the edge weights (edge_grad.hip)
     return rgcn_edge_grad(g, transposed, x, x_f16, d, agg, workspace, workspace_bytes, first_level, last_level, job, amax,
                           stream);

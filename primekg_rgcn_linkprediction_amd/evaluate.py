@@ -179,7 +179,8 @@ class ModelEvaluator:
         return self.model.decoder.top_heads(emb[anchors], relations, emb, k, tail_indices=anchors, **kwargs)
 
     @torch.no_grad()
-    def explain(self, pairs, k: int = 5, max_len: int = 4, by: str = "cosine", relations=None, top_edges: int = 0):
+    def explain(self, pairs, k: int = 5, max_len: int = 4, by: str = "cosine", relations=None, top_edges: int = 0,
+                fidelity=False, mask_steps: int = 100, mask_lr: float = 0.1):
         """why a pair is predicted: for every ``(source, target)`` of ``pairs`` the ``k`` best-scoring simple paths of at
         most ``max_len`` edges through the full graph (``consumers.connecting_paths`` on the cached embeddings) and the
         exact number of such paths of length 1..4 -> ``(paths, counts)``.  The full graph's ``PathGraph`` and the cosine
@@ -190,14 +191,33 @@ class ModelEvaluator:
         score is attributed to the edges of the full graph (``attribution.edge_attribution``, one pair at a time), a
         hop scores the largest ``|attribution|`` of the columns that name it (``consumers.attribution_edge_score``)
         and the paths are ranked as before; ``edges[q]``: the ``top_edges`` columns the score depends on most
-        (``consumers.attributed_edges``)."""
+        (``consumers.attributed_edges``).
+
+        ``by="mask"`` OPTIMISES an explanation -> ``(paths, counts, edges)`` likewise: per pair a soft edge mask is learned
+        so that few edges preserve the prediction (``attribution.learn_edge_mask``, ``mask_steps`` steps of Adam at
+        ``mask_lr``), a hop scores the largest mask value of the columns that name it, and ``edges[q]`` are the
+        ``top_edges`` columns the mask keeps most (``consumers.masked_edges``).
+
+        ``fidelity`` grades the explanation by the model itself and appends one more element, per pair ``{explainer:
+        {"full", "without", "only"}}`` (``consumers.explanation_fidelity``): the score on the whole graph, with the
+        explainer's ``top_edges`` columns deleted, and with only those kept inside the pair's receptive field.  ``True``:
+        the explainer of ``by``; ``"all"``: cosine, gradient and mask side by side.  The cosine route names no columns
+        itself: its set is the columns of the hops of its listed paths, best path first, up to ``top_edges``.  Needs
+        ``relations``."""
         from . import consumers, ops
-        if by not in ("cosine", "gradient"):
-            raise ValueError(f"by must be 'cosine' or 'gradient', got {by!r}")
+        if by not in ("cosine", "gradient", "mask"):
+            raise ValueError(f"by must be 'cosine', 'gradient' or 'mask', got {by!r}")
+        if fidelity not in (False, True, "all"):
+            raise ValueError(f"fidelity must be False, True or 'all', got {fidelity!r}")
+        if (by != "cosine" or fidelity) and relations is None:
+            raise ValueError(f"explain(by={by!r}, fidelity={fidelity!r}) explains the score of a triple: relations (one per "
+                             "pair) is required")
+        if fidelity:
+            return self._explain_graded(pairs, k, max_len, by, relations, int(top_edges), fidelity, mask_steps, mask_lr)
         if by == "gradient":
-            if relations is None:
-                raise ValueError("explain(by='gradient') attributes the score of a triple: relations (one per pair) is required")
             return self._explain_by_gradient(pairs, k, max_len, relations, int(top_edges))
+        if by == "mask":
+            return self._explain_by_mask(pairs, k, max_len, relations, int(top_edges), mask_steps, mask_lr)
         if self._path_graph is None:
             self._path_graph = ops.PathGraph(self.full_edge_index, self.full_edge_type, self.num_nodes)
         emb = self.embeddings()
@@ -224,6 +244,61 @@ class ModelEvaluator:
             counts.extend(c)
             edges.append(consumers.attributed_edges(attr, self.full_edge_index, self.full_edge_type, top_edges))
         return paths, counts, edges
+
+    def _pairs_relations(self, pairs, relations):
+        pairs = torch.as_tensor(pairs, dtype=torch.int64).reshape(-1, 2)
+        relations = torch.as_tensor(relations, dtype=torch.int64).view(-1)
+        if relations.numel() == 1 and pairs.size(0) != 1:
+            relations = relations.expand(pairs.size(0))
+        if relations.numel() != pairs.size(0):
+            raise ValueError("one relation per pair (or a single relation for all) expected")
+        return pairs.tolist(), relations.tolist()
+
+    def _explain_by_mask(self, pairs, k: int, max_len: int, relations, top_edges: int, steps: int, lr: float):
+        from . import attribution, consumers
+        pairs, relations = self._pairs_relations(pairs, relations)
+        graph, emb = self._structure(), self.embeddings()
+        paths, counts, edges = [], [], []
+        for (h, t), r in zip(pairs, relations):
+            result = attribution.learn_edge_mask(self.model, self.full_edge_index, self.full_edge_type, h, r, t, steps=steps, lr=lr)
+            hop_score = consumers.mask_edge_score(result, graph, self.full_edge_index)
+            p, c = consumers.connecting_paths(emb, graph, [(h, t)], k, max_len, return_counts=True, edge_score=hop_score)
+            paths.extend(p)
+            counts.extend(c)
+            edges.append(consumers.masked_edges(result, self.full_edge_index, self.full_edge_type, top_edges))
+        return paths, counts, edges
+
+    def _path_columns(self, per_pair, limit: int):
+        """the columns of the hops of a pair's listed paths, best path first, without repeats, at most ``limit``: per hop
+        the lowest column that names it"""
+        ei = self.full_edge_index
+        cols = []
+        for path in per_pair:
+            for a, b in zip(path["nodes"][:-1], path["nodes"][1:]):
+                hit = torch.nonzero((ei[0] == a) & (ei[1] == b)).view(-1)
+                if hit.numel() and int(hit[0]) not in cols:
+                    cols.append(int(hit[0]))
+        return cols[:max(limit, 0)]
+
+    def _explain_graded(self, pairs, k, max_len, by, relations, top_edges, fidelity, steps, lr):
+        from . import consumers
+        pairs, relations = self._pairs_relations(pairs, relations)
+        routes = ("cosine", "gradient", "mask") if fidelity == "all" else (by,)
+        found = {}
+        for route in routes:
+            if route == "cosine":
+                p, c = self.explain(pairs, k, max_len)
+                found[route] = (p, c, [[(col,) for col in self._path_columns(per_pair, top_edges)] for per_pair in p])
+            elif route == "gradient":
+                found[route] = self._explain_by_gradient(pairs, k, max_len, relations, top_edges)
+            else:
+                found[route] = self._explain_by_mask(pairs, k, max_len, relations, top_edges, steps, lr)
+        sets = [{route: [edge[0] for edge in found[route][2][q]] for route in routes} for q in range(len(pairs))]
+        graded = consumers.explanation_fidelity(self.model, self.full_edge_index, self.full_edge_type, pairs, relations, sets)
+        paths, counts, edges = found[by]
+        if by == "cosine":
+            return paths, counts, graded
+        return paths, counts, edges, graded
 
     def _structure(self):
         """the full graph's ``PathGraph``, built on first use and kept (``explain`` shares it)"""

@@ -922,8 +922,8 @@ class EdgeDropout:
         handle = self.handle                       # raises once this object or its parent graph is destroyed
         if not 0.0 <= float(p) < 1.0:
             raise ValueError(f"edge dropout p must be in [0, 1), got {p}")
-        if not 0 <= int(batch) < _lib.EDGE_DROPOUT_PAIRED:
-            raise ValueError("batch must be >= 0 and below 2**61 (the bits above carry the draw's options)")
+        if not 0 <= int(batch) < _lib.EDGE_DROPOUT_MASK:     # (bit 60 would turn the call into a mask draw: set_mask)
+            raise ValueError("batch must be >= 0 and below 2**60 (the bits above carry the draw's options)")
         if hide_twins and position is None:
             raise ValueError("hide_twins hides the twins of the window's columns: it needs position")
         for name, t, n in (("rng", rng, 2), ("cursor", cursor, 1), ("position", position, self.graph.num_edges),
@@ -940,6 +940,39 @@ class EdgeDropout:
             rc = _lib.load().rgcn_edge_dropout_draw(handle, float(p), _ptr(rng), _ptr(cursor), word,
                                                     _ptr(position), _ptr(stats), _stream())
         _lib.check(rc, "rgcn_edge_dropout_draw")
+
+    def set_mask(self, mask: torch.Tensor, position: Optional[torch.Tensor] = None, cursor: Optional[torch.Tensor] = None,
+                 batch: int = 0, stats: Optional[torch.Tensor] = None, hide_twins: bool = False) -> None:
+        """A CONTINUOUS mask into the view (``RGCN_EDGE_DROPOUT_MASK`` of ``rgcn_edge_dropout_draw``; asynchronous,
+        capturable): ``mask`` is float32 ``[E]`` on the graph's device, one value per ORIGINAL column, and every weight of
+        both directions becomes ``m / M`` with ``M`` the sum of ``m`` over the edge's (destination, relation) segment in
+        the fixed order ``rgcn_edge_dropout.h`` states (``M > 0``; otherwise 0).  Nothing is drawn.  ``position``,
+        ``cursor``, ``batch`` and ``hide_twins`` hide columns as in ``draw`` (a hidden column counts as ``m = 0``);
+        ``stats`` accumulates (edges with ``m > 0``, hidden edges); ``kept_counts()`` is the number of edges with
+        ``m > 0`` per segment.  Values are not clamped: see the header for what a negative or NaN value does."""
+        handle = self.handle                       # raises once this object or its parent graph is destroyed
+        if not isinstance(mask, torch.Tensor):
+            raise TypeError("mask must be a float32 tensor on the graph's device")
+        _need_gpu("mask", mask, torch.float32)
+        if mask.dim() != 1 or mask.numel() != self.graph.num_edges or mask.device != self.device:
+            raise ValueError(f"mask must be float32[{self.graph.num_edges}] on the graph's device (one value per column)")
+        if mask.data_ptr() % 8:
+            raise ValueError("mask must start at an 8-byte boundary")
+        if not 0 <= int(batch) < _lib.EDGE_DROPOUT_MASK:
+            raise ValueError("batch must be >= 0 and below 2**60 (the bits above carry the draw's options)")
+        if hide_twins and position is None:
+            raise ValueError("hide_twins hides the twins of the window's columns: it needs position")
+        for name, t, n in (("cursor", cursor, 1), ("position", position, self.graph.num_edges), ("stats", stats, 2)):
+            if t is None:
+                continue
+            _need_gpu(name, t, torch.int64)
+            if t.numel() != n or t.device != self.device:
+                raise ValueError(f"{name} must be int64[{n}] on the graph's device")
+        word = int(batch) | _lib.EDGE_DROPOUT_MASK | (_lib.EDGE_DROPOUT_HIDE_TWINS if hide_twins else 0)
+        with _on(self.device):
+            rc = _lib.load().rgcn_edge_dropout_draw(handle, 0.0, _ptr(mask), _ptr(cursor), word, _ptr(position),
+                                                    _ptr(stats), _stream())
+        _lib.check(rc, "rgcn_edge_dropout_draw (mask)")
 
     def kept_counts(self) -> torch.Tensor:
         """int32[N * R]: the kept edges of every (destination, relation) segment under the last draw (a copy)"""
@@ -1111,7 +1144,8 @@ def aggregate_sparse(graph: BucketedGraph, x: torch.Tensor, transposed: bool = F
 
 
 def aggregate_weight_grad(graph: BucketedGraph, x: torch.Tensor, gagg: torch.Tensor, transposed: bool = False,
-                          through_mean: bool = False, original_order: bool = False) -> torch.Tensor:
+                          through_mean: bool = False, original_order: bool = False,
+                          through_normalisation: bool = False) -> torch.Tensor:
     """float32 ``[E]``: the adjoint of ``aggregate(graph, x, transposed)`` in its per-edge weights - for every edge p
     of that direction the dot product of ``gagg``'s row of p's segment (``gagg``: ``[N, R * d]``, the gradient of the
     aggregate) and the row of ``x`` the edge reads (``RGCN_MODE_WEIGHT_GRAD`` of ``rgcn_aggregate_ex``,
@@ -1119,7 +1153,11 @@ def aggregate_weight_grad(graph: BucketedGraph, x: torch.Tensor, gagg: torch.Ten
     structure only: the forward direction of a graph or an unweighted shard): the gradient in the edge's MASK ``m`` at
     ``m = 1`` for ``w = m / sum(m)`` instead - what deleting the edge does to the mean, to first order.  The result is in
     the direction's bucketed order (``graph.arrays(transposed)``: the order of ``col``), or with ``original_order`` in
-    the order of the columns the graph was built from.  An analysis call: it cannot be part of a recorded pass."""
+    the order of the columns the graph was built from.  ``through_normalisation`` (the forward direction of an
+    edge-dropout view only; never with ``through_mean``): the view's weights are ``w = m / sum(m)`` per segment, and the
+    result is the gradient in ``log m`` - ``w[p] * (dot[p] - sum_q w[q] dot[q])``, the logit gradient of a segment
+    softmax (``RGCN_MODE_LOG_WEIGHT_GRAD``); an edge of weight 0 gets exactly 0.  An analysis call: it cannot be part
+    of a recorded pass."""
     guard_torch_op("aggregate_weight_grad is an analysis call, not part of a pass")
     if not isinstance(graph, BucketedGraph):
         raise TypeError("graph must be an ops.BucketedGraph")
@@ -1140,10 +1178,17 @@ def aggregate_weight_grad(graph: BucketedGraph, x: torch.Tensor, gagg: torch.Ten
         raise ValueError(f"gagg must be [{graph.num_nodes}, {graph.num_relations * d}], got {tuple(gagg.shape)}")
     if x.device != graph.device or gagg.device != graph.device:
         raise RuntimeError("x, gagg and the bucketed graph must be on one device")
+    if through_mean and through_normalisation:
+        raise ValueError("through_mean and through_normalisation are two parametrisations: choose one")
     if through_mean and (transposed or graph.weighted_shard):
         raise NotImplementedError("through_mean differentiates the mean's mask: a weighted structure (a transposed "
                                   "direction, a weighted shard, an edge-dropout view) has none")
-    mode = _lib.MODE_WEIGHT_GRAD | (_lib.MODE_MEAN_GRAD if through_mean else 0)
+    if through_normalisation:
+        if transposed or not graph.edge_dropout:
+            raise NotImplementedError("through_normalisation differentiates the per-segment normalisation of an "
+                                      "edge-dropout view's forward weights: no other structure carries one")
+    mode = _lib.MODE_WEIGHT_GRAD | (_lib.MODE_MEAN_GRAD if through_mean else 0) | (
+        _lib.MODE_LOG_WEIGHT_GRAD if through_normalisation else 0)
     e = graph.num_edges
     with _on(x.device):
         out = _empty(e, dtype=torch.float32, device=x.device)

@@ -53,11 +53,19 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--explain", type=int, default=0, metavar="K",
                    help="also list the K best-scoring connecting paths of every (anchor, candidate) (0: off)")
     p.add_argument("--max_path_length", type=int, default=4, help="edges of the longest connecting path, 1..4")
-    p.add_argument("--explain_by", choices=("cosine", "gradient"), default="cosine",
-                   help="what scores a hop of a connecting path: the cosine of its two embedding rows, or the gradient of "
-                        "the candidate's score in the edge (what the model itself rests on)")
+    p.add_argument("--explain_by", choices=("cosine", "gradient", "mask"), default="cosine",
+                   help="what scores a hop of a connecting path: the cosine of its two embedding rows, the gradient of "
+                        "the candidate's score in the edge (what the model itself rests on), or an edge mask learned so "
+                        "that few edges preserve the candidate's prediction")
     p.add_argument("--explain_edges", type=int, default=0, metavar="M",
-                   help="with --explain_by gradient: also list the M edges every candidate's score depends on most (0: off)")
+                   help="with --explain_by gradient or mask: also list the M edges every candidate's score depends on most "
+                        "(0: off)")
+    p.add_argument("--mask_steps", type=int, default=100, help="with --explain_by mask: optimisation steps per candidate")
+    p.add_argument("--mask_lr", type=float, default=0.1, help="with --explain_by mask: Adam's step size")
+    p.add_argument("--explain_fidelity", action="store_true",
+                   help="grade the explanations by the model: per candidate the score on the whole graph, with the M named "
+                        "edges deleted and with only them kept, for the cosine, gradient and mask explainers side by side "
+                        "(needs --explain K and --explain_edges M)")
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--trust_checkpoint", action="store_true",
                    help="allow the unrestricted pickle loader for --model_path (only for files you wrote yourself)")
@@ -78,10 +86,17 @@ def parse_args(argv=None) -> argparse.Namespace:
         parser.error("--max_path_length must be in 1..4")
     if args.explain_edges < 0:
         parser.error("--explain_edges must be >= 0")
-    if args.explain_edges > 0 and args.explain_by != "gradient":
+    if args.explain_edges > 0 and args.explain_by == "cosine" and not args.explain_fidelity:
         parser.error("--explain_edges lists attributed edges: it needs --explain_by gradient")
-    if args.explain_by == "gradient" and args.explain < 1:
-        parser.error("--explain_by gradient ranks connecting paths: it needs --explain K with K >= 1")
+    if args.explain_by != "cosine" and args.explain < 1:
+        parser.error(f"--explain_by {args.explain_by} ranks connecting paths: it needs --explain K with K >= 1")
+    if args.mask_steps < 0:
+        parser.error("--mask_steps must be >= 0")
+    if not args.mask_lr > 0:
+        parser.error("--mask_lr must be > 0")
+    if args.explain_fidelity and (args.explain < 1 or args.explain_edges < 1):
+        parser.error("--explain_fidelity deletes the M named edges of every candidate: it needs --explain K and "
+                     "--explain_edges M, both >= 1")
     return args
 
 
@@ -126,8 +141,20 @@ def predict(evaluator, args: argparse.Namespace, names: Optional[Dict[int, str]]
         pairs = [(q["anchor"], c) if args.side == "tail" else (c, q["anchor"]) for q in queries for c, _ in q["candidates"]]
         max_len = int(getattr(args, "max_path_length", 4))
         by, top_edges = getattr(args, "explain_by", "cosine"), int(getattr(args, "explain_edges", 0) or 0)
-        edges = None
-        if by == "gradient":
+        edges, graded = None, None
+        if by == "mask" or getattr(args, "explain_fidelity", False):
+            kwargs = {"by": by, "relations": [args.relation], "top_edges": top_edges}
+            if by == "mask" or args.explain_fidelity:
+                kwargs.update(mask_steps=int(getattr(args, "mask_steps", 100)), mask_lr=float(getattr(args, "mask_lr", 0.1)))
+            if getattr(args, "explain_fidelity", False):
+                kwargs["fidelity"] = "all"
+            got = evaluator.explain(pairs, explain, max_len, **kwargs) if pairs else ([], [], [], [])
+            paths, counts = got[0], got[1]
+            if by != "cosine":
+                edges = got[2]
+            if getattr(args, "explain_fidelity", False):
+                graded = got[-1]
+        elif by == "gradient":
             paths, counts, edges = (evaluator.explain(pairs, explain, max_len, by="gradient", relations=[args.relation],
                                                       top_edges=top_edges) if pairs else ([], [], []))
         else:
@@ -138,6 +165,8 @@ def predict(evaluator, args: argparse.Namespace, names: Optional[Dict[int, str]]
             q["paths"], q["path_counts"] = paths[at:at + n], counts[at:at + n]
             if edges is not None and top_edges > 0:
                 q["edges"] = [[list(e) for e in per_candidate] for per_candidate in edges[at:at + n]]
+            if graded is not None:
+                q["fidelity"] = graded[at:at + n]
             at += n
             if names is not None:
                 for per_candidate in q["paths"]:
@@ -154,6 +183,19 @@ def predict(evaluator, args: argparse.Namespace, names: Optional[Dict[int, str]]
             if top_edges > 0:
                 protocol["edges"] = {"per_candidate": top_edges, "entry": "[column, source, relation, target, d score / d edge mask]",
                                      "order": "|value| descending, equal magnitudes by column ascending"}
+        if by == "mask":
+            protocol["paths"]["score"] = ("mean over the hops of the largest learned mask value of the columns naming the "
+                                          "hop * 1 / (1 + 0.2 * (edges - 1)), float32")
+            protocol["mask"] = {"steps": int(getattr(args, "mask_steps", 100)), "lr": float(getattr(args, "mask_lr", 0.1))}
+            if top_edges > 0:
+                protocol["edges"] = {"per_candidate": top_edges, "entry": "[column, source, relation, target, mask value]",
+                                     "order": "mask value descending inside the pair's receptive field, equal values by "
+                                              "column ascending"}
+        if graded is not None:
+            protocol["fidelity"] = {"explainers": ["cosine", "gradient", "mask"], "edges_per_explainer": top_edges,
+                                    "full": "the score on the whole graph",
+                                    "without": "the score with the explainer's edges deleted",
+                                    "only": "the score with only the explainer's edges kept inside the pair's receptive field"}
     return {"protocol": protocol, "queries": queries}
 
 
