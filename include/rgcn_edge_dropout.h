@@ -17,7 +17,8 @@
  * weighted-sum structures.  The view SHARES rowptr, col, perm, the work items, the hub index, the item heads' column
  * ids and the occupancy masks with the parent - it does not own them, and the parent must outlive the view.  The
  * view OWNS, per direction, val (float[E]) and head_w (float[level-0 items * 8]), one int32[N * R] array of kept
- * counts (and the int32[N * R] counters a draw adds into), and two int32[E] index arrays (the forward segment of
+ * counts (and the int32[N * R] counters a draw adds into, and two float[N * R] arrays: M of a mask or attention draw, mx of
+ * an attention draw), and two int32[E] index arrays (the forward segment of
  * every forward position and of every transposed position), which make the draw a flat walk of the edges, and twin
  * (int32[E], below).  Ownership lives in the wrapper, not in the structure:
  * rgcn_edge_dropout_destroy frees only what the view owns.  After create the view holds the draw p = 0,
@@ -109,6 +110,43 @@
  * memset node, no allocation (M lives in a float[N * R] create allocated), no host synchronisation: capturable.  The
  * plain draw's launches are not the mask draw's and run the instructions they always ran.
  *
+ * THE ATTENTION DRAW - RGCN_EDGE_DROPOUT_ATTENTION, a fourth option bit of `batch`; tests restate it on the host
+ * (tests/attention_reference.py).  A segment's weights are the softmax of per-edge logits formed from per-(node,
+ * relation) scalars: within-relation attention on the layer's input (Busbridge et al. 2019).  Nothing is drawn and the
+ * parameters take these roles:
+ *   p          the negative slope of the leaky ReLU, 0 <= p <= 1 (anything else, NaN included: RGCN_ERR_ARG); the
+ *              kernels use (float)p.  RGCN_EDGE_DROPOUT_MASK or RGCN_EDGE_DROPOUT_PAIRED beside the bit: RGCN_ERR_ARG.
+ *              Nothing is launched on a refusal.
+ *   rng        NOT {seed, epoch}: DEVICE const float a[2 * N * R], read and never written: a[i * R + r] = a_dst[i, r],
+ *              a[N * R + j * R + r] = a_src[j, r].  It needs 8 bytes (RGCN_ERR_ALIGN) and must not be NULL.
+ *   cursor, position, batch's length, RGCN_EDGE_DROPOUT_HIDE_TWINS, stats      as in the plain draw: hard hiding
+ *              composes with attention.
+ * With e = (j -> i, r) the edge of a position and s = (i, r) its forward segment:
+ *   z(e)      = a[i * R + r] + a[N * R + j * R + r]                one fp32 addition
+ *   l(e)      = z(e) >= 0 ? z(e) : fl((float)p * z(e))             a select; the product rounded by itself
+ *   mx[s]     = the maximum of l over the positions of s that are not hidden (a NaN is passed over; -inf without one)
+ *   m(e)      = hidden(e) ? 0.0f : exp(fl(l(e) - mx[s]))           a select: a hidden edge's scalars change nothing.
+ *               exp is expf of the ROCm device library, fp32 in and out, without fast-math: the contract is an error of
+ *               at most 2 ulp (the library's table says 1), exp(+-0) = 1 exactly, exp(-inf) = +0, results below the
+ *               normal range may be flushed or denormal, and the same argument gives the same bits on every call.
+ *   M[s]      = the sum of m over the positions of s in the FIXED order stated above for the mask draw
+ *   k[s]      = the number of positions of s that are not hidden (int32)  - rgcn_edge_dropout_kept
+ *   w_fwd[pos] = w_t[pos'] = k[s] > 0 ? m(e) / M[s] : 0.0f          one IEEE division; the same value in both directions
+ *   head_w     refreshed for both directions
+ *   stats[0]  += edges that are not hidden,  stats[1] += hidden edges
+ * The maximum contributes exp(0) = 1, so M[s] >= 1 for finite logits and no quotient overflows.  a = 0 everywhere is
+ * the plain draw p = 0 under the same hiding, bit for bit: every m is 1, a sum of fewer than 2^24 ones is exact in any
+ * order, and the division is the same.
+ * Non-finite values: a NaN logit (exp of it is NaN) or a +inf one (inf - inf) makes M[s] NaN and with it EVERY weight
+ * of that segment, hidden positions included (0 / NaN) - the layer's output raises the alarm; so does
+ * a segment whose non-hidden logits are all -inf.  A -inf logit beside a finite one has weight +0.  No other segment
+ * is touched, and a segment whose edges are all hidden holds zeros (k = 0) whatever its scalars are.
+ * Three kernels, no memset node, no allocation (mx and M live in two float[N * R] arrays create allocated), no host
+ * synchronisation: capturable.  The plain draw's and the mask draw's launches are not this draw's and run the
+ * instructions they always ran.  rgcn_graph_weight_bound of the view stays true: the weights are non-negative and
+ * normalised by the mask draw's rule - a quotient by a sum in the same fixed order - so the mask draw's argument above
+ * carries over word for word with m = exp(l - mx) in [0, 1] (while the logits are finite; a NaN voids it as there).
+ *
  * Non-finite values - a deliberate deviation.  A dropped or hidden edge contributes 0 * x: it is MULTIPLIED by a zero
  * weight, not skipped, so a non-finite source row still reaches the aggregate of a segment it was dropped from
  * (0 * NaN = NaN), where RGCNConv on the kept subgraph would not see it.  The hot gather is not changed for it.
@@ -129,6 +167,7 @@ extern "C" {
 #define RGCN_EDGE_DROPOUT_HIDE_TWINS (1LL << 62)   /* a column whose twin stands in the window is hidden too */
 #define RGCN_EDGE_DROPOUT_PAIRED     (1LL << 61)   /* a column and its twin share one Philox word: dropped or kept together */
 #define RGCN_EDGE_DROPOUT_MASK       ((int64_t)1 << 60)   /* = 1LL << 60.  THE MASK DRAW above: rng is const float mask[E], p must be 0 */
+#define RGCN_EDGE_DROPOUT_ATTENTION  ((int64_t)1 << 59)   /* = 1LL << 59.  THE ATTENTION DRAW above: rng is const float a[2 * N * R], p the slope */
 
 typedef struct rgcn_edge_dropout rgcn_edge_dropout;
 
@@ -146,12 +185,14 @@ int rgcn_edge_dropout_kept_export(const rgcn_edge_dropout* ed, int32_t* out, voi
 
 /* One draw: asynchronous on `stream`, no allocation, no host synchronisation, capturable into a HIP graph (three
  * kernels, no memset node: the draw's last launch clears the counters the next one adds into).  rng: DEVICE int64[2] =
- * {seed, epoch}; cursor: DEVICE int64[1] or NULL (= 0); batch >= 0: the window's length, below 2^60, ORed with any of
- * RGCN_EDGE_DROPOUT_HIDE_TWINS and RGCN_EDGE_DROPOUT_PAIRED, or with RGCN_EDGE_DROPOUT_MASK (rng is the mask then);
+ * {seed, epoch}; cursor: DEVICE int64[1] or NULL (= 0); batch >= 0: the window's length, below 2^59, ORed with any of
+ * RGCN_EDGE_DROPOUT_HIDE_TWINS and RGCN_EDGE_DROPOUT_PAIRED, or with RGCN_EDGE_DROPOUT_MASK (rng is the mask then), or
+ * with RGCN_EDGE_DROPOUT_ATTENTION (rng holds the attention scalars, p the slope in [0, 1]);
  * position: DEVICE int64[E] or NULL, position[e] = where column e stands in the epoch's order; stats: DEVICE int64[2]
  * or NULL.  RGCN_ERR_ARG: ed or rng NULL, batch < 0, p outside [0, 1) (NaN included).  RGCN_ERR_ALIGN: rng, cursor,
  * position, stats need 8.  With RGCN_EDGE_DROPOUT_MASK: p != 0 or RGCN_EDGE_DROPOUT_PAIRED RGCN_ERR_ARG (after the range
- * of p, before the alignment). */
+ * of p, before the alignment).  With RGCN_EDGE_DROPOUT_ATTENTION: p outside [0, 1], RGCN_EDGE_DROPOUT_MASK or
+ * RGCN_EDGE_DROPOUT_PAIRED RGCN_ERR_ARG, then the alignment. */
 int rgcn_edge_dropout_draw(rgcn_edge_dropout* ed, double p, const int64_t* rng, const int64_t* cursor, int64_t batch,
                            const int64_t* position, int64_t* stats, void* stream);
 

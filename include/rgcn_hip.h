@@ -310,6 +310,27 @@ typedef struct rgcn_slab_job {
 #define RGCN_MODE_WEIGHT_GRAD 8
 #define RGCN_MODE_MEAN_GRAD 16     /* only together with RGCN_MODE_WEIGHT_GRAD */
 #define RGCN_MODE_LOG_WEIGHT_GRAD 32   /* only together with RGCN_MODE_WEIGHT_GRAD, never with RGCN_MODE_MEAN_GRAD */
+/* PER-EDGE VALUES SUMMED PER SEGMENT (x_f16 of rgcn_aggregate_ex only) - the inverse shape of RGCN_MODE_WEIGHT_GRAD:
+ * edges in, segments out.  It is the adjoint of "every edge reads a scalar of its segment's node": the deterministic
+ * stand-in for an index_add_ over E values (the library has no floating-point atomics).  With the bit set the call is
+ * not a gather and its parameters take these roles:
+ *   x          const float[E], one value per ORIGINAL column (the order the graph was built from).  Not written.
+ *   d          must be 1 (RGCN_ERR_ARG otherwise).
+ *   agg        THE OUTPUT: float[n_key * R].  out[s] = the sum over the positions pos of segment s of x[perm[pos]], in
+ *              the FIXED order stated above for S[s] under RGCN_MODE_MEAN_GRAD (<= 64 edges: eight strided partial sums
+ *              and the tree; > 64 edges: 256 strided partial sums, the butterfly per 64 and three adds - a hub of any
+ *              length takes this rule), every partial sum starting from +0.0f.  Every entry is written, a segment
+ *              without an edge with +0.0f; nothing else is written, and no value depends on what agg held before.
+ *   transposed 0: the (destination, relation) segments; 1: the (source, relation) segments.
+ *   workspace  not used, may be NULL.  Weights are not read: mean, weighted, a shard, the view of an edge dropout.
+ *   refusals   in this order, nothing launched on any of them: any other bit of the option word RGCN_ERR_ARG; d != 1
+ *              RGCN_ERR_ARG; amax != NULL RGCN_ERR_UNSUPPORTED; a job with a non-NULL slab RGCN_ERR_UNSUPPORTED; a
+ *              direction that was not built RGCN_ERR_ARG; first_level != 0, or last_level neither < 0 nor
+ *              rgcn_graph_num_levels, RGCN_ERR_ARG.  Then no key rows: RGCN_OK, nothing written.  Then agg NULL, or x
+ *              NULL while E > 0, RGCN_ERR_ARG (E == 0 reads no x and writes zeros), and last x or agg below 4 bytes
+ *              RGCN_ERR_ALIGN.  One launch, no allocation, no host synchronisation: capturable.
+ *   non-finite values   a NaN or infinity reaches exactly its own segment's sum (infinities of both signs: NaN). */
+#define RGCN_MODE_EDGE_SUM 64
 size_t rgcn_aggregate_workspace_bytes(const rgcn_graph* g, int transposed, int64_t d);
 int rgcn_aggregate_deferrable(const rgcn_graph* g, int transposed, int64_t d);
 int rgcn_aggregate(const rgcn_graph* g, int transposed, const float* x, int64_t d, float* agg,

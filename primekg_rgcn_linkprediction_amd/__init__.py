@@ -8,7 +8,8 @@ behind a C ABI (``include/rgcn_hip.h`` -> ``librgcn_hip.so``).  See DESIGN.md.
 from .conv import RGCNConv, rgcn_conv, rgcn_encoder2, rgcn_encoder2_step
 from .head import LinkPredictor, distmult
 from .model import DrugDiseaseModel, DrugDiseaseRGCN
+from .attention import RelationalAttentionConv
 from . import baselines, consumers, ops, synth
 
 __all__ = ["RGCNConv", "rgcn_conv", "rgcn_encoder2", "rgcn_encoder2_step", "LinkPredictor", "distmult", "DrugDiseaseModel",
-           "DrugDiseaseRGCN", "baselines", "consumers", "ops", "synth"]
+           "DrugDiseaseRGCN", "RelationalAttentionConv", "baselines", "consumers", "ops", "synth"]

@@ -254,6 +254,7 @@ EDGE_DROPOUT_PROTOTYPES = {
 EDGE_DROPOUT_STREAM = 0x45444F50   # RGCN_EDGE_DROPOUT_STREAM
 EDGE_DROPOUT_HIDE_TWINS, EDGE_DROPOUT_PAIRED = 1 << 62, 1 << 61   # option bits of the draw's `batch`
 EDGE_DROPOUT_MASK = 1 << 60        # RGCN_EDGE_DROPOUT_MASK: the mask draw - `rng` is float mask[E], nothing is drawn
+EDGE_DROPOUT_ATTENTION = 1 << 59   # RGCN_EDGE_DROPOUT_ATTENTION: the attention draw - `rng` is float a[2 * N * R], p the slope
 
 # rgcn_sparse.h: the row-granular occupancy behind sparse aggregates (csrc/rgcn_graph.hip).  MODE_SPARSE_ROWS:
 # RGCN_MODE_SPARSE_ROWS of rgcn_hip.h, the bit a training pass sets in the `int` option word of its gathers and of the
@@ -283,6 +284,7 @@ MODE_ROW_ORDER = 4
 MODE_WEIGHT_GRAD = 8
 MODE_MEAN_GRAD = 16
 MODE_LOG_WEIGHT_GRAD = 32          # RGCN_MODE_LOG_WEIGHT_GRAD: through a weighted structure's per-segment normalisation
+MODE_EDGE_SUM = 64                 # RGCN_MODE_EDGE_SUM: float[E] by original column in, float[n_key * R] segment sums out
 
 # header of include/ -> its table, in the order the headers arrived: what load() types and every test enumerates
 HEADERS = {

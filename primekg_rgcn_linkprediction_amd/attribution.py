@@ -29,6 +29,14 @@ def _aggregate_grad(g: Tensor, weight: Tensor) -> Tensor:
     return torch.einsum("no,rio->nri", g, weight).reshape(g.size(0), -1).contiguous()
 
 
+def _refuse_attention(encoder, what: str) -> None:
+    """these explanations differentiate the MEAN's weights; an attention encoder's weights are its own function of the
+    input (``attention.py``) and are not explained"""
+    if getattr(encoder, "attention", False):
+        raise NotImplementedError(f"{what} explains the mean encoder: a model trained with attention (--attention) is "
+                                  "not explained")
+
+
 def edge_attribution(model, edge_index: Tensor, edge_type: Tensor, heads, relations, tails, coeff: Optional[Tensor] = None,
                      graph: Optional["ops.BucketedGraph"] = None) -> Dict[str, Tensor]:
     """``{"layer1", "layer2", "total": float32 [E], "score": float32 [Q]}`` for the triples ``(heads[q], relations[q],
@@ -41,6 +49,7 @@ def edge_attribution(model, edge_index: Tensor, edge_type: Tensor, heads, relati
     if model.training:
         raise ValueError("edge_attribution explains the model as it predicts: call model.eval() first")
     enc = model.encoder
+    _refuse_attention(enc, "edge_attribution")
     conv1, conv2 = enc.conv1, enc.conv2
     if conv1.gather_dtype == torch.float16 or conv2.gather_dtype == torch.float16:
         raise NotImplementedError("edge_attribution reads fp32 feature tables (gather_dtype=torch.float16 is not attributed)")
@@ -112,6 +121,7 @@ def _check_explained(model, edge_index, graph, what):
     if model.training:
         raise ValueError(f"{what} explains the model as it predicts: call model.eval() first")
     enc = model.encoder
+    _refuse_attention(enc, what)
     if enc.conv1.gather_dtype == torch.float16 or enc.conv2.gather_dtype == torch.float16:
         raise NotImplementedError(f"{what} reads fp32 feature tables (gather_dtype=torch.float16 is not explained)")
     x = enc.node_embeddings.weight.detach().contiguous()

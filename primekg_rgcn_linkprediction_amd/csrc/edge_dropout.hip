@@ -32,6 +32,17 @@
 //                  as k_edge_long of edge_grad.hip takes them.  M[s] and k[s] are written by the owner.
 //   k_ed_mask_t    one thread per transposed position: m of its column again, divided by M of its forward segment.
 //   k_ed_heads     as in the plain draw (the counters it clears were never raised).
+//
+// The attention draw (RGCN_EDGE_DROPOUT_ATTENTION).  The mask draw's frame with the value computed instead of loaded:
+// the logit of an edge is a select over one add of two per-(node, relation) scalars, and a segment's weights are its
+// softmax.  Its own kernels again - the mask draw's launches are not touched:
+//   k_ed_att_fwd   the owners of k_ed_mask_fwd.  A first walk leaves the logit in w_fwd (-inf for a hidden column: it
+//                  then drops out of the maximum, and exp gives the 0 the header asks for) and finds the maximum - an
+//                  order-free operation; the second walk is the mask draw's: m = exp(l - mx) summed in the FIXED order,
+//                  then the owner's own stores divided.  mx[s], M[s] and k[s] are written by the owner.
+//   k_ed_att_t     one thread per transposed position: its transposed segment (source, relation) by a search in rowptr
+//                  - that index IS the index of a_src - the logit again, exp(l - mx) / M of its forward segment.
+//   k_ed_heads     as ever.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -57,6 +68,7 @@ struct rgcn_edge_dropout {
   int32_t* seg_t = nullptr;     // [E] forward segment (dst * R + rel) of every transposed position
   int32_t* twin = nullptr;      // [E] by ORIGINAL column: the column holding the reversed triple, -1 without one
   float* msum = nullptr;        // [N * R] M of the last mask draw (the transposed half of that draw divides by it)
+  float* mmax = nullptr;        // [N * R] mx of the last attention draw (its transposed half subtracts it)
 };
 
 namespace {
@@ -391,6 +403,218 @@ int mask_impl(rgcn_edge_dropout* ed, const draw_params& p, const float* mask, bo
   return RGCN_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------ attention draw
+// l(e) of the header: one fp32 add, then a select (the product rounded by itself).  `s` = i * R + r is the index of
+// a_dst, `js` = j * R + r the index of a_src behind the N * R scalars of a_dst.
+__device__ inline float att_logit(const float* __restrict__ a, int64_t NR, int64_t s, int64_t js, float slope) {
+  const float z = __fadd_rn(a[s], a[NR + js]);
+  return z >= 0.f ? z : __fmul_rn(slope, z);     // NaN >= 0 is false: slope * NaN is NaN
+}
+__device__ inline float att_value(float l, float mx) { return expf(__fsub_rn(l, mx)); }   // hidden: l = -inf
+__device__ inline float att_weight(float m, float M, int k) { return k > 0 ? __fdiv_rn(m, M) : 0.f; }
+
+template <bool kHideTwins>
+__global__ __launch_bounds__(kThreads) void k_ed_att_fwd(const int32_t* __restrict__ rowptr,
+                                                         const int32_t* __restrict__ col,
+                                                         const int64_t* __restrict__ perm, int64_t NR, int64_t E, int64_t R,
+                                                         draw_params p, const float* __restrict__ a, float slope,
+                                                         float* w_fwd, float* __restrict__ mmax, float* __restrict__ msum,
+                                                         int32_t* __restrict__ kept, unsigned long long* __restrict__ stats) {
+  constexpr int kBatch = 8;
+  constexpr float kNegInf = -__builtin_inff();
+  __shared__ int list[kThreads];
+  __shared__ int nlist, s_stat[2], s_kept[kThreads / 64];
+  __shared__ float wsum[kThreads / 64], wmax[kThreads / 64];
+  const int tid = (int)threadIdx.x;
+  const int64_t base = (int64_t)blockIdx.x * kThreads, s_own = base + tid;
+  const draw_state st = draw_begin_cursor(p);
+  if (tid == 0) nlist = 0;
+  if (tid < 2) s_stat[tid] = 0;
+  __syncthreads();
+  int64_t begin = 0, end = 0;
+  if (s_own < NR) { begin = rowptr[s_own]; end = rowptr[s_own + 1]; }
+  const bool is_long = end - begin > RGCN_CHUNK;
+  if (is_long) list[atomicAdd(&nlist, 1)] = tid;
+  int nk = 0, nh = 0;                              // non-hidden edges, hidden edges: this thread's
+  if (!is_long) {                                  // (a segment without an edge: mx = -inf, M = 0, k = 0)
+    const int64_t last = end > begin ? end - 1 : 0, r_own = s_own % R;
+    float mx = kNegInf;
+    for (int64_t q = begin; q < end; q += kBatch) {
+      int64_t e[kBatch];
+      int j[kBatch];
+      float l[kBatch];
+      bool hid[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) e[u] = clamp64(perm[min(q + u, last)], 0, E - 1);   // clamped: never under a branch
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) j[u] = col[min(q + u, last)];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) hid[u] = mask_hidden<kHideTwins>(p, st, e[u]);
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) l[u] = att_logit(a, NR, s_own, clamp64((int64_t)j[u] * R + r_own, 0, NR - 1), slope);
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const bool in = q + u < end;
+        const float v = hid[u] ? kNegInf : l[u];   // a select: a hidden column's scalars change nothing
+        mx = in ? fmaxf(mx, v) : mx;               // (fmaxf passes a NaN over: it comes back through exp)
+        nk += in && !hid[u];
+        nh += in && hid[u];
+        if (in) w_fwd[q + u] = v;
+      }
+    }
+    float part[kBatch];
+#pragma unroll
+    for (int u = 0; u < kBatch; ++u) part[u] = 0.f;
+    for (int64_t q = begin; q < end; q += kBatch) {         // this thread's own stores, as the mask draw sums them
+      float l[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) l[u] = w_fwd[min(q + u, last)];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const float m = att_value(l[u], mx);
+        part[u] += q + u < end ? m : 0.f;
+        if (q + u < end) w_fwd[q + u] = m;
+      }
+    }
+    const float M = ((part[0] + part[4]) + (part[2] + part[6])) + ((part[1] + part[5]) + (part[3] + part[7]));
+    if (s_own < NR) { mmax[s_own] = mx; msum[s_own] = M; kept[s_own] = nk; }
+    for (int64_t q = begin; q < end; q += kBatch) {
+      float m[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) m[u] = w_fwd[min(q + u, last)];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u)
+        if (q + u < end) w_fwd[q + u] = att_weight(m[u], M, nk);
+    }
+  }
+  __syncthreads();
+  const int n = nlist;
+  for (int i = 0; i < n; ++i) {
+    const int64_t s = base + list[i], r_s = s % R;
+    const int64_t b = rowptr[s], en = rowptr[s + 1];
+    float mx = kNegInf;
+    int cnt = 0;
+    for (int64_t q = b + tid; q < en; q += (int64_t)kBatch * kThreads) {
+      int64_t e[kBatch];
+      int j[kBatch];
+      float l[kBatch];
+      bool hid[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) e[u] = clamp64(perm[min(q + (int64_t)u * kThreads, en - 1)], 0, E - 1);
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) j[u] = col[min(q + (int64_t)u * kThreads, en - 1)];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) hid[u] = mask_hidden<kHideTwins>(p, st, e[u]);
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) l[u] = att_logit(a, NR, s, clamp64((int64_t)j[u] * R + r_s, 0, NR - 1), slope);
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int64_t at = q + (int64_t)u * kThreads;
+        const bool in = at < en;
+        const float v = hid[u] ? kNegInf : l[u];
+        mx = in ? fmaxf(mx, v) : mx;
+        cnt += in && !hid[u];
+        nh += in && hid[u];
+        if (in) w_fwd[at] = v;
+      }
+    }
+    nk += cnt;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      mx = fmaxf(mx, __shfl_xor(mx, off));
+      cnt += __shfl_xor(cnt, off);
+    }
+    if ((tid & 63) == 0) { wmax[tid >> 6] = mx; s_kept[tid >> 6] = cnt; }
+    __syncthreads();
+    mx = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    const int k = s_kept[0] + s_kept[1] + s_kept[2] + s_kept[3];
+    float sum = 0.f;
+    for (int64_t q = b + tid; q < en; q += (int64_t)kBatch * kThreads) {   // ascending j: thread t adds b + t + 256 j
+      float l[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) l[u] = w_fwd[min(q + (int64_t)u * kThreads, en - 1)];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int64_t at = q + (int64_t)u * kThreads;
+        const float m = att_value(l[u], mx);
+        sum += at < en ? m : 0.f;
+        if (at < en) w_fwd[at] = m;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
+    if ((tid & 63) == 0) wsum[tid >> 6] = sum;
+    __syncthreads();
+    const float M = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    if (tid == 0) { mmax[s] = mx; msum[s] = M; kept[s] = k; }
+    for (int64_t q = b + tid; q < en; q += (int64_t)kBatch * kThreads) {
+      float m[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) m[u] = w_fwd[min(q + (int64_t)u * kThreads, en - 1)];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u)
+        if (q + (int64_t)u * kThreads < en) w_fwd[q + (int64_t)u * kThreads] = att_weight(m[u], M, k);
+    }
+    __syncthreads();                               // wmax, wsum and s_kept are free again
+  }
+  if (stats) {                                     // integers: order-free
+    if (nk) atomicAdd(&s_stat[0], nk);
+    if (nh) atomicAdd(&s_stat[1], nh);
+    __syncthreads();
+    if (tid < 2 && s_stat[tid] > 0) atomicAdd(&stats[tid], (unsigned long long)s_stat[tid]);
+  }
+}
+
+template <bool kHideTwins>
+__global__ __launch_bounds__(kThreads) void k_ed_att_t(const int32_t* __restrict__ rowptr_t,
+                                                       const int64_t* __restrict__ perm_t,
+                                                       const int32_t* __restrict__ seg_t, int64_t NR, int64_t E,
+                                                       draw_params p, const float* __restrict__ a, float slope,
+                                                       const float* __restrict__ mmax, const float* __restrict__ msum,
+                                                       const int32_t* __restrict__ kept, float* __restrict__ w_t) {
+  const int64_t pos = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (pos >= E) return;
+  const draw_state st = draw_begin_cursor(p);
+  const int64_t e = clamp64(perm_t[pos], 0, E - 1);
+  const int64_t s = clamp64(seg_t[pos], 0, NR - 1);
+  int64_t lo = 0, hi = NR;                         // rowptr_t[lo] <= pos < rowptr_t[hi]: lo = source * R + relation
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((int64_t)rowptr_t[mid] <= pos) lo = mid; else hi = mid;
+  }
+  const float mx = mmax[s], M = msum[s], l = att_logit(a, NR, s, lo, slope);
+  const int k = kept[s];
+  const bool hid = mask_hidden<kHideTwins>(p, st, e);
+  w_t[pos] = att_weight(att_value(hid ? -__builtin_inff() : l, mx), M, k);
+}
+
+template <bool kHideTwins>
+void launch_att(rgcn_edge_dropout* ed, const draw_params& p, const float* a, float slope, int64_t* stats,
+                hipStream_t stream) {
+  const rgcn_graph& v = ed->view;
+  const int64_t E = v.E, NR = v.N * v.R;
+  k_ed_att_fwd<kHideTwins><<<grid_for(NR, kThreads), kThreads, 0, stream>>>(
+      v.dir[0].rowptr, v.dir[0].col, v.dir[0].perm, NR, E, v.R, p, a, slope, ed->val[0], ed->mmax, ed->msum, ed->kept,
+      reinterpret_cast<unsigned long long*>(stats));
+  k_ed_att_t<kHideTwins><<<grid_for(E, kThreads), kThreads, 0, stream>>>(v.dir[1].rowptr, v.dir[1].perm, ed->seg_t, NR, E,
+                                                                         p, a, slope, ed->mmax, ed->msum, ed->kept,
+                                                                         ed->val[1]);
+}
+
+int att_impl(rgcn_edge_dropout* ed, const draw_params& p, const float* a, float slope, bool hide_twins, int64_t* stats,
+             hipStream_t stream) {
+  const rgcn_graph& v = ed->view;
+  const int64_t NR = v.N * v.R;
+  if (v.E <= 0) return RGCN_OK;
+  if (hide_twins && p.position) launch_att<true>(ed, p, a, slope, stats, stream);
+  else launch_att<false>(ed, p, a, slope, stats, stream);
+  const int64_t n0 = v.dir[0].num_items[0], n1 = v.dir[1].num_items[0];
+  k_ed_heads<<<grid_for(std::max((n0 + n1) * RGCN_HEAD, NR), kThreads), kThreads, 0, stream>>>(
+      v.dir[0].items[0], n0, ed->val[0], ed->head_w[0], v.dir[1].items[0], n1, ed->val[1], ed->head_w[1], NR, ed->count);
+  RGCN_HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
 // the two launches that form the mark, instantiated on the options
 template <bool kHideTwins, bool kPaired>
 void launch_mark(rgcn_edge_dropout* ed, const draw_params& p, int64_t* stats, hipStream_t stream) {
@@ -529,6 +753,8 @@ int create_impl(const rgcn_graph* g, hipStream_t stream, rgcn_edge_dropout* ed) 
   RGCN_HIP_TRY(hipMemsetAsync(ed->count, 0, (size_t)std::max<int64_t>(NR, 1) * sizeof(int32_t), stream));
   RGCN_HIP_TRY(hipMalloc((void**)&ed->msum, (size_t)std::max<int64_t>(NR, 1) * sizeof(float)));
   RGCN_HIP_TRY(hipMemsetAsync(ed->msum, 0, (size_t)std::max<int64_t>(NR, 1) * sizeof(float), stream));
+  RGCN_HIP_TRY(hipMalloc((void**)&ed->mmax, (size_t)std::max<int64_t>(NR, 1) * sizeof(float)));
+  RGCN_HIP_TRY(hipMemsetAsync(ed->mmax, 0, (size_t)std::max<int64_t>(NR, 1) * sizeof(float), stream));
   for (int d = 0; d < 2; ++d) {                  // ... but the weights and their item-head copies
     rgcn_csr& c = ed->view.dir[d];
     c.weighted = true;
@@ -623,6 +849,7 @@ void rgcn_edge_dropout_destroy(rgcn_edge_dropout* ed) {
   (void)hipFree(ed->seg_t);
   (void)hipFree(ed->twin);
   (void)hipFree(ed->msum);
+  (void)hipFree(ed->mmax);
   delete ed;                                     // the shared arrays stay the parent's
 }
 
@@ -643,8 +870,15 @@ int rgcn_edge_dropout_draw(rgcn_edge_dropout* ed, double p, const int64_t* rng, 
                            const int64_t* position, int64_t* stats, void* stream) {
   if (!ed || !rng || batch < 0) return RGCN_ERR_ARG;            // (bit 63 is no option: a negative batch)
   const bool hide_twins = (batch & RGCN_EDGE_DROPOUT_HIDE_TWINS) != 0, paired = (batch & RGCN_EDGE_DROPOUT_PAIRED) != 0;
-  const bool masked = (batch & RGCN_EDGE_DROPOUT_MASK) != 0;
-  batch &= ~(RGCN_EDGE_DROPOUT_HIDE_TWINS | RGCN_EDGE_DROPOUT_PAIRED | RGCN_EDGE_DROPOUT_MASK);   // what is left is the window's length
+  const bool masked = (batch & RGCN_EDGE_DROPOUT_MASK) != 0, attention = (batch & RGCN_EDGE_DROPOUT_ATTENTION) != 0;
+  batch &= ~(RGCN_EDGE_DROPOUT_HIDE_TWINS | RGCN_EDGE_DROPOUT_PAIRED | RGCN_EDGE_DROPOUT_MASK |
+             RGCN_EDGE_DROPOUT_ATTENTION);           // what is left is the window's length
+  if (attention) {                                   // p is the slope there: its own range, nothing drawn, no shared word
+    if (!(p >= 0.0 && p <= 1.0) || masked || paired) return RGCN_ERR_ARG;
+    RGCN_ALIGN_TRY(8, rng, cursor, position, stats);
+    return att_impl(ed, draw_params{position, cursor, nullptr, batch, 0u, ed->twin}, reinterpret_cast<const float*>(rng),
+                    (float)p, hide_twins, stats, (hipStream_t)stream);
+  }
   if (!(p >= 0.0 && p < 1.0)) return RGCN_ERR_ARG;            // NaN fails both compares
   if (masked && (p != 0.0 || paired)) return RGCN_ERR_ARG;    // a mask draw draws nothing: no p, no shared word
   RGCN_ALIGN_TRY(8, rng, cursor, position, stats);

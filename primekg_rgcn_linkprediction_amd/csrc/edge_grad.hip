@@ -23,6 +23,11 @@
 // dropout's view): the same frame with one more operand per edge.  The weight of the position a lane stores is loaded
 // from a clamped index before the round's row loads - independent of them, never under a branch - and the rewrite of
 // the later rounds re-reads the weights beside the dots in one batch.
+//
+// RGCN_MODE_EDGE_SUM, the inverse shape: one float per ORIGINAL column in, out[s] = the sum over the segment's positions
+// of x[perm[pos]] in the same fixed order.  A segment has one owner, as in k_edge_long: a workgroup looks at 256
+// segments, a thread sums its own if it has at most 64 edges (a round of eight positions IS the eight strided partial
+// sums), the longer ones are taken one at a time by all 256 threads.  Every segment is written, an empty one with +0.0f.
 #include "rgcn_common.h"
 
 namespace {
@@ -291,6 +296,64 @@ __global__ __launch_bounds__(kThreads) void k_edge_long(const int32_t* __restric
   }
 }
 
+// out[s] for every s < NR (the header's RGCN_MODE_EDGE_SUM): nothing but perm, rowptr and the values is read
+__global__ __launch_bounds__(kThreads) void k_edge_sum(const int32_t* __restrict__ rowptr, const int64_t* __restrict__ perm,
+                                                       int64_t NR, int64_t E, const float* __restrict__ x,
+                                                       float* __restrict__ out) {
+  constexpr int kBatch = 8;
+  __shared__ int list[kThreads];
+  __shared__ int nlist;
+  __shared__ float wsum[kThreads / 64];
+  const int tid = (int)threadIdx.x;
+  const int64_t base = (int64_t)blockIdx.x * kThreads, s_own = base + tid;
+  if (tid == 0) nlist = 0;
+  __syncthreads();
+  int64_t begin = 0, end = 0;
+  if (s_own < NR) { begin = rowptr[s_own]; end = rowptr[s_own + 1]; }
+  const bool is_long = end - begin > RGCN_CHUNK;
+  if (is_long) list[atomicAdd(&nlist, 1)] = tid;
+  if (!is_long && s_own < NR) {
+    float part[kBatch];
+#pragma unroll
+    for (int j = 0; j < kBatch; ++j) part[j] = 0.f;
+    const int64_t last = end > begin ? end - 1 : 0;
+    for (int64_t q = begin; q < end; q += kBatch) {
+      int64_t e[kBatch];
+      float v[kBatch];
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) e[j] = clamp64(perm[min(q + j, last)], 0, E - 1);   // clamped: never under a branch
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) v[j] = x[e[j]];
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) part[j] += q + j < end ? v[j] : 0.f;
+    }
+    out[s_own] = ((part[0] + part[4]) + (part[2] + part[6])) + ((part[1] + part[5]) + (part[3] + part[7]));
+  }
+  __syncthreads();
+  const int n = nlist;                            // (the order of the list changes no value: a segment is summed alone)
+  for (int i = 0; i < n; ++i) {
+    const int64_t s = base + list[i];
+    const int64_t b = rowptr[s], en = rowptr[s + 1];
+    float sum = 0.f;
+    for (int64_t q = b + tid; q < en; q += (int64_t)kBatch * kThreads) {   // ascending j: thread t adds b + t + 256 j
+      int64_t e[kBatch];
+      float v[kBatch];
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) e[j] = clamp64(perm[min(q + (int64_t)j * kThreads, en - 1)], 0, E - 1);
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) v[j] = x[e[j]];
+#pragma unroll
+      for (int j = 0; j < kBatch; ++j) sum += q + (int64_t)j * kThreads < en ? v[j] : 0.f;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
+    if ((tid & 63) == 0) wsum[tid >> 6] = sum;
+    __syncthreads();
+    if (tid == 0) out[s] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    __syncthreads();                              // wsum is free again
+  }
+}
+
 template <int G>
 void launch_dot(const rgcn_csr* c, int64_t NR, int what, const float* x, const float* gagg, float* out, int d,
                 hipStream_t stream) {
@@ -345,6 +408,25 @@ int rgcn_edge_grad(const rgcn_graph* g, int transposed, const void* x, int mode,
     k_edge_long<kMean><<<(unsigned)ceil_div64(NR, kThreads), kThreads, 0, stream>>>(c->rowptr, c->val, NR, o);
   else if (logw)
     k_edge_long<kLogW><<<(unsigned)ceil_div64(NR, kThreads), kThreads, 0, stream>>>(c->rowptr, c->val, NR, o);
+  RGCN_HIP_TRY(hipGetLastError());
+  return RGCN_OK;
+}
+
+int rgcn_edge_sum(const rgcn_graph* g, int transposed, const void* x, int mode, int64_t d, float* out, int first_level,
+                  int last_level, const rgcn_slab_job* job, const float* amax, void* stream_) {
+  const rgcn_csr* c = &g->dir[transposed ? 1 : 0];
+  if (mode != RGCN_MODE_EDGE_SUM) return RGCN_ERR_ARG;   // the call is no gather and no dot: no other bit has a meaning
+  if (d != 1) return RGCN_ERR_ARG;
+  if (amax) return RGCN_ERR_UNSUPPORTED;
+  if (job && job->slab) return RGCN_ERR_UNSUPPORTED;   // a pending reduction must not be lost silently
+  if (!c->rowptr || !c->perm) return RGCN_ERR_ARG;     // direction not built
+  if (first_level != 0 || (last_level >= 0 && last_level != c->num_levels)) return RGCN_ERR_ARG;
+  const int64_t NR = c->n_key * g->R;
+  if (NR == 0) return RGCN_OK;                    // nothing to write
+  if (!out || (g->E > 0 && !x)) return RGCN_ERR_ARG;   // (without an edge x is never read: zeros)
+  RGCN_ALIGN_TRY(4, x, out);
+  k_edge_sum<<<(unsigned)ceil_div64(NR, kThreads), kThreads, 0, (hipStream_t)stream_>>>(
+      c->rowptr, c->perm, NR, g->E, reinterpret_cast<const float*>(x), out);
   RGCN_HIP_TRY(hipGetLastError());
   return RGCN_OK;
 }

@@ -524,6 +524,8 @@ int rgcn_aggregate_ex(const rgcn_graph* g, int transposed, const void* x, int x_
                       void* workspace, size_t workspace_bytes, int first_level, int last_level, const rgcn_slab_job* job,
                       float* amax, void* stream) {
   if (!g) return RGCN_ERR_ARG;
+  if (x_f16 & RGCN_MODE_EDGE_SUM)               // not a gather: per-edge values summed per segment (edge_grad.hip)
+    return rgcn_edge_sum(g, transposed, x, x_f16, d, agg, first_level, last_level, job, amax, stream);
   if ((x_f16 & RGCN_MODE_MEAN_GRAD) && !(x_f16 & RGCN_MODE_WEIGHT_GRAD)) return RGCN_ERR_ARG;
   if ((x_f16 & RGCN_MODE_LOG_WEIGHT_GRAD) && !(x_f16 & RGCN_MODE_WEIGHT_GRAD)) return RGCN_ERR_ARG;
   if ((x_f16 & RGCN_MODE_LOG_WEIGHT_GRAD) && (x_f16 & RGCN_MODE_MEAN_GRAD)) return RGCN_ERR_ARG;   // one or the other

@@ -215,6 +215,10 @@ __attribute__((visibility("hidden"))) int rgcn_edge_grad(const rgcn_graph* g, in
                                                          int64_t d, const float* gagg, void* out, size_t out_bytes,
                                                          int first_level, int last_level, const rgcn_slab_job* job,
                                                          const float* amax, void* stream);
+// ... with RGCN_MODE_EDGE_SUM (edge_grad.hip): `x` is float[E] by original column, `out` the call's agg.  g is not NULL.
+__attribute__((visibility("hidden"))) int rgcn_edge_sum(const rgcn_graph* g, int transposed, const void* x, int mode,
+                                                        int64_t d, float* out, int first_level, int last_level,
+                                                        const rgcn_slab_job* job, const float* amax, void* stream);
 
 // ---------------------------------------------------------------------------------------------
 // "amax" buffers: max |tensor| as the split-precision transforms need it (rgcn_transform_split.hip).

@@ -212,6 +212,9 @@ class ModelEvaluator:
         if (by != "cosine" or fidelity) and relations is None:
             raise ValueError(f"explain(by={by!r}, fidelity={fidelity!r}) explains the score of a triple: relations (one per "
                              "pair) is required")
+        if by != "cosine" or fidelity:
+            from . import attribution
+            attribution._refuse_attention(getattr(self.model, "encoder", None), f"explain(by={by!r}, fidelity={fidelity!r})")
         if fidelity:
             return self._explain_graded(pairs, k, max_len, by, relations, int(top_edges), fidelity, mask_steps, mask_lr)
         if by == "gradient":
@@ -471,7 +474,9 @@ def load_model(model_path: str, device: torch.device, trust_pickle: bool = False
                              hidden_dim=args.hidden_dim, dropout=args.dropout,
                              decoder_dropout=getattr(args, "decoder_dropout", 0.0),
                              num_bases=getattr(args, "num_bases", None),
-                             decoder=getattr(args, "decoder", "distmult"))
+                             decoder=getattr(args, "decoder", "distmult"),
+                             attention=bool(getattr(args, "attention", False)),
+                             attention_slope=float(getattr(args, "attention_slope", 0.2)))
     model.load_state_dict(state)
     model = model.to(device).eval()
     info = {"checkpoint_path": str(model_path), "epoch": checkpoint.get("epoch", "unknown"), "num_nodes": num_nodes,

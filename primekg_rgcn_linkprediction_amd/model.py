@@ -30,17 +30,28 @@ class DrugDiseaseRGCN(nn.Module):
 
     def __init__(self, num_nodes: int, num_relations: int, embedding_dim: int = 64,
                  hidden_dim: int = 128, dropout: float = 0.5, num_bases: Optional[int] = None,
-                 gather_dtype=None):
+                 gather_dtype=None, attention: bool = False, attention_slope: float = 0.2):
         super().__init__()
         self.num_nodes = num_nodes
         self.num_relations = num_relations
         self.embedding_dim = embedding_dim
         self.hidden_dim = hidden_dim
         self.node_embeddings = nn.Embedding(num_nodes, embedding_dim)
-        self.conv1 = RGCNConv(in_channels=embedding_dim, out_channels=hidden_dim,
-                              num_relations=num_relations, num_bases=num_bases, gather_dtype=gather_dtype)
-        self.conv2 = RGCNConv(in_channels=hidden_dim, out_channels=hidden_dim,
-                              num_relations=num_relations, num_bases=num_bases, gather_dtype=gather_dtype)
+        # attention (off by default): both layers weigh the in-edges of a (node, relation) by a learned segment softmax
+        # (attention.py); with its parameters at zero - their initial value - the encoder is the mean encoder
+        self.attention = bool(attention)
+        self.attention_window = None       # the trainer's hidden window for both layers' draws (RelationalAttentionConv.forward)
+        if self.attention:
+            from .attention import RelationalAttentionConv
+            layer = dict(num_relations=num_relations, num_bases=num_bases, gather_dtype=gather_dtype,
+                         negative_slope=attention_slope)
+            self.conv1 = RelationalAttentionConv(embedding_dim, hidden_dim, **layer)
+            self.conv2 = RelationalAttentionConv(hidden_dim, hidden_dim, **layer)
+        else:
+            self.conv1 = RGCNConv(in_channels=embedding_dim, out_channels=hidden_dim,
+                                  num_relations=num_relations, num_bases=num_bases, gather_dtype=gather_dtype)
+            self.conv2 = RGCNConv(in_channels=hidden_dim, out_channels=hidden_dim,
+                                  num_relations=num_relations, num_bases=num_bases, gather_dtype=gather_dtype)
         self.dropout = nn.Dropout(dropout)
         self._init_embeddings()
 
@@ -54,6 +65,19 @@ class DrugDiseaseRGCN(nn.Module):
         # the whole table is the layer-1 input (no lookup) unless a subset is asked for
         x = self.node_embeddings.weight if node_indices is None else self.node_embeddings(node_indices)
         p = self.dropout.p if self.training else 0.0
+        if self.attention:
+            # layer by layer (not the fused two-layer node): each layer draws its softmax into a view of its own.  The
+            # hidden window, if the trainer set one, goes to both draws; its counters to the first only.
+            if node_indices is not None:
+                raise NotImplementedError("an attention encoder runs over the whole embedding table")
+            if graph is not None and graph.edge_dropout:
+                raise ValueError("an attention encoder draws into views of its own: pass the graph's bucketing, not the "
+                                 "view of an edge dropout")
+            window = dict(self.attention_window or {})
+            x = self.conv1(x, edge_index, edge_type, activation="relu", graph=graph, window=window)
+            x = self.dropout(x)
+            window.pop("stats", None)
+            return self.conv2(x, edge_index, edge_type, graph=graph, window=window)
         if graph is not None and graph.edge_dropout and not self.training:
             graph = graph.parent
         if p < 1.0:
@@ -73,14 +97,16 @@ class DrugDiseaseModel(nn.Module):
 
     def __init__(self, num_nodes: int, num_relations: int, embedding_dim: int = 64,
                  hidden_dim: int = 128, dropout: float = 0.5, decoder_dropout: float = 0.0,
-                 num_bases: Optional[int] = None, gather_dtype=None, decoder: str = "distmult"):
+                 num_bases: Optional[int] = None, gather_dtype=None, decoder: str = "distmult",
+                 attention: bool = False, attention_slope: float = 0.2):
         super().__init__()
         self.num_nodes = num_nodes
         self.num_relations = num_relations
         self.hidden_dim = hidden_dim
+        extra = dict(attention=True, attention_slope=attention_slope) if attention else {}
         self.encoder = DrugDiseaseRGCN(num_nodes=num_nodes, num_relations=num_relations,
                                        embedding_dim=embedding_dim, hidden_dim=hidden_dim,
-                                       dropout=dropout, num_bases=num_bases, gather_dtype=gather_dtype)
+                                       dropout=dropout, num_bases=num_bases, gather_dtype=gather_dtype, **extra)
         self.decoder = LinkPredictor(num_relations=num_relations, embedding_dim=hidden_dim,
                                      dropout=decoder_dropout, decoder=decoder)
 

@@ -745,6 +745,8 @@ class BucketedGraph:
         for plan in self.__dict__.pop("_fused_plans", {}).values():
             if plan.hub is not None:
                 plan.hub.destroy()
+        for views in self.__dict__.pop("_attention_views", {}).values():
+            views.destroy()                             # attention.py: one EdgeDropout per layer, walking this graph's arrays
         if self._handle is not None:
             try:
                 _L().rgcn_graph_destroy(self._handle)
@@ -922,8 +924,8 @@ class EdgeDropout:
         handle = self.handle                       # raises once this object or its parent graph is destroyed
         if not 0.0 <= float(p) < 1.0:
             raise ValueError(f"edge dropout p must be in [0, 1), got {p}")
-        if not 0 <= int(batch) < _lib.EDGE_DROPOUT_MASK:     # (bit 60 would turn the call into a mask draw: set_mask)
-            raise ValueError("batch must be >= 0 and below 2**60 (the bits above carry the draw's options)")
+        if not 0 <= int(batch) < _lib.EDGE_DROPOUT_ATTENTION:   # (bits 59 and 60 would turn the call into another draw)
+            raise ValueError("batch must be >= 0 and below 2**59 (the bits above carry the draw's options)")
         if hide_twins and position is None:
             raise ValueError("hide_twins hides the twins of the window's columns: it needs position")
         for name, t, n in (("rng", rng, 2), ("cursor", cursor, 1), ("position", position, self.graph.num_edges),
@@ -958,8 +960,8 @@ class EdgeDropout:
             raise ValueError(f"mask must be float32[{self.graph.num_edges}] on the graph's device (one value per column)")
         if mask.data_ptr() % 8:
             raise ValueError("mask must start at an 8-byte boundary")
-        if not 0 <= int(batch) < _lib.EDGE_DROPOUT_MASK:
-            raise ValueError("batch must be >= 0 and below 2**60 (the bits above carry the draw's options)")
+        if not 0 <= int(batch) < _lib.EDGE_DROPOUT_ATTENTION:
+            raise ValueError("batch must be >= 0 and below 2**59 (the bits above carry the draw's options)")
         if hide_twins and position is None:
             raise ValueError("hide_twins hides the twins of the window's columns: it needs position")
         for name, t, n in (("cursor", cursor, 1), ("position", position, self.graph.num_edges), ("stats", stats, 2)):
@@ -973,6 +975,46 @@ class EdgeDropout:
             rc = _lib.load().rgcn_edge_dropout_draw(handle, 0.0, _ptr(mask), _ptr(cursor), word, _ptr(position),
                                                     _ptr(stats), _stream())
         _lib.check(rc, "rgcn_edge_dropout_draw (mask)")
+
+    def set_attention(self, a: torch.Tensor, slope: float, position: Optional[torch.Tensor] = None,
+                      cursor: Optional[torch.Tensor] = None, batch: int = 0, stats: Optional[torch.Tensor] = None,
+                      hide_twins: bool = False) -> None:
+        """Segment-softmax ATTENTION weights into the view (``RGCN_EDGE_DROPOUT_ATTENTION`` of
+        ``rgcn_edge_dropout_draw``; asynchronous, capturable).  ``a`` is float32 ``[2, N, R]`` (or flat ``[2 * N * R]``)
+        on the graph's device: ``a[0, i, r]`` the destination scalar and ``a[1, j, r]`` the source scalar of relation
+        ``r``.  An edge ``j -> i`` of relation ``r`` gets the logit ``leaky_relu(a[0, i, r] + a[1, j, r], slope)``, and
+        every weight of both directions becomes the softmax of the logits over the edge's (destination, relation)
+        segment - maximum subtracted, summed in the fixed order ``rgcn_edge_dropout.h`` states.  ``0 <= slope <= 1``.
+        ``position``, ``cursor``, ``batch`` and ``hide_twins`` hide columns as in ``draw`` (a hidden column has weight 0
+        and leaves the softmax); ``stats`` accumulates (edges not hidden, hidden edges); ``kept_counts()`` is the number
+        of edges not hidden per segment.  ``a = 0`` is ``draw(0.0, ...)`` under the same hiding, bit for bit."""
+        handle = self.handle                       # raises once this object or its parent graph is destroyed
+        if not isinstance(a, torch.Tensor):
+            raise TypeError("a must be a float32 tensor on the graph's device")
+        _need_gpu("a", a, torch.float32)
+        n = 2 * self.graph.num_nodes * self.graph.num_relations
+        if a.numel() != n or a.device != self.device or not a.is_contiguous():
+            raise ValueError(f"a must be contiguous float32[2, {self.graph.num_nodes}, {self.graph.num_relations}] on the "
+                             "graph's device (destination scalars, then source scalars)")
+        if a.data_ptr() % 8:
+            raise ValueError("a must start at an 8-byte boundary")
+        if not 0.0 <= float(slope) <= 1.0:         # NaN fails both compares
+            raise ValueError(f"the negative slope must be in [0, 1], got {slope}")
+        if not 0 <= int(batch) < _lib.EDGE_DROPOUT_ATTENTION:
+            raise ValueError("batch must be >= 0 and below 2**59 (the bits above carry the draw's options)")
+        if hide_twins and position is None:
+            raise ValueError("hide_twins hides the twins of the window's columns: it needs position")
+        for name, t, m in (("cursor", cursor, 1), ("position", position, self.graph.num_edges), ("stats", stats, 2)):
+            if t is None:
+                continue
+            _need_gpu(name, t, torch.int64)
+            if t.numel() != m or t.device != self.device:
+                raise ValueError(f"{name} must be int64[{m}] on the graph's device")
+        word = int(batch) | _lib.EDGE_DROPOUT_ATTENTION | (_lib.EDGE_DROPOUT_HIDE_TWINS if hide_twins else 0)
+        with _on(self.device):
+            rc = _lib.load().rgcn_edge_dropout_draw(handle, float(slope), _ptr(a), _ptr(cursor), word, _ptr(position),
+                                                    _ptr(stats), _stream())
+        _lib.check(rc, "rgcn_edge_dropout_draw (attention)")
 
     def kept_counts(self) -> torch.Tensor:
         """int32[N * R]: the kept edges of every (destination, relation) segment under the last draw (a copy)"""
@@ -1203,6 +1245,31 @@ def aggregate_weight_grad(graph: BucketedGraph, x: torch.Tensor, gagg: torch.Ten
         by_column = _empty(e, dtype=torch.float32, device=x.device)
         by_column[perms[bool(transposed)]] = out                     # perm is a permutation: a plain indexed store
     return by_column
+
+
+def edge_segment_sum(graph: BucketedGraph, values: torch.Tensor, transposed: bool = False) -> torch.Tensor:
+    """float32 ``[N, R]``: per-edge ``values`` (float32 ``[E]``, one per ORIGINAL column of the graph) summed over the
+    (destination, relation) segments, or with ``transposed`` over the (source, relation) segments
+    (``RGCN_MODE_EDGE_SUM`` of ``rgcn_aggregate_ex``, ``include/rgcn_hip.h``): the deterministic adjoint of "every edge
+    reads a scalar of its endpoint".  A segment is summed in the fixed order the header states - no floating-point
+    atomics, the same bits on every call - and a segment without an edge gets ``+0.0``.  Weights are not read, so any
+    structure qualifies, an edge-dropout view included."""
+    guard_torch_op("edge_segment_sum is not part of a recorded pass")
+    if not isinstance(graph, BucketedGraph):
+        raise TypeError("graph must be an ops.BucketedGraph")
+    _need_gpu("values", values, torch.float32)
+    if graph.bipartite and transposed:
+        raise ValueError("a shard structure has one direction only (transposed=False)")
+    if values.dim() != 1 or values.numel() != graph.num_edges:
+        raise ValueError(f"values must be float32[{graph.num_edges}] (one value per column), got {tuple(values.shape)}")
+    if values.device != graph.device:
+        raise RuntimeError("values and the bucketed graph must be on one device")
+    with _on(values.device):
+        out = _empty((graph.num_nodes, graph.num_relations), dtype=torch.float32, device=values.device)
+        rc = _lib.load().rgcn_aggregate_ex(graph.handle, int(transposed), _ptr(values), _lib.MODE_EDGE_SUM, 1, _ptr(out),
+                                           None, 0, 0, -1, None, None, _stream())
+    _lib.check(rc, "rgcn_aggregate_ex (edge sum)")
+    return out
 
 
 def fused_bwd_supported(num_relations: int, d_in: int, d_out: int) -> bool:

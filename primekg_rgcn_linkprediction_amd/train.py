@@ -118,6 +118,20 @@ class Trainer:
             raise ValueError("--hide_reverse_edges hides the reverse columns of the batch's own: it needs --hide_batch_edges")
         if self.paired_edge_dropout and not self.edge_dropout_p > 0.0:
             raise ValueError("--paired_edge_dropout draws one word per pair of columns: it needs --edge_dropout P with P > 0")
+        # --attention (off by default): both layers weigh a (node, relation) segment's in-edges by a learned segment softmax
+        # (attention.py).  Each layer draws into a view of its own, so the trainer holds none; the hidden window of
+        # --hide_batch_edges goes to both layers' draws through the encoder.  The slot of the draw's p carries the slope.
+        self.attention = bool(getattr(args, "attention", False))
+        if self.attention:
+            if self.edge_dropout_p > 0.0:
+                raise ValueError("--attention and --edge_dropout P > 0 do not combine: the draw that writes the attention "
+                                 "weights takes the negative slope where the dropout draw takes P")
+            if getattr(args, "fp16_gather", False):
+                raise ValueError("--attention reads an fp32 feature table: drop --fp16_gather")
+            if not getattr(getattr(model, "encoder", None), "attention", False):
+                raise ValueError("--attention needs a model built with attention=True (train.create_model does it)")
+            if device.type != "cuda":
+                raise ValueError("--attention runs on the GPU only (the attention weights are written by a device kernel)")
         self._edge_dropout = self._ed_stats = self._ed_position = None
         self.edge_dropout_stats = (0, 0)       # (kept edges, hidden edges) summed over the steps of the last training epoch
         self._ed_steps = 0                     # steps of that epoch: kept fraction = kept / (steps * train columns)
@@ -145,7 +159,10 @@ class Trainer:
             for d, ei, et in ((train_data, self.train_edge_index, self.train_edge_type),
                               (full_graph, self.full_edge_index, self.full_edge_type)):
                 ops.bucket(ei, et, d["num_nodes"], d["num_relations"], sidecar=d.get("sidecar"))
-        if self.edge_dropout_p or self.hide_batch_edges:
+        if self.attention:
+            if self.hide_batch_edges:
+                self._ed_stats = torch.zeros(2, dtype=torch.int64, device=device)
+        elif self.edge_dropout_p or self.hide_batch_edges:
             self._edge_dropout = ops.EdgeDropout(ops.bucket(self.train_edge_index, self.train_edge_type,
                                                             train_data["num_nodes"], train_data["num_relations"]))
             self._ed_stats = torch.zeros(2, dtype=torch.int64, device=device)
@@ -155,7 +172,12 @@ class Trainer:
         # whole-step HIP graph (sampler -> encoder -> head -> BCE -> backward -> clip -> Adam ->
         # running metrics) for the full-size batches of an epoch; needs a device-side Adam step count
         self.use_hip_graph = (device.type == "cuda" and not getattr(args, "no_hip_graph", False)
-                              and max(1, getattr(args, "gradient_accumulation_steps", 1)) == 1 and not self.softmax)
+                              and max(1, getattr(args, "gradient_accumulation_steps", 1)) == 1 and not self.softmax
+                              and not self.attention)
+        if self.attention:
+            logger.info("--attention (slope %g): every step runs eagerly - the layer's backward forms the attention "
+                        "gradients with torch ops that have never been captured into a HIP graph",
+                        float(getattr(args, "attention_slope", 0.2)))
         # on the GPU: the single-kernel update (same rule; the default one runs ~10 list kernels
         # per step, ~125 us here), with its step count on the device when the step is captured
         extra = {"fused": True, "capturable": self.use_hip_graph} if device.type == "cuda" else {}
@@ -282,6 +304,11 @@ class Trainer:
         """This step's message-passing graph: one draw into the trainer's edge-dropout view at the device cursor, keyed by
         the sampler's ``(seed, epoch)`` -> the ``graph=`` keyword of the model's loss (empty without the flags).  Part of
         the captured step: a replay draws at whatever the cursor then holds."""
+        if self.attention:                              # the layers draw themselves; this step's window for both of them
+            self.model.encoder.attention_window = None if not self.hide_batch_edges else dict(
+                position=self._ed_position, cursor=self._cursor, batch=size, stats=self._ed_stats,
+                hide_twins=self.hide_reverse_edges)
+            return {}
         if self._edge_dropout is None:
             return {}
         self._edge_dropout.draw(self.edge_dropout_p, self._rng, cursor=self._cursor, batch=size if self.hide_batch_edges else 0,
@@ -295,7 +322,7 @@ class Trainer:
         target is a best eligible candidate).  Eager: ``lo`` is the position."""
         idx = self._order[lo:lo + size]
         heads, tails, rels = self.train_edge_index[0, idx], self.train_edge_index[1, idx], self.train_edge_type[idx]
-        if self._edge_dropout is not None:
+        if self._ed_stats is not None:
             self._cursor.fill_(lo)                      # (nothing else moves the cursor of an eager softmax step)
         view = self._draw_edges(size)
         loss, _ = self.model.softmax_loss(self.train_edge_index, self.train_edge_type, heads, tails, rels,
@@ -383,7 +410,7 @@ class Trainer:
             self._neg_stats.zero_()
         # the permutation is drawn on the host like the reference's torch.randperm(num_edges)
         self._order.copy_(torch.randperm(e))
-        if self._edge_dropout is not None:
+        if self._ed_stats is not None:
             self._ed_stats.zero_()
             if self.hide_batch_edges:                # where every column stands in this epoch's order: one scatter per epoch
                 if self._ed_position is None:
@@ -435,6 +462,8 @@ class Trainer:
     def validate(self):
         """Validation triples scored with messages passed over the FULL graph."""
         self.model.eval()
+        if self.attention:
+            self.model.encoder.attention_window = None   # the train graph's window says nothing about the full graph
         loss_sum = torch.zeros((), device=self.device, dtype=torch.float64)
         correct = torch.zeros((), device=self.device, dtype=torch.int64)
         seen = 0
@@ -512,7 +541,7 @@ class Trainer:
             self.val_losses.append(va_loss); self.val_accs.append(va_acc)
             negatives = ("" if not self.constrained_negatives else
                          " | Neg Rejected: %d | Neg Gave Up: %d" % self.negative_stats)
-            if self._edge_dropout is not None:
+            if self._ed_stats is not None:
                 kept, hidden = self.edge_dropout_stats
                 drawn = max(1, self._ed_steps * self.train_edge_index.size(1))
                 negatives += " | Edges Kept: %.4f | Edges Hidden: %d" % (kept / drawn, hidden)
@@ -593,7 +622,9 @@ def create_model(num_nodes: int, num_relations: int, args: argparse.Namespace) -
                              dropout=args.dropout, decoder_dropout=args.decoder_dropout,
                              num_bases=args.num_bases,
                              gather_dtype=torch.float16 if getattr(args, "fp16_gather", False) else None,
-                             decoder=getattr(args, "decoder", "distmult"))
+                             decoder=getattr(args, "decoder", "distmult"),
+                             attention=bool(getattr(args, "attention", False)),
+                             attention_slope=float(getattr(args, "attention_slope", 0.2)))
     logger.info("Model created with %s parameters",
                 f"{sum(p.numel() for p in model.parameters() if p.requires_grad):,}")
     return model
@@ -659,6 +690,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "as well - data that stores both directions leaks the positive through it otherwise")
     p.add_argument("--paired_edge_dropout", action="store_true",
                    help="with --edge_dropout P: a column and its reverse column are dropped or kept together")
+    p.add_argument("--attention", action="store_true",
+                   help="relational attention: both layers weigh the in-edges of a (node, relation) by a learned segment "
+                        "softmax instead of the plain mean (starts as the mean model; composes with --hide_batch_edges / "
+                        "--hide_reverse_edges, not with --edge_dropout P > 0 or --fp16_gather; steps run eagerly)")
+    p.add_argument("--attention_slope", type=float, default=0.2,
+                   help="--attention: negative slope of the leaky ReLU on the attention logits, in [0, 1]")
     p.add_argument("--no_hip_graph", action="store_true",
                    help="launch every training step eagerly instead of replaying one captured HIP graph")
     p.add_argument("--synthetic", action="store_true",
